@@ -19,7 +19,17 @@ Launch forms (both give ONE JSON line from rank 0 with n_gpus = rccl_ranks = num
            4 configs[4]: run.inference without --eval on 100 000 detections x H=50: no selection, the one exchange is
              the all-gather of every hypothesis of every pose (weak: 12 500 poses per GPU).
 
-Every run with a process group (--gpus N > 1, or ZEDO_FORCE_DIST=1) additionally
+A plain run (no --full) does only what the headline needs: it sets up, runs --warmup passes, times --steps passes, writes
+the last timed pass's outputs if --dump-outputs DIR is given, and prints the JSON line (metric, value, unit, higher_is_better,
+dtype, ms_per_step = milliseconds per timed pass, the quality of the selection, ...).  Every other measurement or check below
+runs only with --full (its keys are null otherwise), which also samples kernel timings inside the headline's timed passes.
+
+--dump-outputs DIR: after the timed passes, what the last one computed as DIR/<name>.npy (float32 / float64): x (the optimised
+poses of this rank's rows, [rows, 17, 3]), T ([rows, 3]) and the selection (p1_best, p1_hypothesis, p2_best, p2_hypothesis
+[poses]; h36m: the action-wise means too) - or, for the all-gather workload, results.  An array of more than DUMP_ROWS rows is
+a fixed, seeded sample of them (<name>_rows.npy: the row indices); inputs are seeded, so the same arguments give the same inputs.
+
+With --full, every run with a process group (--gpus N > 1, or ZEDO_FORCE_DIST=1) additionally
   * checks itself before anything is timed (multi_rank_selfcheck): a fixed small problem sharded over the live ranks through BOTH exchange
     steps of the path - the P1/P2 MIN selection and the all-gather of run.inference - against the unsharded run on rank 0, whatever the
     workload; a mismatch of either ends every rank with exit code 4;
@@ -27,7 +37,7 @@ Every run with a process group (--gpus N > 1, or ZEDO_FORCE_DIST=1) additionally
     on rank 0 alone and split over all N ranks, timed back to back (--strong-steps passes each, both math modes): speed-up, efficiency,
     the projection from one-GPU shard measurements (profiles/strong_shards_r*.jsonl) and bit-identity of the two selections.
 
-The JSON line also carries
+With --full the JSON line also carries (besides alt_mode, the other arithmetic mode, and geometry_kernels)
   roofline     : the dominant kernel (the four 1024x1024 fp32-MFMA dense layers): algorithmic FLOP per launch
                  / its average launch duration, measured live with sampled HIP events on the launch stream;
   cpu_baseline : the CPU port under oracle/ (numpy IPO + torch-CPU-operator OIL steps on every host core, i.e. the
@@ -281,6 +291,49 @@ def selection_digest(out):
     return h.hexdigest()[:16]
 
 
+DUMP_ROWS = 1 << 17          # rows of one dumped array at most (x: 204 bytes a row, 26.7 MB); longer outputs are sampled
+DUMP_SEED = 2024
+DUMP_BYTES = 64 << 20        # all files of one --dump-outputs together
+
+
+def output_arrays(wl, x, T, out):
+    """What a caller of the timed path receives from one pass, as {name: device tensor or float}."""
+    if wl["select"] == "gather":
+        return {"results": out["results"]}
+    arrs = {"x": x, "T": T}
+    for k in ("p1", "p2"):
+        arrs[k + "_best"], arrs[k + "_hypothesis"] = out[k]
+        if k + "_actionwise" in out:
+            arrs[k + "_actionwise"] = out[k + "_actionwise"]
+    return arrs
+
+
+def host_outputs(arrs):
+    """Device outputs -> host float32 / float64 arrays; an output of more than DUMP_ROWS rows becomes the fixed, seeded sample
+    of DUMP_ROWS of them (gathered on the device) plus <name>_rows (its row indices)."""
+    res = {}
+    for name, v in arrs.items():
+        if not isinstance(v, torch.Tensor):
+            res[name] = np.asarray([v], dtype=np.float64)
+            continue
+        if v.shape[0] > DUMP_ROWS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(v.shape[0], DUMP_ROWS, replace=False))
+            v = v[torch.as_tensor(idx, device=v.device)]
+            res[name + "_rows"] = idx.astype(np.float64)
+        a = v.detach().cpu().numpy()
+        res[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    return res
+
+
+def write_outputs(arrays, d):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_BYTES}")
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 WORKLOADS = {
     # poses = the configuration's TOTAL pose count; weak scaling gives every GPU `weak` poses instead
     2: dict(name="BASELINE configs[2] (3DPW pw3d_test, H=50, 1000 steps)", settings="pw3d", poses=1015, weak=1015,
@@ -476,20 +529,27 @@ def main():
     ap.add_argument("--poses", type=int, default=None, help="override the workload's pose count (per GPU if weak, total if strong)")
     ap.add_argument("--hypo", type=int, default=N_HYPO)
     ap.add_argument("--oil", type=int, default=S_OIL)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline too: sampled kernel timings and roofline, the other math mode (alt_mode), "
+                         "MFMA probes, geometry_kernels, cpu_baseline; with a process group the self-check and the `strong` object")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed pass computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline object")
     ap.add_argument("--math", choices=("f32", "f16x3"), default="f32",
                     help="arithmetic of the hidden layers for the HEADLINE numbers (default: exact fp32 MFMA)")
-    ap.add_argument("--no-alt-mode", action="store_true", help="skip the second timed run in the other math mode (alt_mode object)")
+    ap.add_argument("--no-alt-mode", action="store_true", help="--full: skip the second timed run in the other math mode (alt_mode object)")
     ap.add_argument("--dry-launch", action="store_true", help="print the rank environments the launcher would start, and exit")
     ap.add_argument("--strong-poses", type=int, default=N_POSES,
                     help="poses of the fixed problem of the `strong` object (multi-rank runs of workload 2; default BASELINE configs[2]'s 1015)")
     ap.add_argument("--strong-steps", type=int, default=3, help="timed passes of the `strong` object (each also run by rank 0 alone)")
-    ap.add_argument("--no-strong", action="store_true", help="multi-rank runs: skip the `strong` object")
-    ap.add_argument("--no-geometry", action="store_true", help="skip the geometry_kernels object (one-GPU runs: IPO / reprojection / selection "
-                                                                 "kernels timed on their own at 50 750 and 3 544 000 rows)")
+    ap.add_argument("--no-strong", action="store_true", help="--full, multi-rank runs: skip the `strong` object")
+    ap.add_argument("--no-geometry", action="store_true", help="--full: skip the geometry_kernels object (one-GPU runs: IPO / reprojection / "
+                                                                 "selection kernels timed on their own at 50 750 and 3 544 000 rows)")
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     # ZEDO_BENCH_FORCE_LAUNCH=1: go through the launcher with one rank too (how the launcher itself is exercised on a one-GPU box)
     if "WORLD_SIZE" not in os.environ and (a.gpus > 1 or a.dry_launch or os.environ.get("ZEDO_BENCH_FORCE_LAUNCH") == "1"):
@@ -540,7 +600,7 @@ def main():
     fail_rank = os.environ.get("ZEDO_BENCH_FAIL_RANK")      # test hook: that rank dies before the exchange step
 
     selfcheck = None
-    if use_dist:     # every run that has a process group checks N ranks == 1 rank before it times anything
+    if use_dist and a.full:     # every --full run that has a process group checks N ranks == 1 rank before it times anything
         selfcheck = multi_rank_selfcheck(zp, dist, weights, wl, dev, rank, world)
         if not selfcheck["ok"]:
             if rank == 0:
@@ -557,7 +617,7 @@ def main():
             torch.cuda.synchronize()
             os._exit(9)
         if wl["select"] == "gather":     # run/inference.py:233-236: every hypothesis of every pose, on every rank
-            return x, {"results": gather_row_shards(x, H * N_total)}
+            return x, T, {"results": gather_row_shards(x, H * N_total)}
         sel = pipe.select(x, gt_dev, row_offset=lo)
         out = {}
         for k, (best, idx) in sel.items():
@@ -566,7 +626,7 @@ def main():
             for k in ("p1", "p2"):
                 b = out[k][0].cpu().numpy()
                 out[k + "_actionwise"] = float(np.mean([b[actions == act].mean() for act in range(2, 17)]))
-        return x, out
+        return x, T, out
 
     def fence():
         torch.cuda.synchronize()
@@ -574,17 +634,18 @@ def main():
             zp.barrier()
             torch.cuda.synchronize()
 
-    def timed_run():
+    def timed_run(profile):
         for _ in range(a.warmup):
             one_pass()
         fence()
-        zh.profile_start(sample_every=37, max_samples=4096)   # prime stride: samples all four hidden layers evenly
+        if profile:
+            zh.profile_start(sample_every=37, max_samples=4096)   # prime stride: samples all four hidden layers evenly
         t0 = time.perf_counter()
         for _ in range(a.steps):
-            x, out = one_pass()
+            x, T, out = one_pass()
         fence()
         dt = time.perf_counter() - t0
-        prof = zh.profile_stop()
+        prof = zh.profile_stop() if profile else None
         per_rank = [dt]
         if use_dist:
             # every rank's own time of the K passes (between the two fences): value uses the MAX, the JSON shows all of them
@@ -595,7 +656,7 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device=dev)
             zp.all_reduce(tt, dist.ReduceOp.MAX)
             dt = float(tt.item())
-        return dt, prof, x, out, per_rank
+        return dt, prof, (x, T), out, per_rank
 
     def strong_run(math):
         """The `strong` object of a multi-rank run: ONE fixed problem - BASELINE configs[2]'s 1015 poses x H hypotheses - (a) on rank 0
@@ -660,19 +721,21 @@ def main():
                                            if proj else None)
         return res
 
-    dt, prof, x, out, per_rank = timed_run()
+    dt, prof, (x, T), out, per_rank = timed_run(profile=a.full)
+    if a.dump_outputs and rank == 0:      # the last timed pass, before anything else runs on the device
+        write_outputs(host_outputs(output_arrays(wl, x, T, out)), a.dump_outputs)
     # the other arithmetic mode of the hidden layers on the same problem (reported as alt_mode, never as `value`)
     alt = None
-    if not a.no_alt_mode and wl["select"] != "gather":
+    if a.full and not a.no_alt_mode and wl["select"] != "gather":
         alt_math = "f16x3" if a.math == "f32" else "f32"
         pipe.weights.set_math(alt_math)
-        dt2, prof2, _, out2, _ = timed_run()
+        dt2, prof2, _, out2, _ = timed_run(profile=True)
         pipe.weights.set_math(a.math)
         alt = dict(math=alt_math, dt=dt2, prof=prof2, out=out2)
 
     # multi-rank runs of workload 2: the fixed-problem (strong-scaling) object beside the weak-scaling headline
     strong = None
-    if use_dist and a.workload == 2 and not a.no_strong:
+    if a.full and use_dist and a.workload == 2 and not a.no_strong:
         strong = strong_run(a.math)
         if not a.no_alt_mode:
             strong["alt_mode"] = strong_run("f16x3" if a.math == "f32" else "f32")
@@ -683,14 +746,14 @@ def main():
             sys.exit(4)
 
     box_tf = box_ghz = box16 = None
-    if rank == 0:
+    if rank == 0 and a.full:
         box_tf, box_ghz = zh.probe_mfma_peak(200000)      # ~0.2 s, outside the timed region
         box16 = zh.probe_mfma_peak_f16(1000000)           # ~0.5 s of bare fp16 MFMAs: long enough for power management to settle
     if rank == 0:
         ms_per_step = dt / a.steps * 1e3
         poses_per_s = N_total * a.steps / dt
         row_steps_per_s = poses_per_s * H * S
-        hid = prof["hidden_dense"]
+        hid = prof["hidden_dense"] if prof else {"avg_ms": None}     # sampled kernel timings: --full only
         roof = None
         if hid["avg_ms"]:
             # zedo_oil_run walks the rows in chunks of at most ZEDO_CHUNK_ROWS (default 2^20) per launch
@@ -752,7 +815,7 @@ def main():
             "n_gpus": world, "rccl_ranks": (dist.get_world_size() if use_dist else 1),
             "dist_backend": (dist.get_backend() if use_dist else None), "devices_shared": os.environ.get("ZEDO_SHARE_DEVICE") == "1",
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 2),
-            "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "full": a.full,
             # exact fp32 throughout by default; --math f16x3: fp32 state / epilogues / thin layers, hidden layers as split-fp16 products
             "dtype": "f32" if a.math == "f32" else "f32 (hidden layers: split fp16 x3, fp32 accumulate)", "math": a.math, "data": "synthetic",
             "config": {"workload": (wl["name"] if stated else wl["name"] + " - NON-STATED size") +
@@ -769,14 +832,15 @@ def main():
                                 if a.math == "f32" else None),     # algorithmic fp32 flop against the fp32 peak: exact-fp32 mode only
             **quality,
             "roofline": roof,
-            "kernel_time_ms_sampled_avg": {k: (round(v["avg_ms"], 4) if v["avg_ms"] else None) for k, v in prof.items()},
+            "kernel_time_ms_sampled_avg": {k: (round(v["avg_ms"], 4) if v["avg_ms"] else None) for k, v in prof.items()} if prof else None,
             # self-check (tests/test_rccl_gpu.py asserts it): the sampled per-class kernel times, each less the cost of an
             # empty event bracket on the same stream (event_bracket_ms; kernel_time_ms_sampled_raw keeps the bracketed
             # values), scaled to ALL launches of the timed region, per OIL iteration - against the wall time per OIL
             # iteration, which also contains the IPO, the selection and the gaps between launches: sum <= wall
-            "kernel_time_ms_sampled_raw": {k: (round(v["avg_ms_raw"], 4) if v["avg_ms_raw"] else None) for k, v in prof.items()},
-            "event_bracket_ms": round(prof["hidden_dense"].get("bracket_ms") or 0.0, 5),
-            "sum_kernel_ms_per_oil_step": round(sum(v["launches"] * v["avg_ms"] for v in prof.values() if v["avg_ms"]) / (a.steps * S), 5),
+            "kernel_time_ms_sampled_raw": {k: (round(v["avg_ms_raw"], 4) if v["avg_ms_raw"] else None) for k, v in prof.items()} if prof else None,
+            "event_bracket_ms": round(prof["hidden_dense"].get("bracket_ms") or 0.0, 5) if prof else None,
+            "sum_kernel_ms_per_oil_step": (round(sum(v["launches"] * v["avg_ms"] for v in prof.values() if v["avg_ms"]) / (a.steps * S), 5)
+                                           if prof else None),
             "wall_ms_per_oil_step": round(dt * 1e3 / (a.steps * S), 5),
             # N ranks == 1 rank, bit for bit, on the live transport, checked before the timed region (None without a process group)
             "multi_rank_selfcheck": selfcheck,
@@ -787,7 +851,7 @@ def main():
                             "argmin": int(np.argmin(per_rank)), "argmax": int(np.argmax(per_rank)),
                             "all": [round(v / a.steps, 5) for v in per_rank]},
         }
-        if scaling == "strong" and a.workload == 2 and S == S_OIL and H == N_HYPO:
+        if a.full and scaling == "strong" and a.workload == 2 and S == S_OIL and H == N_HYPO:
             # strong scaling of configs[2]: what one GPU measured for a shard of this size (no communication) against this run
             proj = strong_projection(rows, a.math)
             line["efficiency_vs_projection"] = (dict(projected_ms_per_step=proj[1], projected_rows_per_rank=proj[0],
@@ -817,8 +881,8 @@ def main():
         else:
             line["alt_mode"] = None
         # GB/s of the HBM / latency-bound kernels, at configs[2]'s rows and at configs[3]'s per-GPU shard
-        line["geometry_kernels"] = geometry_kernels(zh, dev) if (world == 1 and not a.no_geometry) else None
-        if world == 1 and not a.no_cpu_baseline:
+        line["geometry_kernels"] = geometry_kernels(zh, dev) if (a.full and world == 1 and not a.no_geometry) else None
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(weights, None, 2024)
         else:
             line["cpu_baseline"] = None

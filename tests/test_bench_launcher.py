@@ -191,3 +191,32 @@ def test_ulp_perturbation_and_tile_split_helpers():
     for rows in (1, 64, 886, 2048, 2049, 6350, 8192, 12700, 20000, 50750, 1 << 20):
         sp = bench.f16x3_tile_split(rows)
         assert sum(r for _, _, r in sp) == -(-rows // 64) * 64 and all(r % bm == 0 for bm, _, r in sp)
+
+
+def test_dump_outputs_are_float_arrays_a_fixed_sample_and_capped(tmp_path):
+    """bench.py --dump-outputs: what a caller of the timed path receives, as float32 / float64 arrays; an output of more than
+    DUMP_ROWS rows is the same seeded sample of its rows in every run (indices in <name>_rows); all files stay within DUMP_BYTES."""
+    sys.path.insert(0, ROOT)
+    import bench
+    n, N = bench.DUMP_ROWS + 5, 7
+    x = torch.arange(n * 51, dtype=torch.float32).reshape(n, 17, 3)
+    T = torch.arange(n * 3, dtype=torch.float32).reshape(n, 3)
+    out = {k: (torch.rand(N, dtype=torch.float64), torch.arange(N, dtype=torch.int32) % 3) for k in ("p1", "p2")}
+    out.update(p1_actionwise=0.25, p2_actionwise=0.125)
+    a, b = (bench.host_outputs(bench.output_arrays(bench.WORKLOADS[3], x, T, out)) for _ in range(2))
+    assert set(a) == {"x", "x_rows", "T", "T_rows", "p1_best", "p1_hypothesis", "p2_best", "p2_hypothesis", "p1_actionwise", "p2_actionwise"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    rows = a["x_rows"].astype(np.int64)
+    assert a["x"].shape == (bench.DUMP_ROWS, 17, 3) and len(np.unique(rows)) == bench.DUMP_ROWS and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["x"], x.numpy()[rows]) and np.array_equal(a["T"], T.numpy()[rows])
+    assert np.array_equal(a["p1_hypothesis"], out["p1"][1].numpy()) and a["p2_actionwise"].tolist() == [0.125]
+    bench.write_outputs(a, str(tmp_path / "d"))
+    for k, v in a.items():
+        got = np.load(tmp_path / "d" / (k + ".npy"))
+        assert got.dtype == v.dtype and np.array_equal(got, v)
+    g = bench.host_outputs(bench.output_arrays(bench.WORKLOADS[4], x, T, {"results": x[:10]}))
+    assert set(g) == {"results"} and g["results"].shape == (10, 17, 3)
+    with pytest.raises(SystemExit):
+        bench.write_outputs({"big": np.zeros(bench.DUMP_BYTES // 8 + 1)}, str(tmp_path / "e"))
+    assert not (tmp_path / "e").exists()

@@ -49,7 +49,7 @@ def a_hypo(args):
 def _bench(args, share, extra_env=None, ok=True):
     e = _env(share)
     e.update(extra_env or {})
-    r = subprocess.run([sys.executable, BENCH] + args + ["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-alt-mode",
+    r = subprocess.run([sys.executable, BENCH] + args + ["--full", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-alt-mode",
                                                          "--strong-poses", "61", "--strong-steps", "2"],
                        env=e, cwd=ROOT, capture_output=True, text=True, timeout=900)
     if not ok:

@@ -42,14 +42,14 @@ def _run(cmd, dist, cwd=ROOT):
 
 
 def test_bench_exchange_step_on_rccl_is_bit_identical():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--oil", "20", "--poses", "64",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0", "--oil", "20", "--poses", "64",
            "--hypo", "5", "--no-cpu-baseline", "--strong-poses", "96", "--strong-steps", "2"]
     lines = {}
     for dist in (False, True):
         out = _run(cmd, dist)
         lines[dist] = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     a, b = lines[False], lines[True]
-    # the bench contract: one JSON line with the driver's keys, the roofline object and the cpu_baseline slot
+    # the bench contract (--full): one JSON line with the driver's keys, the roofline object and the cpu_baseline slot
     for k, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                    ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str),
                    ("config", dict), ("roofline", dict)):
