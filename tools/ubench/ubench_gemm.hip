@@ -13,7 +13,7 @@ using namespace zedo;
 
 // the split-K reduce of post_dense lives in zedo_geom.hip; this harness never reaches it (LayerArgs::scratch stays null)
 namespace zedo {
-hipError_t launch_post_reduce(float *, const float *, const float *, float, float, int, float *, const float *, float *, int, int, int, int, long long, hipStream_t) {
+hipError_t launch_post_reduce(float *, const float *, const float *, float, float, int, float *, const ReprojArgs &, int, hipStream_t) {
     return hipErrorNotSupported;
 }
 }

@@ -493,15 +493,6 @@ extern "C" int zedo_reproj_grad(const float *d_x, const float *d_geom, float *d_
     return ZEDO_OK;
 }
 
-// The six dense layers of one score-network evaluation on Bp padded rows (model.py:264-291), ending either in
-// eps -> xpad (EPI_BIAS, for zedo_score_eps) or in the SDE update of xpad (EPI_SDE).
-struct NextReproj {          // reprojection of the next loop iteration, fused into the SDE epilogue (may be all-null)
-    const float *geom = nullptr;
-    float *T = nullptr;
-    int solve = 0, B = 0, N = 0;
-    long long row0 = 0;
-};
-
 // The six dense layers of one score-network evaluation (model.py:264-291) as three pieces - pre_dense, the four hidden layers,
 // post_dense (round 6 measured post_dense of iteration i and pre_dense of iteration i + 1 in ONE launch: bit-identical, slower in both
 // math modes, not adopted - profiles/seam_r06.txt).  h / h1: activations [rows][1024] fp32 (exact-fp32 mode) or split-fp16 planes
@@ -529,25 +520,23 @@ struct Net {
         b.bias = tb; b.gamma = w->gamma[0]; b.beta = w->beta[0]; b.out = h; b.out_f32 = 0;
         return b;
     }
-    LayerArgs post_args(bool sde, float sa, float sc, float *eps_out, const NextReproj &nr) const {
+    LayerArgs post_args(bool sde, float sa, float sc, float *eps_out, const ReprojArgs &nr) const {
         LayerArgs a{};
         a.Mp = Bp; a.X = h; a.ldx = HID; a.W = w->W_post; a.ldw = HID; a.K = HID; a.N = XLD; a.bias = w->b_post; a.ldo = XLD;
         a.scratch = h1 + (size_t)Bp * XLD;      // h1 is free here ([Bp][XLD] of it may hold eps_out): K-quarter sums of small batches
         if (sde) {
-            a.out = xpad; a.sde_a = sa; a.sde_c = sc;
-            a.rp_geom = nr.geom; a.rp_T = nr.T; a.rp_solve = nr.solve; a.rp_B = nr.B; a.rp_N = nr.N; a.rp_row0 = nr.row0;
+            a.out = xpad; a.sde_a = sa; a.sde_c = sc; a.rp = nr;
         } else {
             a.out = eps_out;
         }
         return a;
     }
-    Layer16Args post_args16(bool sde, float sa, float sc, float *eps_out, const NextReproj &nr) const {
+    Layer16Args post_args16(bool sde, float sa, float sc, float *eps_out, const ReprojArgs &nr) const {
         Layer16Args b{};
         b.K = HID; b.N = XLD; b.Mp = Bp; b.ldx = ld; b.X = reinterpret_cast<const uint16_t *>(h);
         b.W = W_post16(); b.unscale = w->unscale[5]; b.bias = w->b_post;
         if (sde) {
-            b.xio = xpad; b.sde_a = sa; b.sde_c = sc;
-            b.rp_geom = nr.geom; b.rp_T = nr.T; b.rp_solve = nr.solve; b.rp_B = nr.B; b.rp_N = nr.N; b.rp_row0 = nr.row0;
+            b.xio = xpad; b.sde_a = sa; b.sde_c = sc; b.rp = nr;
         } else {
             b.out = eps_out;
         }
@@ -592,12 +581,12 @@ struct Net {
         return e;
     }
     // post_dense, ending either in eps -> eps_out (EPI_BIAS, zedo_score_eps) or in the SDE update of xpad (EPI_SDE) [+ nr]
-    hipError_t post(bool sde, float sa, float sc, float *eps_out, const NextReproj &nr) const {
+    hipError_t post(bool sde, float sa, float sc, float *eps_out, const ReprojArgs &nr) const {
         ProfScope ps(ZEDO_PROF_POST, st);
         if (f16()) return launch_layer16(post_args16(sde, sa, sc, eps_out, nr), sde ? EPI_SDE : EPI_BIAS, st);
         return launch_layer(post_args(sde, sa, sc, eps_out, nr), sde ? EPI_SDE : EPI_BIAS, st);
     }
-    hipError_t all(const float *tb, bool sde, float sa, float sc, float *eps_out, const NextReproj &nr = NextReproj()) const {
+    hipError_t all(const float *tb, bool sde, float sa, float sc, float *eps_out, const ReprojArgs &nr = ReprojArgs{}) const {
         hipError_t e = pre(tb);
         if (e == hipSuccess) e = hidden(tb);
         if (e == hipSuccess) e = post(sde, sa, sc, eps_out, nr);
@@ -665,17 +654,13 @@ extern "C" int zedo_oil_run(const zedo_weights_t *w, const zedo_schedule_t *s, f
         // (ZEDO_UNFUSED_REPROJ=1: one launch per iteration, the A/B and parity reference)
         static const bool unfused = getenv("ZEDO_UNFUSED_REPROJ") != nullptr;
         const Net net{w, k.xpad, k.h, k.h1, Bp, (int)k.rows, st};
+        auto reproj = [&](int it) { return ReprojArgs{d_geom, d_T + r0 * 3, it >= switch_step, Bc, N, row_offset + (long long)r0}; };
         for (int i = step_begin; i < step_end; ++i) {
             if (i == step_begin || unfused) {
                 ProfScope ps(ZEDO_PROF_REPROJ, st);
-                HIPCHK(launch_reproj_step_padded(k.xpad, d_geom, d_T + r0 * 3, i >= switch_step, Bc, N,
-                                                 row_offset + (long long)r0, st));
+                HIPCHK(launch_reproj_step_padded(k.xpad, reproj(i), st));
             }
-            NextReproj nr;
-            if (i + 1 < step_end && !unfused) {
-                nr.geom = d_geom; nr.T = d_T + r0 * 3; nr.solve = (i + 1) >= switch_step; nr.B = Bc; nr.N = N;
-                nr.row0 = row_offset + (long long)r0;
-            }
+            const ReprojArgs nr = (i + 1 < step_end && !unfused) ? reproj(i + 1) : ReprojArgs{};
             // sampling_fn(...) (run/opt_main.py:210-218) -> x = a_i x + c_i eps(x, t_i)  [+ the next correction]
             HIPCHK(net.all(s->d_tbias + (size_t)i * NLAYER * HID, true, s->a[i], s->c[i], nullptr, nr));
         }

@@ -97,10 +97,8 @@ __device__ __forceinline__ void layer_tile(const LayerArgs &a, const int m0, con
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *As = smem;                    // [NBUF][BN][32]  W tile, chunk-swizzled
     float *Bs = smem + NBUF * BN * BK;   // [NBUF][BM][32]  X tile, chunk-swizzled
-    // the epilogue stages WM*32 rows x BN channels in the (then free) tile ring; where that is larger than the ring
-    // itself (64-row tiles on a 16-deep ring) the parameter block simply sits behind the larger of the two
-    constexpr int RING_F = NBUF * (BM + BN) * BK, STAGE_F = WM * 32 * BN, BODY_F = RING_F > STAGE_F ? RING_F : STAGE_F;
-    float *Ps = smem + BODY_F;   // [3][BN]  bias | gamma | beta of this tile's channels (epilogue)
+    // the epilogue stages WM*32 rows x BN channels in the (then free) tile ring
+    float *Ps = smem + layer_tile_lds(BM, BN, WM, NBUF, BK) / sizeof(float) - 3 * BN;   // [3][BN]  bias | gamma | beta of this tile's channels
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -290,7 +288,6 @@ __device__ __forceinline__ void layer_tile(const LayerArgs &a, const int m0, con
         constexpr int CPRW = BN / 4;         // 16-byte chunks per stage row
         constexpr int RPI = 64 / CPRW;       // stage rows filled by one DMA instruction
         static_assert(CPRW <= 64 && 64 % CPRW == 0 && SR % (RPI * NW) == 0 && (SR * CPRW) % NT == 0, "stage shape");
-        static_assert(SR * BN == STAGE_F, "stage size");
         constexpr bool HAS_RES = (EPI == EPI_GN_SILU_RES || EPI == EPI_SDE);
         float *S = smem;
         float *obase = a.out + (size_t)out_m0 * a.ldo + n0;
@@ -346,32 +343,12 @@ __device__ __forceinline__ void layer_tile(const LayerArgs &a, const int m0, con
             __syncthreads();
             if constexpr (EPI == EPI_SDE && BN == XLD) {
                 // reprojection correction of the next iteration on the updated rows, one lane per row, straight from the
-                // stage (chunk c of stage row sr sits at position c ^ (sr & 7)); same source as reproj_step_kernel
-                if (a.rp_geom != nullptr) {
-                    constexpr int NV = (17 * 3 + 3) / 4;
+                // stage (chunk c of stage row sr sits at position c ^ (sr & 7)): ZEDO_REPROJ_STAGED_ROW
+                if (a.rp.geom != nullptr) {
                     if (tid < SR) {
                         const int sr = tid;
                         const int b = m0 + (sr >> 5) * TM + j * 32 + (sr & 31);
-                        if (b < a.rp_B) {
-                            float xr[NV * 4], gr[17 * 3], Tr[3];
-                            float *srow = S + sr * BN;
-#pragma unroll
-                            for (int v = 0; v < NV; ++v) {
-                                const f32x4 t = *reinterpret_cast<const f32x4 *>(srow + ((v ^ (sr & 7)) << 2));
-                                xr[4 * v] = t[0]; xr[4 * v + 1] = t[1]; xr[4 * v + 2] = t[2]; xr[4 * v + 3] = t[3];
-                            }
-                            Tr[0] = a.rp_T[(size_t)b * 3]; Tr[1] = a.rp_T[(size_t)b * 3 + 1]; Tr[2] = a.rp_T[(size_t)b * 3 + 2];
-                            const int n = (int)((a.rp_row0 + b) % a.rp_N);
-                            reproj_row<17>(xr, a.rp_geom + (size_t)n * 17 * GEOM_F, Tr, a.rp_solve != 0, gr);
-                            if (a.rp_solve) { a.rp_T[(size_t)b * 3] = Tr[0]; a.rp_T[(size_t)b * 3 + 1] = Tr[1]; a.rp_T[(size_t)b * 3 + 2] = Tr[2]; }
-#pragma unroll
-                            for (int c = 0; c < 17 * 3; ++c) xr[c] += gr[c];
-#pragma unroll
-                            for (int v = 0; v < NV; ++v) {
-                                const f32x4 t = {xr[4 * v], xr[4 * v + 1], xr[4 * v + 2], xr[4 * v + 3]};
-                                *reinterpret_cast<f32x4 *>(srow + ((v ^ (sr & 7)) << 2)) = t;
-                            }
-                        }
+                        if (b < a.rp.B) ZEDO_REPROJ_STAGED_ROW(17, S + sr * BN, sr & 7, b, a.rp);
                     }
                     __syncthreads();
                 }
@@ -396,10 +373,7 @@ __device__ __forceinline__ void layer_tile(const LayerArgs &a, const int m0, con
 // One tile per workgroup: block index -> tile.
 template <int BM, int BN, int WM, int WN, int EPI, int NBUF = 2, int BK = 32, int SCHED = 0, int KSKIP = 0, int KQ = 1>
 __device__ __forceinline__ void layer_body(const LayerArgs &a, const int bid, const int nwg) {
-    // XCD-aware, bijective block -> tile map: the hardware places block b on XCD b % 8; give every
-    // XCD a contiguous range of tiles so that the column tiles of one row tile share one L2.
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int lid = xcd_tile(bid, nwg);
     const int ncol = a.N / BN;
     if constexpr (EPI == EPI_PARTIAL) {
         // one K quarter per workgroup: block lid -> (row tile lid / 4, quarter lid % 4); a.K is the quarter's depth;
@@ -435,10 +409,7 @@ constexpr int PAIR_BK = 16, PLAIN_WGS = 3, PLAIN_WPE = 2;
 template <int EPI, int W8>
 // (a waves-per-SIMD bound >= 2 also makes hipcc keep the accumulators in VGPRs: no v_accvgpr_read/write, -0.6 %)
 __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 6 : PLAIN_WGS) void layer_pair_kernel(LayerArgs big, LayerArgs small, int nbig) {
-    // diagnostic: the shader clock this launch really runs at (power management differs box to box and with the load)
-    long long c0 = 0, w0 = 0;
-    const bool probe = big.clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0;
-    if (probe) { c0 = clock64(); w0 = wall_clock64(); }
+    const ClockProbe probe(big.clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0);
     if constexpr (W8) {
         if ((int)blockIdx.x < nbig) layer_body<128, 128, 2, 4, EPI, 2, PAIR_BK, SCHED_BK16>(big, blockIdx.x, nbig);
         else layer_body<64, 128, 2, 4, EPI, 2, 32, SCHED_SMALL>(small, (int)blockIdx.x - nbig, (int)gridDim.x - nbig);
@@ -449,7 +420,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 6 : PLAIN_WGS) void layer_pair
         // per pass, 50 750 rows: 3107.8 -> 3099.9 ms, A/B/A/B on one box; bit-identical)
         else layer_body<64, 64, 2, 2, EPI, 2, 32, SCHED_SMALL>(small, (int)blockIdx.x - nbig, (int)gridDim.x - nbig);
     }
-    if (probe) { big.clk[0] = clock64() - c0; big.clk[1] = wall_clock64() - w0; }
+    probe.stop(big.clk);
 }
 
 // (per-device launch state: allow_lds / num_cus of zedo_internal.h)
@@ -457,9 +428,8 @@ __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 6 : PLAIN_WGS) void layer_pair
 template <int EPI, int W8>
 static hipError_t launch_pair(const LayerArgs &big, const LayerArgs &small, hipStream_t st) {
     constexpr int SM = 64, SN = W8 ? 128 : 64;             // remainder tile rows / columns
-    constexpr size_t lds_big = ((size_t)2 * (128 + 128) * PAIR_BK + 3 * 128) * sizeof(float);
-    constexpr size_t lds_small = ((size_t)2 * (SM + SN) * 32 + 3 * SN) * sizeof(float);
-    constexpr size_t lds = lds_big > lds_small ? lds_big : lds_small;
+    constexpr size_t lds_big = layer_tile_lds(128, 128, 2, 2, PAIR_BK), lds_small = layer_tile_lds(SM, SN, 2, 2, 32);
+    constexpr size_t lds = lds_big > lds_small ? lds_big : lds_small;      // each tile shape finds its parameter block in ITS footprint
     if (big.Mp % 128 || small.Mp % SM || big.N % 128 || big.K % 64) return hipErrorInvalidValue;
     auto kern = layer_pair_kernel<EPI, W8>;
     static std::atomic<bool> attr_done[MAX_DEVICES];      // per instantiation and per device
@@ -471,8 +441,7 @@ static hipError_t launch_pair(const LayerArgs &big, const LayerArgs &small, hipS
 
 template <int BM, int BN, int WM, int WN, int EPI, int NBUF = 2, int BK = 32, int SCHED = 0, int WPE = 1, int KSKIP = 0, int KQ = 1>
 static hipError_t launch_cfg(const LayerArgs &a, hipStream_t st) {
-    constexpr size_t ring_f = (size_t)NBUF * (BM + BN) * BK, stage_f = (size_t)WM * 32 * BN;
-    constexpr size_t lds = ((ring_f > stage_f ? ring_f : stage_f) + 3 * BN) * sizeof(float);
+    constexpr size_t lds = layer_tile_lds(BM, BN, WM, NBUF, BK);
     if (a.Mp <= 0 || a.Mp % BM || a.N % BN || a.K % (BK * NBUF * KQ)) return hipErrorInvalidValue;
     if (KSKIP && a.K != BK * NBUF) return hipErrorInvalidValue;
     auto kern = layer_kernel<BM, BN, WM, WN, EPI, NBUF, BK, SCHED, WPE, KSKIP, KQ>;
@@ -587,7 +556,7 @@ hipError_t launch_layer(const LayerArgs &a, int epilogue, hipStream_t st) {
             if (hipError_t e = launch_cfg<32, 64, 1, 2, EPI_PARTIAL, 4, 32, SCHED_THIN>(p, st); e != hipSuccess) return e;
             const bool sde = epilogue == EPI_SDE;
             return launch_post_reduce(sde ? a.out : nullptr, a.scratch, a.bias, a.sde_a, a.sde_c, sde ? 1 : 0, sde ? nullptr : a.out,
-                                      sde ? a.rp_geom : nullptr, a.rp_T, a.rp_solve, a.rp_B, a.Mp, a.rp_N, a.rp_row0, st);
+                                      sde ? a.rp : ReprojArgs{}, a.Mp, st);
         }
         const bool small = a.Mp <= 8192 && a.Mp % 32 == 0;
         switch (epilogue) {

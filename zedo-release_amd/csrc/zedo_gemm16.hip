@@ -90,10 +90,9 @@ __device__ __forceinline__ void layer16_tile(const Layer16Args &a, const int m0,
     constexpr int SLOT = (BN + BM) * RB;                              // one ring slot: [BN rows of W][BM rows of X]
     constexpr int SR = WM * 32;                                       // epilogue stage rows per phase
     static_assert(NBUF >= 2 && (NBUF - 1) * IPW <= 63, "ring depth (6-bit vmcnt)");
-    constexpr int RING_B = NBUF * SLOT, STAGE_B = SR * BN * 4, BODY_B = RING_B > STAGE_B ? RING_B : STAGE_B;
 
     extern __shared__ __attribute__((aligned(16))) char smem16[];
-    float *Ps = reinterpret_cast<float *>(smem16 + BODY_B);           // [3][BN] bias | gamma | beta
+    float *Ps = reinterpret_cast<float *>(smem16 + layer16_tile_lds(BM, BN, WM, NBUF)) - 3 * BN;   // [3][BN] bias | gamma | beta
 
     TL_MARK(tl0)
     const int tid = threadIdx.x, lane = tid & 63;
@@ -389,32 +388,12 @@ __device__ __forceinline__ void layer16_tile(const Layer16Args &a, const int m0,
                 }
                 __syncthreads();
                 // reprojection correction of the next iteration on the updated rows, one lane per row, straight from the
-                // stage; same source (reproj_row) as the exact-fp32 path and the stand-alone kernel
-                if (a.rp_geom != nullptr) {
-                    constexpr int NV = (17 * 3 + 3) / 4;
+                // stage; the same source (ZEDO_REPROJ_STAGED_ROW) as the exact-fp32 path and the geometry kernels
+                if (a.rp.geom != nullptr) {
                     if (tid < SR) {
                         const int sr = tid;
                         const int b = m0 + (sr >> 5) * TM + j * 32 + (sr & 31);
-                        if (b < a.rp_B) {
-                            float xr[NV * 4], gr[17 * 3], Tr[3];
-                            float *srow = S + sr * BN;
-#pragma unroll
-                            for (int v = 0; v < NV; ++v) {
-                                const f32x4 t = *reinterpret_cast<const f32x4 *>(srow + ((v ^ (sr & 7)) << 2));
-                                xr[4 * v] = t[0]; xr[4 * v + 1] = t[1]; xr[4 * v + 2] = t[2]; xr[4 * v + 3] = t[3];
-                            }
-                            Tr[0] = a.rp_T[(size_t)b * 3]; Tr[1] = a.rp_T[(size_t)b * 3 + 1]; Tr[2] = a.rp_T[(size_t)b * 3 + 2];
-                            const int n = (int)((a.rp_row0 + b) % a.rp_N);
-                            reproj_row<17>(xr, a.rp_geom + (size_t)n * 17 * GEOM_F, Tr, a.rp_solve != 0, gr);
-                            if (a.rp_solve) { a.rp_T[(size_t)b * 3] = Tr[0]; a.rp_T[(size_t)b * 3 + 1] = Tr[1]; a.rp_T[(size_t)b * 3 + 2] = Tr[2]; }
-#pragma unroll
-                            for (int c = 0; c < 17 * 3; ++c) xr[c] += gr[c];
-#pragma unroll
-                            for (int v = 0; v < NV; ++v) {
-                                const f32x4 t = {xr[4 * v], xr[4 * v + 1], xr[4 * v + 2], xr[4 * v + 3]};
-                                *reinterpret_cast<f32x4 *>(srow + ((v ^ (sr & 7)) << 2)) = t;
-                            }
-                        }
+                        if (b < a.rp.B) ZEDO_REPROJ_STAGED_ROW(17, S + sr * BN, sr & 7, b, a.rp);
                     }
                     __syncthreads();
                 }
@@ -431,12 +410,10 @@ __device__ __forceinline__ void layer16_tile(const Layer16Args &a, const int m0,
     TL_FLUSH(tl0, tl1, tl2)
 }
 
-// block -> tile, XCD aware (the hardware places block b on XCD b % 8): every XCD gets a contiguous range of tiles so that
-// the column tiles of one row tile share one L2 (same map as zedo_gemm.hip)
+// block -> tile: xcd_tile (zedo_tile.h), as in zedo_gemm.hip
 template <int BM, int BN, int WM, int WN, int EPI, int NBUF, int XF32 = 0>
 __device__ __forceinline__ void layer16_body(const Layer16Args &a, const int bid, const int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int lid = xcd_tile(bid, nwg);
     const int ncol = a.N / BN;
     layer16_tile<BM, BN, WM, WN, EPI, NBUF, XF32>(a, (lid / ncol) * BM, (lid % ncol) * BN);
 }
@@ -457,12 +434,10 @@ constexpr int BIG_NBUF16 = 3;     // ring depth of the 128 x 256 tile: 3 x 24 KB
 constexpr int MID_NBUF16 = 2;     // ring depth of the 128 x 128 tile (batches of 2 048 - 8 192 rows, three workgroups per CU)
 template <int EPI, int BIG_N>
 __global__ __launch_bounds__(256, BIG_N == 256 ? 2 : 3) void layer16_pair_kernel(Layer16Args big, Layer16Args small, int nbig) {
-    long long c0 = 0, w0 = 0;
-    const bool probe = big.clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0;
-    if (probe) { c0 = clock64(); w0 = wall_clock64(); }
+    const ClockProbe probe(big.clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0);
     if ((int)blockIdx.x < nbig) layer16_body<BIG_M, BIG_N, 2, 2, EPI, BIG_N == 256 ? BIG_NBUF16 : MID_NBUF16>(big, blockIdx.x, nbig);
     else layer16_body<64, 64, 2, 2, EPI, 4>(small, (int)blockIdx.x - nbig, (int)gridDim.x - nbig);
-    if (probe) { big.clk[0] = clock64() - c0; big.clk[1] = wall_clock64() - w0; }
+    probe.stop(big.clk);
 }
 
 // The thin layers: pre_dense (51 -> 1024: 64x128 tiles, the four k blocks resident, X split from the fp32 pose state) and
@@ -500,11 +475,8 @@ static hipError_t launch_thin16(K kern, std::atomic<bool> *attr_done, size_t lds
 
 template <int EPI, int BIG_N>
 static hipError_t launch_pair16(const Layer16Args &big, const Layer16Args &small, hipStream_t st) {
-    constexpr size_t ring_big = (BIG_N == 256 ? BIG_NBUF16 : MID_NBUF16) * (BIG_M + BIG_N) * 64, stage_big = (size_t)64 * BIG_N * 4, par_big = 3 * BIG_N * sizeof(float);
-    constexpr size_t ring_small = 4 * (64 + 64) * 64, stage_small = (size_t)64 * 64 * 4, par_small = 3 * 64 * sizeof(float);
-    constexpr size_t lds_big = (ring_big > stage_big ? ring_big : stage_big) + par_big;
-    constexpr size_t lds_small = (ring_small > stage_small ? ring_small : stage_small) + par_small;
-    constexpr size_t lds = lds_big > lds_small ? lds_big : lds_small;      // each tile shape finds its parameter block behind ITS body
+    constexpr size_t lds_big = layer16_tile_lds(BIG_M, BIG_N, 2, BIG_N == 256 ? BIG_NBUF16 : MID_NBUF16), lds_small = layer16_tile_lds(64, 64, 2, 4);
+    constexpr size_t lds = lds_big > lds_small ? lds_big : lds_small;      // each tile shape finds its parameter block in ITS footprint
     auto kern = layer16_pair_kernel<EPI, BIG_N>;
     static std::atomic<bool> attr_done[MAX_DEVICES16];
     if (hipError_t e = allow_lds(reinterpret_cast<const void *>(kern), lds, attr_done); e != hipSuccess) return e;
@@ -533,12 +505,11 @@ hipError_t launch_layer16(const Layer16Args &a, int epilogue, hipStream_t st) {
     if (a.Xf32) {               // pre_dense
         if (a.K != XLD || a.N % 128 || epilogue != EPI_GN_SILU || !a.out) return hipErrorInvalidValue;
         static std::atomic<bool> done[MAX_DEVICES16];
-        constexpr size_t lds = (size_t)4 * (128 + 64) * 64 + 3 * 128 * sizeof(float);
-        return launch_thin16(layer16_pre_kernel<EPI_GN_SILU>, done, lds, (a.Mp / 64) * (a.N / 128), a, st);
+        return launch_thin16(layer16_pre_kernel<EPI_GN_SILU>, done, layer16_tile_lds(64, 128, 2, 4), (a.Mp / 64) * (a.N / 128), a, st);
     }
     if (a.N == XLD) {           // post_dense
         if (!a.X) return hipErrorInvalidValue;
-        constexpr size_t lds = (size_t)8 * (64 + 64) * 64 + 3 * 64 * sizeof(float);
+        constexpr size_t lds = layer16_tile_lds(64, 64, 2, 8);
         if (epilogue == EPI_SDE && a.xio) {
             static std::atomic<bool> done[MAX_DEVICES16];
             return launch_thin16(layer16_post_kernel<EPI_SDE>, done, lds, a.Mp / 64, a, st);
@@ -552,7 +523,7 @@ hipError_t launch_layer16(const Layer16Args &a, int epilogue, hipStream_t st) {
     if (a.N % 256 || !a.X || !a.out) return hipErrorInvalidValue;
     if (epilogue == EPI_GN_SILU_RES && !a.res) return hipErrorInvalidValue;
     if (a.Mp <= 2048) {
-        constexpr size_t lds = (size_t)4 * (64 + 64) * 64 + 3 * 64 * sizeof(float);
+        constexpr size_t lds = layer16_tile_lds(64, 64, 2, 4);
         const int grid = (a.Mp / 64) * (a.N / 64);
         if (epilogue == EPI_GN_SILU) {
             static std::atomic<bool> done[MAX_DEVICES16];

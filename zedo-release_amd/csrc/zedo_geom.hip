@@ -117,8 +117,8 @@ hipError_t launch_reproj_degenerate(const float *geom, int N, int J, int *d_coun
     return hipGetLastError();
 }
 
-// reproj_row<J> (gradient_field_gen for one pose row held in registers) lives in zedo_internal.h: the fused
-// post_dense + reprojection + pre_dense kernel of zedo_gemm.hip runs the same source.
+// reproj_row<J> (gradient_field_gen for one pose row held in registers) and ZEDO_REPROJ_STAGED_ROW live in zedo_internal.h:
+// the fused post_dense epilogues of zedo_gemm.hip / zedo_gemm16.hip run the same source.
 
 // Standalone surface op: x [B][J*3] -> g [B][J*3] (+T).  128 rows per workgroup, tile staged through
 // LDS with unit-stride global accesses; odd row stride (51) keeps the per-lane row reads conflict free.
@@ -161,49 +161,39 @@ hipError_t launch_reproj_grad(const float *x, const float *geom, float *T, int s
     return hipGetLastError();
 }
 
-// Fused-loop variant on the padded state: xpad[row][64] += g, in place.  64 rows (one wavefront) per workgroup:
-// the 16 KB tile moves as 16-byte, fully coalesced accesses through LDS (row stride 68 floats so
-// that each lane's ds_read_b128 / ds_write_b128 of its own row is bank-conflict free).
+// The padded state tile [BATCH_PAD][XLD] of one 64-lane workgroup <-> LDS rows of TILE_LD floats, as 16-byte fully coalesced
+// accesses (row stride 68 floats so that each lane's ds_read_b128 / ds_write_b128 of its own row is bank-conflict free).
+constexpr int TILE_LD = XLD + 4;
+__device__ __forceinline__ void tile_to_lds(float *sx, const float *base, const int tid) {
+#pragma unroll
+    for (int it = 0; it < XLD / 4; ++it) {
+        const int idx = it * BATCH_PAD + tid, r = idx >> 4, c4 = idx & 15;
+        *reinterpret_cast<f32x4 *>(sx + r * TILE_LD + c4 * 4) = *reinterpret_cast<const f32x4 *>(base + (size_t)idx * 4);
+    }
+}
+__device__ __forceinline__ void tile_from_lds(float *base, const float *sx, const int tid) {
+#pragma unroll
+    for (int it = 0; it < XLD / 4; ++it) {
+        const int idx = it * BATCH_PAD + tid, r = idx >> 4, c4 = idx & 15;
+        *reinterpret_cast<f32x4 *>(base + (size_t)idx * 4) = *reinterpret_cast<const f32x4 *>(sx + r * TILE_LD + c4 * 4);
+    }
+}
+
+// Fused-loop variant on the padded state: xpad[row][64] += g, in place.  64 rows (one wavefront) per workgroup, the tile
+// staged through LDS.
 template <int J>
 __global__ __launch_bounds__(64) void reproj_step_kernel(float *__restrict__ xpad, const float *__restrict__ geom,
                                                          float *__restrict__ T, int solve, int B, int N,
                                                          long long row_offset) {
-    constexpr int D = J * 3, R = BATCH_PAD, LD = XLD + 4, NV = (D + 3) / 4;
-    __shared__ __attribute__((aligned(16))) float sx[R * LD];
-    const int row0 = blockIdx.x * R, tid = threadIdx.x;
+    __shared__ __attribute__((aligned(16))) float sx[BATCH_PAD * TILE_LD];
+    const int row0 = blockIdx.x * BATCH_PAD, tid = threadIdx.x;
     float *base = xpad + (size_t)row0 * XLD;  // Bp is a multiple of BATCH_PAD: the whole tile exists
-#pragma unroll
-    for (int it = 0; it < XLD / 4; ++it) {
-        const int idx = it * R + tid, r = idx >> 4, c4 = idx & 15;
-        *reinterpret_cast<f32x4 *>(sx + r * LD + c4 * 4) = *reinterpret_cast<const f32x4 *>(base + (size_t)idx * 4);
-    }
+    tile_to_lds(sx, base, tid);
     __syncthreads();
     const int b = row0 + tid;
-    if (b < B) {
-        float xr[NV * 4], gr[D], Tr[3];
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            const f32x4 t = *reinterpret_cast<const f32x4 *>(sx + tid * LD + v * 4);
-            xr[4 * v] = t[0]; xr[4 * v + 1] = t[1]; xr[4 * v + 2] = t[2]; xr[4 * v + 3] = t[3];
-        }
-        Tr[0] = T[(size_t)b * 3]; Tr[1] = T[(size_t)b * 3 + 1]; Tr[2] = T[(size_t)b * 3 + 2];
-        const int n = (int)((row_offset + b) % N);
-        reproj_row<J>(xr, geom + (size_t)n * J * GEOM_F, Tr, solve != 0, gr);
-        if (solve) { T[(size_t)b * 3] = Tr[0]; T[(size_t)b * 3 + 1] = Tr[1]; T[(size_t)b * 3 + 2] = Tr[2]; }
-#pragma unroll
-        for (int c = 0; c < D; ++c) xr[c] += gr[c];  // denoise_x += joint_gradient (run/opt_main.py:208)
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            f32x4 t = {xr[4 * v], xr[4 * v + 1], xr[4 * v + 2], xr[4 * v + 3]};
-            *reinterpret_cast<f32x4 *>(sx + tid * LD + v * 4) = t;
-        }
-    }
+    if (b < B) ZEDO_REPROJ_STAGED_ROW(J, sx + tid * TILE_LD, 0, b, (ReprojArgs{geom, T, solve, B, N, row_offset}));
     __syncthreads();
-#pragma unroll
-    for (int it = 0; it < XLD / 4; ++it) {
-        const int idx = it * R + tid, r = idx >> 4, c4 = idx & 15;
-        *reinterpret_cast<f32x4 *>(base + (size_t)idx * 4) = *reinterpret_cast<const f32x4 *>(sx + r * LD + c4 * 4);
-    }
+    tile_from_lds(base, sx, tid);
 }
 
 // Second half of post_dense on small batches (zedo_gemm.hip, EPI_PARTIAL): the four K-quarter sums of every row are
@@ -216,25 +206,18 @@ __global__ __launch_bounds__(64) void post_reduce_kernel(float *__restrict__ xpa
                                                          const float *__restrict__ bias, float sde_a, float sde_c, int sde,
                                                          float *__restrict__ eps_out, const float *__restrict__ geom,
                                                          float *__restrict__ T, int solve, int B, int N, long long row_offset) {
-    constexpr int D = J * 3, R = BATCH_PAD, LD = XLD + 4, NV = (D + 3) / 4;
-    __shared__ __attribute__((aligned(16))) float sx[R * LD];
+    __shared__ __attribute__((aligned(16))) float sx[BATCH_PAD * TILE_LD];
     __shared__ __attribute__((aligned(16))) float sb[XLD];
-    const int row0 = blockIdx.x * R, tid = threadIdx.x;
+    const int row0 = blockIdx.x * BATCH_PAD, tid = threadIdx.x;
     float *base = (sde ? xpad : eps_out) + (size_t)row0 * XLD;  // Bp is a multiple of BATCH_PAD: the whole tile exists
     sb[tid] = bias[tid];
-    if (sde) {
-#pragma unroll
-        for (int it = 0; it < XLD / 4; ++it) {
-            const int idx = it * R + tid, r = idx >> 4, c4 = idx & 15;
-            *reinterpret_cast<f32x4 *>(sx + r * LD + c4 * 4) = *reinterpret_cast<const f32x4 *>(base + (size_t)idx * 4);
-        }
-    }
+    if (sde) tile_to_lds(sx, base, tid);
     __syncthreads();
     const int b = row0 + tid;
     {
         // quarter sums of row b: partial[(b / 32) * 4 + q][b % 32][64]
         const float *p0 = partial + ((size_t)(b >> 5) * 4 * 32 + (b & 31)) * XLD;
-        float *xr = sx + tid * LD;
+        float *xr = sx + tid * TILE_LD;
 #pragma unroll
         for (int v = 0; v < XLD / 4; ++v) {
             const f32x4 q0 = *reinterpret_cast<const f32x4 *>(p0 + v * 4);
@@ -259,46 +242,22 @@ __global__ __launch_bounds__(64) void post_reduce_kernel(float *__restrict__ xpa
             *reinterpret_cast<f32x4 *>(xr + v * 4) = o;
         }
     }
-    if (geom != nullptr && b < B) {
-        float xr[NV * 4], gr[D], Tr[3];
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            const f32x4 t = *reinterpret_cast<const f32x4 *>(sx + tid * LD + v * 4);
-            xr[4 * v] = t[0]; xr[4 * v + 1] = t[1]; xr[4 * v + 2] = t[2]; xr[4 * v + 3] = t[3];
-        }
-        Tr[0] = T[(size_t)b * 3]; Tr[1] = T[(size_t)b * 3 + 1]; Tr[2] = T[(size_t)b * 3 + 2];
-        const int n = (int)((row_offset + b) % N);
-        reproj_row<J>(xr, geom + (size_t)n * J * GEOM_F, Tr, solve != 0, gr);
-        if (solve) { T[(size_t)b * 3] = Tr[0]; T[(size_t)b * 3 + 1] = Tr[1]; T[(size_t)b * 3 + 2] = Tr[2]; }
-#pragma unroll
-        for (int c = 0; c < D; ++c) xr[c] += gr[c];
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            f32x4 t = {xr[4 * v], xr[4 * v + 1], xr[4 * v + 2], xr[4 * v + 3]};
-            *reinterpret_cast<f32x4 *>(sx + tid * LD + v * 4) = t;
-        }
-    }
+    if (geom != nullptr && b < B) ZEDO_REPROJ_STAGED_ROW(J, sx + tid * TILE_LD, 0, b, (ReprojArgs{geom, T, solve, B, N, row_offset}));
     __syncthreads();
-#pragma unroll
-    for (int it = 0; it < XLD / 4; ++it) {
-        const int idx = it * R + tid, r = idx >> 4, c4 = idx & 15;
-        *reinterpret_cast<f32x4 *>(base + (size_t)idx * 4) = *reinterpret_cast<const f32x4 *>(sx + r * LD + c4 * 4);
-    }
+    tile_from_lds(base, sx, tid);
 }
 
 hipError_t launch_post_reduce(float *xpad, const float *partial, const float *bias, float sde_a, float sde_c, int sde,
-                              float *eps_out, const float *geom, float *T, int solve_T, int B, int Bp, int N, long long row0,
-                              hipStream_t st) {
+                              float *eps_out, const ReprojArgs &rp, int Bp, hipStream_t st) {
     if (Bp % BATCH_PAD || !partial || !bias || (sde ? !xpad : !eps_out)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(post_reduce_kernel<17>, dim3(Bp / BATCH_PAD), dim3(BATCH_PAD), 0, st, xpad, partial, bias, sde_a, sde_c, sde,
-                       eps_out, geom, T, solve_T, B, N > 0 ? N : 1, row0);
+                       eps_out, rp.geom, rp.T, rp.solve, rp.B, rp.N > 0 ? rp.N : 1, rp.row0);
     return hipGetLastError();
 }
 
-hipError_t launch_reproj_step_padded(float *xpad, const float *geom, float *T, int solve_T, int B, int N,
-                                     long long row0, hipStream_t st) {
-    hipLaunchKernelGGL(reproj_step_kernel<17>, dim3((B + BATCH_PAD - 1) / BATCH_PAD), dim3(BATCH_PAD), 0, st, xpad, geom, T,
-                       solve_T, B, N, row0);
+hipError_t launch_reproj_step_padded(float *xpad, const ReprojArgs &rp, hipStream_t st) {
+    hipLaunchKernelGGL(reproj_step_kernel<17>, dim3((rp.B + BATCH_PAD - 1) / BATCH_PAD), dim3(BATCH_PAD), 0, st, xpad, rp.geom, rp.T,
+                       rp.solve, rp.B, rp.N, rp.row0);
     return hipGetLastError();
 }
 

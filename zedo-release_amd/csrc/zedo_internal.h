@@ -58,6 +58,16 @@ enum Epilogue : int {
     EPI_PARTIAL = 5,      // out = acc of ONE K quarter, no bias (post_dense on small batches: see LayerArgs::scratch)
 };
 
+// The reprojection correction of the NEXT loop iteration (gradient_field_gen + "denoise_x += joint_gradient",
+// run/opt_main.py:203-208) on the rows of one launch; geom == nullptr: none.  Fused into the SDE epilogue of post_dense
+// (LayerArgs / Layer16Args, post_reduce_kernel) or a launch of its own (reproj_step_kernel).
+struct ReprojArgs {
+    const float *geom;   // [N][17][8]
+    float *T;            // [rows][3], row 0 = first row of this launch
+    int solve, B, N;     // least-squares T?, valid rows of this launch, poses
+    long long row0;      // global row index of row 0 of this launch
+};
+
 // One dense layer out[M][N] (+epilogue) = X[M][K] . W[N][K]^T ; all row-major fp32, K contiguous.
 struct LayerArgs {
     const float *X;   // [Mp][ldx]
@@ -73,13 +83,9 @@ struct LayerArgs {
     float sde_a, sde_c;  // EPI_SDE
     int kzero8;          // K == 64 only: columns k = 56..63 of X and W are zero padding (their MFMAs are skipped)
     long long *clk;      // diagnostic (may be null): workgroup 0 writes {shader cycles, 100 MHz wall ticks} it spent in the tile
-    // EPI_SDE only, optional (rp_geom != nullptr): the reprojection correction of the NEXT loop iteration
-    // (gradient_field_gen + "denoise_x += joint_gradient", run/opt_main.py:203-208) applied to the freshly updated rows
-    // while they are still in LDS, instead of a separate launch that reads and rewrites them.
-    const float *rp_geom;   // [N][17][8]
-    float *rp_T;            // [rows][3], row 0 = first row of this launch
-    int rp_solve, rp_B, rp_N;   // least-squares T?, valid rows of this launch, poses
-    long long rp_row0;      // global row index of row 0 of this launch
+    // EPI_SDE only, optional: the reprojection correction of the next iteration applied to the freshly updated rows while they
+    // are still in LDS, instead of a separate launch that reads and rewrites them.
+    ReprojArgs rp;
     // post_dense (N == XLD) sums its K = 1024 products as FOUR quarter chains q0..q3 (k in [256 q, 256 q + 256), each an fma
     // chain from zero) combined as ((q0 + q1) + q2) + q3 - in every launch shape, so that results do not depend on it:
     // large batches fold the quarters inside one tile, batches of up to POST_SPLIT_ROWS rows give every quarter its own
@@ -111,10 +117,7 @@ struct Layer16Args {
     // [Mp][64] (EPI_BIAS); the optional fused reprojection of the next iteration as in LayerArgs
     float *xio;             // [Mp][64]
     float sde_a, sde_c;
-    const float *rp_geom;
-    float *rp_T;
-    int rp_solve, rp_B, rp_N;
-    long long rp_row0;
+    ReprojArgs rp;
 };
 hipError_t launch_layer16(const Layer16Args &a, int epilogue, hipStream_t st);
 // fp32 [rows][cols] (row stride ld floats) * scale -> planes [cols/16][ldr][2][16] (k-block-major; ldr >= rows); cols % 16 == 0
@@ -169,6 +172,35 @@ __device__ __forceinline__ void reproj_row(const float *x, const float *__restri
     }
 }
 
+// The correction of row B of a launch (ReprojArgs RP), held in LDS at ROW, in place: T read, reproj_row, T written back
+// when solving, x += g (run/opt_main.py:203-208).  16-byte chunk v of the row sits at position v ^ SWZ: sr & 7 in the
+// epilogue stages of the dense tiles, 0 in the padded rows of the geometry kernels.  Every launch form that ends an OIL
+// iteration runs this one source, so that they agree bit for bit.
+// A macro, not a function: hipcc optimises an always-inline callee on its own before it inlines it, and the post_dense
+// tiles built from such a function were not instruction-identical to the ones built from these statements in place (they
+// ordered their LDS reads and address arithmetic differently).
+#define ZEDO_REPROJ_STAGED_ROW(J, ROW, SWZ, B, RP)                                                                           \
+    do {                                                                                                                      \
+        constexpr int NV_ = (J * 3 + 3) / 4;                                                                                  \
+        float *const row_ = (ROW);                                                                                            \
+        const int swz_ = (SWZ), b_ = (B);                                                                                     \
+        const ReprojArgs &rp_ = (RP);                                                                                         \
+        float xr[NV_ * 4], gr[J * 3], Tr[3];                                                                                  \
+        _Pragma("unroll") for (int v = 0; v < NV_; ++v) {                                                                     \
+            const f32x4 t = *reinterpret_cast<const f32x4 *>(row_ + ((v ^ swz_) << 2));                                      \
+            xr[4 * v] = t[0]; xr[4 * v + 1] = t[1]; xr[4 * v + 2] = t[2]; xr[4 * v + 3] = t[3];                              \
+        }                                                                                                                     \
+        Tr[0] = rp_.T[(size_t)b_ * 3]; Tr[1] = rp_.T[(size_t)b_ * 3 + 1]; Tr[2] = rp_.T[(size_t)b_ * 3 + 2];                 \
+        const int n_ = (int)((rp_.row0 + b_) % rp_.N);                                                                        \
+        reproj_row<J>(xr, rp_.geom + (size_t)n_ * J * GEOM_F, Tr, rp_.solve != 0, gr);                                        \
+        if (rp_.solve) { rp_.T[(size_t)b_ * 3] = Tr[0]; rp_.T[(size_t)b_ * 3 + 1] = Tr[1]; rp_.T[(size_t)b_ * 3 + 2] = Tr[2]; } \
+        _Pragma("unroll") for (int c = 0; c < J * 3; ++c) xr[c] += gr[c];                                                     \
+        _Pragma("unroll") for (int v = 0; v < NV_; ++v) {                                                                     \
+            const f32x4 t = {xr[4 * v], xr[4 * v + 1], xr[4 * v + 2], xr[4 * v + 3]};                                        \
+            *reinterpret_cast<f32x4 *>(row_ + ((v ^ swz_) << 2)) = t;                                                         \
+        }                                                                                                                     \
+    } while (0)
+
 
 
 // geometry kernels (zedo_geom.hip)
@@ -179,13 +211,11 @@ hipError_t launch_reproj_prepare(const float *uv, const float *K, const float *c
 hipError_t launch_reproj_grad(const float *x, const float *geom, float *T, int solve_T, float *g, int B, int N,
                               int J, long long row_offset, hipStream_t st);
 // the second half of post_dense on small batches: x' = a x + c (((q0 + q1) + q2) + q3 + bias) on the padded state (sde != 0)
-// or eps = ((q0 + q1) + q2) + q3 + bias -> eps_out [Bp][64] (sde == 0), then - geom != nullptr - the reprojection correction of
-// the next iteration on rows < B, exactly as the fused epilogue of the large-batch tile does it
+// or eps = ((q0 + q1) + q2) + q3 + bias -> eps_out [Bp][64] (sde == 0), then - rp.geom != nullptr - the reprojection correction
+// of the next iteration on rows < rp.B, exactly as the fused epilogue of the large-batch tile does it
 hipError_t launch_post_reduce(float *xpad, const float *partial, const float *bias, float sde_a, float sde_c, int sde,
-                              float *eps_out, const float *geom, float *T, int solve_T, int B, int Bp, int N, long long row0,
-                              hipStream_t st);
-hipError_t launch_reproj_step_padded(float *xpad, const float *geom, float *T, int solve_T, int B, int N,
-                                     long long row0, hipStream_t st);
+                              float *eps_out, const ReprojArgs &rp, int Bp, hipStream_t st);
+hipError_t launch_reproj_step_padded(float *xpad, const ReprojArgs &rp, hipStream_t st);
 hipError_t launch_posemb(const float *t, int S, int Sp, float label_scale, float *pe, hipStream_t st);
 hipError_t launch_ipo_fit(const float *x0, const float *uv, const float *K, const int *h_keylist, int k,
                           int axes_mask, float ipo_T, float min_scale, float max_scale, int iters,

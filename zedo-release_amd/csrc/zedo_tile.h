@@ -1,5 +1,6 @@
 // Device helpers shared by the two dense-layer translation units (zedo_gemm.hip: exact-fp32 MFMA tiles; zedo_gemm16.hip:
-// split-fp16 tiles): the LDS-DMA issue helper and the GroupNorm / SiLU / SDE epilogue arithmetic.  gfx950 only.
+// split-fp16 tiles): the LDS-DMA issue helper, the GroupNorm / SiLU / SDE epilogue arithmetic and the launch plumbing (LDS
+// footprint of a tile, block -> tile map, clock probe).  gfx950 only.
 #pragma once
 #include "zedo_internal.h"
 
@@ -188,5 +189,40 @@ __device__ __forceinline__ void epilogue_values(const f32x16 &acc, const f32x4 (
     }
 }
 
+// ---- launch plumbing ------------------------------------------------------------------------------------------------
+// LDS of one tile: its operand ring or, where that is smaller, the epilogue stage of WM * 32 rows x BN fp32 channels that
+// reuses it, then the [3][BN] parameter block (bias | gamma | beta) as its last 3 * BN floats.  The tile places that
+// block with these functions and every launcher sizes its dynamic LDS with them, so the two cannot disagree.
+// exact-fp32 layer_tile (zedo_gemm.hip): a ring of NBUF K tiles of (BM + BN) rows x BK floats
+constexpr size_t layer_tile_lds(int BM, int BN, int WM, int NBUF, int BK) {
+    const size_t ring = (size_t)NBUF * (BM + BN) * BK, stage = (size_t)WM * 32 * BN;
+    return ((ring > stage ? ring : stage) + 3 * BN) * sizeof(float);
+}
+// split-fp16 layer16_tile (zedo_gemm16.hip): a ring of NBUF 16-k blocks of (BM + BN) rows x 64 bytes
+constexpr size_t layer16_tile_lds(int BM, int BN, int WM, int NBUF) {
+    const size_t ring = (size_t)NBUF * (BM + BN) * 64, stage = (size_t)WM * 32 * BN * sizeof(float);
+    return (ring > stage ? ring : stage) + 3 * BN * sizeof(float);
+}
+
+// XCD-aware, bijective block -> tile map: the hardware places block b on XCD b % 8; every XCD gets a contiguous range of
+// tiles, so that the column tiles of one row tile share one L2
+__device__ __forceinline__ int xcd_tile(const int bid, const int nwg) {
+    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
+// Diagnostic of the pair kernels (LayerArgs::clk / Layer16Args::clk, may be null): the probing thread - thread 0 of
+// workgroup 0, named by the caller - writes {shader cycles, 100 MHz wall ticks} it spent in the launch: the shader clock
+// the launch really runs at (power management differs box to box and with the load).
+struct ClockProbe {
+    long long c0 = 0, w0 = 0;
+    bool on;
+    __device__ explicit ClockProbe(bool probe) : on(probe) {
+        if (on) { c0 = clock64(); w0 = wall_clock64(); }
+    }
+    __device__ void stop(long long *clk) const {
+        if (on) { clk[0] = clock64() - c0; clk[1] = wall_clock64() - w0; }
+    }
+};
 
 }  // namespace zedo
