@@ -39,7 +39,8 @@ extern "C" {
 #endif
 
 #define ZEDO_ABI_VERSION 5   /* 3: + zedo_reproj_degenerate, zedo_pose_min, zedo_weights_set_math / zedo_weights_get_math;
-                              * 4: + zedo_profile_bracket_ms;  5: + zedo_probe_mfma_peak_f16, workspace rows rounded to 64 again */
+                              * 4: + zedo_profile_bracket_ms;  5: + zedo_probe_mfma_peak_f16, workspace rows rounded to 64 again;
+                              * still 5 (additive): + zedo_pc_plan_create / _destroy, zedo_pc_workspace_bytes, zedo_pc_step */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -149,6 +150,48 @@ int zedo_score_eps(const zedo_weights_t *w, const zedo_schedule_t *s, int step, 
 /* one pc_sampler call (advanced/sampling.py:450-527): x <- a[step] x + c[step] eps(x). In place. */
 int zedo_sde_step(const zedo_weights_t *w, const zedo_schedule_t *s, int step, float *d_x, int B,
                   void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* ---- generic predictor-corrector step -------------------------------------------------------------
+ * The native body of pc_sampler for EVERY registered predictor / corrector / SDE combination
+ * (advanced/sampling.py:180-331, 400-529; reverse SDE / ODE: sde_lib.py:71-109).  With vec_t = ones(B)*t (:497)
+ *   predictor:       x_mean = A x + B score(x),  x_new = x_mean + C z          (:180-248)
+ *   corrector step:  x_mean = x + s score(x),    x     = x_mean + sqrt(2 s) z  (:259-331)
+ *   score(x) = net_scale * eps(x, label)                                       (utils.py:751-800, model.py:294)
+ * and every scalar depends on the step only.  A plan holds them for S steps (host arrays, fp32, length S):
+ *   h_label, h_net_scale;  has_predictor != 0: h_pA, h_pB, h_pC (C = 0: no noise term, e.g. probability flow);
+ *   corrector ZEDO_PC_CORR_ALD: h_corr = s[S];  ZEDO_PC_CORR_LANGEVIN: h_corr = factor[S] = 2 alpha snr^2 and
+ *   s = factor (mean_b ||z_b|| / mean_b ||score_b||)^2 is formed on the device per corrector step (:281-284);
+ *   n_corr corrector steps per call (ignored with ZEDO_PC_CORR_NONE).
+ * The plan owns the time-bias table of its labels (zedo_schedule_create's machinery, label_scale 1; plans of up to 256
+ * steps borrow the weights handle's scratch).  zedo_pc_plan_create is the only call here that allocates or synchronises
+ * `stream`; the host arrays may be freed when it returns.
+ */
+typedef struct zedo_pc_plan zedo_pc_plan_t;
+#define ZEDO_PC_CORR_NONE 0
+#define ZEDO_PC_CORR_LANGEVIN 1
+#define ZEDO_PC_CORR_ALD 2
+int zedo_pc_plan_create(const zedo_weights_t *w, int S, const float *h_label, const float *h_net_scale, int has_predictor,
+                        const float *h_pA, const float *h_pB, const float *h_pC, int corrector, int n_corr,
+                        const float *h_corr, void *stream, zedo_pc_plan_t **out);
+void zedo_pc_plan_destroy(zedo_pc_plan_t *p);
+/* equals zedo_workspace_bytes(B): eps, the row norms and the step size of a Langevin step live in the network's buffers */
+size_t zedo_pc_workspace_bytes(const zedo_pc_plan_t *p, int B);
+/* One pc_sampler call (advanced/sampling.py:450-527): n_corr corrector steps, then the predictor, at plan entry `step`.
+ * d_x [B,J,3] in: x, out: x_new.  d_x_mean [B,J,3] out, may be NULL (with no predictor it receives x_new, as NonePredictor
+ * hands back, :248-256).
+ * h_z: HOST array of n_corr + (has_predictor ? 1 : 0) device pointers, each one noise draw [B,J,3] of the caller, in the order
+ * the reference draws them (corrector steps first); consumed before the call returns.  The corrector entries are required.
+ * The predictor entry may be NULL - and h_z itself when n_corr == 0 - which means "keep x_mean only" (noise_removal: the
+ * caller still makes the draw for its RNG stream but does not hand it over): d_x then returns x_mean and the noise launch is
+ * skipped, as it is when C[step] == 0.
+ * Batches above the chunk size of zedo_workspace_bytes are walked in chunks, except Langevin plans: the mean spans the
+ * whole call, so B above the chunk size returns ZEDO_E_BADARG.  The mean is over the B rows of the call - a batch split
+ * over several calls (or ranks) gets a different step size than the whole, as it does in the reference.
+ * Allocates nothing, copies nothing to the host, synchronises nothing; the Langevin step size never leaves the device:
+ * legal under stream capture.  Bit-identical from run to run (fixed-order sums, no atomics).
+ */
+int zedo_pc_step(const zedo_weights_t *w, const zedo_pc_plan_t *p, int step, float *d_x, float *d_x_mean,
+                 const float *const *h_z, int B, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* ---- the fused OIL loop: run/opt_main.py:202-220 -------------------------------------------------
  * for i in [step_begin, step_end): g,T = gradient_field_gen(x, T if i < switch_step else None);

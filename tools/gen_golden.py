@@ -684,6 +684,71 @@ def gen_pc_generic():
     save("pc_generic", **out)
 
 
+PC_LOOP_CASES = PC_GENERIC_CASES + [("vp_em_langevin", "vpsde", True, "euler_maruyama", "langevin", False, True, None)]
+PC_LOOP_STEPS, PC_LOOP_SNAPS, PC_LOOP_ROWS, PC_LOOP_EPS = 20, (1, 10, 20), 70, 0.01
+
+
+class DetNoise32(DetNoise):
+    """The same stream rounded to fp32 first: what a float32 run draws, handed to a float64 run unchanged."""
+
+    def __call__(self, x):
+        g = np.random.Generator(np.random.Philox(key=[555, self.calls]))
+        self.calls += 1
+        return torch.tensor(g.standard_normal(tuple(x.shape)).astype(np.float32)).to(x.dtype)
+
+
+def _pc_loop_chain(w, case, x0, dtype):
+    """PC_LOOP_STEPS consecutive pc_sampler calls on t = linspace(T, eps, S), t_step = i, `res` fed back as the reference's
+    driver does (run/opt_main.py:210-220).  dtype float64: sde tables, vec_t, model and state in double (the arbiter)."""
+    tag, sname, cont, pred, corr, pf, denoise, _ = case
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(dtype)
+    orig = torch.randn_like
+    try:
+        sde = make_sde(sname)
+        m = ref_model(w, dtype)
+        cfg = ref_config()
+        cfg.training.sde, cfg.training.continuous = sname, cont
+        cfg.sampling.predictor, cfg.sampling.corrector, cfg.sampling.probability_flow = pred, corr, pf
+        cfg.sampling.noise_removal = denoise
+        cfg.sampling.n_steps_each = 2 if tag == "vp_em_langevin" else 1
+        n = x0.shape[0]
+        fn = sampling.get_sampling_fn(cfg, sde, (n, 17, 3), lambda v: v, PC_LOOP_EPS, device=torch.device("cpu"))
+        ts = torch.linspace(float(sde.T), PC_LOOP_EPS, PC_LOOP_STEPS, dtype=torch.float32)   # the times of the fp32 run in both
+        noise = DetNoise32()
+        torch.randn_like = noise
+        x = torch.tensor(x0, dtype=dtype)
+        snaps = []
+        for i in range(PC_LOOP_STEPS):
+            _, res = fn(m, condition=torch.zeros(n, 17, 2), denoise_x=x, t=ts[i], t_step=i)
+            x = torch.as_tensor(res).clone()
+            if i + 1 in PC_LOOP_SNAPS:
+                snaps.append(x.numpy().astype(np.float64))
+        return np.stack(snaps), noise.calls
+    finally:
+        torch.randn_like = orig
+        torch.set_default_dtype(old)
+
+
+def gen_pc_generic_loop():
+    """Chained pc_sampler calls for every generic combination of PC_GENERIC_CASES plus Langevin with two corrector steps: the
+    reference as shipped (fp32: the yardstick, only its distance `gap` to the arbiter is kept) and the same code with model
+    and state in float64 (the arbiter, stored after steps 1, 10 and 20).  Both runs draw the same fp32-rounded noise."""
+    w = syn.make_weights(seed=0)
+    g = np.random.Generator(np.random.Philox(key=[7, 13]))
+    x0 = (0.3 * g.standard_normal((PC_LOOP_ROWS, 17, 3))).astype(np.float32)
+    out = dict(x=x0, snaps=np.array(PC_LOOP_SNAPS), steps=np.int64(PC_LOOP_STEPS), eps=np.float64(PC_LOOP_EPS),
+               cases=np.array([c[0] for c in PC_LOOP_CASES]))
+    for case in PC_LOOP_CASES:
+        r32, n32 = _pc_loop_chain(w, case, x0, torch.float32)
+        r64, n64 = _pc_loop_chain(w, case, x0, torch.float64)
+        gap = np.abs(r32 - r64).reshape(len(PC_LOOP_SNAPS), -1).max(1)
+        assert n32 == n64 and np.isfinite(r32).all() and np.isfinite(r64).all() and (gap > 0).all(), (case[0], n32, n64, gap)
+        print(f"  {case[0]}: draws {n32}  gap {gap}  |res64| {np.abs(r64[-1]).max():.3g}")
+        out[f"{case[0]}_res64"], out[f"{case[0]}_gap"], out[f"{case[0]}_draws"] = r64, gap, np.int64(n32)
+    save("pc_generic_loop", **out)
+
+
 
 # ------------------------------------------------------------------ 3DHP / SkiPose (SURVEY 8f row 4)
 
@@ -1153,7 +1218,7 @@ def gen_driver_pw3d_full_c_oil64():
 
 GENS = dict(model=gen_model, weights_alt=gen_weights_alt, pc_step=gen_pc_step, reproj=gen_reproj, ipo=gen_ipo, ipo_custom=gen_ipo_custom, oil=gen_oil,
             eval=gen_eval, driver=gen_driver, datasets=gen_datasets,
-            driver_files=gen_driver_files, samplers=gen_samplers, pc_generic=gen_pc_generic, hp3d_ski=gen_3dhp_ski, driver_full=gen_driver_full,
+            driver_files=gen_driver_files, samplers=gen_samplers, pc_generic=gen_pc_generic, pc_generic_loop=gen_pc_generic_loop, hp3d_ski=gen_3dhp_ski, driver_full=gen_driver_full,
             driver_h36m_full=gen_driver_h36m_full, driver_pw3d_full=gen_driver_pw3d_full,
             driver_h36m_full_f64=gen_driver_h36m_full_f64, driver_pw3d_full_f64=gen_driver_pw3d_full_f64,
             driver_pw3d_full_b=gen_driver_pw3d_full_b, driver_pw3d_full_c=gen_driver_pw3d_full_c,

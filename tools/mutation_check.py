@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: nine one-line arithmetic mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: eleven one-line arithmetic mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -27,6 +27,9 @@ MUTANTS = [
     # round 5: the split-fp16 mode (every GPU test runs in both modes; these two must turn f16x3 cells red and leave f32 cells green)
     ("ZEDO_MUT_F16_DROP_LH", "f16x3: the W_low x X_high MFMA of every k block is dropped - W as plain fp16 (zedo_gemm16.hip mma)"),
     ("ZEDO_MUT_F16_XLOW0", "f16x3: the low pieces of the activations are lost in the first of the 64 k blocks of every dense layer (zedo_gemm16.hip)"),
+    # the native predictor-corrector step (zedo_pc_step)
+    ("ZEDO_MUT_PC_NOISE", "pc step: the predictor's noise coefficient C * (1 + 1e-4) (zedo_capi.hip plan; advanced/sampling.py:185-191)"),
+    ("ZEDO_MUT_PC_MEAN", "pc step, Langevin: mean ||eps|| divided by the padded row count instead of B (zedo_pc.hip; advanced/sampling.py:281-283)"),
 ]
 
 

@@ -18,14 +18,28 @@ import torch
 
 
 def generic(a):
-    """a 1000-step run of a non-shipped sampler configuration at BASELINE configs[1]'s 886 rows, H = 1, before / after."""
+    """A 1000-step run of a non-shipped sampler configuration at BASELINE configs[1]'s 886 rows, H = 1, through
+    run/_driver.py::stepwise_loop.  Legs, alternating in ONE process after a warm-up pass: `native` (the default route: one
+    zedo_pc_step per sampler call), `device_resident` (the torch route pinned with ZEDO_GENERIC_PC=torch: the update rule as
+    torch element-wise operators around model.forward) and `host_round_trip` (the pinned torch route stepped through the
+    numpy-returning callable, as the reference's driver does).  --generic shipped: the shipped sub-VP configuration stepped
+    through the same loop (one zedo_sde_step per call), for orientation."""
+    from lib.algorithms.advanced import sampling
     from lib.algorithms.advanced.model import ScoreModelFC_Adv
     from lib.dataset import synthetic as syn
     from run import _driver
+    import zedo_hip as zh
     cfg = _driver.load_config(os.path.join(ROOT, "zedo-release_amd", "configs", "optim", "concat_pose_optimization_h36m.py"))
-    cfg.training.sde = a.generic
     cfg.sampling.probability_flow = True
-    assert _driver.not_fused_because(cfg) is not None
+    shipped = a.generic == "shipped"
+    if not shipped:
+        cfg.training.sde = a.generic
+        if a.predictor:
+            cfg.sampling.predictor = a.predictor
+        if a.corrector:
+            cfg.sampling.corrector, cfg.sampling.probability_flow = a.corrector, False
+        cfg.sampling.n_steps_each = a.n_steps_each
+        assert _driver.not_fused_because(cfg) is not None
     N, S = a.poses, a.steps
     cfg.ZeDO.OIL_iterations = S
     dev = torch.device("cuda")
@@ -37,20 +51,50 @@ def generic(a):
     d = syn.make_poses(N, seed=101, conf_mode="uniform")
     cl = syn.make_clusters(1, seed=17)
     sde = _driver.make_sde(cfg)
+    has_knob = hasattr(sampling.get_sampling_fn(cfg, sde, (N, 17, 3), lambda v: v, cfg.ZeDO.sampling_eps, device=dev), "native_plan")
+    legs = [("native", False, None), ("device_resident", False, "torch"), ("host_round_trip", True, "torch")]
+    if shipped:
+        legs = [("shipped_stepwise", False, None)]
+    elif not has_knob:        # a tree without the native route: its two legs, as before
+        legs = legs[1:]
     out, res = {}, {}
-    for tag, rt in (("host_round_trip", True), ("device_resident", False), ("host_round_trip", True), ("device_resident", False)):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        x = _driver.stepwise_loop(cfg, model, sde, cl, d["db_2d"].copy(), d["camera_param"], S, dev, host_round_trip=rt)
-        torch.cuda.synchronize()
-        out.setdefault(tag, []).append(round((time.perf_counter() - t0) * 1e3, 1))
-        res[tag] = x
-    print(json.dumps(dict(config=f"training.sde = {a.generic}, euler_maruyama / none, probability flow: generic per-step route "
-                                 "(score network on the HIP path, update rule in torch element-wise operators)",
-                          poses=N, steps=S, host_threads=torch.get_num_threads(), ms_per_pass_incl_ipo=out,
-                          ms_per_step={k: round(min(v) / S, 4) for k, v in out.items()},
-                          speedup=round(min(out["host_round_trip"]) / min(out["device_resident"]), 3),
-                          bitwise_equal=bool(torch.equal(res["host_round_trip"], res["device_resident"])))))
+
+    def one(tag, rt, pin, keep=True):
+        old = os.environ.pop("ZEDO_GENERIC_PC", None)
+        if pin:
+            os.environ["ZEDO_GENERIC_PC"] = pin
+        try:
+            torch.manual_seed(0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            x = _driver.stepwise_loop(cfg, model, sde, cl, d["db_2d"].copy(), d["camera_param"], S, dev, host_round_trip=rt)
+            torch.cuda.synchronize()
+            if keep:
+                out.setdefault(tag, []).append(round((time.perf_counter() - t0) * 1e3, 1))
+                res[tag] = x
+        finally:
+            os.environ.pop("ZEDO_GENERIC_PC", None)
+            if old is not None:
+                os.environ["ZEDO_GENERIC_PC"] = old
+    for leg in legs:
+        one(*leg, keep=False)          # warm-up: library load, allocator, plan / schedule caches
+    for _ in range(a.repeats):
+        for leg in legs:
+            one(*leg)
+    tf, ghz = zh.probe_mfma_peak()
+    rec = dict(config=f"training.sde = {cfg.training.sde}, {cfg.sampling.predictor} / {cfg.sampling.corrector}, "
+                      f"probability_flow = {cfg.sampling.probability_flow}, n_steps_each = {cfg.sampling.n_steps_each}",
+               poses=N, steps=S, host_threads=torch.get_num_threads(), ms_per_pass_incl_ipo=out,
+               ms_per_step={k: round(min(v) / S, 4) for k, v in out.items()},
+               box=dict(mfma_fp32_peak_tflops=round(tf, 1), shader_clock_ghz=round(ghz, 3)))
+    if "native" in res:
+        rec["native_over_device_resident"] = round(min(out["native"]) / min(out["device_resident"]), 3)
+        rec["bitwise_equal"] = bool(torch.equal(res["native"], res["device_resident"]))
+        rec["max_abs_diff"] = float((res["native"] - res["device_resident"]).abs().max())
+        rec["max_abs_value"] = float(res["device_resident"].abs().max())
+    if "host_round_trip" in res and "device_resident" in res:
+        rec["torch_route_legs_bitwise_equal"] = bool(torch.equal(res["host_round_trip"], res["device_resident"]))
+    print(json.dumps(rec))
 
 
 def main():
@@ -59,7 +103,12 @@ def main():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--generic", default=None, metavar="SDE",
                     help="time run/_driver.py::stepwise_loop for a configuration OUTSIDE the fused pipeline (e.g. vpsde): the "
-                         "device-resident loop (sampling_fn.step_device) against the reference's per-step D2H/H2D round trip")
+                         "native route (zedo_pc_step) against the pinned torch route, device-resident and with the reference's "
+                         "per-step D2H/H2D round trip; 'shipped': the shipped configuration through the same loop")
+    ap.add_argument("--predictor", default=None, help="with --generic: sampling.predictor (default: the config's euler_maruyama)")
+    ap.add_argument("--corrector", default=None, help="with --generic: sampling.corrector; switches probability flow off")
+    ap.add_argument("--n-steps-each", type=int, default=1, help="with --generic: corrector steps per call")
+    ap.add_argument("--repeats", type=int, default=2, help="with --generic: timed passes per leg")
     a = ap.parse_args()
     if a.generic:
         return generic(a)

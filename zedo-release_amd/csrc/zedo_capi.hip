@@ -669,6 +669,101 @@ extern "C" int zedo_oil_run(const zedo_weights_t *w, const zedo_schedule_t *s, f
     return ZEDO_OK;
 }
 
+// ---- one predictor-corrector call of the generic sampler (advanced/sampling.py:180-331, 400-529) ----------------------
+// Per step and per update the scalars of  x_mean = a x + c eps(x)  and of the noise term, folded once at plan creation;
+// the time-bias rows are an ordinary schedule over the plan's labels (label_scale 1).
+struct zedo_pc_plan {
+    int S, has_pred, corr, n_corr;
+    std::vector<float> ns;              // score = ns eps
+    std::vector<float> pa, pc, pz;      // predictor: x_mean = pa x + pc eps, x = x_mean + pz z       (pc = fl32(B ns))
+    std::vector<float> cc, cz;          // ALD: x_mean = x + cc eps, x = x_mean + cz z               (cc = fl32(step ns), cz = sqrt(2 step))
+    std::vector<float> factor;          // Langevin: s = factor (mean||z|| / (|ns| mean||eps||))^2
+    zedo_schedule *sched;
+};
+
+extern "C" int zedo_pc_plan_create(const zedo_weights_t *w, int S, const float *h_label, const float *h_net_scale, int has_predictor,
+                                   const float *h_pA, const float *h_pB, const float *h_pC, int corrector, int n_corr,
+                                   const float *h_corr, void *stream, zedo_pc_plan_t **out) {
+    if (!w || !h_label || !h_net_scale || !out || S < 1 || n_corr < 0) return ZEDO_E_BADARG;
+    if (corrector != ZEDO_PC_CORR_NONE && corrector != ZEDO_PC_CORR_LANGEVIN && corrector != ZEDO_PC_CORR_ALD) return ZEDO_E_BADARG;
+    if (has_predictor && (!h_pA || !h_pB || !h_pC)) return ZEDO_E_BADARG;
+    if (corrector == ZEDO_PC_CORR_NONE) n_corr = 0;
+    if (n_corr > 0 && !h_corr) return ZEDO_E_BADARG;
+    zedo_pc_plan *p = new (std::nothrow) zedo_pc_plan();
+    if (!p) return (int)hipErrorOutOfMemory;
+    p->S = S; p->has_pred = has_predictor != 0; p->corr = n_corr > 0 ? corrector : ZEDO_PC_CORR_NONE; p->n_corr = n_corr;
+    p->sched = nullptr;
+    p->ns.assign(h_net_scale, h_net_scale + S);
+    if (p->has_pred) {
+        p->pa.assign(h_pA, h_pA + S); p->pc.resize(S); p->pz.assign(h_pC, h_pC + S);
+        for (int i = 0; i < S; ++i) {
+            p->pc[i] = h_pB[i] * h_net_scale[i];
+#ifdef ZEDO_MUT_PC_NOISE    // tools/mutation_check.py only
+            p->pz[i] = (float)((double)h_pC[i] * (1.0 + 1e-4));
+#endif
+        }
+    }
+    if (p->corr == ZEDO_PC_CORR_ALD) {
+        p->cc.resize(S); p->cz.resize(S);
+        for (int i = 0; i < S; ++i) {
+            p->cc[i] = h_corr[i] * h_net_scale[i];
+            p->cz[i] = (float)std::sqrt(2.0 * (double)h_corr[i]);
+        }
+    } else if (p->corr == ZEDO_PC_CORR_LANGEVIN) {
+        p->factor.assign(h_corr, h_corr + S);
+    }
+    // the a / c tables of the schedule are not used by this path; its SDE parameters are the header's defaults
+    const int rc = zedo_schedule_create(w, h_label, S, 1.0f, 0.1f, 20.0f, 1000, stream, &p->sched);
+    if (rc != ZEDO_OK) { delete p; return rc; }
+    *out = p;
+    return ZEDO_OK;
+}
+
+extern "C" void zedo_pc_plan_destroy(zedo_pc_plan_t *p) {
+    if (!p) return;
+    zedo_schedule_destroy(p->sched);
+    delete p;
+}
+
+// the network's workspace holds everything: eps of a Langevin step sits where zedo_score_eps keeps it (h1), the two [B] norm
+// vectors and the two step-size floats in h, which is dead between post_dense and the next pre_dense
+extern "C" size_t zedo_pc_workspace_bytes(const zedo_pc_plan_t *p, int B) { return p ? zedo_workspace_bytes(B) : 0; }
+
+extern "C" int zedo_pc_step(const zedo_weights_t *w, const zedo_pc_plan_t *p, int step, float *d_x, float *d_x_mean,
+                            const float *const *h_z, int B, void *d_workspace, size_t workspace_bytes, void *stream) {
+    if (!w || !p || !d_x || !d_workspace || B < 1 || step < 0 || step >= p->S) return ZEDO_E_BADARG;
+    for (int k = 0; k < p->n_corr; ++k)
+        if (!h_z || !h_z[k]) return ZEDO_E_BADARG;
+    if (workspace_bytes < zedo_workspace_bytes(B)) return ZEDO_E_WORKSPACE;
+    const size_t cap = chunk_rows_cap();
+    if (p->corr == ZEDO_PC_CORR_LANGEVIN && (size_t)B > cap) return ZEDO_E_BADARG;      // the mean spans the whole call
+    hipStream_t st = (hipStream_t)stream;
+    const float *z_pred = (p->has_pred && h_z) ? h_z[p->n_corr] : nullptr;
+    const float pz = p->has_pred ? p->pz[step] : 0.0f;
+    const float *tb = p->sched->d_tbias + (size_t)step * NLAYER * HID;
+    const int D = w->J3;
+    for (size_t r0 = 0; r0 < (size_t)B; r0 += cap) {
+        const int Bc = (int)std::min(cap, (size_t)B - r0), Bp = round_up(Bc, BATCH_PAD);
+        Ws k = carve(d_workspace, B);
+        HIPCHK(launch_pack_rows(d_x + r0 * D, k.xpad, Bc, Bp, D, st));
+        const Net net{w, k.xpad, k.h, k.h1, Bp, (int)k.rows, st};
+        for (int c = 0; c < p->n_corr; ++c) {
+            const float *z = h_z[c] + r0 * D;
+            if (p->corr == ZEDO_PC_CORR_ALD) {
+                HIPCHK(net.all(tb, true, 1.0f, p->cc[step], nullptr));
+                HIPCHK(launch_pc_noise(k.xpad, z, p->cz[step], Bc, D, st));
+            } else {
+                HIPCHK(net.all(tb, false, 0.f, 0.f, k.h1));
+                HIPCHK(launch_pc_langevin(k.xpad, k.h1, z, p->factor[step], p->ns[step], k.h, k.h + k.rows, k.h + 2 * k.rows, Bc, D, st));
+            }
+        }
+        if (p->has_pred) HIPCHK(net.all(tb, true, p->pa[step], p->pc[step], nullptr));
+        HIPCHK(launch_pc_finish(k.xpad, (pz != 0.0f && z_pred) ? z_pred + r0 * D : nullptr, pz, d_x + r0 * D,
+                                d_x_mean ? d_x_mean + r0 * D : nullptr, Bc, D, st));
+    }
+    return ZEDO_OK;
+}
+
 extern "C" int zedo_ipo_fit_resume(const float *d_x0, const float *d_uv, const float *d_K, const int *h_keylist, int k,
                                    int axes_mask, float ipo_T, float min_scale, float max_scale, int iters,
                                    double normaliser, float *d_R, float *d_T, float *d_q, float *d_scale,

@@ -228,4 +228,15 @@ hipError_t launch_reproj_degenerate(const float *geom, int N, int J, int *d_coun
 hipError_t launch_min_mpjpe(const float *pred, const double *gt, int B, int N, int J, long long row_offset,
                             int procrustes, double *err, double *best, int *best_h, hipStream_t st);
 
+
+// predictor-corrector step kernels (zedo_pc.hip); z: the caller's noise draw, unpadded [B][D]
+// xpad[b][c] += coef z[b][c] on the B real rows
+hipError_t launch_pc_noise(float *xpad, const float *z, float coef, int B, int D, hipStream_t st);
+// x_mean (may be null) = xpad rows, x = xpad rows + coef z (z == nullptr: x = xpad rows): the unpack of a pc step
+hipError_t launch_pc_finish(const float *xpad, const float *z, float coef, float *x, float *x_mean, int B, int D, hipStream_t st);
+// one Langevin corrector step on the padded state: s = factor (mean||z|| / (|net_scale| mean||eps||))^2 over the B real rows,
+// x = (x + s net_scale eps) + sqrt(2 s) z.  eps [Bp][64]; n_eps, n_z [B] and scal [2] are device scratch.
+hipError_t launch_pc_langevin(float *xpad, const float *eps, const float *z, float factor, float net_scale, float *n_eps,
+                              float *n_z, float *scal, int B, int D, hipStream_t st);
+
 }  // namespace zedo

@@ -56,6 +56,10 @@ SIGNATURES = {
     "zedo_reproj_grad": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _ll, _vp]),
     "zedo_score_eps": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _vp]),
     "zedo_sde_step": (_i, [_vp, _vp, _i, _vp, _i, _vp, _sz, _vp]),
+    "zedo_pc_plan_create": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, ctypes.POINTER(_vp)]),
+    "zedo_pc_plan_destroy": (None, [_vp]),
+    "zedo_pc_workspace_bytes": (_sz, [_vp, _i]),
+    "zedo_pc_step": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "zedo_oil_run": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ll, _vp, _sz, _vp]),
     "zedo_ipo_fit": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _d, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _vp]),
     "zedo_ipo_fit_resume": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _d, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
@@ -121,7 +125,7 @@ def _device_of(*objs):
     for o in objs:
         if o is None:
             continue
-        d = o.device if isinstance(o, (torch.Tensor, Weights, Schedule)) else None
+        d = o.device if isinstance(o, (torch.Tensor, Weights, Schedule, PcPlan)) else None
         if d is None:
             continue
         d = torch.device(d)
@@ -246,6 +250,42 @@ class Schedule:
             self._h = None
 
 
+PC_CORR = {"none": 0, "langevin": 1, "ald": 2}      # ZEDO_PC_CORR_* of include/zedo_hip.h
+
+
+class PcPlan:
+    """Per-step scalars and time-bias rows of a generic predictor-corrector sampler for S steps (zedo_pc_plan_create).
+    `coeffs`: what lib.algorithms.advanced._pc_coeffs.coefficients returns (fp32 arrays of length S)."""
+
+    def __init__(self, weights, coeffs):
+        _need_gpu()
+        f = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1))
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_vp)
+        label, ns, pA, pB, pC, corr = (f(getattr(coeffs, k)) for k in ("label", "net_scale", "pA", "pB", "pC", "corr"))
+        self.S = int(label.size)
+        for a in (ns, pA, pB, pC, corr):
+            if a is not None and a.size != self.S:
+                raise ZedoError(f"PcPlan: every coefficient array must have {self.S} entries")
+        self.has_predictor, self.corrector, self.n_corr = bool(coeffs.has_predictor), int(coeffs.corrector), int(coeffs.n_corr)
+        if self.corrector == PC_CORR["none"]:
+            self.n_corr = 0
+        self.n_draws = self.n_corr + int(self.has_predictor)
+        self.label, self.pC = label, pC
+        self.weights = weights  # keep alive
+        self.device = weights.device
+        self._h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(_lib.zedo_pc_plan_create(weights._h, self.S, ptr(label), ptr(ns), int(self.has_predictor), ptr(pA), ptr(pB),
+                                            ptr(pC), self.corrector, self.n_corr, ptr(corr), _stream(self.device),
+                                            ctypes.byref(self._h)))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.zedo_pc_plan_destroy(h)
+            self._h = None
+
+
 def workspace_bytes(B):
     return int(_lib.zedo_workspace_bytes(int(B)))
 
@@ -318,6 +358,31 @@ def sde_step(weights, sched, step, x):
     with torch.cuda.device(dev):
         ws = workspace(B, dev)
         _check(_lib.zedo_sde_step(weights._h, sched._h, int(step), _p(x), B, _p(ws, torch.uint8), ws.numel(), _stream(dev)))
+    return x
+
+
+def pc_step(weights, plan, step, x, noise=(), x_mean=None):
+    """One generic predictor-corrector call (zedo_pc_step): x <- x_new in place; x_mean (optional tensor like x) receives the
+    noise-free update.  noise: the caller's draws in the reference's order (corrector steps, then the predictor); the predictor's
+    entry may be None or missing = keep x_mean only (x then returns x_mean)."""
+    _need_gpu()
+    noise = list(noise)
+    dev = _device_of(weights, plan, x, x_mean, *noise)
+    B = x.shape[0]
+    if len(noise) < plan.n_corr or len(noise) > plan.n_draws:
+        raise ZedoError(f"pc_step: this plan takes {plan.n_corr} to {plan.n_draws} noise draws, got {len(noise)}")
+    for z in noise:
+        if z is not None and z.shape != x.shape:
+            raise ZedoError(f"pc_step: a noise draw has shape {tuple(z.shape)}, the state {tuple(x.shape)}")
+    if x_mean is not None and x_mean.shape != x.shape:
+        raise ZedoError("pc_step: x_mean must have the shape of x")
+    zs = (ctypes.c_void_p * max(plan.n_draws, 1))()
+    for i, z in enumerate(noise):
+        zs[i] = None if z is None else _p(z).value
+    with torch.cuda.device(dev):
+        ws = workspace(B, dev)
+        _check(_lib.zedo_pc_step(weights._h, plan._h, int(step), _p(x), _p(x_mean), ctypes.cast(zs, _vp), B, _p(ws, torch.uint8),
+                                 ws.numel(), _stream(dev)))
     return x
 
 
