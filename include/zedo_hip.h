@@ -63,7 +63,11 @@ const char *zedo_error_string(int code);
  *       b{b}_dense{k}_t.{weight[H,E],bias[H]}, b{b}_gnorm{k}.{weight,bias}[H],
  *   post_dense.{weight[J3,H],bias[J3]}
  * Supported: hidden H = 1024 (GroupNorm(32): groups of 32 channels), embed E = 512,
- * J3 = n_joints*joint_dim <= 64, n_blocks = 2.  n_floats must equal the exact total.
+ * 1 <= J3 = n_joints*joint_dim <= 64, n_blocks = 2.  n_floats must equal the exact total.
+ * Which entry point takes which size: zedo_score_eps, zedo_sde_step, zedo_pc_step - every J3 of the handle, pose rows
+ * [B][J3]; zedo_reproj_prepare, zedo_reproj_degenerate, zedo_rotate_init, zedo_min_mpjpe - any J >= 1; zedo_ipo_fit(_resume) -
+ * any J >= 1 with 1..17 key indices < J; zedo_oil_run (J3 == 51) and zedo_reproj_grad (J == 17) are the 17-joint, 3-coordinate
+ * path only and return ZEDO_E_BADARG otherwise (tests/test_joint_counts_gpu.py holds each of these to the float64 oracle).
  * Synchronises `stream` before returning (h_params may be freed by the caller).
  */
 int zedo_weights_create(const float *h_params, size_t n_floats, int n_joints, int joint_dim, int hidden,
@@ -245,6 +249,11 @@ int zedo_rotate_init(const float *d_x0, const float *d_R, float *d_x, int B, int
  * d_pred [B,J,3] fp32 rows (h,n); d_gt [N,J,3] float64, root-centred, metres.
  * d_err [B] float64 (output, required); d_best [N] float64; d_best_h [N] int32 (first minimum, the
  * np.argmin rule).  Poses with no local row get +inf / -1.
+ * Any J >= 1.  Alignments of rank 2 (planar joints, three joints) and rank 1 (collinear joints, two joints) return the
+ * reference's value: the error does not depend on how the null directions of the SVD are completed.  With procrustes != 0
+ * and NO direction at all - J == 1, or every joint of the prediction or of the ground truth in one point - the call is
+ * undefined, as the reference is (its SVD is handed 0 / 0 and raises): the kernel writes NaN for such a row, which then
+ * poisons its pose's minimum like any NaN.
  */
 int zedo_min_mpjpe(const float *d_pred, const double *d_gt, int B, int N, int J, long long row_offset,
                    int procrustes, double *d_err, double *d_best, int *d_best_h, void *stream);

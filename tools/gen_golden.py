@@ -59,8 +59,8 @@ def ref_config():
     )
 
 
-def ref_model(weights, dtype=torch.float32):
-    m = ScoreModelFC_Adv(ref_config(), n_joints=17, joint_dim=3, hidden_dim=1024, embed_dim=512, cond_dim=3)
+def ref_model(weights, dtype=torch.float32, n_joints=17, joint_dim=3):
+    m = ScoreModelFC_Adv(ref_config(), n_joints=n_joints, joint_dim=joint_dim, hidden_dim=1024, embed_dim=512, cond_dim=3)
     sd = {k: torch.tensor(v) for k, v in weights.items()}
     sd["sigmas"] = torch.tensor(syn.sigmas_buffer())
     m.load_state_dict(sd, strict=True)
@@ -441,6 +441,83 @@ def gen_eval():
         deg[f"deg_{tag}_gt"], deg[f"deg_{tag}_pred"], deg[f"deg_{tag}_err_p2"], deg[f"deg_{tag}_aligned"] = G, P, e, Zd
     out.update(deg)
     save("eval_multi", **out)
+
+JOINT_COUNT_SIZES = [(1, 1), (1, 3), (16, 3), (14, 4), (19, 3), (21, 3), (16, 4)]      # J3 = 1, 3, 48, 56, 57, 63, 64
+
+
+def gen_joint_counts():
+    """Skeletons other than 17 x 3 (every other capture is 17 joints): the network for seven (n_joints, joint_dim) sizes up to the 64
+    coordinates the C ABI accepts, in fp32 and from the .double() model; procrustes / MPJPE for J = 2, 3, 5, 16, 21; rank-1 alignments
+    at J = 17 (prediction collinear on a coordinate axis / in a random direction, both sets collinear); and what procrustes does with a
+    single joint.  Weights are not stored: make_weights(seed=0, n_joints=, joint_dim=) and their checksum."""
+    out = dict(sizes=np.array(JOINT_COUNT_SIZES), ts=np.array([0.1, 0.0555, 0.01], dtype=np.float32))
+    for nj, jd in JOINT_COUNT_SIZES:
+        tag = f"{nj}x{jd}"
+        w = syn.make_weights(seed=0, n_joints=nj, joint_dim=jd)
+        out[f"sha_{tag}"] = np.array(syn.weights_checksum(w))
+        g = np.random.Generator(np.random.Philox(key=[7, 100 + nj * jd]))
+        x = (0.3 * g.standard_normal((8, nj, jd))).astype(np.float32)
+        m32, m64 = ref_model(w, n_joints=nj, joint_dim=jd), ref_model(w, torch.float64, n_joints=nj, joint_dim=jd)
+        e32, e64 = [], []
+        with torch.no_grad():
+            for t in out["ts"]:
+                labels = torch.ones(8) * torch.tensor(t) * 999
+                e32.append(m32(torch.tensor(x), labels, None, None).numpy())
+                e64.append(m64(torch.tensor(x).double(), labels.double(), None, None).numpy())
+        out[f"x_{tag}"], out[f"eps_{tag}"], out[f"eps64_{tag}"] = x, np.stack(e32), np.stack(e64)
+        assert out[f"eps_{tag}"].shape == (3, 8, nj, jd) and out[f"eps64_{tag}"].dtype == np.float64
+
+    def errors(G, P):
+        """the inner statements of eval_multi (h36m.py:402-408) on root-centred float64 ground truth [N,J,3] and fp32 predictions [N,H,J,3]"""
+        e1, e2 = np.zeros(P.shape[:2]), np.zeros(P.shape[:2])
+        for n in range(P.shape[0]):
+            for h in range(P.shape[1]):
+                e1[n, h] = np.mean(np.sqrt(np.square(P[n, h] - G[n]).sum(axis=1)))
+                Z = procrustes(G[n].copy(), P[n, h].copy())[1]
+                e2[n, h] = np.mean(np.sqrt(np.square(Z - G[n]).sum(axis=1)))
+        return e1, e2
+
+    for J in (2, 3, 5, 16, 21):
+        g = np.random.Generator(np.random.Philox(key=[7, 200 + J]))
+        G = 0.3 * g.standard_normal((6, J, 3))
+        G = G - G[:, 0:1]
+        P = (G[:, None] + 0.05 * g.standard_normal((6, 4, J, 3))).astype(np.float32)
+        P[::3, 3] = (G[::3] * np.array([-1.0, 1.0, 1.0]) * 1.3 + 0.2).astype(np.float32)        # a mirrored hypothesis
+        out[f"gt_j{J}"], out[f"pred_j{J}"] = G, P
+        out[f"err_p1_j{J}"], out[f"err_p2_j{J}"] = errors(G, P)
+    # rank-1 alignments at J = 17: A0^T B0 has ONE non-zero singular value
+    g = np.random.Generator(np.random.Philox(key=[7, 217]))
+    unit = lambda v: v / np.linalg.norm(v)
+    G = 0.3 * g.standard_normal((3, 17, 3))
+    G = G - G[:, 0:1]
+    t = 0.3 * g.standard_normal((3, 17))
+    t = t - t[:, 0:1]
+    axis = np.zeros((3, 17, 3))
+    for n in range(3):
+        axis[n, :, (2, 0, 1)[n]] = t[n]                                                        # exactly on the z, x and y axis
+    rnd = np.stack([t[n][:, None] * unit(g.standard_normal(3))[None] for n in range(3)])
+    Gl = np.stack([(0.3 * g.standard_normal(17))[:, None] * unit(g.standard_normal(3))[None] for n in range(3)])
+    Gl[0] = 0.0
+    Gl[0, :, 0] = 0.3 * g.standard_normal(17)                                                   # both exactly on axes: x against z
+    Gl = Gl - Gl[:, 0:1]
+    both = rnd.copy()
+    both[0] = axis[0]
+    for tag, Gc, Pc in (("axis", G, axis), ("dir", G, rnd), ("both", Gl, both)):
+        P = Pc.astype(np.float32)[:, None]
+        out[f"r1_{tag}_gt"], out[f"r1_{tag}_pred"] = Gc, P[:, 0]
+        e1, e2 = errors(Gc, P)
+        out[f"r1_{tag}_err_p1"], out[f"r1_{tag}_err_p2"] = e1[:, 0], e2[:, 0]
+    # one joint: centring leaves nothing, A_norm = B_norm = 0 and the matrix handed to the SVD is 0 / 0
+    G1, P1 = np.zeros((1, 3)), np.array([[0.1, -0.2, 0.05]], np.float32)
+    out["j1_err_p1"] = np.float64(np.mean(np.sqrt(np.square(P1 - G1).sum(axis=1))))
+    try:
+        with np.errstate(all="ignore"):
+            Z = procrustes(G1.copy(), P1.copy())[1]
+        out["j1_p2_behaviour"], out["j1_err_p2"] = np.array("returns"), np.float64(np.mean(np.sqrt(np.square(Z - G1).sum(axis=1))))
+    except Exception as e:      # recorded, not judged
+        out["j1_p2_behaviour"] = np.array("raises " + type(e).__name__)
+    print("J = 1 with alignment:", out["j1_p2_behaviour"], out.get("j1_err_p2"))
+    save("joint_counts", **out)
 
 
 def gen_driver():
@@ -1217,7 +1294,7 @@ def gen_driver_pw3d_full_c_oil64():
 
 
 GENS = dict(model=gen_model, weights_alt=gen_weights_alt, pc_step=gen_pc_step, reproj=gen_reproj, ipo=gen_ipo, ipo_custom=gen_ipo_custom, oil=gen_oil,
-            eval=gen_eval, driver=gen_driver, datasets=gen_datasets,
+            eval=gen_eval, joint_counts=gen_joint_counts, driver=gen_driver, datasets=gen_datasets,
             driver_files=gen_driver_files, samplers=gen_samplers, pc_generic=gen_pc_generic, pc_generic_loop=gen_pc_generic_loop, hp3d_ski=gen_3dhp_ski, driver_full=gen_driver_full,
             driver_h36m_full=gen_driver_h36m_full, driver_pw3d_full=gen_driver_pw3d_full,
             driver_h36m_full_f64=gen_driver_h36m_full_f64, driver_pw3d_full_f64=gen_driver_pw3d_full_f64,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: eleven one-line arithmetic mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: thirteen one-line arithmetic mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -30,6 +30,9 @@ MUTANTS = [
     # the native predictor-corrector step (zedo_pc_step)
     ("ZEDO_MUT_PC_NOISE", "pc step: the predictor's noise coefficient C * (1 + 1e-4) (zedo_capi.hip plan; advanced/sampling.py:185-191)"),
     ("ZEDO_MUT_PC_MEAN", "pc step, Langevin: mean ||eps|| divided by the padded row count instead of B (zedo_pc.hip; advanced/sampling.py:281-283)"),
+    # skeletons other than 17 x 3 (tests/test_joint_counts_gpu.py): both leave every 51-coordinate test green
+    ("ZEDO_MUT_KZERO8", "pre_dense: k = 56..63 vouched zero for every handle, also J3 = 57..64 (zedo_capi.hip pre_args)"),
+    ("ZEDO_MUT_PACK51", "pack_rows copies at most 51 coordinates of a pose row: J3 = 52..64 lose their last columns (zedo_geom.hip)"),
 ]
 
 

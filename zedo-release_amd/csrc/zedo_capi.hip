@@ -511,6 +511,9 @@ struct Net {
         LayerArgs a{};
         a.Mp = Bp; a.X = xpad; a.ldx = XLD; a.W = w->W_pre; a.ldw = XLD; a.K = XLD; a.N = HID;
         a.kzero8 = w->J3 <= XLD - 8;   // 51 real inputs: k = 56..63 are zero in xpad and in the padded weight
+#ifdef ZEDO_MUT_KZERO8      // tools/mutation_check.py only: vouched for every handle (wrong for J3 = 57..64)
+        a.kzero8 = 1;
+#endif
         a.bias = tb; a.gamma = w->gamma[0]; a.beta = w->beta[0]; a.out = h; a.ldo = HID;
         return a;
     }

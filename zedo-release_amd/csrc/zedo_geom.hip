@@ -18,6 +18,9 @@ __global__ void pack_rows_kernel(const float *__restrict__ x, float *__restrict_
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)Bp * XLD) return;
     const int r = (int)(i / XLD), c = (int)(i % XLD);
+#ifdef ZEDO_MUT_PACK51      // tools/mutation_check.py only: at most the pose width of the shipped datasets is copied (never more than D: no read out of bounds)
+    if (D > 51) D = 51;
+#endif
     xpad[i] = (r < B && c < D) ? x[(size_t)r * D + c] : 0.0f;
 }
 
@@ -304,6 +307,7 @@ struct AdamP {
 __device__ __forceinline__ float sgnf(float e) { return (e > 0.f) ? 1.f : ((e < 0.f) ? -1.f : 0.f); }
 
 constexpr int IPO_KMAX = 17;
+static_assert(IPO_KMAX == 17, "launch_ipo_fit instantiates ipo_row_kernel<1 .. 17>: a longer key list needs its cases");
 constexpr int IPO_TABLE = 2048;      // Adam bias-correction terms of the first IPO_TABLE iterations (the reference runs 500)
 
 struct IpoKeys { int j[IPO_KMAX]; };   // IPO_keylist travels as a kernel argument: no device buffer, no sync
@@ -674,6 +678,7 @@ hipError_t launch_ipo_fit(const float *x0, const float *uv, const float *K, cons
             ZEDO_IPO_ROW_CASE(1) ZEDO_IPO_ROW_CASE(2) ZEDO_IPO_ROW_CASE(3) ZEDO_IPO_ROW_CASE(4) ZEDO_IPO_ROW_CASE(5) ZEDO_IPO_ROW_CASE(6)
             ZEDO_IPO_ROW_CASE(7) ZEDO_IPO_ROW_CASE(8) ZEDO_IPO_ROW_CASE(9) ZEDO_IPO_ROW_CASE(10) ZEDO_IPO_ROW_CASE(11) ZEDO_IPO_ROW_CASE(12)
             ZEDO_IPO_ROW_CASE(13) ZEDO_IPO_ROW_CASE(14) ZEDO_IPO_ROW_CASE(15) ZEDO_IPO_ROW_CASE(16) ZEDO_IPO_ROW_CASE(17)
+            default: return hipErrorInvalidValue;
         }
 #undef ZEDO_IPO_ROW_CASE
         return hipGetLastError();

@@ -40,10 +40,11 @@ __device__ void polar_from_svd(double M[3][3], double R[3][3], double &strace) {
         s[c] = sqrt(M[0][c] * M[0][c] + M[1][c] * M[1][c] + M[2][c] * M[2][c]);
         smax = fmax(smax, s[c]);
     }
-    int nbad = 0, bad = -1;
+    int nbad = 0, bad = -1, good = -1;
     for (int c = 0; c < 3; ++c) {
         if (s[c] > 1e-14 * smax && s[c] > 0) {
             for (int i = 0; i < 3; ++i) U[i][c] = M[i][c] / s[c];
+            good = c;
         } else { ++nbad; bad = c; }
     }
     if (nbad == 1) {
@@ -57,7 +58,24 @@ __device__ void polar_from_svd(double M[3][3], double R[3][3], double &strace) {
                             V[0][2] * (V[1][0] * V[2][1] - V[1][1] * V[2][0]);
         if (detV < 0) for (int i = 0; i < 3; ++i) U[i][bad] = -U[i][bad];
         s[bad] = 0;
-    } else if (nbad > 1) {
+    } else if (nbad == 2) {
+        // rank-1 input (a two-joint skeleton, collinear joints): one column of U is known, V is orthogonal already.  Any
+        // orthonormal completion of U gives the reference's error: the aligned pose has no component along the two null
+        // directions of the ground truth, and the length of the prediction's component there does not depend on the basis.
+        const int g = good, a = (g + 1) % 3, b = (g + 2) % 3;
+        int m = 0;                                                 // the coordinate axis farthest from the known column
+        for (int i = 1; i < 3; ++i) if (fabs(U[i][g]) < fabs(U[m][g])) m = i;
+        double e[3] = {0, 0, 0};
+        e[m] = 1.0;
+        double ua[3] = {U[1][g] * e[2] - U[2][g] * e[1], U[2][g] * e[0] - U[0][g] * e[2], U[0][g] * e[1] - U[1][g] * e[0]};
+        const double na = sqrt(ua[0] * ua[0] + ua[1] * ua[1] + ua[2] * ua[2]);
+        for (int i = 0; i < 3; ++i) U[i][a] = ua[i] / na;
+        U[0][b] = U[1][g] * U[2][a] - U[2][g] * U[1][a];
+        U[1][b] = U[2][g] * U[0][a] - U[0][g] * U[2][a];
+        U[2][b] = U[0][g] * U[1][a] - U[1][g] * U[0][a];
+        s[a] = 0; s[b] = 0;
+    } else if (nbad > 2) {
+        // no direction at all (a zero or non-finite matrix: one joint, or every joint of a set in one point)
         for (int c = 0; c < 3; ++c) for (int i = 0; i < 3; ++i) U[i][c] = (i == c);
         for (int c = 0; c < 3; ++c) for (int i = 0; i < 3; ++i) V[i][c] = (i == c);
     }
@@ -123,6 +141,7 @@ __global__ void row_error_kernel(const float *__restrict__ pred, const double *_
 // 8-byte loads; both land in the LDS ([row][51], odd row stride: a lane reading its own row is bank-conflict free), all loads of the
 // tile in flight at once; then one lane per row as before.
 constexpr int RE_ROWS = 64, RE_D = 17 * 3;
+static_assert(RE_ROWS == 64, "the staged kernels are one wavefront per workgroup: their LDS hand-over relies on it");
 __global__ __launch_bounds__(RE_ROWS) void row_error17_kernel(const float *__restrict__ pred, const double *__restrict__ gt, int B, int N,
                                                                long long row_offset, int procrustes, double *__restrict__ err) {
     __shared__ __attribute__((aligned(16))) float sp[RE_ROWS * RE_D];
@@ -235,6 +254,7 @@ __global__ __launch_bounds__(RE_ROWS) void row_error17_pose_major_kernel(const f
     const long long h_hi = min((row_offset + B - 1) / N, h_lo + h_per_chunk - 1);
     if (h_lo > h_hi) return;
     for (int q = lane; q < poses * RE_D; q += RE_ROWS) sg[q] = gt[(size_t)n0 * RE_D + q];
+    __builtin_amdgcn_wave_barrier();                               // one wave: no instruction, the compiler may not move LDS accesses across it
     // chunk c of hypothesis h: floats [a + 4 c, a + 4 c + 4) of the tensor, a = the first element of the tile rounded down to a multiple of 4
     f32x4 nxt[SEL_T];
     auto fetch = [&](long long h) {
@@ -263,12 +283,14 @@ __global__ __launch_bounds__(RE_ROWS) void row_error17_pose_major_kernel(const f
     fetch(h_lo);
     for (long long h = h_lo; h <= h_hi; ++h) {
         drop();                                                    // tile h: registers -> LDS (one wave: LDS operations execute in order)
+        __builtin_amdgcn_wave_barrier();
         if (h < h_hi) fetch(h + 1);                                // tile h + 1 on its way while tile h is worked on
         const long long loc = h * N + n - row_offset;
         if (n < N && loc >= 0 && loc < B) {
             const int shift = (int)(((h * N + n0 - row_offset) * RE_D) & 3LL);
             err[loc] = row_error(sp + shift + lane * RE_D, sg + lane * RE_D, 17, procrustes);
         }
+        __builtin_amdgcn_wave_barrier();                           // the next drop() overwrites what the lanes have just read
     }
 }
 
