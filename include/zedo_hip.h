@@ -212,7 +212,9 @@ int zedo_oil_run(const zedo_weights_t *w, const zedo_schedule_t *s, float *d_x, 
  * (rot_vect, rot_vect_<axes>, scale) minimising mean |proj(R x0_h[kl] + T0 clamp(scale)) - uv[kl]|
  * where the mean's divisor is `normaliser` (= N*k*2 of the reference batch; pass the GLOBAL value
  * when rows are sharded).  d_x0 [H,J,3] (centred cluster poses), d_uv [N,J,2], d_K [N,3,3],
- * h_keylist[k] joint indices, axes_mask bit0=x bit1=y bit2=z.
+ * h_keylist[k] joint indices, axes_mask bit0=x bit1=y bit2=z (RotOpt's `axis`: 0 = rot_vect and scale only ... 7 = "xyz";
+ * a value outside 0..7 is rejected with ZEDO_E_BADARG, by zedo_ipo_fit_resume as well).  The parameters and Adam moments of an
+ * axis that is not in the mask are never written: d_q holds an exact 0 there (a resumed state: whatever the caller put in).
  * Outputs: d_R [B,3,3], d_T [B,3] = T0*clamp(scale), optional d_q [B,4], d_scale [B] (may be NULL).
  * h_keylist is consumed before the call returns (it travels as a kernel argument); nothing synchronises and nothing is
  * copied (Adam's bias-correction terms are constants of the code object): every call, the first one included, is a plain

@@ -299,13 +299,16 @@ def ipo_loss_and_grads(q, scale, x, T0, K, cond, axes, minT, maxT, normaliser):
 
 
 def ipo_fit(x0k, T0, K, condk, axes="z", minT=0.5, maxT=2.0, iters=500, normaliser=None,
-            lr=0.1, b1=0.9, b2=0.999, adam_eps=1e-8, dtype=np.float32, trace=None):
+            lr=0.1, b1=0.9, b2=0.999, adam_eps=1e-8, dtype=np.float32, trace=None, init=None, it0=0):
     """opt_main.py:180-195: 500 Adam(lr=0.1) iterations on (rot_vect, rot_vect_<axes>, scale).
 
     x0k [B,k,3] = cluster pose restricted to IPO_keylist, condk [B,k,2], T0 [B,1,3].
     Returns (R [B,3,3], T [B,1,3] = T0*clamp(scale), q [B,4], scale [B], last loss).
     trace: optional list receiving (q, scale, loss, exp_avg_q, exp_avg_sq_q, exp_avg_scale, exp_avg_sq_scale,
     |residual| [B,k,2] of the forward that produced this iteration's gradient) copies after each iteration.
+    init: optional Adam state (q [B,4], scale [B], exp_avg_q, exp_avg_sq_q, exp_avg_scale, exp_avg_sq_scale) to continue from
+    (copied and cast to dtype); it0: the number of iterations already applied to it - the bias corrections of the ``iters``
+    iterations run here use it0 + 1 ... it0 + iters.  The defaults are RotOpt's initial values and a fresh optimiser.
     """
     x0k = np.asarray(x0k, dtype=dtype)
     condk = np.asarray(condk, dtype=dtype)
@@ -314,13 +317,16 @@ def ipo_fit(x0k, T0, K, condk, axes="z", minT=0.5, maxT=2.0, iters=500, normalis
     B, k, _ = x0k.shape
     if normaliser is None:
         normaliser = B * k * 2
-    q = np.zeros((B, 4), dtype=dtype)
-    q[:, 0] = 1
-    scale = np.ones(B, dtype=dtype)
-    mq, vq = np.zeros_like(q), np.zeros_like(q)
-    ms, vs = np.zeros_like(scale), np.zeros_like(scale)
+    if init is None:
+        q = np.zeros((B, 4), dtype=dtype)
+        q[:, 0] = 1
+        scale = np.ones(B, dtype=dtype)
+        mq, vq = np.zeros_like(q), np.zeros_like(q)
+        ms, vs = np.zeros_like(scale), np.zeros_like(scale)
+    else:
+        q, scale, mq, vq, ms, vs = (np.array(a, dtype=dtype) for a in init)
     loss = dtype(0)
-    for it in range(1, iters + 1):
+    for it in range(it0 + 1, it0 + iters + 1):
         loss, gq, gs, uv_ = ipo_loss_and_grads(q, scale, x0k, T0, K, condk, axes, minT, maxT, normaliser)
         # torch.optim.Adam single-tensor update (no weight decay / amsgrad)
         step_size = dtype(lr / (1 - b1 ** it))

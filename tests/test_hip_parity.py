@@ -700,6 +700,22 @@ def test_bad_arguments_are_rejected(zh, W):
         zh.ipo_fit(x0, uv, K, [0, 1, 4], "z", 3.0, 0.5, 2.0, 1, 18, 7)
     with pytest.raises(zh.ZedoError):
         zh.ipo_fit(x0, uv, K, [0, 1, 4], "z", 3.0, 0.5, 2.0, 1, 18, 4, row_offset=3)
+    # axes_mask outside 0..7 (raw: the binding builds the mask from letters), both entry points; nothing is written
+    kl = (ctypes.c_int * 3)(0, 1, 4)
+    R, T = torch.full((3, 3, 3), -7.0, device="cuda"), torch.full((3, 3), -7.0, device="cuda")
+    st = torch.full((3, 15), -7.0, device="cuda")
+    fit = lambda m: lib.zedo_ipo_fit(P(x0), P(uv), P(K), ctypes.cast(kl, ctypes.c_void_p), 3, m, 3.0, 0.5, 2.0, 1, 18.0, P(R), P(T),
+                                     None, None, 3, 2, 3, 17, 0, None)
+    resume = lambda m: lib.zedo_ipo_fit_resume(P(x0), P(uv), P(K), ctypes.cast(kl, ctypes.c_void_p), 3, m, 3.0, 0.5, 2.0, 1, 18.0, P(R),
+                                               P(T), None, None, P(st), 0, 3, 2, 3, 17, 0, None)
+    for m in (8, -1, 15, 1 << 16):
+        assert fit(m) == -1 and resume(m) == -1
+    torch.cuda.synchronize()
+    assert bool((R == -7.0).all()) and bool((T == -7.0).all()) and bool((st == -7.0).all())
+    assert fit(7) == 0 and fit(0) == 0 and resume(7) == 0
+    with pytest.raises(zh.ZedoError, match=r"letters of 'xyz'"):     # the binding: a letter outside xyz
+        zh.ipo_fit(x0, uv, K, [0, 1, 4], "xw", 3.0, 0.5, 2.0, 1, 18, 3)
+    assert zh.axes_mask("") == 0 and zh.axes_mask("zx") == 5 and zh.axes_mask("xyz") == 7
     with pytest.raises(zh.ZedoError):
         zh.rotate_init(x0, torch.zeros(7, 3, 3, device="cuda"), 3)
     with pytest.raises(zh.ZedoError):

@@ -319,6 +319,79 @@ def gen_ipo_custom():
     save("ipo_custom", cluster0=centred[0], **out)
 
 
+IPO_GENERAL_KEYLISTS = dict(h36m=([0, 1, 4], 3.0, 0.5), pw3d=(list(range(17)), 8.0, 0.2), k5=IPO_CUSTOM_KEYLISTS["k5"])
+IPO_GENERAL_AXES = ["", "x", "y", "z", "xy", "xz", "yz", "xyz"]
+IPO_GENERAL_SNAPS = {8: (10, 50), 64: (50,)}          # iterations (1-based) whose parameters are stored, per N
+
+
+def gen_ipo_general():
+    """The reference's IPO loop and gradient_field_gen on GENERAL intrinsics (synthetic.general_intrinsics: skew, a homogeneous row
+    other than (0, 0, 1), K22 != 1) and for all eight subsets of rotation axes: the problems of gen_ipo (same clusters and poses) with the
+    detections re-projected through the general K.  A file of its own: the other fixtures stay byte for byte what they were.
+
+    Size: the full float64 traces of 50 iterations for 3 key lists x 8 axis subsets x N = 8 and 64 are 2.6 MB of incompressible
+    mantissas; the file is to stay below tests/golden/joint_counts.npz (125 KiB).  Stored instead: the float64 LOSS of every one of the
+    50 iterations (a function of every pose's parameters at every iteration) and the float64 PARAMETERS of every pose after iteration 50
+    (N = 8: also after iteration 10) - the recurrence is deterministic, so the state after 50 iterations carries the 49 before it.
+    For axes "xy" and "": the reference's fp32 parameters at the same iterations and its fp32 end state after 500 iterations
+    (R | T | scale per pose, and the loss).  gradient_field_gen: fp32 as gen_reproj captures it, and with T given also from double tensors.
+    One array per (N, key list) with the axis subsets stacked in the order of IPO_GENERAL_AXES:
+    an .npz member costs ~350 bytes of headers, which was a third of the file with one member per case."""
+    out = {}
+    clusters = syn.make_clusters(2, seed=5)
+    centred = clusters - clusters[:, 0:1]
+    for N in (8, 64):
+        d = syn.make_poses(N, seed=11 + N)
+        K = syn.general_intrinsics(d["camera_param"], [41, N])
+        uv = syn.project(K, d["db_3d"])
+        out[f"uv_{N}"], out[f"K_{N}"] = uv, K
+        x0 = np.broadcast_to(centred[0][None], (N, 17, 3)).astype(np.float32).copy()
+        snaps = IPO_GENERAL_SNAPS[N]
+        for kname, (kl, ipoT, minT) in IPO_GENERAL_KEYLISTS.items():
+            out[f"keylist_{kname}"] = np.array(kl, np.int32)
+            if (N, kname) == (64, "pw3d"):                    # the 17-joint list at N = 8 only: the file's size limit
+                continue
+            tag = f"{N}_{kname}"
+            loss64, p64 = [], {it: [] for it in snaps}
+            for axes in IPO_GENERAL_AXES:
+                r64 = run_ref_ipo(x0, uv, K, axes, kl, ipoT, minT, 2.0, IPO_TRACE, trace_upto=IPO_TRACE, dtype=torch.float64)
+                loss64.append(r64["trace_loss"])
+                for it in snaps:
+                    p64[it].append(np.concatenate([r64["trace_q"][it - 1], r64["trace_scale"][it - 1][:, None]], 1))
+                if axes in ("xy", ""):
+                    r32 = run_ref_ipo(x0, uv, K, axes, kl, ipoT, minT, 2.0, 500, trace_upto=IPO_TRACE)
+                    at = f"{tag}_{axes or 'none'}"
+                    out[f"p32_{at}"] = np.stack([np.concatenate([r32["trace_q"][it - 1], r32["trace_scale"][it - 1][:, None]], 1) for it in snaps])
+                    out[f"end32_{at}"] = np.concatenate([r32["R"].reshape(N, 9), r32["T"].reshape(N, 3), r32["scale"].reshape(N, 1)], 1)
+                    out[f"loss32_{at}"] = r32["loss"]
+                    out[f"T0_{tag}"], out[f"T0f64_{tag}"] = r32["T0"], r64["T0"]
+            out[f"trace_loss64_{tag}"] = np.stack(loss64)                          # [8 axis subsets (IPO_GENERAL_AXES), 50]
+            for it in snaps:
+                out[f"p64_it{it}_{tag}"] = np.stack(p64[it])                       # [8, N, 5]: rot_vect, x, y, z, scale
+    # gradient_field_gen on 16 poses (the inputs of gen_reproj, general K, detections re-projected), T given and solved, with the
+    # confidences that take both clamps and without confidences
+    d = syn.make_poses(16, seed=3, conf_mode="wild")
+    g = np.random.Generator(np.random.Philox(key=[7, 3]))
+    K = syn.general_intrinsics(d["camera_param"], [41, 16])
+    uv = syn.project(K, d["db_3d"])
+    x = (0.25 * g.standard_normal((16, 17, 3))).astype(np.float32)
+    x[:, 0] = 0
+    Tgiven = (np.array([0.1, -0.2, 5.0]) + 0.1 * g.standard_normal((16, 1, 3))).astype(np.float32)
+    for tag, conf in (("wild", d["db_2d"][:, :, 2].copy()), ("none", None)):
+        c = None if conf is None else torch.tensor(conf.copy())
+        gT = gradient_field_gen(torch.tensor(uv), torch.tensor(x), torch.tensor(K), t=torch.tensor(Tgiven), conf=c)
+        c2 = None if conf is None else torch.tensor(conf.copy())
+        gS, Ts = gradient_field_gen(torch.tensor(uv), torch.tensor(x), torch.tensor(K), conf=c2, returnT=True)
+        out[f"rp_g_given_{tag}"], out[f"rp_g_solve_{tag}"], out[f"rp_T_solve_{tag}"] = gT.numpy(), gS.numpy(), Ts.numpy()
+    # The same call with double tensors (T given: every statement of the function is then evaluated in double; with T solved its
+    # normal equations stay fp32 whatever the input).  The float64 oracle is pinned to THIS: the fp32 output above is itself 1.27e-6
+    # from it, more than the 1e-6 the oracle is held to.  The confidences do not enter with T given.
+    dbl = lambda a: torch.tensor(a).double()
+    out["rp_g_given_f64"] = gradient_field_gen(dbl(uv), dbl(x), dbl(K), t=dbl(Tgiven)).numpy()
+    assert out["rp_g_given_f64"].dtype == np.float64
+    save("ipo_general", cluster0=centred[0], rp_uv=uv, rp_K=K, rp_x=x, rp_T_given=Tgiven, rp_conf_wild=d["db_2d"][:, :, 2], **out)
+
+
 def run_ref_oil(m, x, cond, conf, K, T, S, snaps, dtype=torch.float32):
     """opt_main.py:197-222 (the torch.no_grad block), CPU tensors."""
     fn = ref_sampling_fn(x.shape[0])
@@ -1293,7 +1366,7 @@ def gen_driver_pw3d_full_c_oil64():
 
 
 
-GENS = dict(model=gen_model, weights_alt=gen_weights_alt, pc_step=gen_pc_step, reproj=gen_reproj, ipo=gen_ipo, ipo_custom=gen_ipo_custom, oil=gen_oil,
+GENS = dict(model=gen_model, weights_alt=gen_weights_alt, pc_step=gen_pc_step, reproj=gen_reproj, ipo=gen_ipo, ipo_custom=gen_ipo_custom, ipo_general=gen_ipo_general, oil=gen_oil,
             eval=gen_eval, joint_counts=gen_joint_counts, driver=gen_driver, datasets=gen_datasets,
             driver_files=gen_driver_files, samplers=gen_samplers, pc_generic=gen_pc_generic, pc_generic_loop=gen_pc_generic_loop, hp3d_ski=gen_3dhp_ski, driver_full=gen_driver_full,
             driver_h36m_full=gen_driver_h36m_full, driver_pw3d_full=gen_driver_pw3d_full,

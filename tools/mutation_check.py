@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: thirteen one-line arithmetic mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: sixteen one-line arithmetic mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -33,6 +33,10 @@ MUTANTS = [
     # skeletons other than 17 x 3 (tests/test_joint_counts_gpu.py): both leave every 51-coordinate test green
     ("ZEDO_MUT_KZERO8", "pre_dense: k = 56..63 vouched zero for every handle, also J3 = 57..64 (zedo_capi.hip pre_args)"),
     ("ZEDO_MUT_PACK51", "pack_rows copies at most 51 coordinates of a pose row: J3 = 52..64 lose their last columns (zedo_geom.hip)"),
+    # general intrinsics and all axis subsets (tests/test_general_intrinsics_gpu.py): all three leave every pinhole-K, "z" / "xyz" test green
+    ("ZEDO_MUT_IPO_GPY_K1", "IPO backward: K[1] g_w0 dropped from g_py = (K^T g_w)_y - zero in a pinhole K (zedo_geom.hip ipo_joint_terms)"),
+    ("ZEDO_MUT_IPO_W2_K6", "IPO forward: K[6] p_x dropped from the homogeneous coordinate w2 - zero in a pinhole K (zedo_geom.hip ipo_joint_terms)"),
+    ("ZEDO_MUT_IPO_AXIS_XY", "IPO: rot_vect_y is updated under the x bit of axes_mask, in both kernels - the same for \"z\" and \"xyz\" (zedo_geom.hip)"),
 ]
 
 

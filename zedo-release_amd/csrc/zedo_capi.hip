@@ -773,7 +773,8 @@ extern "C" int zedo_ipo_fit_resume(const float *d_x0, const float *d_uv, const f
                                    float *d_state, int it_begin, int B, int H, int N, int J, long long row_offset,
                                    void *stream) {
     if (!d_x0 || !d_uv || !d_K || !h_keylist || !d_R || !d_T || B < 1 || H < 1 || N < 1 || J < 1 || k < 1 || k > 17 ||
-        iters < 0 || it_begin < 0 || (it_begin > 0 && !d_state) || !(normaliser > 0) || row_offset < 0)
+        iters < 0 || it_begin < 0 || (it_begin > 0 && !d_state) || !(normaliser > 0) || row_offset < 0 || axes_mask < 0 ||
+        axes_mask > 7)
         return ZEDO_E_BADARG;
     if (row_offset + (long long)B > (long long)H * N) return ZEDO_E_BADARG;   // x0[h] would be read out of bounds
     for (int i = 0; i < k; ++i)

@@ -383,13 +383,21 @@ __device__ __forceinline__ void ipo_joint_terms(const float (&K)[9], const float
     const float pz = o.R20 * x + o.R21 * y + o.R22 * z + o.Tz;
     const float w0 = K[0] * px + K[1] * py + K[2] * pz;
     const float w1 = K[3] * px + K[4] * py + K[5] * pz;
+#ifdef ZEDO_MUT_IPO_W2_K6     // tools/mutation_check.py only: the homogeneous row loses its x term (zero in a pinhole K)
+    const float w2 = K[7] * py + K[8] * pz;
+#else
     const float w2 = K[6] * px + K[7] * py + K[8] * pz;
+#endif
     const float gu = sgnf(w0 / w2 - cu) * inv_norm;   // d mean|e| / du
     const float gv = sgnf(w1 / w2 - cv) * inv_norm;
     const float gw0 = gu / w2, gw1 = gv / w2;
     const float gw2 = -gu * ((w0 / w2) / w2) - gv * ((w1 / w2) / w2);  // torch div backward form
     const float gpx = K[0] * gw0 + K[3] * gw1 + K[6] * gw2;       // K^T g_w
+#ifdef ZEDO_MUT_IPO_GPY_K1    // tools/mutation_check.py only: the skew term of the backward product (zero in a pinhole K)
+    const float gpy = K[4] * gw1 + K[7] * gw2;
+#else
     const float gpy = K[1] * gw0 + K[4] * gw1 + K[7] * gw2;
+#endif
     const float gpz = K[2] * gw0 + K[5] * gw1 + K[8] * gw2;
     t[0] = gpx * T0[0] + gpy * T0[1] + gpz * T0[2];
     t[1] = gpx * x; t[2] = gpx * y; t[3] = gpx * z;
@@ -483,7 +491,11 @@ __global__ __launch_bounds__(64) void ipo_kernel(const float *__restrict__ x0, c
     float T0[3];
     ipo_T0(K, uv[(size_t)n * J * 2], uv[(size_t)n * J * 2 + 1], ipo_T, T0);
     AdamP qr{1.f, 0.f, 0.f}, qi{0.f, 0.f, 0.f}, qj{0.f, 0.f, 0.f}, qk{0.f, 0.f, 0.f}, sc{1.f, 0.f, 0.f};
+#ifdef ZEDO_MUT_IPO_AXIS_XY   // tools/mutation_check.py only: rot_vect_y is updated under the x bit ("z" and "xyz" cannot tell)
+    const bool ax = axes_mask & 1, ay = axes_mask & 1, az = axes_mask & 4;
+#else
     const bool ax = axes_mask & 1, ay = axes_mask & 2, az = axes_mask & 4;
+#endif
     // resumable fit: state[b] = (p[5], exp_avg[5], exp_avg_sq[5]) in the order (rot_vect, x, y, z, scale) after
     // it_begin iterations; b1p0 / b2p0 = beta^it_begin.  it_begin == 0 starts from RotOpt's initial values.
     float *stp = state ? state + (size_t)b * 15 : nullptr;
@@ -613,7 +625,11 @@ __global__ __launch_bounds__(IPO_ROW_TB) void ipo_row_kernel(const float *__rest
     float T0[3];
     ipo_T0(K, uv[(size_t)n * J * 2], uv[(size_t)n * J * 2 + 1], ipo_T, T0);
     AdamP qr{1.f, 0.f, 0.f}, qi{0.f, 0.f, 0.f}, qj{0.f, 0.f, 0.f}, qk{0.f, 0.f, 0.f}, sc{1.f, 0.f, 0.f};
+#ifdef ZEDO_MUT_IPO_AXIS_XY   // tools/mutation_check.py only: rot_vect_y is updated under the x bit ("z" and "xyz" cannot tell)
+    const bool ax = axes_mask & 1, ay = axes_mask & 1, az = axes_mask & 4;
+#else
     const bool ax = axes_mask & 1, ay = axes_mask & 2, az = axes_mask & 4;
+#endif
     float *stp = state ? state + (size_t)b * 15 : nullptr;
     if (stp && it_begin > 0) {
         qr = AdamP{stp[0], stp[5], stp[10]}; qi = AdamP{stp[1], stp[6], stp[11]}; qj = AdamP{stp[2], stp[7], stp[12]};

@@ -155,6 +155,28 @@ def make_poses(N, seed=0, conf_mode="ones", rot_z=True, dtype3d=np.float32):
     return dict(db_2d=db_2d, db_3d=cam.astype(dtype3d), camera_param=K.astype(np.float32))
 
 
+def general_intrinsics(K, key):
+    """Pinhole matrices K [N,3,3] -> general 3x3 intrinsics (float32): every entry a pinhole K keeps at 0 or 1 is exercised.
+    K01 ~ 30 N(0,1) and K10 ~ 20 N(0,1) (skew, pixels), K20, K21 ~ 0.02 N(0,1) (the homogeneous row), then the whole matrix
+    times a per-pose factor in [0.5, 1.5): K22 != 1 and det != fx fy.  numpy Philox stream of ``key``; the pinhole entries
+    are kept, so detections have to be re-projected with the result."""
+    g = np.random.Generator(np.random.Philox(key=list(key)))
+    N = len(K)
+    G = np.array(K, dtype=np.float64)
+    G[:, 0, 1] = 30.0 * g.standard_normal(N)
+    G[:, 1, 0] = 20.0 * g.standard_normal(N)
+    G[:, 2, 0] = 0.02 * g.standard_normal(N)
+    G[:, 2, 1] = 0.02 * g.standard_normal(N)
+    G *= (0.5 + g.random(N))[:, None, None]
+    return G.astype(np.float32)
+
+
+def project(K, cam):
+    """Detections uv [N,J,2] (float32) of camera-frame points cam [N,J,3] under K [N,3,3], evaluated in float64."""
+    w = np.einsum("nij,nkj->nki", np.asarray(K, dtype=np.float64), np.asarray(cam, dtype=np.float64))
+    return (w[..., :2] / w[..., 2:]).astype(np.float32)
+
+
 def perturb_ulp(a, seed):
     """A copy of the float32 array ``a`` with every element moved by -1, 0 or +1 unit in the last place
     (equiprobable, Philox stream of ``seed``).  The end-to-end loop is chaotic in the IPO's last iterate (Adam on an

@@ -400,7 +400,12 @@ def oil_run(weights, sched, x, geom, T, step_begin, step_end, switch_step, row_o
 
 
 def axes_mask(axes):
-    return sum({"x": 1, "y": 2, "z": 4}[a] for a in set(axes))
+    """RotOpt's axis string ("", "z", "xy", ... any order) -> the C ABI's axes_mask (bit 0 = x, bit 1 = y, bit 2 = z)."""
+    bits = {"x": 1, "y": 2, "z": 4}
+    bad = sorted(set(axes) - set(bits))
+    if bad:
+        raise ZedoError(f"ipo_fit: rotation axes must be letters of 'xyz', got {axes!r} (unknown: {''.join(bad)!r})")
+    return sum(bits[a] for a in set(axes))
 
 
 def ipo_fit(x0, uv, K, keylist, axes, ipo_T, min_scale, max_scale, iters, normaliser, B, row_offset=0,
