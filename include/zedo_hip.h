@@ -40,7 +40,8 @@ extern "C" {
 
 #define ZEDO_ABI_VERSION 5   /* 3: + zedo_reproj_degenerate, zedo_pose_min, zedo_weights_set_math / zedo_weights_get_math;
                               * 4: + zedo_profile_bracket_ms;  5: + zedo_probe_mfma_peak_f16, workspace rows rounded to 64 again;
-                              * still 5 (additive): + zedo_pc_plan_create / _destroy, zedo_pc_workspace_bytes, zedo_pc_step */
+                              * still 5 (additive): + zedo_pc_plan_create / _destroy, zedo_pc_workspace_bytes, zedo_pc_step;
+                              * still 5 (additive): + zedo_min_mpjpe_both */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -65,7 +66,7 @@ const char *zedo_error_string(int code);
  * Supported: hidden H = 1024 (GroupNorm(32): groups of 32 channels), embed E = 512,
  * 1 <= J3 = n_joints*joint_dim <= 64, n_blocks = 2.  n_floats must equal the exact total.
  * Which entry point takes which size: zedo_score_eps, zedo_sde_step, zedo_pc_step - every J3 of the handle, pose rows
- * [B][J3]; zedo_reproj_prepare, zedo_reproj_degenerate, zedo_rotate_init, zedo_min_mpjpe - any J >= 1; zedo_ipo_fit(_resume) -
+ * [B][J3]; zedo_reproj_prepare, zedo_reproj_degenerate, zedo_rotate_init, zedo_min_mpjpe(_both) - any J >= 1; zedo_ipo_fit(_resume) -
  * any J >= 1 with 1..17 key indices < J; zedo_oil_run (J3 == 51) and zedo_reproj_grad (J == 17) are the 17-joint, 3-coordinate
  * path only and return ZEDO_E_BADARG otherwise (tests/test_joint_counts_gpu.py holds each of these to the float64 oracle).
  * Synchronises `stream` before returning (h_params may be freed by the caller).
@@ -259,6 +260,18 @@ int zedo_rotate_init(const float *d_x0, const float *d_R, float *d_x, int B, int
  */
 int zedo_min_mpjpe(const float *d_pred, const double *d_gt, int B, int N, int J, long long row_offset,
                    int procrustes, double *d_err, double *d_best, int *d_best_h, void *stream);
+
+/* Both protocols from ONE pass over the rows: the reference scores every batch of hypotheses twice from the same preds,
+ * eval_multi(protocol2=False) then eval_multi(protocol2=True) (run/opt_main.py:227-228); this reads d_pred and d_gt once,
+ * evaluates both errors of a row from the same staged operands and takes both arg-mins in one launch.
+ * Outputs are protocol-major: d_err [2][B], d_best [2][N], d_best_h [2][N].  Slot 0 holds what
+ * zedo_min_mpjpe(..., procrustes = 0, ...) writes, slot 1 what procrustes = 1 writes - bit for bit (the same statements
+ * on the same operands): row errors, minima, first arg-min indices, +inf / -1 of poses with no local row, NaN winning
+ * the minimum.  With J == 1 slot 1 is NaN (see above) and slot 0 stays finite.  Each half of d_err is a valid input of
+ * zedo_pose_min.  Inputs, argument checks (ZEDO_E_BADARG, nothing written) and the contract are those of zedo_min_mpjpe:
+ * any J >= 1, any contiguous shard (row_offset); allocates nothing, synchronises nothing, enqueues on `stream` only. */
+int zedo_min_mpjpe_both(const float *d_pred, const double *d_gt, int B, int N, int J, long long row_offset,
+                        double *d_err, double *d_best, int *d_best_h, void *stream);
 
 /* The second half of zedo_min_mpjpe on its own: per pose n the minimum of d_err over the hypotheses present in
  * [0,B) and the first hypothesis index that attains it (np.amin / np.argmin, NaN wins: h36m.py:411-412).  For

@@ -811,6 +811,14 @@ extern "C" int zedo_min_mpjpe(const float *d_pred, const double *d_gt, int B, in
                               int procrustes, double *d_err, double *d_best, int *d_best_h, void *stream) {
     if (!d_pred || !d_gt || !d_err || !d_best || !d_best_h || B < 1 || N < 1 || J < 1 || row_offset < 0)
         return ZEDO_E_BADARG;
-    HIPCHK(launch_min_mpjpe(d_pred, d_gt, B, N, J, row_offset, procrustes, d_err, d_best, d_best_h, (hipStream_t)stream));
+    HIPCHK(launch_min_mpjpe(d_pred, d_gt, B, N, J, row_offset, procrustes, false, d_err, d_best, d_best_h, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
+extern "C" int zedo_min_mpjpe_both(const float *d_pred, const double *d_gt, int B, int N, int J, long long row_offset,
+                                   double *d_err, double *d_best, int *d_best_h, void *stream) {
+    if (!d_pred || !d_gt || !d_err || !d_best || !d_best_h || B < 1 || N < 1 || J < 1 || row_offset < 0)
+        return ZEDO_E_BADARG;
+    HIPCHK(launch_min_mpjpe(d_pred, d_gt, B, N, J, row_offset, 0, true, d_err, d_best, d_best_h, (hipStream_t)stream));
     return ZEDO_OK;
 }

@@ -2,7 +2,8 @@
 // per-pose minimum over hypotheses (reference lib/dataset/h36m.py:394-417, lib/dataset/pw3d.py:302-331,
 // lib/utils/transforms.py:42-127).  One lane per row for the errors, the rows of a wave staged through the LDS
 // with coalesced loads; the arg-min with one wavefront per pose (few poses) or one lane per pose (many: coalesced
-// reads of one hypothesis' errors at a time).
+// reads of one hypothesis' errors at a time).  Both protocols of a batch (run/opt_main.py:227-228) come from one pass: the <true> instantiations
+// of the row-error kernels evaluate both errors on the tile they have staged, and one arg-min launch serves both (zedo_min_mpjpe_both).
 #include "zedo_internal.h"
 
 #include <algorithm>
@@ -126,13 +127,32 @@ __device__ __forceinline__ double row_error(const P &p, const G &g, int J, int p
     return e / J;
 }
 
+// What a row-error kernel writes for local row `loc` from the operands it has staged.  One protocol: err[loc].  BOTH (zedo_min_mpjpe_both,
+// opt_main.py:227-228 scores every batch under both protocols): the same operands are read twice, err [2][B] protocol-major - err[loc] the
+// MPJPE, err[B + loc] the Procrustes-aligned one; `procrustes` is not read.  The statements are row_error's either way: the same bits.
+template <bool BOTH, class P, class G>
+__device__ __forceinline__ void store_row_error(const P &p, const G &g, int J, int procrustes, double *__restrict__ err, long long loc, int B) {
+    if constexpr (!BOTH) err[loc] = row_error(p, g, J, procrustes);
+    else {
+        const double e1 = row_error(p, g, J, 0), e2 = row_error(p, g, J, 1);
+#ifdef ZEDO_MUT_BOTH_SLOT   // tools/mutation_check.py only: the aligned error lands in the slot of the plain one as well
+        (void)e1;
+        err[loc] = e2;
+#else
+        err[loc] = e1;
+#endif
+        err[(long long)B + loc] = e2;
+    }
+}
+
 // Any joint count: one lane per row straight from global memory (rows are J*12 bytes apart: every load instruction touches 64 cache lines).
-__global__ void row_error_kernel(const float *__restrict__ pred, const double *__restrict__ gt, int B, int N, int J,
-                                 long long row_offset, int procrustes, double *__restrict__ err) {
+template <bool BOTH>
+__global__ __launch_bounds__(128) void row_error_kernel(const float *__restrict__ pred, const double *__restrict__ gt, int B, int N, int J,
+                                                        long long row_offset, int procrustes, double *__restrict__ err) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const int n = (int)((row_offset + b) % N);
-    err[b] = row_error(pred + (size_t)b * J * 3, gt + (size_t)n * J * 3, J, procrustes);
+    store_row_error<BOTH>(pred + (size_t)b * J * 3, gt + (size_t)n * J * 3, J, procrustes, err, b, B);
 }
 
 // J = 17 (every dataset of the path), round 6: the 64 rows of a wave arrive as ONE contiguous 13 KB piece of the pose tensor, fetched with
@@ -142,6 +162,7 @@ __global__ void row_error_kernel(const float *__restrict__ pred, const double *_
 // tile in flight at once; then one lane per row as before.
 constexpr int RE_ROWS = 64, RE_D = 17 * 3;
 static_assert(RE_ROWS == 64, "the staged kernels are one wavefront per workgroup: their LDS hand-over relies on it");
+template <bool BOTH>
 __global__ __launch_bounds__(RE_ROWS) void row_error17_kernel(const float *__restrict__ pred, const double *__restrict__ gt, int B, int N,
                                                                long long row_offset, int procrustes, double *__restrict__ err) {
     __shared__ __attribute__((aligned(16))) float sp[RE_ROWS * RE_D];
@@ -164,7 +185,7 @@ __global__ __launch_bounds__(RE_ROWS) void row_error17_kernel(const float *__res
         }
     }
     __syncthreads();
-    if (tid < rows) err[b0 + tid] = row_error(sp + tid * RE_D, sg + tid * RE_D, 17, procrustes);
+    if (tid < rows) store_row_error<BOTH>(sp + tid * RE_D, sg + tid * RE_D, 17, procrustes, err, b0 + tid, B);
 }
 
 // np.amin / np.argmin order: NaN is smaller than everything (a diverged hypothesis poisons the pose, and the first
@@ -185,8 +206,10 @@ __device__ __forceinline__ bool min_takes(double ov, int oh, double v, int h) {
 // the minimum does not depend on the order in which the candidates are visited, so both kernels below return the same bits.
 // Few poses (N below POSE_MIN_LANE_N): one WAVEFRONT per pose, lanes stride over the hypotheses (N * 8 bytes apart: one cache line per
 // lane), butterfly reduction - the parallelism is across hypotheses, a pass is one load deep.
+// blockIdx.y (both kernels): the protocol of a protocol-major err [gridDim.y][B] -> best / best_h [gridDim.y][N]; 0 in a launch of one.
 __global__ void pose_min_wave_kernel(const double *__restrict__ err, int B, int N, long long row_offset,
                                      double *__restrict__ best, int *__restrict__ best_h) {
+    err += (size_t)blockIdx.y * B; best += (size_t)blockIdx.y * N; best_h += (size_t)blockIdx.y * N;
     const int lane = threadIdx.x & 63;
     const int n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (n >= N) return;
@@ -215,6 +238,7 @@ __global__ void pose_min_wave_kernel(const double *__restrict__ err, int B, int 
 constexpr int POSE_MIN_LANE_N = 8192;
 __global__ void pose_min_kernel(const double *__restrict__ err, int B, int N, long long row_offset,
                                 double *__restrict__ best, int *__restrict__ best_h) {
+    err += (size_t)blockIdx.y * B; best += (size_t)blockIdx.y * N; best_h += (size_t)blockIdx.y * N;
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
     long long h0 = (row_offset - n + N - 1) / N;
@@ -242,6 +266,7 @@ __global__ void pose_min_kernel(const double *__restrict__ err, int B, int N, lo
 // (tests/test_hip_parity.py::test_selection_pose_major_kernel_is_bitwise_the_row_major_pair).
 constexpr int SEL_CHUNKS = (RE_ROWS * RE_D + 3) / 4 + 1;          // 16-byte chunks that cover 64 rows at any 4-byte alignment of their first element
 constexpr int SEL_T = (SEL_CHUNKS + RE_ROWS - 1) / RE_ROWS;       // per lane
+template <bool BOTH>
 __global__ __launch_bounds__(RE_ROWS) void row_error17_pose_major_kernel(const float *__restrict__ pred, const double *__restrict__ gt, int B, int N,
                                                                           long long row_offset, int procrustes, int h_per_chunk,
                                                                           double *__restrict__ err) {
@@ -288,20 +313,22 @@ __global__ __launch_bounds__(RE_ROWS) void row_error17_pose_major_kernel(const f
         const long long loc = h * N + n - row_offset;
         if (n < N && loc >= 0 && loc < B) {
             const int shift = (int)(((h * N + n0 - row_offset) * RE_D) & 3LL);
-            err[loc] = row_error(sp + shift + lane * RE_D, sg + lane * RE_D, 17, procrustes);
+            store_row_error<BOTH>(sp + shift + lane * RE_D, sg + lane * RE_D, 17, procrustes, err, loc, B);   // (BOTH: sp / sg read twice, here)
         }
         __builtin_amdgcn_wave_barrier();                           // the next drop() overwrites what the lanes have just read
     }
 }
 
-hipError_t launch_pose_min(const double *err, int B, int N, long long row_offset, double *best, int *best_h, hipStream_t st) {
-    if (N >= POSE_MIN_LANE_N) hipLaunchKernelGGL(pose_min_kernel, dim3((N + 127) / 128), dim3(128), 0, st, err, B, N, row_offset, best, best_h);
-    else hipLaunchKernelGGL(pose_min_wave_kernel, dim3((N + 3) / 4), dim3(256), 0, st, err, B, N, row_offset, best, best_h);
+hipError_t launch_pose_min(const double *err, int B, int N, long long row_offset, double *best, int *best_h, hipStream_t st, int protocols) {
+    if (N >= POSE_MIN_LANE_N) hipLaunchKernelGGL(pose_min_kernel, dim3((N + 127) / 128, protocols), dim3(128), 0, st, err, B, N, row_offset, best, best_h);
+    else hipLaunchKernelGGL(pose_min_wave_kernel, dim3((N + 3) / 4, protocols), dim3(256), 0, st, err, B, N, row_offset, best, best_h);
     return hipGetLastError();
 }
 
-hipError_t launch_min_mpjpe(const float *pred, const double *gt, int B, int N, int J, long long row_offset,
-                            int procrustes, double *err, double *best, int *best_h, hipStream_t st) {
+// The one dispatch of the row-error kernels (zedo_min_mpjpe: BOTH = false; zedo_min_mpjpe_both: BOTH = true, err [2][B]).
+template <bool BOTH>
+static hipError_t launch_row_errors(const float *pred, const double *gt, int B, int N, int J, long long row_offset, int procrustes,
+                                    double *err, hipStream_t st) {
     // (the staged kernels fetch the pose tensor with 16-byte loads: a row pointer that is not 16-byte aligned takes the generic kernel)
     const bool aligned = (reinterpret_cast<uintptr_t>(pred) & 15) == 0;
     if (J == 17 && aligned && N >= POSE_MIN_LANE_N) {              // many poses: the row errors pose-major
@@ -312,15 +339,22 @@ hipError_t launch_min_mpjpe(const float *pred, const double *gt, int B, int N, i
         chunks = std::max(1LL, std::min(chunks, (h_local + 1) / 2));
         const int per = (int)((h_local + chunks - 1) / chunks);
         chunks = (h_local + per - 1) / per;
-        hipLaunchKernelGGL(row_error17_pose_major_kernel, dim3(tiles, (unsigned)chunks), dim3(RE_ROWS), 0, st, pred, gt, B, N, row_offset, procrustes, per, err);
+        hipLaunchKernelGGL(row_error17_pose_major_kernel<BOTH>, dim3(tiles, (unsigned)chunks), dim3(RE_ROWS), 0, st, pred, gt, B, N, row_offset, procrustes, per, err);
     } else
     if (J == 17 && aligned)
-        hipLaunchKernelGGL(row_error17_kernel, dim3((B + RE_ROWS - 1) / RE_ROWS), dim3(RE_ROWS), 0, st, pred, gt, B, N, row_offset, procrustes, err);
+        hipLaunchKernelGGL(row_error17_kernel<BOTH>, dim3((B + RE_ROWS - 1) / RE_ROWS), dim3(RE_ROWS), 0, st, pred, gt, B, N, row_offset, procrustes, err);
     else
-        hipLaunchKernelGGL(row_error_kernel, dim3((B + 127) / 128), dim3(128), 0, st, pred, gt, B, N, J, row_offset, procrustes, err);
-    hipError_t e = hipGetLastError();
+        hipLaunchKernelGGL(row_error_kernel<BOTH>, dim3((B + 127) / 128), dim3(128), 0, st, pred, gt, B, N, J, row_offset, procrustes, err);
+    return hipGetLastError();
+}
+
+// both: err [2][B], best / best_h [2][N], protocol-major (`procrustes` is not read); otherwise the one protocol asked for
+hipError_t launch_min_mpjpe(const float *pred, const double *gt, int B, int N, int J, long long row_offset,
+                            int procrustes, bool both, double *err, double *best, int *best_h, hipStream_t st) {
+    const hipError_t e = both ? launch_row_errors<true>(pred, gt, B, N, J, row_offset, 0, err, st)
+                              : launch_row_errors<false>(pred, gt, B, N, J, row_offset, procrustes, err, st);
     if (e != hipSuccess) return e;
-    return launch_pose_min(err, B, N, row_offset, best, best_h, st);
+    return launch_pose_min(err, B, N, row_offset, best, best_h, st, both ? 2 : 1);
 }
 
 }  // namespace zedo

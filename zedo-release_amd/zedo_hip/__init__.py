@@ -66,6 +66,7 @@ SIGNATURES = {
                                  _i, _ll, _vp]),
     "zedo_rotate_init": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _ll, _vp]),
     "zedo_min_mpjpe": (_i, [_vp, _vp, _i, _i, _i, _ll, _i, _vp, _vp, _vp, _vp]),
+    "zedo_min_mpjpe_both": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp, _vp]),
     "zedo_pose_min": (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp]),
     "zedo_probe_mfma_peak": (_i, [_i, _vp, _vp, _vp]),
     "zedo_probe_mfma_peak_f16": (_i, [_i, _vp, _vp, _vp]),
@@ -454,6 +455,21 @@ def min_mpjpe(pred, gt_centred, N, procrustes=False, row_offset=0):
         best_h = torch.empty((N,), dtype=torch.int32, device=dev)
         _check(_lib.zedo_min_mpjpe(_p(pred), _p(gt_centred, torch.float64), B, N, J, int(row_offset), int(bool(procrustes)),
                                    _p(err, torch.float64), _p(best, torch.float64), _p(best_h, torch.int32), _stream(dev)))
+    return err, best, best_h
+
+
+def min_mpjpe_both(pred, gt_centred, N, row_offset=0):
+    """Both protocols from one pass over the rows (zedo_min_mpjpe_both): -> (err [2,B], best [2,N], best_h [2,N]), slot 0 the
+    bits of min_mpjpe(procrustes=False), slot 1 those of min_mpjpe(procrustes=True)."""
+    _need_gpu()
+    dev = _device_of(pred, gt_centred)
+    B, J = pred.shape[0], pred.shape[1]
+    with torch.cuda.device(dev):
+        err = torch.empty((2, B), dtype=torch.float64, device=dev)
+        best = torch.empty((2, N), dtype=torch.float64, device=dev)
+        best_h = torch.empty((2, N), dtype=torch.int32, device=dev)
+        _check(_lib.zedo_min_mpjpe_both(_p(pred), _p(gt_centred, torch.float64), B, N, J, int(row_offset),
+                                        _p(err, torch.float64), _p(best, torch.float64), _p(best_h, torch.int32), _stream(dev)))
     return err, best, best_h
 
 

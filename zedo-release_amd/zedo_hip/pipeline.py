@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, min_mpjpe, oil_run, reproj_degenerate, reproj_prepare,
+from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, min_mpjpe_both, oil_run, reproj_degenerate, reproj_prepare,
                rotate_init)
 
 
@@ -101,9 +101,8 @@ class Pipeline:
         if x.shape[0] == 0:
             return {k: empty_selection(self.N, self.device) for k in ("p1", "p2")}
         with torch.cuda.device(self.device):
-            _, b1, i1 = min_mpjpe(x, gt, self.N, False, row_offset)
-            _, b2, i2 = min_mpjpe(x, gt, self.N, True, row_offset)
-        return dict(p1=(b1, i1), p2=(b2, i2))
+            _, best, idx = min_mpjpe_both(x, gt, self.N, row_offset)     # one pass over the rows: the bits of the two min_mpjpe calls
+        return dict(p1=(best[0], idx[0]), p2=(best[1], idx[1]))
 
 
 def empty_selection(N, device):
