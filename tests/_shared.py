@@ -1,0 +1,283 @@
+"""What the two sides of a comparison must share, defined once: the noise stream and the case tables of the captures
+(tools/gen_golden.py writes a fixture with them, the tests read it with them), the problem builders that
+lib.dataset.synthetic does not pin, a BASELINE-size capture regenerated from its fixture's seeds, and the plumbing of the GPU tests.
+Imported by the tests, by the child scripts they embed and by tools/ the way tests/_ipo_summary.py is.
+
+Nothing of lib.*, run.*, zedo_hip or zedo_oracle is imported at module level: tools/gen_golden.py runs with the reference's `lib`
+first on sys.path, the tests with the mirror's, and each function binds the one its caller has."""
+import hashlib
+import json
+import os
+import socket
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+# ---- 1. noise and scores -------------------------------------------------------------------------------------------------
+
+class DetNoise:
+    """Replacement for torch.randn_like during capture and test: numpy Philox keyed by the call count, independent of the
+    torch build."""
+
+    def __init__(self):
+        self.calls = 0
+
+    def __call__(self, x):
+        g = np.random.Generator(np.random.Philox(key=[555, self.calls]))
+        self.calls += 1
+        return torch.tensor(g.standard_normal(tuple(x.shape)), dtype=x.dtype, device=x.device)
+
+
+class DetNoise32(DetNoise):
+    """The same stream rounded to fp32 first: what a float32 run draws, handed to a float64 run unchanged."""
+
+    def __call__(self, x):
+        g = np.random.Generator(np.random.Philox(key=[555, self.calls]))
+        self.calls += 1
+        return torch.tensor(g.standard_normal(tuple(x.shape)).astype(np.float32)).to(x.dtype)
+
+
+def analytic_score(x, t, condition, mask):
+    return -(x - 0.3 * condition) / (0.5 + t)[:, None, None]
+
+
+def sampler_inputs():
+    g = np.random.Generator(np.random.Philox(key=[2024, 3]))
+    x = g.standard_normal((6, 17, 3)).astype(np.float32)
+    cond = g.standard_normal((6, 17, 3)).astype(np.float32)
+    t = np.array([0.9, 0.5, 0.1, 0.013, 0.0005, 0.7], np.float32)     # 0.0005 -> discrete step 0 (VE adjacent sigma = 0)
+    return x, cond, t
+
+
+# ---- 2. case tables ------------------------------------------------------------------------------------------------------
+
+SDE_KW = dict(vpsde=dict(beta_min=0.1, beta_max=20.0, N=1000, T=1.0),
+              subvpsde=dict(beta_min=0.1, beta_max=20.0, N=1000, T=1.0),
+              vesde=dict(sigma_min=0.01, sigma_max=50.0, N=1000, T=1.0))
+
+
+def make_sde(sde_lib, name):
+    """sde_lib: the caller's module - the reference's in tools/gen_golden.py, the mirror's in the tests."""
+    return getattr(sde_lib, dict(vpsde="VPSDE", subvpsde="subVPSDE", vesde="VESDE")[name])(**SDE_KW[name])
+
+
+def sampler_cases():
+    """(sde name) x (predictor, probability_flow) and x (corrector) combinations of tests/golden/samplers.npz."""
+    preds = [("euler_maruyama", False), ("euler_maruyama", True), ("reverse_diffusion", False),
+             ("reverse_diffusion", True), ("ancestral_sampling", False)]
+    corrs = ["langevin", "ald"]
+    return list(SDE_KW), preds, corrs
+
+
+PC_LOOP_CASES = [
+    # tag, sde, continuous, predictor, corrector, probability_flow, noise_removal, t (single call; None: chained only), n_steps_each
+    ("vp_rd_langevin", "vpsde", True, "reverse_diffusion", "langevin", False, True, 0.31, 1),
+    ("vp_anc_none_disc", "vpsde", False, "ancestral_sampling", "none", False, True, 0.52, 1),
+    ("vp_em_none_pf", "vpsde", True, "euler_maruyama", "none", True, True, 0.2, 1),
+    ("ve_rd_ald", "vesde", True, "reverse_diffusion", "ald", False, True, 0.4, 1),
+    ("ve_anc_langevin", "vesde", True, "ancestral_sampling", "langevin", False, False, 0.15, 1),
+    ("subvp_em_none_sde", "subvpsde", True, "euler_maruyama", "none", False, False, 0.07, 1),
+    ("subvp_rd_none", "subvpsde", True, "reverse_diffusion", "none", False, True, 0.05, 1),
+    ("vp_em_langevin", "vpsde", True, "euler_maruyama", "langevin", False, True, None, 2),
+]
+PC_GENERIC_CASES = [c for c in PC_LOOP_CASES if c[7] is not None]
+PC_LOOP_STEPS, PC_LOOP_SNAPS, PC_LOOP_ROWS, PC_LOOP_EPS = 20, (1, 10, 20), 70, 0.01
+
+IPO_CASES = [(N, axes, kname) for N in (8, 64) for axes in ("z", "xyz") for kname in ("h36m", "pw3d")]
+
+
+# ---- 3. problem builders that lib.dataset.synthetic does not pin ---------------------------------------------------------
+
+IPO_T, IPO_MIN, IPO_MAX = 5.0, 0.5, 2.0
+IPO_KEYS = [(2, [0, 1]), (5, [0, 2, 4]), (5, [0, 1, 2, 3, 4]), (21, [0, 1, 4, 20]), (21, list(range(4, 21))), (33, [0, 16, 32]),
+            (17, [0, 1, 4])]
+KEYS = [(17, [0, 1, 4]), (17, list(range(17))), (5, list(range(5))), (21, [0, 1, 4, 20])]          # the general-intrinsics problems
+TWIN_AXES = ["", "x", "y", "xy", "xz", "yz"]                                   # "z" and "xyz": the existing twin tests
+
+
+def ulp32(a):
+    return np.spacing(np.abs(a).astype(np.float32)).astype(np.float64)
+
+
+def cameras(g, N):
+    K = np.zeros((N, 3, 3), np.float32)
+    K[:, 0, 0], K[:, 1, 1] = 1145 + 20 * g.standard_normal(N), 1144 + 20 * g.standard_normal(N)
+    K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = 512 + 5 * g.standard_normal(N), 515 + 5 * g.standard_normal(N), 1
+    return K
+
+
+def general_cameras(g, N):
+    from lib.dataset import synthetic as syn
+    return syn.general_intrinsics(cameras(g, N), [44, N])
+
+
+def make_ipo_problem(J, N, H=1):
+    """A J-joint problem for the IPO (lib.dataset.synthetic.make_poses is 17-joint and pinned by checksums): H centred random
+    cluster poses (0.25 m spread), N detections of a rotated, slightly deformed copy of cluster 0 with its root about 5 m in front
+    of the camera, projected with K.  numpy Philox, key [5, J]."""
+    g = np.random.Generator(np.random.Philox(key=[5, J]))
+    cl = 0.25 * g.standard_normal((H, J, 3))
+    cl = cl - cl[:, 0:1]
+    K = cameras(g, N)
+    q = g.standard_normal((N, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    r, i, j, k = q.T
+    R = np.stack([1 - 2 * (j * j + k * k), 2 * (i * j - k * r), 2 * (i * k + j * r), 2 * (i * j + k * r), 1 - 2 * (i * i + k * k),
+                  2 * (j * k - i * r), 2 * (i * k - j * r), 2 * (j * k + i * r), 1 - 2 * (i * i + j * j)], -1).reshape(N, 3, 3)
+    root = np.stack([0.4 * g.standard_normal(N), 0.4 * g.standard_normal(N), 5 + 0.5 * g.standard_normal(N)], -1)
+    p3 = np.einsum("nij,kj->nki", R, cl[0]) + 0.02 * g.standard_normal((N, J, 3)) + root[:, None]
+    w = np.einsum("nij,nkj->nki", K.astype(np.float64), p3)
+    uv = w[..., :2] / w[..., 2:]
+    return cl.astype(np.float32), uv.astype(np.float32), K
+
+
+def problem(J, N, H=1, general=True):
+    """make_ipo_problem; general: its pinhole K replaced by general intrinsics (Philox key [43, 1000 * J + N]) and the detections
+    carried over by the homography K_general K_pinhole^-1, i.e. the same 3-D points projected through the general K.
+    Returns (clusters [H,J,3], uv [N,J,2], K [N,3,3]), float32."""
+    from lib.dataset import synthetic as syn
+    cl, uv, Kp = make_ipo_problem(J, N, H)
+    if not general:
+        return cl, uv, Kp
+    K = syn.general_intrinsics(Kp, [43, 1000 * J + N])
+    hom = np.concatenate([uv.astype(np.float64), np.ones((N, J, 1))], -1)
+    ray = np.einsum("nij,nkj->nki", np.linalg.inv(Kp.astype(np.float64)), hom)
+    return cl, syn.project(K, ray), K
+
+
+def pack(q, sc, mq, vq, ms, vs):
+    """An Adam state of the oracle in the layout of zedo_ipo_fit_resume: param[5], exp_avg[5], exp_avg_sq[5]."""
+    return np.concatenate([q, sc[:, None], mq, ms[:, None], vq, vs[:, None]], axis=1)
+
+
+def unpack(st):
+    return st[:, 0:4], st[:, 4], st[:, 5:9], st[:, 10:14], st[:, 9], st[:, 14]
+
+
+# ---- 4. a BASELINE-size capture ------------------------------------------------------------------------------------------
+
+def sha_of(*arrs):
+    h = hashlib.sha256()
+    for a in arrs:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+class Capture:
+    """tests/golden/<name>.npz of tools/gen_golden.py::_driver_full_size: poses and clusters regenerated from the fixture's seeds
+    (H36M: float64 ground truth) and checked against its hash, the configuration from its fields, the root-centred ground truth
+    the way the capture's dataset class centres it (h36m.py:400-401 in millimetres)."""
+
+    def __init__(self, name):
+        from lib.dataset import synthetic as syn
+        self.name = name
+        self.g = g = np.load(os.path.join(GOLDEN, name + ".npz"))
+        self.N, self.H, self.S = int(g["N"]), int(g["H"]), int(g["S"])
+        self.h36m = str(g["dataset"]) == "h36m"
+        self.d = syn.make_poses(self.N, seed=int(g["seed_pose"]), conf_mode=str(g["conf_mode"]),
+                                dtype3d=np.float64 if self.h36m else np.float32)
+        self.cl = syn.make_clusters(self.H, seed=int(g["seed_cl"]))
+        assert sha_of(self.d["db_2d"], self.d["camera_param"], self.cl) == str(g["inputs_sha"]), "inputs differ from the captured run"
+        self.K = self.d["camera_param"]
+        if self.h36m:
+            self.gt = (self.d["db_3d"] * 1000.0 - (self.d["db_3d"] * 1000.0)[:, 0:1]) / 1000.0
+        else:
+            self.gt = (self.d["db_3d"] - self.d["db_3d"][:, 0:1]).astype(np.float64)
+
+    @property
+    def config(self):
+        from zedo_hip.pipeline import ZeDOConfig
+        g = self.g
+        return ZeDOConfig(IPO_keylist=[int(k) for k in g["keylist"]], IPO_T=float(g["ipo_T"]), IPO_minScaleT=float(g["minT"]),
+                          OIL_iterations=self.S)
+
+    def detections(self, seed):
+        """db_2d with the pixel coordinates moved by -1/0/+1 ulp (stream `seed`; 0: unchanged)."""
+        from lib.dataset import synthetic as syn
+        db2 = self.d["db_2d"].copy()
+        db2[:, :, :2] = syn.perturb_ulp(db2[:, :, :2], seed)
+        return db2
+
+    def pipeline(self, weights, seed=None):
+        """The fused pipeline loaded with this capture; its configuration is pipe.cfg."""
+        from zedo_hip.pipeline import Pipeline
+        db2 = self.d["db_2d"] if seed is None else self.detections(seed)
+        return Pipeline(weights, self.config, "cuda").load(self.cl, db2, self.K)
+
+    def dataset(self):
+        """The object whose eval_multi the reference's run of this capture reported."""
+        if self.h36m:
+            from lib.dataset.h36m import H36MDataset3D
+            return H36MDataset3D.from_arrays(self.d["db_2d"], self.d["db_3d"] * 1000.0, self.K, 2 + (np.arange(self.N) % 15))
+        from lib.dataset.pw3d import PW3D
+        return PW3D.from_arrays(self.d["db_2d"], self.d["db_3d"], self.K)
+
+
+# ---- 5. plumbing ---------------------------------------------------------------------------------------------------------
+
+def dev(a, dtype=torch.float32):
+    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
+
+
+def cfg_path(name):
+    return os.path.join(ROOT, "zedo-release_amd", "configs", "optim", f"concat_pose_optimization_{name}.py")
+
+
+def free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def report_env(rec):
+    """Measured figures go to stdout (-s) and, with ZEDO_PARITY_REPORT=<file>, to that file."""
+    print(json.dumps(rec))
+    if os.environ.get("ZEDO_PARITY_REPORT"):
+        with open(os.environ["ZEDO_PARITY_REPORT"], "a") as f:
+            f.write(json.dumps(rec) + "\n")
+
+
+# Fixtures: a test module imports the ones it uses by name (W needs zh beside it).  A module-scope fixture is built once per
+# importing module.
+
+@pytest.fixture(scope="module")
+def zh():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import zedo_hip
+    return zedo_hip
+
+
+@pytest.fixture(scope="module")
+def W(zh, weights0, math_mode):
+    w = zh.Weights(weights0)              # in the arithmetic mode of this part of the run (conftest.py::math_mode)
+    assert w.math == math_mode
+    return w
+
+
+@pytest.fixture(scope="module")
+def model(weights0):
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from lib.algorithms.advanced.model import ScoreModelFC_Adv
+    from lib.dataset import synthetic as syn
+    from run._driver import load_config
+    m = ScoreModelFC_Adv(load_config(cfg_path("h36m")), 17, 3, 1024, 512, 3)
+    sd = {k: torch.tensor(v) for k, v in weights0.items()}
+    sd["sigmas"] = torch.tensor(syn.sigmas_buffer())
+    m.load_state_dict(sd)
+    return m.eval()
+
+
+@pytest.fixture(autouse=True)
+def one_arithmetic_mode(request, math_mode):
+    """For modules whose subject does not depend on the arithmetic mode of the dense layers: they run in the f32 session only."""
+    if math_mode != "f32":
+        pytest.skip(f"{request.module.__name__} does not depend on the arithmetic mode of the dense layers: covered by the f32 session")

@@ -3,7 +3,6 @@
 (error, first-arg-min) inputs are computed with the oracle, emulating zedo_min_mpjpe's contract
 (+inf / -1 for poses without a local row); the result must equal the unsharded eval_multi."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -11,15 +10,9 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from _shared import free_port
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _local_min(err_rows, N, lo):
@@ -61,7 +54,7 @@ def _worker(rank, world, port, N, H, protocol2, out_dir):
 @pytest.mark.parametrize("protocol2", [False, True])
 def test_two_rank_min_reduction_equals_unsharded(tmp_path, protocol2):
     N, H, world = 23, 5, 2
-    mp.spawn(_worker, args=(world, _free_port(), N, H, protocol2, str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, free_port(), N, H, protocol2, str(tmp_path)), nprocs=world, join=True)
     r = np.load(tmp_path / f"res_{int(protocol2)}.npz")
     assert np.array_equal(r["best"], r["ref_best"])
     assert np.array_equal(r["idx"], r["ref_idx"])          # lowest hypothesis index wins ties, like np.argmin
@@ -107,7 +100,7 @@ def _worker_gather_nan(rank, world, port, out_dir):
 
 
 def test_three_rank_gather_of_uneven_shards_and_nan_minimum(tmp_path):
-    mp.spawn(_worker_gather_nan, args=(3, _free_port(), str(tmp_path)), nprocs=3, join=True)
+    mp.spawn(_worker_gather_nan, args=(3, free_port(), str(tmp_path)), nprocs=3, join=True)
     r = np.load(tmp_path / "gn.npz")
     assert bool(r["ok_gather"]) and bool(r["ok_empty"])
     np.testing.assert_array_equal(r["best"], np.array([0.4, np.nan, np.nan, np.inf, np.nan]))

@@ -23,11 +23,11 @@ import os
 import numpy as np
 import pytest
 
+from _shared import GOLDEN, Capture, W, zh  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 HIP_SEED0 = 100            # reference members use perturbation streams 1, 2, ...; the HIP members 101, 102, ...
 
 
@@ -43,63 +43,25 @@ def _report(rec):
         f.write(json.dumps(rec) + "\n")
 
 
-class Draw:
-    """One configs[2] capture: inputs regenerated from the fixture's seeds, checked against its hash."""
-
-    def __init__(self, name):
-        import hashlib
-        from lib.dataset import synthetic as syn
-        self.name = name
-        g = np.load(os.path.join(GOLDEN, name + ".npz"))
-        self.g = g
-        self.N, self.H, self.S = int(g["N"]), int(g["H"]), int(g["S"])
-        self.d = syn.make_poses(self.N, seed=int(g["seed_pose"]), conf_mode=str(g["conf_mode"]))
-        self.cl = syn.make_clusters(self.H, seed=int(g["seed_cl"]))
-        h = hashlib.sha256()
-        for a in (self.d["db_2d"], self.d["camera_param"], self.cl):
-            h.update(np.ascontiguousarray(a).tobytes())
-        assert h.hexdigest() == str(g["inputs_sha"]), "inputs differ from the captured run"
-        self.keylist = [int(k) for k in g["keylist"]]
-        self.ipo_T, self.minT = float(g["ipo_T"]), float(g["minT"])
-        self.gt = (self.d["db_3d"] - self.d["db_3d"][:, 0:1]).astype(np.float64)
-
-    def detections(self, seed):
-        from lib.dataset import synthetic as syn
-        db2 = self.d["db_2d"].copy()
-        db2[:, :, :2] = syn.perturb_ulp(db2[:, :, :2], seed)
-        return db2
-
-    def pipeline(self, W, seed):
-        from zedo_hip.pipeline import Pipeline, ZeDOConfig
-        cfg = ZeDOConfig(IPO_keylist=self.keylist, IPO_T=self.ipo_T, IPO_minScaleT=self.minT, OIL_iterations=self.S)
-        return Pipeline(W, cfg, "cuda").load(self.cl, self.detections(seed), self.d["camera_param"]), cfg
-
-    def ipo_summary(self, W, seed):
-        import zedo_hip
-        import _ipo_summary as ips
-        pipe, cfg = self.pipeline(W, seed)
-        R, T = zedo_hip.ipo_fit(pipe.x0, pipe.uv, pipe.K, cfg.IPO_keylist, cfg.RotAxes, cfg.IPO_T, cfg.IPO_minScaleT, cfg.IPO_maxScaleT,
-                                cfg.IPO_iterations, self.N * len(cfg.IPO_keylist) * 2, self.H * self.N)
-        cs = torch.stack([R[:, 0, 0], R[:, 1, 0]], -1).reshape(self.H, self.N, 2).cpu().numpy()
-        return ips.summary(cs, T.reshape(self.H, self.N, 3).cpu().numpy(), (self.cl - self.cl[:, 0:1])[:, None],
-                           self.detections(seed)[:, :, :2], self.d["camera_param"], cfg.IPO_keylist, cfg.IPO_T)
-
-    def end_to_end(self, W, seed):
-        import zedo_hip
-        pipe, _ = self.pipeline(W, seed)
-        x, _ = pipe.run()
-        gt = torch.as_tensor(self.gt, device="cuda")
-        _, b1, _ = zedo_hip.min_mpjpe(x, gt, self.N, procrustes=False)
-        _, b2, _ = zedo_hip.min_mpjpe(x, gt, self.N, procrustes=True)
-        return float(b1.mean().item()) * 1e3, float(b2.mean().item()) * 1e3            # mm
-
-
-@pytest.fixture(scope="module")
-def W(weights0, math_mode):
+def ipo_summary(cap, W, seed):
     import zedo_hip
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return zedo_hip.Weights(weights0)
+    import _ipo_summary as ips
+    pipe = cap.pipeline(W, seed)
+    cfg = pipe.cfg
+    R, T = zedo_hip.ipo_fit(pipe.x0, pipe.uv, pipe.K, cfg.IPO_keylist, cfg.RotAxes, cfg.IPO_T, cfg.IPO_minScaleT, cfg.IPO_maxScaleT,
+                            cfg.IPO_iterations, cap.N * len(cfg.IPO_keylist) * 2, cap.H * cap.N)
+    cs = torch.stack([R[:, 0, 0], R[:, 1, 0]], -1).reshape(cap.H, cap.N, 2).cpu().numpy()
+    return ips.summary(cs, T.reshape(cap.H, cap.N, 3).cpu().numpy(), (cap.cl - cap.cl[:, 0:1])[:, None],
+                       cap.detections(seed)[:, :, :2], cap.K, cfg.IPO_keylist, cfg.IPO_T)
+
+
+def end_to_end(cap, W, seed):
+    import zedo_hip
+    x, _ = cap.pipeline(W, seed).run()
+    gt = torch.as_tensor(cap.gt, device="cuda")
+    _, b1, _ = zedo_hip.min_mpjpe(x, gt, cap.N, procrustes=False)
+    _, b2, _ = zedo_hip.min_mpjpe(x, gt, cap.N, procrustes=True)
+    return float(b1.mean().item()) * 1e3, float(b2.mean().item()) * 1e3            # mm
 
 
 DRAWS = ["driver_pw3d_full", "driver_pw3d_full_b", "driver_pw3d_full_c"]
@@ -115,10 +77,10 @@ def test_ipo_end_state_distribution_matches_the_references(W, math_mode, name):
     <= 5.5 (angle), 1.6 (scale), 6.2 (loss) such deviations; in absolute terms 5.1e-3 rad, 1.5e-3, 1.3e-2 px of 43."""
     if math_mode != "f32":
         pytest.skip("the IPO kernel does not depend on the arithmetic mode of the dense layers: covered by the f32 session")
-    dr = Draw(name)
+    dr = Capture(name)
     ref = np.load(os.path.join(GOLDEN, name + "_ipoens.npz"))
     assert str(ref["inputs_sha"]) == str(dr.g["inputs_sha"])
-    ms = [dr.ipo_summary(W, HIP_SEED0 + i) for i in range(1, 13)]
+    ms = [ipo_summary(dr, W, HIP_SEED0 + i) for i in range(1, 13)]
     hip = {k: np.stack([np.asarray(m[k]) for m in ms]) for k in ms[0]}
     rec = {"test": "ipo_end_state_distribution", "capture": name, "members_hip": len(ms), "members_ref": int(ref["q_loss"].shape[0])}
     sl = slice(2, -2)          # the outermost 1 % on either side are single extreme rows
@@ -155,9 +117,9 @@ def test_reference_runs_lie_inside_the_hip_ensemble(W, math_mode, name):
       (b) PA-MPJPE: every reference run within 0.05 mm of the HIP ensemble mean - the bar, outright;
       (c) MPJPE: HIP ensemble mean within max(0.05 mm, E) of the reference mean, E = what the two ensembles can resolve:
           t(0.975) x pooled member sd x sqrt(1/M + 1/K) - with the member sd of the REFERENCE where it has members."""
-    dr = Draw(name)
+    dr = Capture(name)
     M = _members(name, math_mode)
-    e = np.array([dr.end_to_end(W, HIP_SEED0 + i) for i in range(1, M + 1)])
+    e = np.array([end_to_end(dr, W, HIP_SEED0 + i) for i in range(1, M + 1)])
     _ENSEMBLES[(name, math_mode)] = e
     refs = [(float(dr.g["mpjpe"]) * 1e3, float(dr.g["pa_mpjpe"]) * 1e3)]
     k = 1
@@ -228,14 +190,13 @@ def test_contractive_prior_collapses_the_spread(math_mode):
     from lib.dataset import synthetic as syn
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    dr = Draw("driver_pw3d_full")
+    dr = Capture("driver_pw3d_full")
     g = np.load(os.path.join(GOLDEN, "driver_pw3d_full_tied.npz"))
     assert str(g["inputs_sha"]) == str(dr.g["inputs_sha"])
     w = syn.make_weights(seed=0, prior="tied")
     assert syn.weights_checksum(w) == str(g["weights_sha"])
     Wt = zedo_hip.Weights(w)
-    pipe, _ = dr.pipeline(Wt, 0)
-    x, _ = pipe.run()
+    x, _ = dr.pipeline(Wt, 0).run()
     assert bool(torch.isfinite(x).all())
     gt = torch.as_tensor(dr.gt, device="cuda")
     rec = {"test": "contractive_prior", "math": math_mode}
@@ -246,7 +207,7 @@ def test_contractive_prior_collapses_the_spread(math_mode):
                          per_pose_abs_max_mm=float(np.abs(b - g[f"best_{key}"]).max()) * 1e3,
                          per_pose_abs_p99_mm=float(np.percentile(np.abs(b - g[f"best_{key}"]), 99)) * 1e3,
                          per_pose_abs_median_mm=float(np.median(np.abs(b - g[f"best_{key}"]))) * 1e3)
-    ms = np.array([dr.end_to_end(Wt, HIP_SEED0 + i) for i in range(1, 5)])
+    ms = np.array([end_to_end(dr, Wt, HIP_SEED0 + i) for i in range(1, 5)])
     rec["hip_members_sd_mm"] = [float(ms[:, 0].std(ddof=1)), float(ms[:, 1].std(ddof=1))]
     _report(rec)
     print(json.dumps(rec))
@@ -263,26 +224,12 @@ def test_configs1_reference_runs_lie_inside_the_hip_ensemble(W, math_mode):
     so with one hypothesis it is the ALIGNED error the last iterate moves.  A single HIP run sits 0.046 mm from the unperturbed
     reference run in PA-MPJPE: inside the reference's own range.  32 HIP members (0.1 s each): every reference run inside the
     central 95 % (family-wise) in both metrics, ensemble means within max(0.05 mm, resolvable)."""
-    import hashlib
-    from lib.dataset import synthetic as syn
-    from lib.dataset.h36m import H36MDataset3D
-    from zedo_hip.pipeline import Pipeline, ZeDOConfig
-    g = np.load(os.path.join(GOLDEN, "driver_h36m_full.npz"))
-    N, H, S = int(g["N"]), int(g["H"]), int(g["S"])
-    d = syn.make_poses(N, seed=int(g["seed_pose"]), conf_mode=str(g["conf_mode"]), dtype3d=np.float64)
-    cl = syn.make_clusters(H, seed=int(g["seed_cl"]))
-    h = hashlib.sha256()
-    for a in (d["db_2d"], d["camera_param"], cl):
-        h.update(np.ascontiguousarray(a).tobytes())
-    assert h.hexdigest() == str(g["inputs_sha"])
-    cfg = ZeDOConfig(IPO_keylist=[int(k) for k in g["keylist"]], IPO_T=float(g["ipo_T"]), IPO_minScaleT=float(g["minT"]), OIL_iterations=S)
-    ds = H36MDataset3D.from_arrays(d["db_2d"], d["db_3d"] * 1000.0, d["camera_param"], 2 + (np.arange(N) % 15))
+    cap = Capture("driver_h36m_full")
+    g, ds = cap.g, cap.dataset()
     M = 32 if math_mode == "f32" else 8
     e = []
     for i in range(1, M + 1):
-        db2 = d["db_2d"].copy()
-        db2[:, :, :2] = syn.perturb_ulp(db2[:, :, :2], HIP_SEED0 + i)
-        x, _ = Pipeline(W, cfg, "cuda").load(cl, db2, d["camera_param"]).run()
+        x, _ = cap.pipeline(W, HIP_SEED0 + i).run()
         e.append((ds.eval_multi(("rows", x), protocol2=False) * 1e3, ds.eval_multi(("rows", x), protocol2=True) * 1e3))
     e = np.array(e)
     refs = [(float(g["mpjpe"]) * 1e3, float(g["pa_mpjpe"]) * 1e3)]

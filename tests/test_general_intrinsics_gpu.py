@@ -18,47 +18,15 @@ import sys
 import numpy as np
 import pytest
 
-from test_joint_counts_gpu import IPO_MAX, IPO_MIN, IPO_T, _report, dev, make_ipo_problem, ulp32
+from _shared import (IPO_MAX, IPO_MIN, IPO_T, KEYS, TWIN_AXES, dev, general_cameras, pack, problem, report_env as _report, ulp32,
+                     unpack, zh)  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 AXES = ["", "x", "y", "z", "xy", "xz", "yz", "xyz"]
-KEYS = [(17, [0, 1, 4]), (17, list(range(17))), (5, list(range(5))), (21, [0, 1, 4, 20])]
 SLOT = {"x": 1, "y": 2, "z": 3}
-
-
-@pytest.fixture(scope="module")
-def zh():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import zedo_hip
-    return zedo_hip
-
-
-@functools.lru_cache(maxsize=None)
-def problem(J, N, H=1, general=True):
-    """make_ipo_problem (tests/test_joint_counts_gpu.py); general: its pinhole K replaced by general intrinsics (Philox key
-    [43, 1000 * J + N]) and the detections carried over by the homography K_general K_pinhole^-1, i.e. the same 3-D points projected
-    through the general K.  Returns (clusters [H,J,3], uv [N,J,2], K [N,3,3]), float32."""
-    from lib.dataset import synthetic as syn
-    cl, uv, Kp = make_ipo_problem(J, N, H)
-    if not general:
-        return cl, uv, Kp
-    K = syn.general_intrinsics(Kp, [43, 1000 * J + N])
-    hom = np.concatenate([uv.astype(np.float64), np.ones((N, J, 1))], -1)
-    ray = np.einsum("nij,nkj->nki", np.linalg.inv(Kp.astype(np.float64)), hom)
-    return cl, syn.project(K, ray), K
-
-
-def pack(q, sc, mq, vq, ms, vs):
-    """An Adam state of the oracle in the layout of zedo_ipo_fit_resume: param[5], exp_avg[5], exp_avg_sq[5]."""
-    return np.concatenate([q, sc[:, None], mq, ms[:, None], vq, vs[:, None]], axis=1)
-
-
-def unpack(st):
-    return st[:, 0:4], st[:, 4], st[:, 5:9], st[:, 10:14], st[:, 9], st[:, 14]
 
 
 def initial_state(N):
@@ -214,12 +182,6 @@ def test_adam_bias_corrections_across_the_end_of_the_table(zh):
 
 # ---- d. rays, T0, singular systems ------------------------------------------------------------------------------------------------
 
-def general_cameras(g, N):
-    from lib.dataset import synthetic as syn
-    from test_joint_counts_gpu import cameras
-    return syn.general_intrinsics(cameras(g, N), [44, N])
-
-
 @pytest.mark.parametrize("N", [1, 5, 300])
 @pytest.mark.parametrize("J", [1, 17, 21])
 def test_reproj_prepare_on_general_intrinsics(zh, J, N):
@@ -317,7 +279,6 @@ def test_ipo_shard_equals_the_unsharded_rows_on_general_intrinsics(zh):
 
 # ---- f. the two IPO kernels are twins here as well -------------------------------------------------------------------------------
 
-TWIN_AXES = ["", "x", "y", "xy", "xz", "yz"]                                   # "z" and "xyz": the existing twin tests
 IPO_TWINS_GENERAL = r"""
 import hashlib, json, os, sys
 import numpy as np
@@ -325,9 +286,8 @@ root = %r
 sys.path[:0] = [os.path.join(root, "zedo-release_amd"), os.path.join(root, "tests")]
 import torch
 import zedo_hip as zh
-from test_general_intrinsics_gpu import KEYS, TWIN_AXES, IPO_T, IPO_MIN, IPO_MAX, problem
+from _shared import KEYS, TWIN_AXES, IPO_T, IPO_MIN, IPO_MAX, dev, problem
 out = {}
-dev = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda")
 for J, kl in KEYS:
     for N in (8, 64):
         cl, uv, K = problem(J, N, 2)

@@ -7,28 +7,11 @@ reference's own fp32-vs-fp64 drift recorded in the fixtures (SURVEY.md section 7
 import numpy as np
 import pytest
 
+from _shared import IPO_CASES, W, dev, pack, zh  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(scope="module")
-def zh():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import zedo_hip
-    return zedo_hip
-
-
-@pytest.fixture(scope="module")
-def W(zh, weights0, math_mode):
-    w = zh.Weights(weights0)              # in the arithmetic mode of this part of the run (conftest.py::math_mode)
-    assert w.math == math_mode
-    return w
-
-
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
 
 
 def test_abi_version(zh):
@@ -230,9 +213,6 @@ def test_oil_loop_vs_oracle_ragged(zh, W, weights0):
         assert dT <= 1.5 * gapT + 2e-5, (h, dT, gapT)
 
 
-IPO_CASES = [(N, axes, kname) for N in (8, 64) for axes in ("z", "xyz") for kname in ("h36m", "pw3d")]
-
-
 @pytest.mark.parametrize("N,axes,kname", IPO_CASES)
 def test_ipo_trajectory_golden(zh, golden, N, axes, kname):
     """IPO against the reference's own parameter trajectories (tools/gen_golden.py::gen_ipo, opt_main.py:180-195).
@@ -413,8 +393,6 @@ def test_ipo_single_iterations_from_reference_state(zh, golden, N, axes, kname):
         assert np.abs(tr[it][0] - g[f"trace_q64_{tag}"][it]).max() <= 1e-8
         assert np.abs(tr[it][1] - g[f"trace_scale64_{tag}"][it].reshape(-1)).max() <= 1e-8
 
-    def pack(q, sc, mq, vq, ms, vs):
-        return np.concatenate([q, sc[:, None], mq, ms[:, None], vq, vs[:, None]], axis=1)
     z4, z1 = np.zeros((N, 4)), np.zeros(N)
     q0 = z4.copy(); q0[:, 0] = 1
     states = [pack(q0, np.ones(N), z4, z4, z1, z1)] + [pack(t[0], t[1], t[3], t[4], t[5], t[6]) for t in tr]

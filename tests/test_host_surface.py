@@ -1,16 +1,10 @@
 """CPU tests of the host-side mirror of the reference's callable surface (no GPU, no HIP calls)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import zedo_oracle as O
-
-
-def cfg_path(name):
-    return os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "zedo-release_amd", "configs",
-                        "optim", f"concat_pose_optimization_{name}.py")
+from _shared import cfg_path
 
 
 def test_module_paths_of_the_reference_exist():

@@ -12,14 +12,13 @@ Measured (round 5): worst quantile oracle-vs-reference 4.1 / 3.7 / 4.5 (angle), 
 standard deviations on draws A / b / c - against 5.5 / 4.2 / 3.6, 0.9 / 0.9 / 1.6, 6.2 / 5.5 / 5.5 for the HIP kernels: the same band.
 The median quantile sits at ~1 sd for both.  The distance is what two fp32 summation orders are worth inside 500 x 17 operations of
 a fit; the kernels are not farther from the reference than an independent reimplementation is."""
-import json
 import os
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
+from _shared import GOLDEN, report_env
+
 DRAWS = ["driver_pw3d_full", "driver_pw3d_full_b", "driver_pw3d_full_c"]
 
 
@@ -49,9 +48,7 @@ def test_the_numpy_oracle_sits_in_the_same_band_as_the_kernels(name):
     # the record goes to the parity report only when asked for (ZEDO_PARITY_REPORT=<path>): a plain CPU pytest run leaves the tree alone;
     # how the oracle's distance compares with the kernels' is a report (tools/parity_summary.py reads both records), not an assertion
     # about committed fixtures
-    if os.environ.get("ZEDO_PARITY_REPORT"):
-        with open(os.environ["ZEDO_PARITY_REPORT"], "a") as f:
-            f.write(json.dumps(rec) + "\n")
+    report_env(rec)
     # the kernels' own bars (tests/test_ensemble_gpu.py), applied to the oracle: an independent fp32 implementation passes them too
     for k, abs_tol in (("q_angle", 1.2e-2), ("q_scale", 3e-3), ("q_loss", 3e-2)):
         assert dist[k]["max_in_member_sd"] <= 8.0 and dist[k]["max_abs_diff"] <= abs_tol, (k, dist[k])

@@ -15,6 +15,9 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+from _shared import (IPO_KEYS, IPO_MAX, IPO_MIN, IPO_T, cameras, cfg_path, dev, make_ipo_problem, pack, report_env as _report, ulp32,
+                     zh)  # noqa: F401  (fixture)
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
@@ -24,18 +27,6 @@ SIZES = [(1, 1), (1, 3), (16, 3), (14, 4), (19, 3), (21, 3), (16, 4)]          #
 CONTROL = (17, 3)
 BY_J3 = {nj * jd: (nj, jd) for nj, jd in SIZES + [CONTROL]}
 TS = np.array([0.1, 0.05, 0.011], np.float32)
-
-
-@pytest.fixture(scope="module")
-def zh():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import zedo_hip
-    return zedo_hip
-
-
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
 
 
 @functools.lru_cache(maxsize=None)
@@ -78,18 +69,6 @@ def handle(zh, nj, jd, mode, lifted=False):
         _HANDLES[k] = zh.Weights(weights_of(nj, jd, lifted), n_joints=nj, joint_dim=jd, math=mode)
     assert _HANDLES[k].math == mode
     return _HANDLES[k]
-
-
-def _report(rec):
-    """Measured figures go to the parity report (ZEDO_PARITY_REPORT=<file>, as tests/test_pc_native_gpu.py) and to stdout (-s)."""
-    print(json.dumps(rec))
-    if os.environ.get("ZEDO_PARITY_REPORT"):
-        with open(os.environ["ZEDO_PARITY_REPORT"], "a") as f:
-            f.write(json.dumps(rec) + "\n")
-
-
-def ulp32(a):
-    return np.spacing(np.abs(a).astype(np.float32)).astype(np.float64)
 
 
 # ---- 1. the network, single calls ----------------------------------------------------------------------------------------
@@ -380,7 +359,7 @@ def test_model_surface_with_nineteen_joints(zh, math_mode):
     from lib.algorithms.advanced.model import ScoreModelFC_Adv
     from lib.dataset import synthetic as syn
     from run._driver import load_config
-    cfg = load_config(os.path.join(ROOT, "zedo-release_amd", "configs", "optim", "concat_pose_optimization_h36m.py"))
+    cfg = load_config(cfg_path("h36m"))
     m = ScoreModelFC_Adv(cfg, 19, 3, 1024, 512, 3)
     sd = {k: torch.tensor(v) for k, v in weights_of(19, 3).items()}
     sd["sigmas"] = torch.tensor(syn.sigmas_buffer())
@@ -398,13 +377,6 @@ def test_model_surface_with_nineteen_joints(zh, math_mode):
 
 
 # ---- 6. geometry ---------------------------------------------------------------------------------------------------------
-
-def cameras(g, N):
-    K = np.zeros((N, 3, 3), np.float32)
-    K[:, 0, 0], K[:, 1, 1] = 1145 + 20 * g.standard_normal(N), 1144 + 20 * g.standard_normal(N)
-    K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = 512 + 5 * g.standard_normal(N), 515 + 5 * g.standard_normal(N), 1
-    return K
-
 
 @pytest.mark.parametrize("N", [1, 5, 300])
 @pytest.mark.parametrize("J", [1, 2, 16, 17, 21, 40])
@@ -477,30 +449,7 @@ def test_rotate_init_at_other_joint_counts(zh, J):
 
 # ---- 7. IPO --------------------------------------------------------------------------------------------------------------
 
-IPO_T, IPO_MIN, IPO_MAX = 5.0, 0.5, 2.0
-IPO_KEYS = [(2, [0, 1]), (5, [0, 2, 4]), (5, [0, 1, 2, 3, 4]), (21, [0, 1, 4, 20]), (21, list(range(4, 21))), (33, [0, 16, 32]),
-            (17, [0, 1, 4])]
 IPO_IDS = [f"J{J}-k{len(kl)}" for J, kl in IPO_KEYS]
-
-
-def make_ipo_problem(J, N, H=1):
-    """A J-joint problem for the IPO (lib.dataset.synthetic.make_poses is 17-joint and pinned by checksums): H centred random
-    cluster poses (0.25 m spread), N detections of a rotated, slightly deformed copy of cluster 0 with its root about 5 m in front
-    of the camera, projected with K.  numpy Philox, key [5, J]."""
-    g = np.random.Generator(np.random.Philox(key=[5, J]))
-    cl = 0.25 * g.standard_normal((H, J, 3))
-    cl = cl - cl[:, 0:1]
-    K = cameras(g, N)
-    q = g.standard_normal((N, 4))
-    q /= np.linalg.norm(q, axis=1, keepdims=True)
-    r, i, j, k = q.T
-    R = np.stack([1 - 2 * (j * j + k * k), 2 * (i * j - k * r), 2 * (i * k + j * r), 2 * (i * j + k * r), 1 - 2 * (i * i + k * k),
-                  2 * (j * k - i * r), 2 * (i * k - j * r), 2 * (j * k + i * r), 1 - 2 * (i * i + j * j)], -1).reshape(N, 3, 3)
-    root = np.stack([0.4 * g.standard_normal(N), 0.4 * g.standard_normal(N), 5 + 0.5 * g.standard_normal(N)], -1)
-    p3 = np.einsum("nij,kj->nki", R, cl[0]) + 0.02 * g.standard_normal((N, J, 3)) + root[:, None]
-    w = np.einsum("nij,nkj->nki", K.astype(np.float64), p3)
-    uv = w[..., :2] / w[..., 2:]
-    return cl.astype(np.float32), uv.astype(np.float32), K
 
 
 @pytest.mark.parametrize("axes", ["z", "xyz"])
@@ -522,8 +471,6 @@ def test_ipo_single_iterations_from_the_oracle_state(zh, J, kl, N, axes):
     O.ipo_fit(x64[:, kl], O.ipo_init_T(c64, K64, IPO_T, dtype=np.float64), K64, c64[:, kl], axes, IPO_MIN, IPO_MAX, 50,
               normaliser=norm, dtype=np.float64, trace=tr)
 
-    def pack(q, sc, mq, vq, ms, vs):
-        return np.concatenate([q, sc[:, None], mq, ms[:, None], vq, vs[:, None]], axis=1)
     z4, z1 = np.zeros((N, 4)), np.zeros(N)
     q0 = z4.copy(); q0[:, 0] = 1
     states = [pack(q0, np.ones(N), z4, z4, z1, z1)] + [pack(t[0], t[1], t[3], t[4], t[5], t[6]) for t in tr]
@@ -566,9 +513,8 @@ root = %r
 sys.path[:0] = [os.path.join(root, "zedo-release_amd"), os.path.join(root, "tests")]
 import torch
 import zedo_hip as zh
-from test_joint_counts_gpu import IPO_KEYS, IPO_T, IPO_MIN, IPO_MAX, make_ipo_problem
+from _shared import IPO_KEYS, IPO_T, IPO_MIN, IPO_MAX, dev, make_ipo_problem
 out = {}
-dev = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=torch.float32, device="cuda")
 for J, kl in IPO_KEYS:
     for N in (8, 64):
         cl, uv, K = make_ipo_problem(J, N, H=2)

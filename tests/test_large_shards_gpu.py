@@ -9,15 +9,11 @@ import numpy as np
 import pytest
 import torch
 
+from _shared import dev, zh  # noqa: F401  (fixture)
+
 pytestmark = pytest.mark.gpu
 
 CHUNK = 1 << 20
-
-
-@pytest.fixture(scope="module")
-def zh():
-    import zedo_hip
-    return zedo_hip
 
 
 @pytest.mark.parametrize("N,H", [(12500, 50), (24000, 50), (70880, 50)],
@@ -28,7 +24,6 @@ def test_large_shard_slices_are_bitwise_the_full_run(zh, weights0, N, H):
     B = N * H
     d = syn.make_poses(N, seed=404, conf_mode="uniform")
     cl = syn.make_clusters(H, seed=404)
-    dev = lambda a, dt=torch.float32: torch.tensor(np.ascontiguousarray(a), dtype=dt, device="cuda")
     W = zh.Weights(weights0)
     S = 1000
     sched = zh.Schedule(W, O.oil_timestamps(S))

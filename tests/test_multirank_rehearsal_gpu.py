@@ -10,22 +10,16 @@ RCCL-only: the transport itself (nccl process group, device-side collectives ove
 tests/test_rccl_gpu.py.  The N-rank results must be bit-identical to the 1-rank run of the same global problem."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
 
+# Ranks, shards, transport and launcher do not depend on the arithmetic of the dense layers: rehearsed in the default (exact fp32)
+# mode only; the sharded arithmetic of the f16x3 mode is covered by the bitwise slice / virtual-rank tests.
+from _shared import free_port, one_arithmetic_mode  # noqa: F401  (autouse fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def _one_arithmetic_mode(math_mode):
-    """Ranks, shards, transport and launcher do not depend on the arithmetic of the dense layers: rehearsed in the default
-    (exact fp32) mode only; the sharded arithmetic of the f16x3 mode is covered by the bitwise slice / virtual-rank tests."""
-    if math_mode != "f32":
-        pytest.skip("multi-rank rehearsal runs in the default arithmetic mode only")
-
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
@@ -137,14 +131,6 @@ def test_ranks_without_the_gloo_switch_are_refused_on_one_device():
     assert r.returncode != 0 and "ZEDO_DIST_BACKEND=gloo" in r.stderr
 
 
-def _port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _driver(nranks, module, args, tmp):
     """run.opt_main / run.inference under torchrun (the README's recipe): no launcher of ours in front, the ranks
     serialise on the build lock themselves."""
@@ -152,7 +138,7 @@ def _driver(nranks, module, args, tmp):
     e["PYTHONPATH"] = os.path.join(ROOT, "zedo-release_amd") + os.pathsep + e.get("PYTHONPATH", "")
     if nranks > 1:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nranks}", "--master-addr", "127.0.0.1",
-               "--master-port", str(_port()), "-m", module] + args
+               "--master-port", str(free_port()), "-m", module] + args
     else:
         cmd = [sys.executable, "-m", module] + args
     r = subprocess.run(cmd, env=e, cwd=str(tmp), capture_output=True, text=True, timeout=900)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import zedo_oracle as O
+from _shared import IPO_CASES
 from lib.dataset import synthetic as syn
 
 
@@ -102,9 +103,6 @@ def test_gradient_field_gen(golden):
     g, T = O.gradient_field_gen(r["uv"], r["x_far"], r["K"], conf=ones)
     np.testing.assert_allclose(T, r["T_far"], atol=1e-4, rtol=0)
     np.testing.assert_allclose(g, r["g_far"], atol=2e-5, rtol=0)
-
-
-IPO_CASES = [(N, axes, kname) for N in (8, 64) for axes in ("z", "xyz") for kname in ("h36m", "pw3d")]
 
 
 @pytest.mark.parametrize("N,axes,kname", IPO_CASES)

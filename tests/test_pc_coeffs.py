@@ -13,15 +13,12 @@ import numpy as np
 import pytest
 import torch
 
+from _shared import make_sde, sampler_cases
 from lib.algorithms.advanced import _pc_coeffs, sampling, sde_lib
 from lib.algorithms.advanced import utils as mutils
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SDES = dict(vpsde=(sde_lib.VPSDE, dict(beta_min=0.1, beta_max=20.0, N=1000, T=1.0)),
-            subvpsde=(sde_lib.subVPSDE, dict(beta_min=0.1, beta_max=20.0, N=1000, T=1.0)),
-            vesde=(sde_lib.VESDE, dict(sigma_min=0.01, sigma_max=50.0, N=1000, T=1.0)))
-PREDS = [("euler_maruyama", False), ("euler_maruyama", True), ("reverse_diffusion", False),
-         ("reverse_diffusion", True), ("ancestral_sampling", False)]
+SDES, PREDS, CORRS = sampler_cases()
 SNR, N_CORR = 0.16, 2          # what gen_samplers ran the correctors with
 
 
@@ -50,11 +47,11 @@ def col(v):
     return v.astype(np.float32)[:, None, None]
 
 
-@pytest.mark.parametrize("name", list(SDES))
+@pytest.mark.parametrize("name", SDES)
 @pytest.mark.parametrize("pname,pf", PREDS)
 def test_predictor_coefficients_reproduce_the_reference(golden, name, pname, pf):
     g = golden("samplers")
-    sde = SDES[name][0](**SDES[name][1])
+    sde = make_sde(sde_lib, name)
     key = f"{name}_pred_{pname}_pf{int(pf)}"
     c = coeffs(sde, pname, "none", pf, g["t"])
     if key + "_raises" in g.files:
@@ -72,11 +69,11 @@ def test_predictor_coefficients_reproduce_the_reference(golden, name, pname, pf)
         assert not c.pC.any()
 
 
-@pytest.mark.parametrize("name", list(SDES))
-@pytest.mark.parametrize("cname", ["langevin", "ald"])
+@pytest.mark.parametrize("name", SDES)
+@pytest.mark.parametrize("cname", CORRS)
 def test_corrector_coefficients_reproduce_the_reference(golden, name, cname):
     g = golden("samplers")
-    sde = SDES[name][0](**SDES[name][1])
+    sde = make_sde(sde_lib, name)
     key = f"{name}_corr_{cname}"
     c = coeffs(sde, "none", cname, False, g["t"])
     if key + "_raises" in g.files:
@@ -114,7 +111,7 @@ class Recorder(torch.nn.Module):
 @pytest.mark.parametrize("name,continuous", [("vpsde", True), ("vpsde", False), ("subvpsde", True), ("subvpsde", False),
                                              ("vesde", True), ("vesde", False)])
 def test_labels_are_bit_identical_to_get_score_fn(name, continuous):
-    sde = SDES[name][0](**SDES[name][1])
+    sde = make_sde(sde_lib, name)
     ts = np.concatenate([torch.linspace(1.0, 0.01, 37).numpy(), np.float32([0.9, 0.5, 0.31, 0.1, 0.013, 0.0005])])
     rec = Recorder()
     score_fn = mutils.get_score_fn(sde, rec, train=False, continuous=continuous)

@@ -2,7 +2,6 @@
 the C ABI on hand-set coefficients against the network's own eps, chained sampler calls of every generic combination
 against float64 captures of the reference (tools/gen_golden.py::gen_pc_generic_loop), the caller's RNG stream, and the
 invariants of the route (device twin, determinism, whole-loop plan, chunking, batch-mean semantics of Langevin, fallback)."""
-import json
 import os
 import subprocess
 import sys
@@ -11,85 +10,27 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+from _shared import PC_LOOP_CASES, DetNoise, cfg_path, dev, make_sde, model, report_env, zh  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-PC_LOOP_CASES = [
-    # tag, sde, continuous, predictor, corrector, probability_flow, noise_removal, n_steps_each   (tools/gen_golden.py)
-    ("vp_rd_langevin", "vpsde", True, "reverse_diffusion", "langevin", False, True, 1),
-    ("vp_anc_none_disc", "vpsde", False, "ancestral_sampling", "none", False, True, 1),
-    ("vp_em_none_pf", "vpsde", True, "euler_maruyama", "none", True, True, 1),
-    ("ve_rd_ald", "vesde", True, "reverse_diffusion", "ald", False, True, 1),
-    ("ve_anc_langevin", "vesde", True, "ancestral_sampling", "langevin", False, False, 1),
-    ("subvp_em_none_sde", "subvpsde", True, "euler_maruyama", "none", False, False, 1),
-    ("subvp_rd_none", "subvpsde", True, "reverse_diffusion", "none", False, True, 1),
-    ("vp_em_langevin", "vpsde", True, "euler_maruyama", "langevin", False, True, 2),
-]
 CASE_IDS = [c[0] for c in PC_LOOP_CASES]
 CASE = {c[0]: c for c in PC_LOOP_CASES}
 
 
-def cfg_path(name):
-    return os.path.join(ROOT, "zedo-release_amd", "configs", "optim", f"concat_pose_optimization_{name}.py")
-
-
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-
-
-@pytest.fixture(scope="module")
-def zh():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import zedo_hip
-    return zedo_hip
-
-
-@pytest.fixture(scope="module")
-def model(weights0):
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from lib.algorithms.advanced.model import ScoreModelFC_Adv
-    from lib.dataset import synthetic as syn
-    from run._driver import load_config
-    m = ScoreModelFC_Adv(load_config(cfg_path("h36m")), 17, 3, 1024, 512, 3)
-    sd = {k: torch.tensor(v) for k, v in weights0.items()}
-    sd["sigmas"] = torch.tensor(syn.sigmas_buffer())
-    m.load_state_dict(sd)
-    return m.eval()
-
-
-class DetNoise:
-    """torch.randn_like replacement shared with the capture script: numpy Philox, keyed by the call count."""
-
-    def __init__(self):
-        self.calls = 0
-
-    def __call__(self, x):
-        g = np.random.Generator(np.random.Philox(key=[555, self.calls]))
-        self.calls += 1
-        return torch.tensor(g.standard_normal(tuple(x.shape)), dtype=x.dtype, device=x.device)
-
-
-def make_sde(name):
-    from lib.algorithms.advanced import sde_lib
-    return dict(vpsde=lambda: sde_lib.VPSDE(0.1, 20.0, 1000, 1.0), vesde=lambda: sde_lib.VESDE(0.01, 50.0, 1000, 1.0),
-                subvpsde=lambda: sde_lib.subVPSDE(0.1, 20.0, 1000, 1.0))[name]()
-
-
 def make_fn(case, rows, eps=0.01, hint=20, predictor=None):
     """get_sampling_fn for one case -> (fn, sde)"""
-    from lib.algorithms.advanced import sampling
+    from lib.algorithms.advanced import sampling, sde_lib
     from run._driver import load_config
-    tag, sname, cont, pred, corr, pf, denoise, n_each = case
+    tag, sname, cont, pred, corr, pf, denoise, _, n_each = case
     cfg = load_config(cfg_path("h36m"))
     cfg.training.sde, cfg.training.continuous = sname, cont
     cfg.sampling.predictor, cfg.sampling.corrector, cfg.sampling.probability_flow = predictor or pred, corr, pf
     cfg.sampling.noise_removal, cfg.sampling.n_steps_each = denoise, n_each
     cfg.ZeDO.OIL_iterations = hint
-    sde = make_sde(sname)
+    sde = make_sde(sde_lib, sname)
     return sampling.get_sampling_fn(cfg, sde, (rows, 17, 3), lambda v: v, eps, device=torch.device("cuda")), sde
 
 
@@ -191,10 +132,8 @@ def test_chained_steps_against_the_float64_reference(model, golden, monkeypatch,
         worst = max(worst, d / bound)
         print(f"pc_chain[{tag}, {route}, {math_mode}] step {s}: max|d| {d:.3e}  ref gap {gap:.3e}  magnitude {mag:.3g}  "
               f"ratio to bound {d / bound:.3f}")
-    if os.environ.get("ZEDO_PARITY_REPORT"):
-        with open(os.environ["ZEDO_PARITY_REPORT"], "a") as f:
-            for r in recs:
-                f.write(json.dumps(r) + "\n")
+    for r in recs:
+        report_env(r)
     assert worst <= 1.0, recs
 
 
@@ -387,9 +326,9 @@ def test_user_registered_predictor_stays_on_the_torch_route(model, golden, monke
 
 def test_combinations_that_raise_in_the_reference_keep_raising(model, golden):
     g = golden("pc_generic_loop")
-    for case, err in ((("x", "subvpsde", True, "ancestral_sampling", "none", False, True, 1), NotImplementedError),
-                      (("x", "subvpsde", True, "euler_maruyama", "langevin", False, True, 1), AttributeError),
-                      (("x", "vpsde", True, "ancestral_sampling", "none", True, True, 1), AssertionError)):
+    for case, err in ((("x", "subvpsde", True, "ancestral_sampling", "none", False, True, None, 1), NotImplementedError),
+                      (("x", "subvpsde", True, "euler_maruyama", "langevin", False, True, None, 1), AttributeError),
+                      (("x", "vpsde", True, "ancestral_sampling", "none", True, True, None, 1), AssertionError)):
         fn, sde = make_fn(case, 70)
         assert fn.native_plan is None
         with pytest.raises(err):

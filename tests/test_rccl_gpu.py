@@ -5,23 +5,16 @@ RANK=0 WORLD_SIZE=1 ZEDO_FORCE_DIST=1, and compared bit for bit with the same ru
 The multi-rank arithmetic itself is covered on CPU over gloo (tests/test_distributed_gloo.py)."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from _shared import free_port
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _env(dist):
@@ -31,7 +24,7 @@ def _env(dist):
     e["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     if dist:
         e.update(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", ZEDO_FORCE_DIST="1", MASTER_ADDR="127.0.0.1",
-                 MASTER_PORT=str(_free_port()))
+                 MASTER_PORT=str(free_port()))
     return e
 
 

@@ -22,6 +22,8 @@ import os
 import numpy as np
 import pytest
 
+from _shared import cfg_path
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
@@ -35,10 +37,6 @@ def _sha(path):
         for blk in iter(lambda: f.read(1 << 20), b""):
             h.update(blk)
     return h.hexdigest()
-
-
-def cfg_path(name):
-    return os.path.join(ROOT, "zedo-release_amd", "configs", "optim", f"concat_pose_optimization_{name}.py")
 
 
 @pytest.mark.parametrize("fixture", FIXTURES, ids=[os.path.basename(f)[:-4] for f in FIXTURES])

@@ -10,22 +10,12 @@ import threading
 import numpy as np
 import pytest
 
+from _shared import dev, zh  # noqa: F401  (fixture)
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 REPS = 20
-
-
-@pytest.fixture(scope="module")
-def zh():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import zedo_hip
-    return zedo_hip
-
-
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
 
 
 class Problem:

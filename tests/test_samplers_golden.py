@@ -7,24 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from _shared import DetNoise, analytic_score, make_sde, sampler_cases
 from lib.algorithms.advanced import sampling, sde_lib
 
-SDES = dict(vpsde=(sde_lib.VPSDE, dict(beta_min=0.1, beta_max=20.0, N=1000, T=1.0)),
-            subvpsde=(sde_lib.subVPSDE, dict(beta_min=0.1, beta_max=20.0, N=1000, T=1.0)),
-            vesde=(sde_lib.VESDE, dict(sigma_min=0.01, sigma_max=50.0, N=1000, T=1.0)))
-PREDS = [("euler_maruyama", False), ("euler_maruyama", True), ("reverse_diffusion", False),
-         ("reverse_diffusion", True), ("ancestral_sampling", False)]
+SDES, PREDS, CORRS = sampler_cases()
 ERRORS = dict(NotImplementedError=NotImplementedError, AssertionError=AssertionError, AttributeError=AttributeError)
-
-
-class DetNoise:
-    def __init__(self):
-        self.calls = 0
-
-    def __call__(self, x):
-        g = np.random.Generator(np.random.Philox(key=[555, self.calls]))
-        self.calls += 1
-        return torch.tensor(g.standard_normal(tuple(x.shape)), dtype=x.dtype)
 
 
 @pytest.fixture(autouse=True)
@@ -53,10 +40,6 @@ def _capture_sqrt(request, monkeypatch, golden):
     monkeypatch.setattr(torch, "sqrt", capture_sqrt)
 
 
-def analytic_score(x, t, condition, mask):
-    return -(x - 0.3 * condition) / (0.5 + t)[:, None, None]
-
-
 def close(a, b):
     a = a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
     np.testing.assert_allclose(np.broadcast_to(a, b.shape) if a.shape != b.shape else a, b, rtol=2e-6, atol=1e-7)
@@ -68,10 +51,10 @@ def inputs(golden):
     return g, torch.tensor(g["x"]), torch.tensor(g["cond"]), torch.tensor(g["t"])
 
 
-@pytest.mark.parametrize("name", list(SDES))
+@pytest.mark.parametrize("name", SDES)
 def test_sde_schedule_methods(inputs, name):
     g, x, cond, t = inputs
-    sde = SDES[name][0](**SDES[name][1])
+    sde = make_sde(sde_lib, name)
     for got, key in zip(sde.sde(x, t), ("drift", "diffusion")):
         close(got, g[f"{name}_{key}"])
     for got, key in zip(sde.marginal_prob(x, t), ("mean", "std")):
@@ -88,11 +71,11 @@ def test_sde_schedule_methods(inputs, name):
             close(got, g[f"{name}_{key}_pf{int(pf)}"])
 
 
-@pytest.mark.parametrize("name", list(SDES))
+@pytest.mark.parametrize("name", SDES)
 @pytest.mark.parametrize("pname,pf", PREDS)
 def test_predictor_update_rules(inputs, monkeypatch, name, pname, pf):
     g, x, cond, t = inputs
-    sde = SDES[name][0](**SDES[name][1])
+    sde = make_sde(sde_lib, name)
     key = f"{name}_pred_{pname}_pf{int(pf)}"
     monkeypatch.setattr(torch, "randn_like", DetNoise())
     if key + "_raises" in g.files:
@@ -104,11 +87,11 @@ def test_predictor_update_rules(inputs, monkeypatch, name, pname, pf):
     close(xm, g[key + "_mean"])
 
 
-@pytest.mark.parametrize("name", list(SDES))
-@pytest.mark.parametrize("cname", ["langevin", "ald"])
+@pytest.mark.parametrize("name", SDES)
+@pytest.mark.parametrize("cname", CORRS)
 def test_corrector_update_rules(inputs, monkeypatch, name, cname):
     g, x, cond, t = inputs
-    sde = SDES[name][0](**SDES[name][1])
+    sde = make_sde(sde_lib, name)
     key = f"{name}_corr_{cname}"
     monkeypatch.setattr(torch, "randn_like", DetNoise())
     if key + "_raises" in g.files:

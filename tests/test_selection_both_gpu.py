@@ -10,26 +10,10 @@ import ctypes
 import numpy as np
 import pytest
 
+from _shared import dev, one_arithmetic_mode, zh  # noqa: F401  (fixtures; one_arithmetic_mode is autouse)
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-
-@pytest.fixture(autouse=True)
-def _one_arithmetic_mode(math_mode):
-    if math_mode != "f32":
-        pytest.skip("the selection kernels do not depend on the arithmetic mode of the dense layers: covered by the f32 session")
-
-
-@pytest.fixture(scope="module")
-def zh():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import zedo_hip
-    return zedo_hip
-
-
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
 
 
 def bits(t):

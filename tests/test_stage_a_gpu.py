@@ -20,6 +20,8 @@ import os
 import numpy as np
 import pytest
 
+from _shared import Capture
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
@@ -30,28 +32,12 @@ CAPTURES = [n for n in ("driver_h36m_full", "driver_pw3d_full", "driver_pw3d_ful
             if os.path.exists(os.path.join(ROOT, "tests", "golden", n + "_ipo.npz"))]
 
 
-def _sha(*arrs):
-    import hashlib
-    h = hashlib.sha256()
-    for a in arrs:
-        h.update(np.ascontiguousarray(a).tobytes())
-    return h.hexdigest()
-
-
-def run_oil_from_pins(weights0, g, pin, math_mode=None):
-    """-> (x rows [H*N,17,3] on the GPU, problem dict).  (R, T) of every row come from the fixture, nothing from
-    zedo_ipo_fit."""
+def run_oil_from_pins(weights0, cap, pin):
+    """-> x rows [H*N,17,3] on the GPU.  (R, T) of every row come from the fixture, nothing from zedo_ipo_fit."""
     import zedo_hip as zh
-    from zedo_hip.pipeline import Pipeline, ZeDOConfig
-    from lib.dataset import synthetic as syn
-    N, H, S = int(g["N"]), int(g["H"]), int(g["S"])
-    h36m = str(g["dataset"]) == "h36m"
-    d = syn.make_poses(N, seed=int(g["seed_pose"]), conf_mode=str(g["conf_mode"]), dtype3d=np.float64 if h36m else np.float32)
-    cl = syn.make_clusters(H, seed=int(g["seed_cl"]))
-    assert _sha(d["db_2d"], d["camera_param"], cl) == str(g["inputs_sha"]) == str(pin["inputs_sha"])
-    cfg = ZeDOConfig(IPO_keylist=[int(k) for k in g["keylist"]], IPO_T=float(g["ipo_T"]), IPO_minScaleT=float(g["minT"]),
-                     OIL_iterations=S)
-    pipe = Pipeline(weights0, cfg, "cuda").load(cl, d["db_2d"], d["camera_param"])
+    N, H, S = cap.N, cap.H, cap.S
+    assert str(cap.g["inputs_sha"]) == str(pin["inputs_sha"])
+    pipe = cap.pipeline(weights0)
     cs = pin["cs"].reshape(H * N, 2)
     R = np.zeros((H * N, 3, 3), np.float32)
     R[:, 0, 0], R[:, 0, 1], R[:, 1, 0], R[:, 1, 1], R[:, 2, 2] = cs[:, 0], -cs[:, 1], cs[:, 1], cs[:, 0], 1.0
@@ -59,27 +45,20 @@ def run_oil_from_pins(weights0, g, pin, math_mode=None):
     T = torch.tensor(np.ascontiguousarray(pin["T"].reshape(H * N, 3)), device="cuda")
     x = zh.rotate_init(pipe.x0, Rd, N)                                     # opt_main.py:201
     zh.oil_run(pipe.weights, pipe.sched, x, pipe.geom, T, 0, S, S // 5)    # opt_main.py:202-220
-    return x, dict(N=N, H=H, S=S, h36m=h36m, d=d)
+    return x
 
 
 @pytest.mark.parametrize("name", CAPTURES)
 def test_oil_loop_from_the_reference_ipo_output_meets_the_bar(weights0, golden, name):
     import zedo_hip as zh
-    from lib.dataset.h36m import H36MDataset3D
-    from lib.dataset.pw3d import PW3D
-    g, pin = golden(name), golden(name + "_ipo")
-    x, P = run_oil_from_pins(weights0, g, pin)
-    N, H, d = P["N"], P["H"], P["d"]
+    cap = Capture(name)
+    g, N, H = cap.g, cap.N, cap.H
+    x = run_oil_from_pins(weights0, cap, golden(name + "_ipo"))
     assert x.shape == (H * N, 17, 3) and bool(torch.isfinite(x).all())
-    if P["h36m"]:
-        ds = H36MDataset3D.from_arrays(d["db_2d"], d["db_3d"] * 1000.0, d["camera_param"], 2 + (np.arange(N) % 15))
-        gtc = (d["db_3d"] * 1000.0 - (d["db_3d"] * 1000.0)[:, 0:1]) / 1000.0
-    else:
-        ds = PW3D.from_arrays(d["db_2d"], d["db_3d"], d["camera_param"])
-        gtc = (d["db_3d"] - d["db_3d"][:, 0:1]).astype(np.float64)
+    ds, gtc = cap.dataset(), cap.gt
     p1 = ds.eval_multi(("rows", x), protocol2=False)
     p2 = ds.eval_multi(("rows", x), protocol2=True)
-    rep = {"test": "stage_a:" + name, "N": N, "H": H, "S": P["S"], "mpjpe_hip": p1, "mpjpe_ref": float(g["mpjpe"]),
+    rep = {"test": "stage_a:" + name, "N": N, "H": H, "S": cap.S, "mpjpe_hip": p1, "mpjpe_ref": float(g["mpjpe"]),
            "pa_hip": p2, "pa_ref": float(g["pa_mpjpe"]), "d_mpjpe_mm": (p1 - float(g["mpjpe"])) * 1e3,
            "d_pa_mpjpe_mm": (p2 - float(g["pa_mpjpe"])) * 1e3}
     gt = torch.as_tensor(gtc, device="cuda")

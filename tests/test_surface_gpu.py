@@ -6,32 +6,12 @@ import sys
 import numpy as np
 import pytest
 
+from _shared import PC_GENERIC_CASES, Capture, DetNoise, cfg_path, dev, make_sde, model  # noqa: F401  (fixture)
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def cfg_path(name):
-    return os.path.join(ROOT, "zedo-release_amd", "configs", "optim", f"concat_pose_optimization_{name}.py")
-
-
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-
-
-@pytest.fixture(scope="module")
-def model(weights0):
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from lib.algorithms.advanced.model import ScoreModelFC_Adv
-    from lib.dataset import synthetic as syn
-    from run._driver import load_config
-    m = ScoreModelFC_Adv(load_config(cfg_path("h36m")), 17, 3, 1024, 512, 3)
-    sd = {k: torch.tensor(v) for k, v in weights0.items()}
-    sd["sigmas"] = torch.tensor(syn.sigmas_buffer())
-    m.load_state_dict(sd)
-    return m.eval()
 
 
 def test_model_forward_surface(model, golden):
@@ -284,14 +264,6 @@ def test_reference_loop_through_the_per_step_surface(model, weights0):
     assert "scale_by_sigma" in _driver.not_fused_because(bad)
 
 
-def _sha(*arrs):
-    import hashlib
-    h = hashlib.sha256()
-    for a in arrs:
-        h.update(np.ascontiguousarray(a).tobytes())
-    return h.hexdigest()
-
-
 FULL_SIZE_CAPTURES = [n for n in ("driver_h36m_full", "driver_pw3d_full", "driver_pw3d_full_b", "driver_pw3d_full_c")
                       if os.path.exists(os.path.join(ROOT, "tests", "golden", n + ".npz"))]
 
@@ -308,28 +280,13 @@ def test_fused_driver_at_baseline_size_matches_reference(weights0, golden, name)
     agreement, error deltas) goes to the parity report."""
     import json
     import zedo_hip
-    from zedo_hip.pipeline import Pipeline, ZeDOConfig
-    from lib.dataset import synthetic as syn
-    from lib.dataset.h36m import H36MDataset3D
-    from lib.dataset.pw3d import PW3D
-    g = golden(name)
-    N, H, S = int(g["N"]), int(g["H"]), int(g["S"])
-    h36m = str(g["dataset"]) == "h36m"
-    d = syn.make_poses(N, seed=int(g["seed_pose"]), conf_mode=str(g["conf_mode"]),
-                       dtype3d=np.float64 if h36m else np.float32)
-    cl = syn.make_clusters(H, seed=int(g["seed_cl"]))
-    assert _sha(d["db_2d"], d["camera_param"], cl) == str(g["inputs_sha"]), "inputs differ from the captured run"
-    cfg = ZeDOConfig(IPO_keylist=[int(k) for k in g["keylist"]], IPO_T=float(g["ipo_T"]),
-                     IPO_minScaleT=float(g["minT"]), OIL_iterations=S)
-    pipe = Pipeline(weights0, cfg, "cuda").load(cl, d["db_2d"], d["camera_param"])
+    cap = Capture(name)
+    g, N, H, S = cap.g, cap.N, cap.H, cap.S
+    pipe = cap.pipeline(weights0)
+    cfg = pipe.cfg
     x, T = pipe.run()
     assert x.shape == (H * N, 17, 3) and bool(torch.isfinite(x).all())
-    if h36m:
-        ds = H36MDataset3D.from_arrays(d["db_2d"], d["db_3d"] * 1000.0, d["camera_param"], 2 + (np.arange(N) % 15))
-        gtc = (d["db_3d"] * 1000.0 - (d["db_3d"] * 1000.0)[:, 0:1]) / 1000.0
-    else:
-        ds = PW3D.from_arrays(d["db_2d"], d["db_3d"], d["camera_param"])
-        gtc = (d["db_3d"] - d["db_3d"][:, 0:1]).astype(np.float64)
+    ds, gtc = cap.dataset(), cap.gt
     p1 = ds.eval_multi(("rows", x), protocol2=False)
     p2 = ds.eval_multi(("rows", x), protocol2=True)
     rep = {"test": name, "N": N, "H": H, "S": S, "mpjpe_hip": p1, "mpjpe_ref": float(g["mpjpe"]), "pa_hip": p2,
@@ -542,45 +499,19 @@ def test_opt_main_accepts_a_cluster_file_built_by_the_tool(tmp_path, weights0, m
         assert all(np.isfinite(v) for v in res[H]) and res[H][1] <= res[H][0] + 1e-9
 
 
-PC_GENERIC_CASES = [
-    # tag, sde, continuous, predictor, corrector, probability_flow, noise_removal, t   (tools/gen_golden.py)
-    ("vp_rd_langevin", "vpsde", True, "reverse_diffusion", "langevin", False, True, 0.31),
-    ("vp_anc_none_disc", "vpsde", False, "ancestral_sampling", "none", False, True, 0.52),
-    ("vp_em_none_pf", "vpsde", True, "euler_maruyama", "none", True, True, 0.2),
-    ("ve_rd_ald", "vesde", True, "reverse_diffusion", "ald", False, True, 0.4),
-    ("ve_anc_langevin", "vesde", True, "ancestral_sampling", "langevin", False, False, 0.15),
-    ("subvp_em_none_sde", "subvpsde", True, "euler_maruyama", "none", False, False, 0.07),
-    ("subvp_rd_none", "subvpsde", True, "reverse_diffusion", "none", False, True, 0.05),
-]
-
-
-class DetNoise:
-    """torch.randn_like replacement shared with the capture script: numpy Philox, keyed by the call count."""
-
-    def __init__(self):
-        self.calls = 0
-
-    def __call__(self, x):
-        g = np.random.Generator(np.random.Philox(key=[555, self.calls]))
-        self.calls += 1
-        return torch.tensor(g.standard_normal(tuple(x.shape)), dtype=x.dtype, device=x.device)
-
-
 @pytest.mark.parametrize("case", PC_GENERIC_CASES, ids=[c[0] for c in PC_GENERIC_CASES])
 def test_pc_sampler_other_sdes_and_update_rules(model, golden, monkeypatch, case):
     """the config-reachable but non-shipped SDE / predictor / corrector combinations behind
     get_sampling_fn, with the score network on the HIP path, against the reference's pc_sampler (same noise)."""
     from lib.algorithms.advanced import sampling, sde_lib
     from run._driver import load_config
-    tag, sname, cont, pred, corr, pf, denoise, t = case
+    tag, sname, cont, pred, corr, pf, denoise, t, _ = case
     p = golden("pc_generic")
     cfg = load_config(cfg_path("h36m"))
     cfg.training.sde, cfg.training.continuous = sname, cont
     cfg.sampling.predictor, cfg.sampling.corrector, cfg.sampling.probability_flow = pred, corr, pf
     cfg.sampling.noise_removal = denoise
-    sde = dict(vpsde=lambda: sde_lib.VPSDE(0.1, 20.0, 1000, 1.0), vesde=lambda: sde_lib.VESDE(0.01, 50.0, 1000, 1.0),
-               subvpsde=lambda: sde_lib.subVPSDE(0.1, 20.0, 1000, 1.0))[sname]()
-    fn = sampling.get_sampling_fn(cfg, sde, (8, 17, 3), lambda v: v, 0.01, device=torch.device("cuda"))
+    fn = sampling.get_sampling_fn(cfg, make_sde(sde_lib, sname), (8, 17, 3), lambda v: v, 0.01, device=torch.device("cuda"))
     monkeypatch.setattr(torch, "randn_like", DetNoise())
     trajs, res = fn(model, condition=torch.zeros(8, 17, 2, device="cuda"), denoise_x=dev(p["x"]),
                     t=torch.tensor(t), t_step=3)

@@ -7,38 +7,12 @@ import os
 import numpy as np
 import pytest
 
+from _shared import cfg_path, dev, model, zh  # noqa: F401  (fixtures)
+
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def cfg_path(name):
-    return os.path.join(ROOT, "zedo-release_amd", "configs", "optim", f"concat_pose_optimization_{name}.py")
-
-
-def dev(a, dtype=torch.float32):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-
-
-@pytest.fixture(scope="module")
-def zh():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import zedo_hip
-    return zedo_hip
-
-
-@pytest.fixture(scope="module")
-def model(weights0, zh):
-    from lib.algorithms.advanced.model import ScoreModelFC_Adv
-    from lib.dataset import synthetic as syn
-    from run._driver import load_config
-    m = ScoreModelFC_Adv(load_config(cfg_path("h36m")), 17, 3, 1024, 512, 3)
-    sd = {k: torch.tensor(v) for k, v in weights0.items()}
-    sd["sigmas"] = torch.tensor(syn.sigmas_buffer())
-    m.load_state_dict(sd)
-    return m.eval()
 
 
 def _eval_problem(N=37, H=6, seed=3):

@@ -24,28 +24,23 @@ for p in (os.path.join(ROOT, "zedo-release_amd"), os.path.join(ROOT, "tests")):
 
 import _ipo_summary as ips                                                    # noqa: E402
 import zedo_hip                                                               # noqa: E402
+from _shared import Capture                                                   # noqa: E402
 from lib.dataset import synthetic as syn                                      # noqa: E402
-from zedo_hip.pipeline import Pipeline, ZeDOConfig                            # noqa: E402
 
 HIP_SEED0 = 100        # the reference's members use streams 1, 2, ...; the HIP ensemble 101, 102, ... (+ 0 = unperturbed)
 
 
-def member(W, g, seed):
-    N, H, S = int(g["N"]), int(g["H"]), int(g["S"])
-    d = syn.make_poses(N, seed=int(g["seed_pose"]), conf_mode=str(g["conf_mode"]))
-    cl = syn.make_clusters(H, seed=int(g["seed_cl"]))
-    db2 = d["db_2d"].copy()
-    db2[:, :, :2] = syn.perturb_ulp(db2[:, :, :2], seed)
-    cfg = ZeDOConfig(IPO_keylist=[int(k) for k in g["keylist"]], IPO_T=float(g["ipo_T"]), IPO_minScaleT=float(g["minT"]),
-                     OIL_iterations=S)
-    pipe = Pipeline(W, cfg, "cuda").load(cl, db2, d["camera_param"])
+def member(W, cap, seed):
+    N, H = cap.N, cap.H
+    pipe = cap.pipeline(W, seed)
+    cfg = pipe.cfg
     R, T = zedo_hip.ipo_fit(pipe.x0, pipe.uv, pipe.K, cfg.IPO_keylist, cfg.RotAxes, cfg.IPO_T, cfg.IPO_minScaleT,
                             cfg.IPO_maxScaleT, cfg.IPO_iterations, N * len(cfg.IPO_keylist) * 2, H * N)
     cs = torch.stack([R[:, 0, 0], R[:, 1, 0]], -1).reshape(H, N, 2).cpu().numpy()
-    sm = ips.summary(cs, T.reshape(H, N, 3).cpu().numpy(), (cl - cl[:, 0:1])[:, None], db2[:, :, :2], d["camera_param"],
+    sm = ips.summary(cs, T.reshape(H, N, 3).cpu().numpy(), (cap.cl - cap.cl[:, 0:1])[:, None], cap.detections(seed)[:, :, :2], cap.K,
                      cfg.IPO_keylist, cfg.IPO_T)
     x, _ = pipe.run()
-    gt = torch.as_tensor((d["db_3d"] - d["db_3d"][:, 0:1]).astype(np.float64), device="cuda")
+    gt = torch.as_tensor(cap.gt, device="cuda")
     out = dict(sm)
     for key, proto in (("p1", False), ("p2", True)):
         _, best, idx = zedo_hip.min_mpjpe(x, gt, N, procrustes=proto)
@@ -65,10 +60,11 @@ def main():
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     rep = {}
     for name in a.captures.split(","):
-        g = np.load(os.path.join(ROOT, "tests", "golden", name + ".npz"))
+        cap = Capture(name)
+        g = cap.g
         t0 = time.time()
         seeds = [0] + [HIP_SEED0 + i for i in range(1, a.members + 1)]
-        ms = [member(W, g, s) for s in seeds]
+        ms = [member(W, cap, s) for s in seeds]
         arr = {k: np.stack([np.asarray(m[k]) for m in ms]) for k in ms[0]}
         np.savez_compressed(f"{a.out}_{name}.npz", seeds=np.array(seeds), ref_mpjpe=g["mpjpe"], ref_pa=g["pa_mpjpe"],
                             ref_best_p1=g["best_p1"], ref_best_p2=g["best_p2"], **arr)

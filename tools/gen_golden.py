@@ -34,6 +34,8 @@ import numpy as np
 import torch
 
 import synthetic as syn  # zedo-release_amd/lib/dataset/synthetic.py (numpy only)
+from _shared import (PC_GENERIC_CASES, PC_LOOP_CASES, PC_LOOP_EPS, PC_LOOP_ROWS, PC_LOOP_SNAPS, PC_LOOP_STEPS, DetNoise, DetNoise32,
+                     analytic_score, make_sde, sampler_cases, sampler_inputs, sha_of)  # tests/_shared.py: what the tests share
 
 from lib.algorithms.advanced.model import ScoreModelFC_Adv, get_timestep_embedding
 from lib.algorithms.advanced import sde_lib, sampling
@@ -710,41 +712,6 @@ def gen_driver_files():
 
 # ------------------------------------------------------------------ other SDEs / update rules
 
-def sampler_cases():
-    """(sde name, ctor kwargs) x (predictor, probability_flow) and x (corrector) combinations captured below."""
-    sdes = [("vpsde", dict(beta_min=0.1, beta_max=20.0, N=1000, T=1.0)),
-            ("subvpsde", dict(beta_min=0.1, beta_max=20.0, N=1000, T=1.0)),
-            ("vesde", dict(sigma_min=0.01, sigma_max=50.0, N=1000, T=1.0))]
-    preds = [("euler_maruyama", False), ("euler_maruyama", True), ("reverse_diffusion", False),
-             ("reverse_diffusion", True), ("ancestral_sampling", False)]
-    corrs = ["langevin", "ald"]
-    return sdes, preds, corrs
-
-
-def sampler_inputs():
-    g = np.random.Generator(np.random.Philox(key=[2024, 3]))
-    x = g.standard_normal((6, 17, 3)).astype(np.float32)
-    cond = g.standard_normal((6, 17, 3)).astype(np.float32)
-    t = np.array([0.9, 0.5, 0.1, 0.013, 0.0005, 0.7], np.float32)     # 0.0005 -> discrete step 0 (VE adjacent sigma = 0)
-    return x, cond, t
-
-
-class DetNoise:
-    """Replacement for torch.randn_like during capture and test: numpy Philox, independent of the torch build."""
-
-    def __init__(self):
-        self.calls = 0
-
-    def __call__(self, x):
-        g = np.random.Generator(np.random.Philox(key=[555, self.calls]))
-        self.calls += 1
-        return torch.tensor(g.standard_normal(tuple(x.shape)), dtype=x.dtype)
-
-
-def analytic_score(x, t, condition, mask):
-    return -(x - 0.3 * condition) / (0.5 + t)[:, None, None]
-
-
 def gen_samplers():
     sdes, preds, corrs = sampler_cases()
     xn, cn, tn = sampler_inputs()
@@ -752,9 +719,8 @@ def gen_samplers():
     mask = torch.zeros_like(x)
     out = dict(x=xn, cond=cn, t=tn)
     orig = torch.randn_like
-    for name, kw in sdes:
-        cls = dict(vpsde=sde_lib.VPSDE, subvpsde=sde_lib.subVPSDE, vesde=sde_lib.VESDE)[name]
-        sde = cls(**kw)
+    for name in sdes:
+        sde = make_sde(sde_lib, name)
         out[f"{name}_drift"], out[f"{name}_diffusion"] = [a.numpy() for a in sde.sde(x, t)]
         out[f"{name}_mean"], out[f"{name}_std"] = [a.numpy() for a in sde.marginal_prob(x, t)]
         f, G = sde.discretize(x, t)
@@ -789,26 +755,6 @@ def gen_samplers():
 
 
 
-PC_GENERIC_CASES = [
-    # tag, sde, continuous, predictor, corrector, probability_flow, noise_removal, t
-    ("vp_rd_langevin", "vpsde", True, "reverse_diffusion", "langevin", False, True, 0.31),
-    ("vp_anc_none_disc", "vpsde", False, "ancestral_sampling", "none", False, True, 0.52),
-    ("vp_em_none_pf", "vpsde", True, "euler_maruyama", "none", True, True, 0.2),
-    ("ve_rd_ald", "vesde", True, "reverse_diffusion", "ald", False, True, 0.4),
-    ("ve_anc_langevin", "vesde", True, "ancestral_sampling", "langevin", False, False, 0.15),
-    ("subvp_em_none_sde", "subvpsde", True, "euler_maruyama", "none", False, False, 0.07),
-    ("subvp_rd_none", "subvpsde", True, "reverse_diffusion", "none", False, True, 0.05),
-]
-
-
-def make_sde(name):
-    if name == "vpsde":
-        return sde_lib.VPSDE(beta_min=0.1, beta_max=20.0, N=1000, T=1.0)
-    if name == "vesde":
-        return sde_lib.VESDE(sigma_min=0.01, sigma_max=50.0, N=1000, T=1.0)
-    return sde_lib.subVPSDE(beta_min=0.1, beta_max=20.0, N=1000, T=1.0)
-
-
 def gen_pc_generic():
     """get_sampling_fn with the real network for the config-reachable, non-shipped SDE / predictor / corrector
     combinations (one pc_sampler call each; noise from DetNoise)."""
@@ -817,12 +763,12 @@ def gen_pc_generic():
     x = (0.3 * g.standard_normal((8, 17, 3))).astype(np.float32)
     out = dict(x=x)
     orig = torch.randn_like
-    for tag, sname, cont, pred, corr, pf, denoise, t in PC_GENERIC_CASES:
+    for tag, sname, cont, pred, corr, pf, denoise, t, _ in PC_GENERIC_CASES:
         cfg = ref_config()
         cfg.training.sde, cfg.training.continuous = sname, cont
         cfg.sampling.predictor, cfg.sampling.corrector, cfg.sampling.probability_flow = pred, corr, pf
         cfg.sampling.noise_removal = denoise
-        fn = sampling.get_sampling_fn(cfg, make_sde(sname), (8, 17, 3), lambda v: v, 0.01, device=torch.device("cpu"))
+        fn = sampling.get_sampling_fn(cfg, make_sde(sde_lib, sname), (8, 17, 3), lambda v: v, 0.01, device=torch.device("cpu"))
         torch.randn_like = DetNoise()
         try:
             trajs, res = fn(m, condition=torch.zeros(8, 17, 2), denoise_x=torch.tensor(x), t=torch.tensor(t), t_step=3)
@@ -834,34 +780,21 @@ def gen_pc_generic():
     save("pc_generic", **out)
 
 
-PC_LOOP_CASES = PC_GENERIC_CASES + [("vp_em_langevin", "vpsde", True, "euler_maruyama", "langevin", False, True, None)]
-PC_LOOP_STEPS, PC_LOOP_SNAPS, PC_LOOP_ROWS, PC_LOOP_EPS = 20, (1, 10, 20), 70, 0.01
-
-
-class DetNoise32(DetNoise):
-    """The same stream rounded to fp32 first: what a float32 run draws, handed to a float64 run unchanged."""
-
-    def __call__(self, x):
-        g = np.random.Generator(np.random.Philox(key=[555, self.calls]))
-        self.calls += 1
-        return torch.tensor(g.standard_normal(tuple(x.shape)).astype(np.float32)).to(x.dtype)
-
-
 def _pc_loop_chain(w, case, x0, dtype):
     """PC_LOOP_STEPS consecutive pc_sampler calls on t = linspace(T, eps, S), t_step = i, `res` fed back as the reference's
     driver does (run/opt_main.py:210-220).  dtype float64: sde tables, vec_t, model and state in double (the arbiter)."""
-    tag, sname, cont, pred, corr, pf, denoise, _ = case
+    tag, sname, cont, pred, corr, pf, denoise, _, n_each = case
     old = torch.get_default_dtype()
     torch.set_default_dtype(dtype)
     orig = torch.randn_like
     try:
-        sde = make_sde(sname)
+        sde = make_sde(sde_lib, sname)
         m = ref_model(w, dtype)
         cfg = ref_config()
         cfg.training.sde, cfg.training.continuous = sname, cont
         cfg.sampling.predictor, cfg.sampling.corrector, cfg.sampling.probability_flow = pred, corr, pf
         cfg.sampling.noise_removal = denoise
-        cfg.sampling.n_steps_each = 2 if tag == "vp_em_langevin" else 1
+        cfg.sampling.n_steps_each = n_each
         n = x0.shape[0]
         fn = sampling.get_sampling_fn(cfg, sde, (n, 17, 3), lambda v: v, PC_LOOP_EPS, device=torch.device("cpu"))
         ts = torch.linspace(float(sde.T), PC_LOOP_EPS, PC_LOOP_STEPS, dtype=torch.float32)   # the times of the fp32 run in both
@@ -1124,7 +1057,7 @@ def _driver_full_size(tag, N, H, S, seed_pose, seed_cl, keylist, ipo_T, minT, co
     if f64:       # arbiter: only the metric side is kept
         save(tag, N=np.int64(N), H=np.int64(H), S=np.int64(S), mpjpe=np.float64(p1), pa_mpjpe=np.float64(p2),
              best_p1=e1.min(1), best_p2=e2.min(1), argmin_p1=e1.argmin(1).astype(np.int32),
-             argmin_p2=e2.argmin(1).astype(np.int32), inputs_sha=np.array(_sha(gt_2d, K, cl)))
+             argmin_p2=e2.argmin(1).astype(np.int32), inputs_sha=np.array(sha_of(gt_2d, K, cl)))
         return
     if perturb or weights is not None:
         # an ensemble member / another prior: the metric side + the IPO end state as quantile functions (tests/_ipo_summary.py)
@@ -1134,7 +1067,7 @@ def _driver_full_size(tag, N, H, S, seed_pose, seed_cl, keylist, ipo_T, minT, co
         save(tag, N=np.int64(N), H=np.int64(H), S=np.int64(S), perturb=np.int64(perturb), mpjpe=np.float64(p1), pa_mpjpe=np.float64(p2),
              best_p1=e1.min(1).astype(np.float32), best_p2=e2.min(1).astype(np.float32),
              argmin_p1=e1.argmin(1).astype(np.int8), argmin_p2=e2.argmin(1).astype(np.int8),
-             ipo_loss=np.array(loss, np.float32), inputs_sha=np.array(_sha(gt_2d, K, cl)),
+             ipo_loss=np.array(loss, np.float32), inputs_sha=np.array(sha_of(gt_2d, K, cl)),
              weights_sha=np.array(syn.weights_checksum(w)), **sm)
         return
     save(tag, N=np.int64(N), H=np.int64(H), S=np.int64(S), seed_pose=np.int64(seed_pose), seed_cl=np.int64(seed_cl),
@@ -1143,15 +1076,7 @@ def _driver_full_size(tag, N, H, S, seed_pose, seed_cl, keylist, ipo_T, minT, co
          err_p1=e1.astype(np.float32), err_p2=e2.astype(np.float32),
          best_p1=e1.min(1), best_p2=e2.min(1), argmin_p1=e1.argmin(1).astype(np.int32), argmin_p2=e2.argmin(1).astype(np.int32),
          ipo_angle=np.stack(ang).astype(np.float32), ipo_scale=np.stack(scl).astype(np.float32),
-         ipo_loss=np.array(loss, np.float32), inputs_sha=np.array(_sha(gt_2d, K, cl)))
-
-
-def _sha(*arrs):
-    import hashlib
-    h = hashlib.sha256()
-    for a in arrs:
-        h.update(np.ascontiguousarray(a).tobytes())
-    return h.hexdigest()
+         ipo_loss=np.array(loss, np.float32), inputs_sha=np.array(sha_of(gt_2d, K, cl)))
 
 
 CACHE = os.environ.get("ZEDO_GOLDEN_CACHE", "/tmp/zedo_golden_cache")
@@ -1241,7 +1166,7 @@ def gen_driver_pw3d_ipoens():
     d = syn.make_poses(N, seed=seed_pose, conf_mode=conf_mode)
     cl = syn.make_clusters(H, seed=seed_cl)
     K = d["camera_param"]
-    assert str(np.load(os.path.join(OUT, tag + ".npz"))["inputs_sha"]) == _sha(d["db_2d"], K, cl)
+    assert str(np.load(os.path.join(OUT, tag + ".npz"))["inputs_sha"]) == sha_of(d["db_2d"], K, cl)
     x0c = (cl - cl[:, 0:1, :])[:, None]
     rows = []
     import time
@@ -1256,7 +1181,7 @@ def gen_driver_pw3d_ipoens():
             Ts.append(r["T"][:, 0, :])
         rows.append(ips.summary(np.stack(cs), np.stack(Ts), x0c, uv, K, keylist, ipo_T))
         print(f"  {tag} ipo ensemble: member {run}/{M} in {time.time() - t0:.0f} s", flush=True)
-    save(tag + "_ipoens", members=np.arange(1, M + 1), inputs_sha=np.array(_sha(d["db_2d"], K, cl)),
+    save(tag + "_ipoens", members=np.arange(1, M + 1), inputs_sha=np.array(sha_of(d["db_2d"], K, cl)),
          **{k: np.stack([np.asarray(r[k]) for r in rows]) for k in rows[0]})
 
 
@@ -1271,7 +1196,7 @@ def _driver_ipo_pin(tag, N, H, seed_pose, seed_cl, keylist, ipo_T, minT, conf_mo
     cl = syn.make_clusters(H, seed=seed_cl)
     gt_2d, K = d["db_2d"], d["camera_param"]
     full = np.load(os.path.join(OUT, tag + ".npz"))
-    assert str(full["inputs_sha"]) == _sha(gt_2d, K, cl)
+    assert str(full["inputs_sha"]) == sha_of(gt_2d, K, cl)
     cs, Ts = [], []
     for sid in range(H):
         f = os.path.join(cache_dir, f"{tag}_h{sid:02d}.npz")
@@ -1312,7 +1237,7 @@ def _driver_oil_f64_from_pins(tag, N, H, S, seed_pose, seed_cl, conf_mode, cache
     cl = syn.make_clusters(H, seed=seed_cl)
     gt_2d, K = d["db_2d"], d["camera_param"]
     pin = np.load(os.path.join(OUT, tag + "_ipo.npz"))
-    assert str(pin["inputs_sha"]) == _sha(gt_2d, K, cl)
+    assert str(pin["inputs_sha"]) == sha_of(gt_2d, K, cl)
     os.makedirs(cache_dir, exist_ok=True)
     import time
     res_all = []

@@ -12,7 +12,6 @@ infrastructure; this script does not import the reference (the reference-side me
     python tools/gen_oracle_ipoens.py [--members 12] [--workers 6] [--draws a,b,c]      # ~2 CPU-minutes per member
 """
 import argparse
-import hashlib
 import os
 import sys
 import time
@@ -24,15 +23,7 @@ for p in (os.path.join(ROOT, "zedo-release_amd"), os.path.join(ROOT, "oracle"), 
     sys.path.insert(0, p)
 OUT = os.path.join(ROOT, "tests", "golden")
 SEED0 = 2000
-DRAWS = {"a": ("driver_pw3d_full", 103, 19, "uniform"), "b": ("driver_pw3d_full_b", 203, 29, "ones"), "c": ("driver_pw3d_full_c", 307, 31, "uniform")}
-N, H, KEYLIST, IPO_T, MIN_T = 1015, 50, list(range(17)), 8.0, 0.2
-
-
-def _sha(*arrs):
-    h = hashlib.sha256()
-    for a in arrs:
-        h.update(np.ascontiguousarray(a).tobytes())
-    return h.hexdigest()
+DRAWS = {"a": "driver_pw3d_full", "b": "driver_pw3d_full_b", "c": "driver_pw3d_full_c"}       # seeds and settings: the fixtures' own
 
 
 def member(task):
@@ -40,13 +31,13 @@ def member(task):
     os.environ.setdefault("OMP_NUM_THREADS", "1")
     import _ipo_summary as ips
     import zedo_oracle as O
-    from lib.dataset import synthetic as syn
-    tag, seed_pose, seed_cl, conf_mode = DRAWS[draw]
-    d = syn.make_poses(N, seed=seed_pose, conf_mode=conf_mode)
-    cl = syn.make_clusters(H, seed=seed_cl)
-    K = d["camera_param"]
-    uv = syn.perturb_ulp(d["db_2d"][:, :, :2], SEED0 + run)
-    x0c = (cl - cl[:, 0:1, :]).astype(np.float32)
+    from _shared import Capture
+    tag = DRAWS[draw]
+    cap = Capture(tag)
+    N, H, K = cap.N, cap.H, cap.K
+    KEYLIST, IPO_T, MIN_T = [int(k) for k in cap.g["keylist"]], float(cap.g["ipo_T"]), float(cap.g["minT"])
+    uv = np.ascontiguousarray(cap.detections(SEED0 + run)[:, :, :2])
+    x0c = (cap.cl - cap.cl[:, 0:1, :]).astype(np.float32)
     t0 = time.time()
     T0 = O.ipo_init_T(uv, K, IPO_T)
     cs, Ts = [], []
@@ -67,17 +58,14 @@ def main():
     ap.add_argument("--draws", default="a,b,c")
     a = ap.parse_args()
     from multiprocessing import Pool
-    from lib.dataset import synthetic as syn
+    from _shared import Capture
     draws = a.draws.split(",")
     tasks = [(dr, r) for dr in draws for r in range(1, a.members + 1)]
     with Pool(a.workers) as pool:
         res = pool.map(member, tasks, chunksize=1)
     for dr in draws:
-        tag, seed_pose, seed_cl, conf_mode = DRAWS[dr]
-        d = syn.make_poses(N, seed=seed_pose, conf_mode=conf_mode)
-        cl = syn.make_clusters(H, seed=seed_cl)
-        sha = _sha(d["db_2d"], d["camera_param"], cl)
-        assert str(np.load(os.path.join(OUT, tag + ".npz"))["inputs_sha"]) == sha, "inputs differ from the captured run"
+        tag = DRAWS[dr]
+        sha = str(Capture(tag).g["inputs_sha"])             # Capture regenerates the inputs and checks them against it
         rows = [s for (q, r, s) in sorted((x for x in res if x[0] == dr), key=lambda x: x[1])]
         np.savez_compressed(os.path.join(OUT, tag + "_ipoens_oracle.npz"), members=np.arange(1, len(rows) + 1) + SEED0,
                             inputs_sha=np.array(sha), implementation=np.array("oracle/zedo_oracle.py::ipo_fit (numpy float32)"),
