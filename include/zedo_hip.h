@@ -41,7 +41,8 @@ extern "C" {
 #define ZEDO_ABI_VERSION 5   /* 3: + zedo_reproj_degenerate, zedo_pose_min, zedo_weights_set_math / zedo_weights_get_math;
                               * 4: + zedo_profile_bracket_ms;  5: + zedo_probe_mfma_peak_f16, workspace rows rounded to 64 again;
                               * still 5 (additive): + zedo_pc_plan_create / _destroy, zedo_pc_workspace_bytes, zedo_pc_step;
-                              * still 5 (additive): + zedo_min_mpjpe_both */
+                              * still 5 (additive): + zedo_min_mpjpe_both;
+                              * still 5 (additive): + zedo_min_reproj */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -66,7 +67,7 @@ const char *zedo_error_string(int code);
  * Supported: hidden H = 1024 (GroupNorm(32): groups of 32 channels), embed E = 512,
  * 1 <= J3 = n_joints*joint_dim <= 64, n_blocks = 2.  n_floats must equal the exact total.
  * Which entry point takes which size: zedo_score_eps, zedo_sde_step, zedo_pc_step - every J3 of the handle, pose rows
- * [B][J3]; zedo_reproj_prepare, zedo_reproj_degenerate, zedo_rotate_init, zedo_min_mpjpe(_both) - any J >= 1; zedo_ipo_fit(_resume) -
+ * [B][J3]; zedo_reproj_prepare, zedo_reproj_degenerate, zedo_rotate_init, zedo_min_mpjpe(_both), zedo_min_reproj - any J >= 1; zedo_ipo_fit(_resume) -
  * any J >= 1 with 1..17 key indices < J; zedo_oil_run (J3 == 51) and zedo_reproj_grad (J == 17) are the 17-joint, 3-coordinate
  * path only and return ZEDO_E_BADARG otherwise (tests/test_joint_counts_gpu.py holds each of these to the float64 oracle).
  * Synchronises `stream` before returning (h_params may be freed by the caller).
@@ -272,6 +273,29 @@ int zedo_min_mpjpe(const float *d_pred, const double *d_gt, int B, int N, int J,
  * any J >= 1, any contiguous shard (row_offset); allocates nothing, synchronises nothing, enqueues on `stream` only. */
 int zedo_min_mpjpe_both(const float *d_pred, const double *d_gt, int B, int N, int J, long long row_offset,
                         double *d_err, double *d_best, int *d_best_h, void *stream);
+
+/* ---- hypothesis selection WITHOUT ground truth: the minimum reprojection error --------------------------------------
+ * The criterion the whole loop optimises, evaluated on its result: how far x + T reprojects from the 2D detections,
+ * weighted by detector confidence (the reference's follow-up driver tracks proj2d - condition per step,
+ * run/opt_main_infant.py:307-309).  For local row b, pose n = (row_offset + b) % N, in fp64 on the fp32 inputs:
+ *   X_j = x[b,j] + T[b];   q_j = K[n] . X_j  (the full 3x3 product of RotOpt.forward, simple_zeroshot_opt.py:20-25: skew,
+ *                                             K22 != 1 and a homogeneous row other than (0,0,1) are honoured)
+ *   d_j = || q_j.xy / q_j.z - uv[n,j] ||                                     pixels
+ *   w_j = d_conf ? clamp(conf[n,j], 1e-4, 1) : 1   (the clamp of gradient_field_gen, :64-66, first power, taken in fp32)
+ *   err[b] = sum_j w_j d_j / sum_j w_j             (sums in ascending j)
+ * A row with any joint at or behind the camera plane (q_j.z <= 0) gets err = +inf; NaN inputs fall through that test and
+ * give NaN.  Then, per pose, the minimum over the hypotheses present in [0,B) and its index exactly as zedo_pose_min
+ * takes them: NaN wins (a diverged row does not hide behind a finite one), ties go to the lower hypothesis, a pose with
+ * no local row gets +inf / -1, a pose whose every local row is +inf reports +inf and its first local hypothesis.
+ * d_x [B,J,3] rows (h,n); d_T [B,3] the loop's final translation of each row; d_uv [N,J,2]; d_K [N,3,3];
+ * d_conf [N,J] or NULL (weight 1).  d_err [B] float64 (output, required; a valid input of zedo_pose_min),
+ * d_best [N] float64, d_best_h [N] int32.
+ * Contract as zedo_min_mpjpe: any J >= 1, any contiguous shard (row_offset); ZEDO_E_BADARG with nothing written for a
+ * NULL required pointer, a non-positive size or row_offset < 0; allocates nothing, synchronises nothing, enqueues on
+ * `stream` only: legal under stream capture.  Every row's error is the same bits whichever kernel evaluates it (J == 17
+ * with a 16-byte aligned d_x: rows staged through the LDS; otherwise one lane per row from global memory). */
+int zedo_min_reproj(const float *d_x, const float *d_T, const float *d_uv, const float *d_K, const float *d_conf,
+                    int B, int N, int J, long long row_offset, double *d_err, double *d_best, int *d_best_h, void *stream);
 
 /* The second half of zedo_min_mpjpe on its own: per pose n the minimum of d_err over the hypotheses present in
  * [0,B) and the first hypothesis index that attains it (np.amin / np.argmin, NaN wins: h36m.py:411-412).  For

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: seventeen one-line arithmetic mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: eighteen one-line arithmetic mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -38,6 +38,8 @@ MUTANTS = [
     ("ZEDO_MUT_IPO_W2_K6", "IPO forward: K[6] p_x dropped from the homogeneous coordinate w2 - zero in a pinhole K (zedo_geom.hip ipo_joint_terms)"),
     ("ZEDO_MUT_IPO_AXIS_XY", "IPO: rot_vect_y is updated under the x bit of axes_mask, in both kernels - the same for \"z\" and \"xyz\" (zedo_geom.hip)"),    # the one-pass selection (tests/test_selection_both_gpu.py): leaves every test of the single-protocol entry points green
     ("ZEDO_MUT_BOTH_SLOT", "zedo_min_mpjpe_both: the aligned (P2) row error is written into slot 0 as well (zedo_metric.hip store_row_error)"),
+    # the label-free selection (tests/test_select_reproj_gpu.py): leaves every other test green
+    ("ZEDO_MUT_REPROJ_WEIGHT", "zedo_min_reproj: every joint weighs 1 although confidences were given (zedo_metric.hip row_reproj_error)"),
 ]
 
 

@@ -822,3 +822,11 @@ extern "C" int zedo_min_mpjpe_both(const float *d_pred, const double *d_gt, int 
     HIPCHK(launch_min_mpjpe(d_pred, d_gt, B, N, J, row_offset, 0, true, d_err, d_best, d_best_h, (hipStream_t)stream));
     return ZEDO_OK;
 }
+
+extern "C" int zedo_min_reproj(const float *d_x, const float *d_T, const float *d_uv, const float *d_K, const float *d_conf,
+                               int B, int N, int J, long long row_offset, double *d_err, double *d_best, int *d_best_h, void *stream) {
+    if (!d_x || !d_T || !d_uv || !d_K || !d_err || !d_best || !d_best_h || B < 1 || N < 1 || J < 1 || row_offset < 0)
+        return ZEDO_E_BADARG;
+    HIPCHK(launch_min_reproj(d_x, d_T, d_uv, d_K, d_conf, B, N, J, row_offset, d_err, d_best, d_best_h, (hipStream_t)stream));
+    return ZEDO_OK;
+}

@@ -228,6 +228,8 @@ hipError_t launch_pose_min(const double *err, int B, int N, long long row_offset
 hipError_t launch_reproj_degenerate(const float *geom, int N, int J, int *d_count, hipStream_t st);
 hipError_t launch_min_mpjpe(const float *pred, const double *gt, int B, int N, int J, long long row_offset,
                             int procrustes, bool both, double *err, double *best, int *best_h, hipStream_t st);
+hipError_t launch_min_reproj(const float *x, const float *T, const float *uv, const float *K, const float *conf, int B, int N, int J,
+                             long long row_offset, double *err, double *best, int *best_h, hipStream_t st);
 
 
 // predictor-corrector step kernels (zedo_pc.hip); z: the caller's noise draw, unpadded [B][D]

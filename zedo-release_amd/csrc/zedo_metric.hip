@@ -4,6 +4,8 @@
 // with coalesced loads; the arg-min with one wavefront per pose (few poses) or one lane per pose (many: coalesced
 // reads of one hypothesis' errors at a time).  Both protocols of a batch (run/opt_main.py:227-228) come from one pass: the <true> instantiations
 // of the row-error kernels evaluate both errors on the tile they have staged, and one arg-min launch serves both (zedo_min_mpjpe_both).
+// Without ground truth (zedo_min_reproj): the confidence-weighted reprojection error of x + T in pixels per row, staged the same way, then the
+// same arg-min.
 #include "zedo_internal.h"
 
 #include <algorithm>
@@ -323,6 +325,103 @@ hipError_t launch_pose_min(const double *err, int B, int N, long long row_offset
     if (N >= POSE_MIN_LANE_N) hipLaunchKernelGGL(pose_min_kernel, dim3((N + 127) / 128, protocols), dim3(128), 0, st, err, B, N, row_offset, best, best_h);
     else hipLaunchKernelGGL(pose_min_wave_kernel, dim3((N + 3) / 4, protocols), dim3(256), 0, st, err, B, N, row_offset, best, best_h);
     return hipGetLastError();
+}
+
+// ---- selection without ground truth (zedo_min_reproj): the confidence-weighted mean reprojection distance of x + T, in pixels -------
+// Reprojection error of one row from its operands: p = the row's J*3 fp32 coordinates, T = its 3 translation components, uv = its pose's
+// J*2 detections, K = the pose's 3x3 intrinsics (row-major, all nine entries: the full product of RotOpt.forward,
+// simple_zeroshot_opt.py:20-25), cf = the pose's J confidences (read only when has_conf).  fp64 on the fp32 inputs; the weight is the
+// clamp of gradient_field_gen (:64-66: above 1 -> 1, below 1e-4 -> 1e-4, NaN stays NaN) at the first power, taken in fp32.  A joint at or
+// behind the camera plane (q.z <= 0) makes the row +inf; a NaN falls through that test and ends in the quotient.  The operands are plain
+// indexed reads (global memory or the LDS): both kernels below run these statements and return the same bits.
+template <class P, class TT, class O>
+__device__ __forceinline__ double row_reproj_error(const P &p, const TT &T, const O &uv, const O &K, const O &cf, bool has_conf, int J) {
+    const double k0 = K[0], k1 = K[1], k2 = K[2], k3 = K[3], k4 = K[4], k5 = K[5], k6 = K[6], k7 = K[7], k8 = K[8];
+    const double t0 = T[0], t1 = T[1], t2 = T[2];
+    double num = 0.0, den = 0.0;
+    bool behind = false;
+    for (int j = 0; j < J; ++j) {
+        const double X = (double)p[3 * j] + t0, Y = (double)p[3 * j + 1] + t1, Z = (double)p[3 * j + 2] + t2;
+        const double qx = k0 * X + k1 * Y + k2 * Z, qy = k3 * X + k4 * Y + k5 * Z, qz = k6 * X + k7 * Y + k8 * Z;
+        behind |= qz <= 0.0;
+        const double dx = qx / qz - (double)uv[2 * j], dy = qy / qz - (double)uv[2 * j + 1];
+        const double d = sqrt(dx * dx + dy * dy);
+        double w = 1.0;
+        if (has_conf) {
+            float c = cf[j];
+            if (c > 1.0f) c = 1.0f;
+            if (c < 1e-4f) c = 1e-4f;
+            w = (double)c;
+#ifdef ZEDO_MUT_REPROJ_WEIGHT   // tools/mutation_check.py only: every joint weighs 1 although confidences were given
+            w = 1.0;
+#endif
+        }
+        num += w * d;
+        den += w;
+    }
+    if (behind) return __builtin_huge_val();
+    return num / den;
+}
+
+// Any joint count, any alignment of x: one lane per row straight from global memory; the per-pose operands come through the L2.
+__global__ __launch_bounds__(128) void row_reproj_kernel(const float *__restrict__ x, const float *__restrict__ T, const float *__restrict__ uv,
+                                                         const float *__restrict__ K, const float *__restrict__ conf, int B, int N, int J,
+                                                         long long row_offset, double *__restrict__ err) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const size_t n = (size_t)((row_offset + b) % N);
+    const float *cf = conf ? conf + n * J : uv;                    // (not read without confidences)
+    err[b] = row_reproj_error(x + (size_t)b * J * 3, T + (size_t)b * 3, uv + n * J * 2, K + n * 9, cf, conf != nullptr, J);
+}
+
+// J = 17: the 64 rows of a wave staged through the LDS exactly as row_error17_kernel stages them (one contiguous 13 KB piece, 16-byte
+// loads, [row][51]); the rows' per-pose operands - 34 detections, 9 intrinsics, 17 confidences = 60 floats of three arrays, consecutive
+// poses wrapping behind N - 1 - by lanes 0..59, one float each per row (240 contiguous bytes in three pieces), into [row][61]: an odd
+// row stride again, a lane reading its own row is bank-conflict free.  T is 12 bytes per row, read by the row's lane from global memory
+// (768 contiguous bytes per wave).
+constexpr int RP_UV = 0, RP_K = 34, RP_CF = 43, RP_OPS = 60, RP_LD = 61;
+static_assert(RP_OPS <= RE_ROWS && RP_LD > RP_OPS && (RP_LD & 1), "one lane per operand float, odd row stride");
+__global__ __launch_bounds__(RE_ROWS) void row_reproj17_kernel(const float *__restrict__ x, const float *__restrict__ T, const float *__restrict__ uv,
+                                                               const float *__restrict__ K, const float *__restrict__ conf, int B, int N,
+                                                               long long row_offset, double *__restrict__ err) {
+    __shared__ __attribute__((aligned(16))) float sp[RE_ROWS * RE_D];
+    __shared__ float so[RE_ROWS * RP_LD];
+    const int tid = threadIdx.x, b0 = blockIdx.x * RE_ROWS;
+    const int rows = min(RE_ROWS, B - b0);
+    const int nf = rows * RE_D;                                   // floats of this tile (the last tile of a batch is short)
+    const float *src = x + (size_t)b0 * RE_D;                     // 16-byte aligned: b0 * 204 bytes, b0 a multiple of 64
+    for (int c = tid; c * 4 + 3 < nf; c += RE_ROWS) *reinterpret_cast<f32x4 *>(sp + c * 4) = *reinterpret_cast<const f32x4 *>(src + c * 4);
+    if (tid < (nf & 3)) sp[(nf & ~3) + tid] = src[(nf & ~3) + tid];
+    const float *op = nullptr;                                    // this lane's float of a pose's operands, `stride` floats from pose to pose
+    int stride = 0;
+    if (tid < RP_K) { op = uv + tid; stride = 34; }
+    else if (tid < RP_CF) { op = K + (tid - RP_K); stride = 9; }
+    else if (tid < RP_OPS && conf) { op = conf + (tid - RP_CF); stride = 17; }
+    int n = (int)((row_offset + b0) % N);                         // wave-uniform, advanced by increment / compare as in row_error17_kernel
+    if (op) {
+#pragma unroll 16
+        for (int r = 0; r < rows; ++r) {
+            so[r * RP_LD + tid] = op[(size_t)n * stride];
+            n = (n + 1 == N) ? 0 : n + 1;
+        }
+    }
+    __syncthreads();                                              // the lanes read what other lanes have staged
+    if (tid < rows) {
+        const float *o = so + tid * RP_LD;
+        err[b0 + tid] = row_reproj_error(sp + tid * RE_D, T + (size_t)(b0 + tid) * 3, o + RP_UV, o + RP_K, o + RP_CF, conf != nullptr, 17);
+    }
+}
+
+hipError_t launch_min_reproj(const float *x, const float *T, const float *uv, const float *K, const float *conf, int B, int N, int J,
+                             long long row_offset, double *err, double *best, int *best_h, hipStream_t st) {
+    // (the staged kernel fetches the pose tensor with 16-byte loads: a row pointer that is not 16-byte aligned takes the generic kernel)
+    if (J == 17 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
+        hipLaunchKernelGGL(row_reproj17_kernel, dim3((B + RE_ROWS - 1) / RE_ROWS), dim3(RE_ROWS), 0, st, x, T, uv, K, conf, B, N, row_offset, err);
+    else
+        hipLaunchKernelGGL(row_reproj_kernel, dim3((B + 127) / 128), dim3(128), 0, st, x, T, uv, K, conf, B, N, J, row_offset, err);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_pose_min(err, B, N, row_offset, best, best_h, st);
 }
 
 // The one dispatch of the row-error kernels (zedo_min_mpjpe: BOTH = false; zedo_min_mpjpe_both: BOTH = true, err [2][B]).

@@ -29,6 +29,9 @@ def build_parser(description, inference=False):
     p.add_argument("--math", choices=("f32", "f16x3"), default=None,
                    help="arithmetic of the dense layers: f32 = exact fp32 MFMA (default), f16x3 = split-fp16 operands on the fp16 "
                         "matrix pipe at fp32-level accuracy, ~2x faster (same as the ZEDO_MATH environment variable)")
+    p.add_argument("--select", choices=("none", "reproj"), default="none",
+                   help="run.inference only: reproj = also keep, per pose, the hypothesis whose x + T reprojects closest to the 2D "
+                        "detections (confidence-weighted, no ground truth needed) -> <out>_selected.npz")
     if inference:
         p.add_argument("--eval", action="store_true", default=None, help="evaluation mode")
         p.add_argument("--data", type=str, default=None, help="npz with db_2d, camera_param[, db_3d] ('wild' dataset)")
@@ -123,11 +126,11 @@ def not_fused_because(config):
     return None
 
 
-def stepwise_loop(config, model, sde, sample_poses, gt_2d, K, S, device, hypotheses=None, host_round_trip=False):
+def stepwise_loop(config, model, sde, sample_poses, gt_2d, K, S, device, hypotheses=None, host_round_trip=False, *, return_T=False):
     """run/opt_main.py:166-222 as written there - one hypothesis at a time, IPO through RotOpt (one zedo_ipo_fit
     launch), then S iterations of gradient_field_gen + one sampler step - for configurations outside the fused
     pipeline.  hypotheses = (first, count): only that contiguous range of the hypothesis loop (one rank's share).
-    Returns rows [count*N,17,3] (h-major).
+    Returns rows [count*N,17,3] (h-major); with return_T=True (rows, T [count*N,3]): also the translation each row ended the loop with.
     The loop is device-resident (round 6): the sampler's `step_device` twin hands the updated rows back as a device
     tensor and the time stamps are host floats, so no iteration synchronises or copies - the reference's pc_sampler
     returns numpy (sampling.py:515-527) and its driver re-uploads it (run/opt_main.py:220): 2 x S blocking copies that
@@ -147,7 +150,7 @@ def stepwise_loop(config, model, sde, sample_poses, gt_2d, K, S, device, hypothe
     timestamp = torch.linspace(sde.T, z.sampling_eps, S, device=device)
     t_host = timestamp.cpu().tolist()          # the same fp32 values the reference reads one by one with float(t)
     step_device = None if host_round_trip else getattr(sampling_fn, "step_device", None)
-    out = []
+    out, out_T = [], []
     h_lo, h_cnt = (0, len(sample_poses)) if hypotheses is None else hypotheses
     for sid in range(h_lo, h_lo + h_cnt):
         x0 = centred[sid:sid + 1]
@@ -169,18 +172,31 @@ def stepwise_loop(config, model, sde, sample_poses, gt_2d, K, S, device, hypothe
                                          t=timestamp[i], t_step=i, args=None)
                 denoise_x = torch.as_tensor(results).to(device)
         out.append(denoise_x)
+        out_T.append(T.reshape(N, 3).float())
     if not out:
-        return torch.empty((0, N_JOINTS, JOINT_DIM), dtype=torch.float32, device=device)
-    return torch.cat(out, 0).contiguous()
+        rows, rows_T = (torch.empty((0, N_JOINTS, JOINT_DIM), dtype=torch.float32, device=device),
+                        torch.empty((0, 3), dtype=torch.float32, device=device))
+    else:
+        rows, rows_T = torch.cat(out, 0).contiguous(), torch.cat(out_T, 0).contiguous()
+    return (rows, rows_T) if return_T else rows
+
+
+def selected_path(out):
+    """<out without .npy>_selected.npz: where run.inference --select reproj writes the pose it keeps per detection."""
+    return (out[:-4] if out.endswith(".npy") else out) + "_selected.npz"
 
 
 def run(args, inference=False):
     from lib.algorithms.advanced import sde_lib
     from lib.algorithms.advanced.model import ScoreModelFC_Adv
     from lib.algorithms.ema import ExponentialMovingAverage
-    from zedo_hip.pipeline import (Pipeline, ZeDOConfig, barrier, force_dist, gather_row_shards, init_dist,
-                                   local_device_index, shard_hypotheses, shard_rows)
+    from zedo_hip.pipeline import (Pipeline, ZeDOConfig, barrier, empty_selection, force_dist, gather_row_shards, init_dist,
+                                   local_device_index, reduce_min_over_ranks, shard_hypotheses, shard_rows, take_rows)
 
+    select = getattr(args, "select", "none") or "none"
+    if select != "none" and not inference:
+        raise SystemExit(f"--select {select} is honoured by run.inference only: run.opt_main scores every hypothesis against 3D ground "
+                         "truth (best of H), and the ground-truth evaluation of a selected pose is printed by run.inference --eval")
     config = load_config(args.config)
     if getattr(args, "math", None):
         os.environ["ZEDO_MATH"] = args.math          # read by zedo_hip.Weights when the model's device copy is built
@@ -241,7 +257,9 @@ def run(args, inference=False):
         if rank == 0:
             print(f"configuration outside the fused pipeline ({why}): stepping the loop of run/opt_main.py:166-222 "
                   f"through the per-step sampling_fn surface, hypotheses split over {world} rank(s)")
-        x = stepwise_loop(config, model, sde, sample_poses, gt_2d, K, S, device, hypotheses=(h_lo, h_cnt))
+        x = stepwise_loop(config, model, sde, sample_poses, gt_2d, K, S, device, hypotheses=(h_lo, h_cnt), return_T=select != "none")
+        if select != "none":
+            x, T = x
 
     batch_results = None
     if inference:          # results.npy holds every hypothesis: [N, H, 17, 3] (run/inference.py:233-236)
@@ -249,12 +267,44 @@ def run(args, inference=False):
         batch_results = full.reshape(H, N, N_JOINTS, JOINT_DIM).permute(1, 0, 2, 3).cpu().numpy()
         if rank == 0:
             np.save(args.out, batch_results)
+    selected = None
+    if inference and select == "reproj":
+        # per pose the hypothesis whose x + T reprojects closest to the detections (zedo_min_reproj) on this rank's rows, MIN over the
+        # ranks, the winners taken from the gathered rows: every rank ends with the same four arrays, rank 0 writes them
+        import zedo_hip
+        if rows == 0:
+            best, idx = empty_selection(N, device)
+        elif why is None:
+            best, idx = pipe.select_reproj(x, T, row_offset=lo)
+        else:
+            d2 = torch.tensor(np.ascontiguousarray(gt_2d), dtype=torch.float32, device=device)
+            Kd = torch.tensor(np.ascontiguousarray(K), dtype=torch.float32, device=device)
+            _, best, idx = zedo_hip.min_reproj(x, T.contiguous(), d2[:, :, :2].contiguous(), Kd, d2[:, :, 2].contiguous(), N, lo)
+        best, idx = reduce_min_over_ranks(best, idx)
+        full_T = gather_row_shards(T.contiguous(), H * N, lo=None if why is None else lo)
+        selected = dict(pose=take_rows(full, idx, H, N).cpu().numpy(), hypothesis=idx.cpu().numpy().astype(np.int32),
+                        reproj_px=best.cpu().numpy(), T=take_rows(full_T, idx, H, N).cpu().numpy())
+        if rank == 0:
+            np.savez(selected_path(args.out), **selected)
     errs = None
     if not inference or args.eval:
         print("eval...")
         p1 = test_dataset.eval_multi(("rows", x), protocol2=False, print_verbose=rank == 0, row_offset=lo)
         p2 = test_dataset.eval_multi(("rows", x), protocol2=True, print_verbose=rank == 0, row_offset=lo)
         errs = (p1, p2)
+        if selected is not None:
+            # the selected pose scored as a one-hypothesis set by the same eval_multi (every rank holds all of it: row_offset 0); its
+            # own prints are kept off stdout so that the two best-of-H lines above stay the only `mean ...` lines
+            import contextlib
+            import io
+            sel_rows = torch.tensor(selected["pose"], dtype=torch.float32, device=device)
+            with contextlib.redirect_stdout(io.StringIO()):
+                s1 = test_dataset.eval_multi(("rows", sel_rows), protocol2=False, print_verbose=False, row_offset=0)
+                s2 = test_dataset.eval_multi(("rows", sel_rows), protocol2=True, print_verbose=False, row_offset=0)
+            if rank == 0:
+                print(f"reproj-selected MPJPE : {s1}")
+                print(f"reproj-selected PA-MPJPE : {s2}")
+            errs = (p1, p2, s1, s2)
     if use_dist:
         import torch.distributed as dist
         barrier()

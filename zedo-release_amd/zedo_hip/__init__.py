@@ -67,6 +67,7 @@ SIGNATURES = {
     "zedo_rotate_init": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _ll, _vp]),
     "zedo_min_mpjpe": (_i, [_vp, _vp, _i, _i, _i, _ll, _i, _vp, _vp, _vp, _vp]),
     "zedo_min_mpjpe_both": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp, _vp]),
+    "zedo_min_reproj": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp, _vp]),
     "zedo_pose_min": (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp]),
     "zedo_probe_mfma_peak": (_i, [_i, _vp, _vp, _vp]),
     "zedo_probe_mfma_peak_f16": (_i, [_i, _vp, _vp, _vp]),
@@ -470,6 +471,26 @@ def min_mpjpe_both(pred, gt_centred, N, row_offset=0):
         best_h = torch.empty((2, N), dtype=torch.int32, device=dev)
         _check(_lib.zedo_min_mpjpe_both(_p(pred), _p(gt_centred, torch.float64), B, N, J, int(row_offset),
                                         _p(err, torch.float64), _p(best, torch.float64), _p(best_h, torch.int32), _stream(dev)))
+    return err, best, best_h
+
+
+def min_reproj(x, T, uv, K, conf=None, N=None, row_offset=0):
+    """Selection without ground truth (zedo_min_reproj): x [B,J,3] rows (h,n), T [B,3], uv [N,J,2], K [N,3,3], conf [N,J] or None
+    (weight 1) -> (err [B] f64: the confidence-weighted mean reprojection distance of x + T in pixels, best [N] f64, idx [N] i32)."""
+    _need_gpu()
+    dev = _device_of(x, T, uv, K, conf)
+    B, J = x.shape[0], x.shape[1]
+    N = uv.shape[0] if N is None else int(N)
+    if (tuple(x.shape) != (B, J, 3) or tuple(T.shape) != (B, 3) or tuple(uv.shape) != (N, J, 2) or tuple(K.shape) != (N, 3, 3)
+            or (conf is not None and tuple(conf.shape) != (N, J))):
+        raise ZedoError(f"min_reproj: x [B,J,3], T [B,3], uv [N,J,2], K [N,3,3], conf [N,J] expected, got {tuple(x.shape)}, "
+                        f"{tuple(T.shape)}, {tuple(uv.shape)}, {tuple(K.shape)}, {None if conf is None else tuple(conf.shape)} with N = {N}")
+    with torch.cuda.device(dev):
+        err = torch.empty((B,), dtype=torch.float64, device=dev)
+        best = torch.empty((N,), dtype=torch.float64, device=dev)
+        best_h = torch.empty((N,), dtype=torch.int32, device=dev)
+        _check(_lib.zedo_min_reproj(_p(x), _p(T), _p(uv), _p(K), _p(conf), B, N, J, int(row_offset), _p(err, torch.float64),
+                                    _p(best, torch.float64), _p(best_h, torch.int32), _stream(dev)))
     return err, best, best_h
 
 

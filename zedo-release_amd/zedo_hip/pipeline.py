@@ -6,6 +6,7 @@ batched as rows (h, n) and every stage running in libzedo_hip.so.
          x       = R x0                                           (opt_main.py:201)
     OIL  S steps of {reprojection correction, score-network probability-flow step}   (opt_main.py:202-220)
     selection    = per-pose min over hypotheses of (PA-)MPJPE     (eval_multi)
+                   or, without ground truth, of the confidence-weighted reprojection error of x + T (select_reproj)
 
 Rows may be a contiguous shard of the H*N global rows (one shard per GPU); the only exchange is the final
 MIN over ranks, done by the caller (run/opt_main.py, bench.py) with torch.distributed.
@@ -15,8 +16,8 @@ import os
 import numpy as np
 import torch
 
-from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, min_mpjpe_both, oil_run, reproj_degenerate, reproj_prepare,
-               rotate_init)
+from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, min_mpjpe_both, min_reproj, oil_run, reproj_degenerate,
+               reproj_prepare, rotate_init)
 
 
 def linspace_f32(start, end, steps):
@@ -103,6 +104,31 @@ class Pipeline:
         with torch.cuda.device(self.device):
             _, best, idx = min_mpjpe_both(x, gt, self.N, row_offset)     # one pass over the rows: the bits of the two min_mpjpe calls
         return dict(p1=(best[0], idx[0]), p2=(best[1], idx[1]))
+
+    def select_reproj(self, x, T, row_offset=0):
+        """Selection without ground truth on the problem of load(): -> (best [N] f64, idx [N] i32) for the local rows x [B,17,3] with
+        their final translations T [B,3] - per pose the smallest confidence-weighted reprojection error (pixels) of x + T against the
+        detections and the hypothesis that attains it (zedo_min_reproj).  Ranks are combined with reduce_min_over_ranks."""
+        if x.shape[0] == 0:
+            return empty_selection(self.N, self.device)
+        with torch.cuda.device(self.device):
+            _, best, idx = min_reproj(x, T, self.uv, self.K, self.conf, self.N, row_offset)
+        return best, idx
+
+    def take(self, rows_full, idx):
+        """The winning row of every pose: rows_full [H*N, ...] (all global rows, h-major), idx [N] -> rows_full.view(H, N, ...)[idx, arange(N)].
+        An index of -1 (a pose no row was selected for) is an error."""
+        return take_rows(rows_full, idx, self.H, self.N)
+
+
+def take_rows(rows_full, idx, H, N):
+    """rows_full.view(H, N, ...)[idx, arange(N)] (plain torch indexing); idx [N] with every entry in 0 .. H-1."""
+    if rows_full.shape[0] != H * N or tuple(idx.shape) != (N,):
+        raise ValueError(f"take: rows [{H * N}, ...] and idx [{N}] expected, got {tuple(rows_full.shape)} and {tuple(idx.shape)}")
+    i = idx.to(device=rows_full.device, dtype=torch.int64)
+    if bool(((i < 0) | (i >= H)).any()):
+        raise ValueError("take: a pose has no selected hypothesis (index -1) or an index outside the hypotheses")
+    return rows_full.reshape((H, N) + tuple(rows_full.shape[1:]))[i, torch.arange(N, device=rows_full.device)]
 
 
 def empty_selection(N, device):
