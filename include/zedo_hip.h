@@ -42,7 +42,8 @@ extern "C" {
                               * 4: + zedo_profile_bracket_ms;  5: + zedo_probe_mfma_peak_f16, workspace rows rounded to 64 again;
                               * still 5 (additive): + zedo_pc_plan_create / _destroy, zedo_pc_workspace_bytes, zedo_pc_step;
                               * still 5 (additive): + zedo_min_mpjpe_both;
-                              * still 5 (additive): + zedo_min_reproj */
+                              * still 5 (additive): + zedo_min_reproj;
+                              * still 5 (additive): + zedo_joint_reproj, zedo_joint_compose */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -67,7 +68,7 @@ const char *zedo_error_string(int code);
  * Supported: hidden H = 1024 (GroupNorm(32): groups of 32 channels), embed E = 512,
  * 1 <= J3 = n_joints*joint_dim <= 64, n_blocks = 2.  n_floats must equal the exact total.
  * Which entry point takes which size: zedo_score_eps, zedo_sde_step, zedo_pc_step - every J3 of the handle, pose rows
- * [B][J3]; zedo_reproj_prepare, zedo_reproj_degenerate, zedo_rotate_init, zedo_min_mpjpe(_both), zedo_min_reproj - any J >= 1; zedo_ipo_fit(_resume) -
+ * [B][J3]; zedo_reproj_prepare, zedo_reproj_degenerate, zedo_rotate_init, zedo_min_mpjpe(_both), zedo_min_reproj, zedo_joint_reproj, zedo_joint_compose - any J >= 1; zedo_ipo_fit(_resume) -
  * any J >= 1 with 1..17 key indices < J; zedo_oil_run (J3 == 51) and zedo_reproj_grad (J == 17) are the 17-joint, 3-coordinate
  * path only and return ZEDO_E_BADARG otherwise (tests/test_joint_counts_gpu.py holds each of these to the float64 oracle).
  * Synchronises `stream` before returning (h_params may be freed by the caller).
@@ -296,6 +297,38 @@ int zedo_min_mpjpe_both(const float *d_pred, const double *d_gt, int B, int N, i
  * with a 16-byte aligned d_x: rows staged through the LDS; otherwise one lane per row from global memory). */
 int zedo_min_reproj(const float *d_x, const float *d_T, const float *d_uv, const float *d_K, const float *d_conf,
                     int B, int N, int J, long long row_offset, double *d_err, double *d_best, int *d_best_h, void *stream);
+
+/* ---- joint-wise aggregation WITHOUT ground truth: the minimum reprojection error per joint ------------------------------
+ * Where zedo_min_reproj keeps one whole hypothesis per pose, this keeps, for every joint of every pose, the hypothesis whose
+ * joint reprojects closest to its detection, and zedo_joint_compose assembles the pose from those joints (the joint-wise
+ * reprojection-based aggregation of D3DP, Shan et al., ICCV 2023).  A joint assembled in the camera frame is exactly one
+ * hypothesis's joint, so the confidence-weighted mean of the per-joint minima never exceeds the smallest per-row weighted mean.
+ * Whether this lowers the error against ground truth on real data is not measured.
+ * For local row b, pose n = (row_offset + b) % N, in fp64 on the fp32 inputs, with the statements of zedo_min_reproj:
+ *   X = x[b,j] + T[b];   q = K[n] . X  (full 3x3 product);   d[b,j] = || q.xy / q.z - uv[n,j] ||          pixels
+ * q.z <= 0 gives d[b,j] = +inf for THAT JOINT only (the row-level call makes the whole row +inf); NaN inputs fall through that
+ * test and give NaN.  No confidences: a joint's weight is the same for every hypothesis of its pose and cannot change a
+ * per-joint arg-min.  d_best [N,J] float64 and d_best_h [N,J] int32 (both required): the minimum over the hypotheses present
+ * in [0,B) and the hypothesis that attains it, bit for bit what zedo_pose_min(d_jerr, B*J, N*J, row_offset*J, ...) returns
+ * on the flattened [B,J] distances - NaN wins, ties go to the lower hypothesis, no local row gives +inf / -1, a (pose, joint)
+ * whose every local entry is +inf reports +inf and its first local hypothesis.
+ * d_jerr [B,J] float64 is OPTIONAL.  NULL: one kernel, one lane per (pose, joint), walks the local hypotheses of its pose with
+ * uv[n,j] and K[n] in registers and a running minimum - nothing of size [B,J] is written.  Not NULL: d is written (the same
+ * bits for any alignment of d_x) and zedo_pose_min's kernels run on it.  Both routes return the same bits in d_best / d_best_h.
+ * Contract: any J >= 1, any contiguous shard (row_offset); ZEDO_E_BADARG with nothing written for a NULL required pointer, a
+ * non-positive size, row_offset < 0, or B*J or N*J above INT_MAX; allocates nothing, synchronises nothing, enqueues on
+ * `stream` only: legal under stream capture; no atomics: bit-identical from run to run. */
+int zedo_joint_reproj(const float *d_x, const float *d_T, const float *d_uv, const float *d_K, int B, int N, int J,
+                      long long row_offset, double *d_jerr, double *d_best, int *d_best_h, void *stream);
+
+/* The assembled pose, a gather over ALL rows d_x [H*N,J,3], d_T [H*N,3] (rows (h,n)):
+ *   pose[n,j,c] = fl32( ((double)x[g,j,c] + (double)T[g,c]) - (d_ref_h ? (double)T[ref_h[n]*N + n, c] : 0) ),  g = joint_h[n,j]*N + n
+ * d_joint_h [N,J] int32 (e.g. d_best_h of zedo_joint_reproj after the MIN over ranks); d_ref_h [N] int32 or NULL.  NULL: the
+ * camera frame.  Otherwise the root-relative frame of hypothesis ref_h[n] (e.g. zedo_min_reproj's winner): a joint taken from
+ * the reference hypothesis itself comes back as x exactly (the fp64 sum of two fp32 numbers is exact unless |x| < 2^-29 |T|).  An index outside 0 .. H-1, in d_joint_h or d_ref_h, makes the
+ * affected joints NaN and is never used as an address.  d_pose [N,J,3] fp32.  Contract as zedo_joint_reproj. */
+int zedo_joint_compose(const float *d_x, const float *d_T, const int *d_joint_h, const int *d_ref_h, int H, int N, int J,
+                       float *d_pose, void *stream);
 
 /* The second half of zedo_min_mpjpe on its own: per pose n the minimum of d_err over the hypotheses present in
  * [0,B) and the first hypothesis index that attains it (np.amin / np.argmin, NaN wins: h36m.py:411-412).  For

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: eighteen one-line arithmetic mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: nineteen one-line arithmetic mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -40,6 +40,8 @@ MUTANTS = [
     ("ZEDO_MUT_BOTH_SLOT", "zedo_min_mpjpe_both: the aligned (P2) row error is written into slot 0 as well (zedo_metric.hip store_row_error)"),
     # the label-free selection (tests/test_select_reproj_gpu.py): leaves every other test green
     ("ZEDO_MUT_REPROJ_WEIGHT", "zedo_min_reproj: every joint weighs 1 although confidences were given (zedo_metric.hip row_reproj_error)"),
+    # the joint-wise aggregation (tests/test_joint_reproj_gpu.py): leaves every other test green
+    ("ZEDO_MUT_JOINT_TIE", "zedo_joint_reproj without d_jerr: the running minimum takes ties, the HIGHER hypothesis wins (zedo_metric.hip joint_reproj_walk_kernel)"),
 ]
 
 

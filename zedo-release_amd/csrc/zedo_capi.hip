@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -828,5 +829,21 @@ extern "C" int zedo_min_reproj(const float *d_x, const float *d_T, const float *
     if (!d_x || !d_T || !d_uv || !d_K || !d_err || !d_best || !d_best_h || B < 1 || N < 1 || J < 1 || row_offset < 0)
         return ZEDO_E_BADARG;
     HIPCHK(launch_min_reproj(d_x, d_T, d_uv, d_K, d_conf, B, N, J, row_offset, d_err, d_best, d_best_h, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
+extern "C" int zedo_joint_reproj(const float *d_x, const float *d_T, const float *d_uv, const float *d_K, int B, int N, int J,
+                                 long long row_offset, double *d_jerr, double *d_best, int *d_best_h, void *stream) {
+    if (!d_x || !d_T || !d_uv || !d_K || !d_best || !d_best_h || B < 1 || N < 1 || J < 1 || row_offset < 0) return ZEDO_E_BADARG;
+    if ((long long)B * J > INT_MAX || (long long)N * J > INT_MAX) return ZEDO_E_BADARG;     // the flattened vectors are indexed with int
+    HIPCHK(launch_joint_reproj(d_x, d_T, d_uv, d_K, B, N, J, row_offset, d_jerr, d_best, d_best_h, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
+extern "C" int zedo_joint_compose(const float *d_x, const float *d_T, const int *d_joint_h, const int *d_ref_h, int H, int N, int J,
+                                  float *d_pose, void *stream) {
+    if (!d_x || !d_T || !d_joint_h || !d_pose || H < 1 || N < 1 || J < 1) return ZEDO_E_BADARG;
+    if ((long long)N * J > INT_MAX) return ZEDO_E_BADARG;
+    HIPCHK(launch_joint_compose(d_x, d_T, d_joint_h, d_ref_h, H, N, J, d_pose, (hipStream_t)stream));
     return ZEDO_OK;
 }

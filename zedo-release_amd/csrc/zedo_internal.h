@@ -230,6 +230,11 @@ hipError_t launch_min_mpjpe(const float *pred, const double *gt, int B, int N, i
                             int procrustes, bool both, double *err, double *best, int *best_h, hipStream_t st);
 hipError_t launch_min_reproj(const float *x, const float *T, const float *uv, const float *K, const float *conf, int B, int N, int J,
                              long long row_offset, double *err, double *best, int *best_h, hipStream_t st);
+// jerr == nullptr: the walking kernel (no [B,J] intermediate); otherwise d [B,J] is written and launch_pose_min runs on it flattened
+hipError_t launch_joint_reproj(const float *x, const float *T, const float *uv, const float *K, int B, int N, int J, long long row_offset,
+                               double *jerr, double *best, int *best_h, hipStream_t st);
+hipError_t launch_joint_compose(const float *x, const float *T, const int *joint_h, const int *ref_h, int H, int N, int J, float *pose,
+                                hipStream_t st);
 
 
 // predictor-corrector step kernels (zedo_pc.hip); z: the caller's noise draw, unpadded [B][D]

@@ -5,7 +5,9 @@
 // reads of one hypothesis' errors at a time).  Both protocols of a batch (run/opt_main.py:227-228) come from one pass: the <true> instantiations
 // of the row-error kernels evaluate both errors on the tile they have staged, and one arg-min launch serves both (zedo_min_mpjpe_both).
 // Without ground truth (zedo_min_reproj): the confidence-weighted reprojection error of x + T in pixels per row, staged the same way, then the
-// same arg-min.
+// same arg-min.  Per joint (zedo_joint_reproj): the same per-joint distance, its minimum over the hypotheses per (pose, joint) - one lane
+// per (pose, joint) walking the hypotheses, or every row's distances and the same arg-min on them flattened - and the gather that assembles
+// a pose from the winning joints (zedo_joint_compose).
 #include "zedo_internal.h"
 
 #include <algorithm>
@@ -334,18 +336,27 @@ hipError_t launch_pose_min(const double *err, int B, int N, long long row_offset
 // clamp of gradient_field_gen (:64-66: above 1 -> 1, below 1e-4 -> 1e-4, NaN stays NaN) at the first power, taken in fp32.  A joint at or
 // behind the camera plane (q.z <= 0) makes the row +inf; a NaN falls through that test and ends in the quotient.  The operands are plain
 // indexed reads (global memory or the LDS): both kernels below run these statements and return the same bits.
+// The per-joint part, the one copy every kernel of this section runs (zedo_min_reproj and zedo_joint_reproj): the distance in pixels
+// between the projection of (X, Y, Z) = x[b,j] + T[b] through K (k[9], row-major) and the detection (u, v); `behind` is set when the
+// joint is at or behind the camera plane (the value returned is then whatever the quotient gives: the caller replaces it).
+__device__ __forceinline__ double joint_reproj_dist(const double (&k)[9], double X, double Y, double Z, double u, double v, bool &behind) {
+    const double qx = k[0] * X + k[1] * Y + k[2] * Z, qy = k[3] * X + k[4] * Y + k[5] * Z, qz = k[6] * X + k[7] * Y + k[8] * Z;
+    behind = qz <= 0.0;
+    const double dx = qx / qz - u, dy = qy / qz - v;
+    return sqrt(dx * dx + dy * dy);
+}
+
 template <class P, class TT, class O>
 __device__ __forceinline__ double row_reproj_error(const P &p, const TT &T, const O &uv, const O &K, const O &cf, bool has_conf, int J) {
-    const double k0 = K[0], k1 = K[1], k2 = K[2], k3 = K[3], k4 = K[4], k5 = K[5], k6 = K[6], k7 = K[7], k8 = K[8];
+    const double k[9] = {K[0], K[1], K[2], K[3], K[4], K[5], K[6], K[7], K[8]};
     const double t0 = T[0], t1 = T[1], t2 = T[2];
     double num = 0.0, den = 0.0;
     bool behind = false;
     for (int j = 0; j < J; ++j) {
-        const double X = (double)p[3 * j] + t0, Y = (double)p[3 * j + 1] + t1, Z = (double)p[3 * j + 2] + t2;
-        const double qx = k0 * X + k1 * Y + k2 * Z, qy = k3 * X + k4 * Y + k5 * Z, qz = k6 * X + k7 * Y + k8 * Z;
-        behind |= qz <= 0.0;
-        const double dx = qx / qz - (double)uv[2 * j], dy = qy / qz - (double)uv[2 * j + 1];
-        const double d = sqrt(dx * dx + dy * dy);
+        bool bj;
+        const double d = joint_reproj_dist(k, (double)p[3 * j] + t0, (double)p[3 * j + 1] + t1, (double)p[3 * j + 2] + t2,
+                                           (double)uv[2 * j], (double)uv[2 * j + 1], bj);
+        behind |= bj;
         double w = 1.0;
         if (has_conf) {
             float c = cf[j];
@@ -422,6 +433,119 @@ hipError_t launch_min_reproj(const float *x, const float *T, const float *uv, co
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_pose_min(err, B, N, row_offset, best, best_h, st);
+}
+
+// ---- joint-wise aggregation without ground truth (zedo_joint_reproj, zedo_joint_compose) ----------------------------------------------
+// Per (pose, joint) the hypothesis whose joint reprojects closest to its detection: d[b,j] = joint_reproj_dist of x[b,j] + T[b], +inf
+// for a joint at or behind the camera plane (that joint only), no confidences (a joint's weight is the same for every hypothesis of its
+// pose).  [B,J] flattened is an error vector over B*J rows with N*J "poses" and row offset row_offset*J: the selection is zedo_pose_min's.
+//
+// The walking route (d_jerr == NULL): one lane per (pose, joint) p = n*J + j.  For a fixed hypothesis the elements
+// x[h,n,j,:] over p are contiguous, so the 64 lanes of a wave read 768 contiguous bytes of x per hypothesis (12 per lane) and their
+// poses' T (12 bytes, shared by the J lanes of a pose) - no staging.  uv[n,j] and K[n] stay in registers, the next hypothesis's loads
+// are issued before the current one's fp64 arithmetic, the running minimum and its hypothesis stay in registers: 12 bytes written per
+// lane at the end, no [B,J] intermediate, no LDS, no scratch.  Hypotheses are visited in ascending order, so "takes over" below is
+// min_takes for a candidate with a higher index than the holder: the bits of launch_pose_min on the row kernel's vector.
+__global__ __launch_bounds__(256) void joint_reproj_walk_kernel(const float *__restrict__ x, const float *__restrict__ T, const float *__restrict__ uv,
+                                                                const float *__restrict__ K, int B, int N, int J, long long row_offset,
+                                                                double *__restrict__ best, int *__restrict__ best_h) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N * J) return;
+    const int n = p / J;
+    const double u = uv[2 * (size_t)p], v = uv[2 * (size_t)p + 1];
+    const float *Kn = K + (size_t)n * 9;
+    const double k[9] = {Kn[0], Kn[1], Kn[2], Kn[3], Kn[4], Kn[5], Kn[6], Kn[7], Kn[8]};
+    long long h = (row_offset - n + N - 1) / N;                   // first hypothesis with h*N + n >= row_offset
+    if (row_offset <= n) h = 0;
+    long long loc = h * N + n - row_offset;                        // local row of (h, n): >= 0; the pose's next one is N further
+    const float *xe = x + ((size_t)loc * J + (p - n * J)) * 3;     // (loc < B is tested before anything is read through these)
+    const float *Te = T + (size_t)loc * 3;
+    const size_t xs = (size_t)N * J * 3, Ts = (size_t)N * 3;
+    float c0 = 0.f, c1 = 0.f, c2 = 0.f, t0 = 0.f, t1 = 0.f, t2 = 0.f;
+    if (loc < B) { c0 = xe[0]; c1 = xe[1]; c2 = xe[2]; t0 = Te[0]; t1 = Te[1]; t2 = Te[2]; }
+    double e = __builtin_huge_val();
+    int hi = -1;
+    for (; loc < B; loc += N, ++h) {
+        // hypothesis h + 1 on its way while h is worked on.  Unconditional loads: behind a branch the compiler waits for them at the join,
+        // before the arithmetic; the last hypothesis re-reads its own 24 bytes instead (a valid address, a cache hit, values not used)
+        if (loc + N < B) { xe += xs; Te += Ts; }
+        const float n0 = xe[0], n1 = xe[1], n2 = xe[2], s0 = Te[0], s1 = Te[1], s2 = Te[2];
+        bool behind;
+        double d = joint_reproj_dist(k, (double)c0 + (double)t0, (double)c1 + (double)t1, (double)c2 + (double)t2, u, v, behind);
+        if (behind) d = __builtin_huge_val();
+        bool takes;
+        if (hi < 0) takes = true;
+        else if (e != e) takes = false;                            // a NaN holds: the lowest NaN hypothesis is reported
+        else if (d != d) takes = true;                             // NaN wins
+        else
+#ifdef ZEDO_MUT_JOINT_TIE   // tools/mutation_check.py only: ties to the HIGHER hypothesis index
+            takes = d <= e;
+#else
+            takes = d < e;
+#endif
+        if (takes) { e = d; hi = (int)h; }
+        c0 = n0; c1 = n1; c2 = n2; t0 = s0; t1 = s1; t2 = s2;
+    }
+    best[p] = e;                                                   // (+inf when the pose has no local row)
+    best_h[p] = hi;
+}
+
+// The row route (d_jerr != NULL): one lane per element (b, j) of d [B,J] - x, uv and d are read / written contiguously by a wave at any
+// alignment of x and any J, K[n] and T[b] come through the L2 - then launch_pose_min on the flattened vector.
+__global__ __launch_bounds__(256) void joint_reproj_rows_kernel(const float *__restrict__ x, const float *__restrict__ T, const float *__restrict__ uv,
+                                                                const float *__restrict__ K, int B, int N, int J, long long row_offset,
+                                                                double *__restrict__ jerr) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= B * J) return;
+    const int b = q / J, j = q - b * J;
+    const size_t n = (size_t)((row_offset + b) % N);
+    const float *Kn = K + n * 9, *xe = x + (size_t)q * 3, *Te = T + (size_t)b * 3, *uve = uv + (n * J + j) * 2;
+    const double k[9] = {Kn[0], Kn[1], Kn[2], Kn[3], Kn[4], Kn[5], Kn[6], Kn[7], Kn[8]};
+    bool behind;
+    const double d = joint_reproj_dist(k, (double)xe[0] + (double)Te[0], (double)xe[1] + (double)Te[1], (double)xe[2] + (double)Te[2],
+                                       (double)uve[0], (double)uve[1], behind);
+    jerr[q] = behind ? __builtin_huge_val() : d;
+}
+
+hipError_t launch_joint_reproj(const float *x, const float *T, const float *uv, const float *K, int B, int N, int J, long long row_offset,
+                               double *jerr, double *best, int *best_h, hipStream_t st) {
+    if (!jerr) {
+        hipLaunchKernelGGL(joint_reproj_walk_kernel, dim3((N * J + 255) / 256), dim3(256), 0, st, x, T, uv, K, B, N, J, row_offset, best, best_h);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(joint_reproj_rows_kernel, dim3((B * J + 255) / 256), dim3(256), 0, st, x, T, uv, K, B, N, J, row_offset, jerr);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_pose_min(jerr, B * J, N * J, row_offset * J, best, best_h, st);
+}
+
+// The assembled pose: joint (n, j) taken from hypothesis joint_h[n,j] of ALL rows x [H*N,J,3], T [H*N,3], in the camera frame
+// (ref_h == nullptr) or brought back into the root-relative frame of hypothesis ref_h[n]; fp64 on the fp32 inputs, rounded once.  An
+// index outside 0 .. H-1 makes the joint NaN and is never used as an address.  One lane per output joint.
+__global__ __launch_bounds__(256) void joint_compose_kernel(const float *__restrict__ x, const float *__restrict__ T, const int *__restrict__ joint_h,
+                                                            const int *__restrict__ ref_h, int H, int N, int J, float *__restrict__ pose) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= N * J) return;
+    const int n = p / J, j = p - n * J;
+    const int jh = joint_h[p], rh = ref_h ? ref_h[n] : 0;
+    float *o = pose + (size_t)p * 3;
+    if (jh < 0 || jh >= H || rh < 0 || rh >= H) {
+        o[0] = o[1] = o[2] = __builtin_nanf("");
+        return;
+    }
+    const size_t g = (size_t)jh * N + n, r = (size_t)rh * N + n;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double a = (double)x[(g * J + j) * 3 + c] + (double)T[g * 3 + c];
+        if (ref_h) a = a - (double)T[r * 3 + c];
+        o[c] = (float)a;
+    }
+}
+
+hipError_t launch_joint_compose(const float *x, const float *T, const int *joint_h, const int *ref_h, int H, int N, int J, float *pose,
+                                hipStream_t st) {
+    hipLaunchKernelGGL(joint_compose_kernel, dim3((N * J + 255) / 256), dim3(256), 0, st, x, T, joint_h, ref_h, H, N, J, pose);
+    return hipGetLastError();
 }
 
 // The one dispatch of the row-error kernels (zedo_min_mpjpe: BOTH = false; zedo_min_mpjpe_both: BOTH = true, err [2][B]).

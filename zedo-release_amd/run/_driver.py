@@ -29,9 +29,10 @@ def build_parser(description, inference=False):
     p.add_argument("--math", choices=("f32", "f16x3"), default=None,
                    help="arithmetic of the dense layers: f32 = exact fp32 MFMA (default), f16x3 = split-fp16 operands on the fp16 "
                         "matrix pipe at fp32-level accuracy, ~2x faster (same as the ZEDO_MATH environment variable)")
-    p.add_argument("--select", choices=("none", "reproj"), default="none",
+    p.add_argument("--select", choices=("none", "reproj", "joints"), default="none",
                    help="run.inference only: reproj = also keep, per pose, the hypothesis whose x + T reprojects closest to the 2D "
-                        "detections (confidence-weighted, no ground truth needed) -> <out>_selected.npz")
+                        "detections (confidence-weighted, no ground truth needed) -> <out>_selected.npz; joints = keep, per JOINT, the "
+                        "hypothesis whose joint reprojects closest to its detection and assemble the pose from those joints")
     if inference:
         p.add_argument("--eval", action="store_true", default=None, help="evaluation mode")
         p.add_argument("--data", type=str, default=None, help="npz with db_2d, camera_param[, db_3d] ('wild' dataset)")
@@ -182,7 +183,7 @@ def stepwise_loop(config, model, sde, sample_poses, gt_2d, K, S, device, hypothe
 
 
 def selected_path(out):
-    """<out without .npy>_selected.npz: where run.inference --select reproj writes the pose it keeps per detection."""
+    """<out without .npy>_selected.npz: where run.inference --select reproj / joints writes the pose it keeps per detection."""
     return (out[:-4] if out.endswith(".npy") else out) + "_selected.npz"
 
 
@@ -286,6 +287,36 @@ def run(args, inference=False):
                         reproj_px=best.cpu().numpy(), T=take_rows(full_T, idx, H, N).cpu().numpy())
         if rank == 0:
             np.savez(selected_path(args.out), **selected)
+    if inference and select == "joints":
+        # per (pose, joint) the hypothesis whose joint reprojects closest to its detection (zedo_joint_reproj) on this rank's rows, beside
+        # the pose-level winner (zedo_min_reproj) whose frame the assembled pose is written in; both MIN over the ranks (element-wise), the
+        # joints gathered from all rows (zedo_joint_compose): every rank ends with the same arrays, rank 0 writes them
+        import zedo_hip
+        if why is None:
+            uvd, Kd, cfd = pipe.uv, pipe.K, pipe.conf
+        else:
+            d2 = torch.tensor(np.ascontiguousarray(gt_2d), dtype=torch.float32, device=device)
+            uvd, Kd, cfd = d2[:, :, :2].contiguous(), torch.tensor(np.ascontiguousarray(K), dtype=torch.float32, device=device), d2[:, :, 2].contiguous()
+        if rows == 0:
+            best, idx = empty_selection(N, device)
+            jbest, jidx = (t.reshape(N, N_JOINTS) for t in empty_selection(N * N_JOINTS, device))
+        elif why is None:
+            best, idx = pipe.select_reproj(x, T, row_offset=lo)
+            jbest, jidx = pipe.aggregate_reproj(x, T, row_offset=lo)
+        else:
+            _, best, idx = zedo_hip.min_reproj(x, T.contiguous(), uvd, Kd, cfd, N, lo)
+            jbest, jidx = zedo_hip.joint_reproj(x, T.contiguous(), uvd, Kd, N, lo)
+        best, idx = reduce_min_over_ranks(best, idx)
+        jbest, jidx = reduce_min_over_ranks(jbest, jidx)
+        full_T = gather_row_shards(T.contiguous(), H * N, lo=None if why is None else lo)
+        pose = zedo_hip.joint_compose(full.contiguous(), full_T, jidx.contiguous(), idx.contiguous(), N)
+        T_sel = take_rows(full_T, idx, H, N).contiguous()
+        _, px, _ = zedo_hip.min_reproj(pose, T_sel, uvd, Kd, cfd, N, 0)       # the assembled poses as a one-hypothesis problem
+        selected = dict(pose=pose.cpu().numpy(), joint_hypothesis=jidx.cpu().numpy().astype(np.int32), joint_reproj_px=jbest.cpu().numpy(),
+                        hypothesis=idx.cpu().numpy().astype(np.int32), T=T_sel.cpu().numpy(), reproj_px=px.cpu().numpy(),
+                        reproj_px_pose_level=best.cpu().numpy())
+        if rank == 0:
+            np.savez(selected_path(args.out), **selected)
     errs = None
     if not inference or args.eval:
         print("eval...")
@@ -302,8 +333,9 @@ def run(args, inference=False):
                 s1 = test_dataset.eval_multi(("rows", sel_rows), protocol2=False, print_verbose=False, row_offset=0)
                 s2 = test_dataset.eval_multi(("rows", sel_rows), protocol2=True, print_verbose=False, row_offset=0)
             if rank == 0:
-                print(f"reproj-selected MPJPE : {s1}")
-                print(f"reproj-selected PA-MPJPE : {s2}")
+                label = "joints-aggregated" if select == "joints" else "reproj-selected"
+                print(f"{label} MPJPE : {s1}")
+                print(f"{label} PA-MPJPE : {s2}")
             errs = (p1, p2, s1, s2)
     if use_dist:
         import torch.distributed as dist

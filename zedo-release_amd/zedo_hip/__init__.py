@@ -68,6 +68,8 @@ SIGNATURES = {
     "zedo_min_mpjpe": (_i, [_vp, _vp, _i, _i, _i, _ll, _i, _vp, _vp, _vp, _vp]),
     "zedo_min_mpjpe_both": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp, _vp]),
     "zedo_min_reproj": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp, _vp]),
+    "zedo_joint_reproj": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp, _vp]),
+    "zedo_joint_compose": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "zedo_pose_min": (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp]),
     "zedo_probe_mfma_peak": (_i, [_i, _vp, _vp, _vp]),
     "zedo_probe_mfma_peak_f16": (_i, [_i, _vp, _vp, _vp]),
@@ -492,6 +494,53 @@ def min_reproj(x, T, uv, K, conf=None, N=None, row_offset=0):
         _check(_lib.zedo_min_reproj(_p(x), _p(T), _p(uv), _p(K), _p(conf), B, N, J, int(row_offset), _p(err, torch.float64),
                                     _p(best, torch.float64), _p(best_h, torch.int32), _stream(dev)))
     return err, best, best_h
+
+
+def joint_reproj(x, T, uv, K, N=None, row_offset=0, return_rows=False):
+    """Joint-wise aggregation without ground truth (zedo_joint_reproj): x [B,J,3] rows (h,n), T [B,3], uv [N,J,2], K [N,3,3] ->
+    (best [N,J] f64: per (pose, joint) the smallest reprojection distance of x + T in pixels over the local hypotheses, idx [N,J] i32:
+    the hypothesis that attains it).  return_rows: also jerr [B,J] f64, every row's per-joint distances (the route through
+    zedo_pose_min's kernels; the same bits in best / idx).  Whether the assembled pose is closer to ground truth than the pose-level
+    selection of min_reproj is not measured."""
+    _need_gpu()
+    dev = _device_of(x, T, uv, K)
+    B, J = x.shape[0], x.shape[1]
+    N = uv.shape[0] if N is None else int(N)
+    if tuple(x.shape) != (B, J, 3) or tuple(T.shape) != (B, 3) or tuple(uv.shape) != (N, J, 2) or tuple(K.shape) != (N, 3, 3):
+        raise ZedoError(f"joint_reproj: x [B,J,3], T [B,3], uv [N,J,2], K [N,3,3] expected, got {tuple(x.shape)}, {tuple(T.shape)}, "
+                        f"{tuple(uv.shape)}, {tuple(K.shape)} with N = {N}")
+    with torch.cuda.device(dev):
+        jerr = torch.empty((B, J), dtype=torch.float64, device=dev) if return_rows else None
+        best = torch.empty((N, J), dtype=torch.float64, device=dev)
+        best_h = torch.empty((N, J), dtype=torch.int32, device=dev)
+        _check(_lib.zedo_joint_reproj(_p(x), _p(T), _p(uv), _p(K), B, N, J, int(row_offset), _p(jerr, torch.float64),
+                                      _p(best, torch.float64), _p(best_h, torch.int32), _stream(dev)))
+    return (best, best_h, jerr) if return_rows else (best, best_h)
+
+
+def joint_compose(x_full, T_full, joint_idx, ref_idx=None, N=None):
+    """The pose assembled joint by joint (zedo_joint_compose): x_full [H*N,J,3] and T_full [H*N,3] (ALL rows, h-major), joint_idx [N,J]
+    i32 -> pose [N,J,3] f32, joint (n, j) = x + T of hypothesis joint_idx[n,j]: in the camera frame (ref_idx None) or minus the
+    translation of hypothesis ref_idx[n] ([N] i32: root-relative to that hypothesis's frame).  Like take_rows, an index of -1 or one
+    outside the hypotheses is a ValueError (synchronises to look)."""
+    _need_gpu()
+    dev = _device_of(x_full, T_full, joint_idx, ref_idx)
+    J = x_full.shape[1]
+    N = joint_idx.shape[0] if N is None else int(N)
+    rows = x_full.shape[0]
+    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(T_full.shape) != (rows, 3) or tuple(joint_idx.shape) != (N, J)
+            or (ref_idx is not None and tuple(ref_idx.shape) != (N,))):
+        raise ValueError(f"joint_compose: x [H*N,J,3], T [H*N,3], joint_idx [N,J], ref_idx [N] expected, got {tuple(x_full.shape)}, "
+                         f"{tuple(T_full.shape)}, {tuple(joint_idx.shape)}, {None if ref_idx is None else tuple(ref_idx.shape)} with N = {N}")
+    H = rows // N
+    for name, i in (("joint_idx", joint_idx), ("ref_idx", ref_idx)):
+        if i is not None and bool(((i < 0) | (i >= H)).any()):
+            raise ValueError(f"joint_compose: {name} holds -1 (nothing was selected) or an index outside the {H} hypotheses")
+    with torch.cuda.device(dev):
+        pose = torch.empty((N, J, 3), dtype=torch.float32, device=dev)
+        _check(_lib.zedo_joint_compose(_p(x_full), _p(T_full), _p(joint_idx, torch.int32), _p(ref_idx, torch.int32), H, N, J, _p(pose),
+                                       _stream(dev)))
+    return pose
 
 
 def pose_min(err, N, row_offset=0):

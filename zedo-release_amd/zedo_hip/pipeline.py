@@ -6,7 +6,8 @@ batched as rows (h, n) and every stage running in libzedo_hip.so.
          x       = R x0                                           (opt_main.py:201)
     OIL  S steps of {reprojection correction, score-network probability-flow step}   (opt_main.py:202-220)
     selection    = per-pose min over hypotheses of (PA-)MPJPE     (eval_multi)
-                   or, without ground truth, of the confidence-weighted reprojection error of x + T (select_reproj)
+                   or, without ground truth, of the confidence-weighted reprojection error of x + T (select_reproj),
+                   or per JOINT of the joint's reprojection distance, the pose assembled from the winners (aggregate_reproj, compose)
 
 Rows may be a contiguous shard of the H*N global rows (one shard per GPU); the only exchange is the final
 MIN over ranks, done by the caller (run/opt_main.py, bench.py) with torch.distributed.
@@ -16,8 +17,8 @@ import os
 import numpy as np
 import torch
 
-from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, min_mpjpe_both, min_reproj, oil_run, reproj_degenerate,
-               reproj_prepare, rotate_init)
+from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_compose, joint_reproj, min_mpjpe_both, min_reproj, oil_run,
+               reproj_degenerate, reproj_prepare, rotate_init)
 
 
 def linspace_f32(start, end, steps):
@@ -114,6 +115,25 @@ class Pipeline:
         with torch.cuda.device(self.device):
             _, best, idx = min_reproj(x, T, self.uv, self.K, self.conf, self.N, row_offset)
         return best, idx
+
+    def aggregate_reproj(self, x, T, row_offset=0):
+        """Joint-wise aggregation without ground truth on the problem of load(): -> (best [N,J] f64, idx [N,J] i32) for the local rows -
+        per (pose, joint) the smallest reprojection distance (pixels) of that joint of x + T and the hypothesis that attains it
+        (zedo_joint_reproj, the walking kernel).  Ranks are combined with reduce_min_over_ranks (element-wise)."""
+        J = self.uv.shape[1]
+        if x.shape[0] == 0:
+            best, idx = empty_selection(self.N * J, self.device)
+            return best.reshape(self.N, J), idx.reshape(self.N, J)
+        with torch.cuda.device(self.device):
+            return joint_reproj(x, T, self.uv, self.K, self.N, row_offset)
+
+    def compose(self, x_full, T_full, joint_idx, ref_idx=None):
+        """The pose assembled from the joints aggregate_reproj selected: x_full [H*N,17,3], T_full [H*N,3] (all global rows), joint_idx
+        [N,17] -> [N,17,3], root-relative to hypothesis ref_idx[n] (None: camera frame) (zedo_joint_compose)."""
+        if x_full.shape[0] != self.H * self.N:
+            raise ValueError(f"compose: all {self.H * self.N} rows expected, got {x_full.shape[0]}")
+        with torch.cuda.device(self.device):
+            return joint_compose(x_full, T_full, joint_idx, ref_idx, self.N)
 
     def take(self, rows_full, idx):
         """The winning row of every pose: rows_full [H*N, ...] (all global rows, h-major), idx [N] -> rows_full.view(H, N, ...)[idx, arange(N)].
