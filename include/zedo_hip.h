@@ -330,6 +330,42 @@ int zedo_joint_reproj(const float *d_x, const float *d_T, const float *d_uv, con
 int zedo_joint_compose(const float *d_x, const float *d_T, const int *d_joint_h, const int *d_ref_h, int H, int N, int J,
                        float *d_pose, void *stream);
 
+/* ---- selection along a video WITHOUT ground truth: Viterbi over a unary cost and a motion cost -------------------------
+ * zedo_min_reproj and zedo_joint_reproj decide every frame on its own; on the frames of a video the kept hypothesis then
+ * jumps between depth-ambiguous solutions.  This keeps, per frame, the hypothesis that minimises its own cost plus lambda
+ * times the mean joint displacement to the previous frame's choice - exactly, by dynamic programming over each clip.
+ * Whether this lowers the error against ground truth on real video is not measured.
+ * d_unary [H*N] float64, rows (h,n) h-major, ALL rows (the recurrence needs every hypothesis of consecutive frames: no
+ * row_offset): any per-row cost, e.g. d_err of zedo_min_reproj (pixels), or of zedo_min_mpjpe as an oracle.
+ * d_x [H*N,J,3] fp32, the same rows (metres).  lambda: cost units per metre (pixels per metre on zedo_min_reproj's errors).
+ * d_seq_start [n_seq+1] int32 ON THE DEVICE: strictly ascending, first 0, last N; clip s is frames seq_start[s] ..
+ * seq_start[s+1]-1.  The call cannot look at it without synchronising: every entry is clamped to 0 .. N before use and is
+ * never an address; with an array that breaks the rules the result is unspecified.
+ * All arithmetic in float64 on the inputs as given:
+ *   u[n,h]    = unary[h*N+n] if finite, else +inf (NaN and +-inf: the hypothesis is excluded - NOT zedo_pose_min's "NaN wins":
+ *               one diverged row must not own a whole clip);  a frame is DEAD if no u[n,h] is finite
+ *   m[n,h',h] = (1/J) sum_j sqrt(sum_c ((double)x[h,n,j,c] - (double)x[h',n-1,j,c])^2)      (sums ascending in c, then in j)
+ *   chain start (n first of its clip, or frame n-1 dead):  D[n,h] = u[n,h], back[n,h] = -1
+ *   otherwise:  D[n,h] = u[n,h] + min_h' (D[n-1,h'] + lambda m[n,h',h]),  back[n,h] = the lowest h' that attains the minimum
+ *   dead frame: D[n,.] = +inf
+ * Backwards per clip: at the last frame of a chain (the clip's last frame, or the next frame is dead) path[n] = the lowest h
+ * that minimises D[n,.]; inside a chain path[n] = back[n+1, path[n+1]].
+ * d_path_h [N] int32; d_cost [N] float64 = D[n, path[n]]; a dead frame reports hypothesis 0 and cost +inf.
+ * (x is taken to be finite: a non-finite coordinate makes the affected minima unspecified, never an address.)
+ * Workspace (8-byte aligned): D [N,H] float64, back [N,H] int32, two int32 flags per frame, then C*H*H float64 transition
+ * costs of a chunk of C frames.  zedo_temporal_workspace_bytes(N, H, chunk_frames) returns the bytes for
+ * C = min(chunk_frames, N); chunk_frames <= 0: the largest C whose transition costs stay at or under 256 MB (at least one
+ * frame); 0 for sizes the call refuses.  The call uses the largest C that workspace_bytes admits, capped at N, and returns
+ * the same bits for every C; ZEDO_E_WORKSPACE with nothing written if not even one frame of transitions fits.  The
+ * workspace need not be initialised.
+ * Contract: any J >= 1, H >= 1, N >= 1, 1 <= n_seq <= N, finite lambda >= 0; ZEDO_E_BADARG with nothing written for a NULL
+ * pointer, a non-positive size, n_seq > N, a negative or non-finite lambda, a workspace that is not 8-byte aligned, or H*N
+ * or H*H above INT_MAX; allocates nothing, synchronises nothing, enqueues on `stream` only: legal under stream capture; no
+ * atomics: bit-identical from run to run.  One workgroup per clip: a single long clip is serial in time on one CU. */
+size_t zedo_temporal_workspace_bytes(int N, int H, int chunk_frames);
+int zedo_temporal_select(const double *d_unary, const float *d_x, const int *d_seq_start, int n_seq, int H, int N, int J,
+                         double lambda, void *d_workspace, size_t workspace_bytes, int *d_path_h, double *d_cost, void *stream);
+
 /* The second half of zedo_min_mpjpe on its own: per pose n the minimum of d_err over the hypotheses present in
  * [0,B) and the first hypothesis index that attains it (np.amin / np.argmin, NaN wins: h36m.py:411-412).  For
  * callers that edit the per-row errors first - eval_multi's `valid_ind` (h36m.py:396-397: hypotheses not listed for

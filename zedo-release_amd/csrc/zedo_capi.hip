@@ -847,3 +847,29 @@ extern "C" int zedo_joint_compose(const float *d_x, const float *d_T, const int 
     HIPCHK(launch_joint_compose(d_x, d_T, d_joint_h, d_ref_h, H, N, J, d_pose, (hipStream_t)stream));
     return ZEDO_OK;
 }
+
+// ---- temporal selection: the variable part of the workspace is chunk x H x H doubles of transition costs ----
+constexpr size_t TEMPORAL_DEFAULT_VARIABLE = (size_t)256 << 20;    // the default chunk keeps the transition costs at or under 256 MB
+
+extern "C" size_t zedo_temporal_workspace_bytes(int N, int H, int chunk_frames) {
+    if (N < 1 || H < 1 || (long long)H * N > INT_MAX || (long long)H * H > INT_MAX) return 0;
+    const size_t per = (size_t)H * H * sizeof(double);
+    size_t c = chunk_frames > 0 ? (size_t)chunk_frames : std::max<size_t>(1, TEMPORAL_DEFAULT_VARIABLE / per);
+    c = std::min<size_t>(c, (size_t)N);
+    return temporal_fixed_bytes(N, H) + c * per;
+}
+
+extern "C" int zedo_temporal_select(const double *d_unary, const float *d_x, const int *d_seq_start, int n_seq, int H, int N, int J,
+                                    double lambda, void *d_workspace, size_t workspace_bytes, int *d_path_h, double *d_cost, void *stream) {
+    if (!d_unary || !d_x || !d_seq_start || !d_workspace || !d_path_h || !d_cost || H < 1 || N < 1 || J < 1 || n_seq < 1 || n_seq > N)
+        return ZEDO_E_BADARG;
+    if (!std::isfinite(lambda) || lambda < 0.0) return ZEDO_E_BADARG;
+    if ((long long)H * N > INT_MAX || (long long)H * H > INT_MAX) return ZEDO_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(d_workspace) & 7) return ZEDO_E_BADARG;              // the tables are float64
+    const size_t fixed = temporal_fixed_bytes(N, H), per = (size_t)H * H * sizeof(double);
+    if (workspace_bytes < fixed + per) return ZEDO_E_WORKSPACE;
+    const int chunk = (int)std::min<size_t>((workspace_bytes - fixed) / per, (size_t)N);
+    HIPCHK(launch_temporal_select(d_unary, d_x, d_seq_start, n_seq, H, N, J, lambda, d_workspace, chunk, d_path_h, d_cost,
+                                  (hipStream_t)stream));
+    return ZEDO_OK;
+}

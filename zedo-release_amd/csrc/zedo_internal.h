@@ -235,6 +235,10 @@ hipError_t launch_joint_reproj(const float *x, const float *T, const float *uv, 
                                double *jerr, double *best, int *best_h, hipStream_t st);
 hipError_t launch_joint_compose(const float *x, const float *T, const int *joint_h, const int *ref_h, int H, int N, int J, float *pose,
                                 hipStream_t st);
+// temporal selection (zedo_temporal.hip); ws: temporal_fixed_bytes(N, H) of tables, then chunk * H * H doubles of transition costs
+size_t temporal_fixed_bytes(int N, int H);
+hipError_t launch_temporal_select(const double *unary, const float *x, const int *seq_start, int n_seq, int H, int N, int J, double lambda,
+                                  void *ws, int chunk, int *path, double *cost, hipStream_t st);
 
 
 // predictor-corrector step kernels (zedo_pc.hip); z: the caller's noise draw, unpadded [B][D]

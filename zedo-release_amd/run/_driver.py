@@ -29,15 +29,39 @@ def build_parser(description, inference=False):
     p.add_argument("--math", choices=("f32", "f16x3"), default=None,
                    help="arithmetic of the dense layers: f32 = exact fp32 MFMA (default), f16x3 = split-fp16 operands on the fp16 "
                         "matrix pipe at fp32-level accuracy, ~2x faster (same as the ZEDO_MATH environment variable)")
-    p.add_argument("--select", choices=("none", "reproj", "joints"), default="none",
+    p.add_argument("--select", choices=("none", "reproj", "joints", "temporal"), default="none",
                    help="run.inference only: reproj = also keep, per pose, the hypothesis whose x + T reprojects closest to the 2D "
                         "detections (confidence-weighted, no ground truth needed) -> <out>_selected.npz; joints = keep, per JOINT, the "
-                        "hypothesis whose joint reprojects closest to its detection and assemble the pose from those joints")
+                        "hypothesis whose joint reprojects closest to its detection and assemble the pose from those joints; temporal = "
+                        "the frames are a video: per clip the hypothesis sequence that minimises reprojection error plus --smooth times "
+                        "the mean joint displacement between consecutive frames (Viterbi)")
+    p.add_argument("--smooth", type=float, default=None, metavar="LAMBDA",
+                   help="--select temporal: weight of the motion cost in pixels per metre (default 100: a mean joint jump of 1 cm costs as "
+                        "much as 1 px of reprojection error; the default is UNTUNED - its effect on accuracy has not been measured)")
+    p.add_argument("--seq_len", type=int, default=None, metavar="L",
+                   help="--select temporal: cut the frames into consecutive clips of L (the last one shorter); overrides the dataset's "
+                        "seq_start; with --synthetic the only source of clips (default: the dataset's clips, else one clip)")
     if inference:
         p.add_argument("--eval", action="store_true", default=None, help="evaluation mode")
         p.add_argument("--data", type=str, default=None, help="npz with db_2d, camera_param[, db_3d] ('wild' dataset)")
         p.add_argument("--out", type=str, default="results.npy")
     return p
+
+
+def check_select_args(args):
+    """--smooth / --seq_len belong to --select temporal; --smooth defaults to 100 there."""
+    select = getattr(args, "select", "none") or "none"
+    smooth, seq_len = getattr(args, "smooth", None), getattr(args, "seq_len", None)
+    if select != "temporal":
+        if smooth is not None or seq_len is not None:
+            raise SystemExit("--smooth and --seq_len are switches of --select temporal")
+        return
+    if smooth is None:
+        args.smooth = 100.0
+    elif not (np.isfinite(smooth) and smooth >= 0):
+        raise SystemExit(f"--smooth {smooth}: a finite weight >= 0 expected")
+    if seq_len is not None and seq_len < 1:
+        raise SystemExit(f"--seq_len {seq_len}: at least one frame per clip")
 
 
 def load_config(path):
@@ -183,7 +207,7 @@ def stepwise_loop(config, model, sde, sample_poses, gt_2d, K, S, device, hypothe
 
 
 def selected_path(out):
-    """<out without .npy>_selected.npz: where run.inference --select reproj / joints writes the pose it keeps per detection."""
+    """<out without .npy>_selected.npz: where run.inference --select reproj / joints / temporal writes the pose it keeps per detection."""
     return (out[:-4] if out.endswith(".npy") else out) + "_selected.npz"
 
 
@@ -198,6 +222,7 @@ def run(args, inference=False):
     if select != "none" and not inference:
         raise SystemExit(f"--select {select} is honoured by run.inference only: run.opt_main scores every hypothesis against 3D ground "
                          "truth (best of H), and the ground-truth evaluation of a selected pose is printed by run.inference --eval")
+    check_select_args(args)
     config = load_config(args.config)
     if getattr(args, "math", None):
         os.environ["ZEDO_MATH"] = args.math          # read by zedo_hip.Weights when the model's device copy is built
@@ -317,6 +342,32 @@ def run(args, inference=False):
                         reproj_px_pose_level=best.cpu().numpy())
         if rank == 0:
             np.savez(selected_path(args.out), **selected)
+    if inference and select == "temporal":
+        # the frames are a video: each rank evaluates zedo_min_reproj on its own rows, the per-row errors and T are gathered like the rows,
+        # every rank runs the same Viterbi (zedo_temporal_select) on the full arrays and ends with the same arrays, rank 0 writes them
+        import zedo_hip
+        if args.seq_len is not None:
+            seq = np.array(list(range(0, N, args.seq_len)) + [N], np.int32)
+        else:
+            seq = np.asarray(getattr(test_dataset, "seq_start", [0, N]), np.int32)
+        if rows == 0:
+            err = torch.empty((0,), dtype=torch.float64, device=device)
+        elif why is None:
+            err, _, _ = zedo_hip.min_reproj(x, T, pipe.uv, pipe.K, pipe.conf, N, lo)
+        else:
+            d2 = torch.tensor(np.ascontiguousarray(gt_2d), dtype=torch.float32, device=device)
+            Kd = torch.tensor(np.ascontiguousarray(K), dtype=torch.float32, device=device)
+            err, _, _ = zedo_hip.min_reproj(x, T.contiguous(), d2[:, :, :2].contiguous(), Kd, d2[:, :, 2].contiguous(), N, lo)
+        full_err = gather_row_shards(err, H * N, lo=None if why is None else lo).contiguous()
+        full_T = gather_row_shards(T.contiguous(), H * N, lo=None if why is None else lo)
+        per_frame, idx0 = zedo_hip.pose_min(full_err, N)             # what --select reproj keeps
+        path, cost = zedo_hip.temporal_select(full_err, full.contiguous(), seq, N, args.smooth)
+        selected = dict(pose=take_rows(full, path, H, N).cpu().numpy(), hypothesis=path.cpu().numpy().astype(np.int32),
+                        hypothesis_per_frame=idx0.cpu().numpy().astype(np.int32), reproj_px=take_rows(full_err, path, H, N).cpu().numpy(),
+                        reproj_px_all=full_err.reshape(H, N).t().contiguous().cpu().numpy(), path_cost=cost.cpu().numpy(),
+                        T=take_rows(full_T, path, H, N).cpu().numpy(), seq_start=seq.astype(np.int32), smooth=np.float64(args.smooth))
+        if rank == 0:
+            np.savez(selected_path(args.out), **selected)
     errs = None
     if not inference or args.eval:
         print("eval...")
@@ -333,7 +384,7 @@ def run(args, inference=False):
                 s1 = test_dataset.eval_multi(("rows", sel_rows), protocol2=False, print_verbose=False, row_offset=0)
                 s2 = test_dataset.eval_multi(("rows", sel_rows), protocol2=True, print_verbose=False, row_offset=0)
             if rank == 0:
-                label = "joints-aggregated" if select == "joints" else "reproj-selected"
+                label = {"joints": "joints-aggregated", "temporal": "temporal-selected"}.get(select, "reproj-selected")
                 print(f"{label} MPJPE : {s1}")
                 print(f"{label} PA-MPJPE : {s2}")
             errs = (p1, p2, s1, s2)

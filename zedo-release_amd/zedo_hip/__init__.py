@@ -70,6 +70,8 @@ SIGNATURES = {
     "zedo_min_reproj": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp, _vp]),
     "zedo_joint_reproj": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _ll, _vp, _vp, _vp, _vp]),
     "zedo_joint_compose": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "zedo_temporal_workspace_bytes": (_sz, [_i, _i, _i]),
+    "zedo_temporal_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _sz, _vp, _vp, _vp]),
     "zedo_pose_min": (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp]),
     "zedo_probe_mfma_peak": (_i, [_i, _vp, _vp, _vp]),
     "zedo_probe_mfma_peak_f16": (_i, [_i, _vp, _vp, _vp]),
@@ -541,6 +543,39 @@ def joint_compose(x_full, T_full, joint_idx, ref_idx=None, N=None):
         _check(_lib.zedo_joint_compose(_p(x_full), _p(T_full), _p(joint_idx, torch.int32), _p(ref_idx, torch.int32), H, N, J, _p(pose),
                                        _stream(dev)))
     return pose
+
+
+def temporal_select(unary, x_full, seq_start, N=None, lam=100.0, chunk_frames=0):
+    """Selection along a video without ground truth (zedo_temporal_select): unary [H*N] f64 (ALL rows, h-major: e.g. err of min_reproj,
+    pixels), x_full [H*N,J,3] f32, seq_start [n_seq+1] (a sequence or an int tensor: strictly ascending from 0 to N, the first frame of
+    every clip) -> (path [N] i32, cost [N] f64): per clip the hypothesis sequence that minimises the sum of its unaries plus lam times
+    the mean joint displacement between consecutive choices (Viterbi, fp64).  lam is in cost units per metre; the default of 100 (1 cm of
+    mean joint jump costs as much as 1 px) is untuned.  chunk_frames: frames of transition costs held at once (0: at most 256 MB); the
+    result does not depend on it.  Whether the temporal path is closer to ground truth than the per-frame arg-min is not measured."""
+    _need_gpu()
+    dev = _device_of(unary, x_full, seq_start if isinstance(seq_start, torch.Tensor) and seq_start.is_cuda else None)
+    rows, J = x_full.shape[0], x_full.shape[1]
+    if isinstance(seq_start, torch.Tensor):
+        if seq_start.dtype not in (torch.int32, torch.int64) or seq_start.dim() != 1:
+            raise ValueError(f"temporal_select: seq_start must be a 1-D int tensor, got {seq_start.dtype} {tuple(seq_start.shape)}")
+        seq = seq_start.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        seq = torch.tensor([int(v) for v in seq_start], dtype=torch.int32, device=dev)
+    if N is None:
+        N = int(seq[-1].item()) if seq.numel() else 0
+    N = int(N)
+    if N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(unary.shape) != (rows,) or seq.numel() < 2:
+        raise ValueError(f"temporal_select: unary [H*N], x [H*N,J,3], seq_start [n_seq+1] expected, got {tuple(unary.shape)}, "
+                         f"{tuple(x_full.shape)}, {tuple(seq.shape)} with N = {N}")
+    H = rows // N
+    with torch.cuda.device(dev):
+        nbytes = int(_lib.zedo_temporal_workspace_bytes(N, H, int(chunk_frames)))
+        ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+        path = torch.empty((N,), dtype=torch.int32, device=dev)
+        cost = torch.empty((N,), dtype=torch.float64, device=dev)
+        _check(_lib.zedo_temporal_select(_p(unary, torch.float64), _p(x_full), _p(seq, torch.int32), seq.numel() - 1, H, N, J, float(lam),
+                                         _p(ws, torch.uint8), nbytes, _p(path, torch.int32), _p(cost, torch.float64), _stream(dev)))
+    return path, cost
 
 
 def pose_min(err, N, row_offset=0):

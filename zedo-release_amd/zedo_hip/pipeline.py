@@ -7,7 +7,8 @@ batched as rows (h, n) and every stage running in libzedo_hip.so.
     OIL  S steps of {reprojection correction, score-network probability-flow step}   (opt_main.py:202-220)
     selection    = per-pose min over hypotheses of (PA-)MPJPE     (eval_multi)
                    or, without ground truth, of the confidence-weighted reprojection error of x + T (select_reproj),
-                   or per JOINT of the joint's reprojection distance, the pose assembled from the winners (aggregate_reproj, compose)
+                   or per JOINT of the joint's reprojection distance, the pose assembled from the winners (aggregate_reproj, compose),
+                   or along the clips of a video: reprojection error plus a motion cost, by Viterbi (select_temporal)
 
 Rows may be a contiguous shard of the H*N global rows (one shard per GPU); the only exchange is the final
 MIN over ranks, done by the caller (run/opt_main.py, bench.py) with torch.distributed.
@@ -18,7 +19,7 @@ import numpy as np
 import torch
 
 from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_compose, joint_reproj, min_mpjpe_both, min_reproj, oil_run,
-               reproj_degenerate, reproj_prepare, rotate_init)
+               reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
 def linspace_f32(start, end, steps):
@@ -134,6 +135,19 @@ class Pipeline:
             raise ValueError(f"compose: all {self.H * self.N} rows expected, got {x_full.shape[0]}")
         with torch.cuda.device(self.device):
             return joint_compose(x_full, T_full, joint_idx, ref_idx, self.N)
+
+    def select_temporal(self, x, T, seq_start, lam=100.0):
+        """Selection along a video without ground truth on the problem of load(): x [H*N,17,3] and T [H*N,3], ALL rows (the recurrence
+        needs every hypothesis of consecutive frames), seq_start = the first frame of every clip and N -> (path [N] i32, cost [N] f64,
+        err_rows [H*N] f64): the unaries are zedo_min_reproj's per-row errors (pixels), the path minimises them plus lam (pixels per
+        metre, default untuned) times the mean joint displacement between consecutive choices (zedo_temporal_select).  take(x, path)
+        gathers the rows."""
+        if x.shape[0] != self.H * self.N:
+            raise ValueError(f"select_temporal: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        with torch.cuda.device(self.device):
+            err, _, _ = min_reproj(x, T, self.uv, self.K, self.conf, self.N, 0)
+            path, cost = temporal_select(err, x, seq_start, self.N, lam)
+        return path, cost, err
 
     def take(self, rows_full, idx):
         """The winning row of every pose: rows_full [H*N, ...] (all global rows, h-major), idx [N] -> rows_full.view(H, N, ...)[idx, arange(N)].
