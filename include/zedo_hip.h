@@ -43,7 +43,9 @@ extern "C" {
                               * still 5 (additive): + zedo_pc_plan_create / _destroy, zedo_pc_workspace_bytes, zedo_pc_step;
                               * still 5 (additive): + zedo_min_mpjpe_both;
                               * still 5 (additive): + zedo_min_reproj;
-                              * still 5 (additive): + zedo_joint_reproj, zedo_joint_compose */
+                              * still 5 (additive): + zedo_joint_reproj, zedo_joint_compose;
+                              * still 5 (additive): + zedo_temporal_workspace_bytes, zedo_temporal_select;
+                              * still 5 (additive): + zedo_prune_rank, zedo_prune_gather */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -365,6 +367,31 @@ int zedo_joint_compose(const float *d_x, const float *d_T, const int *d_joint_h,
 size_t zedo_temporal_workspace_bytes(int N, int H, int chunk_frames);
 int zedo_temporal_select(const double *d_unary, const float *d_x, const int *d_seq_start, int n_seq, int H, int N, int J,
                          double lambda, void *d_workspace, size_t workspace_bytes, int *d_path_h, double *d_cost, void *stream);
+
+/* ---- pruning hypotheses DURING the loop, without ground truth: keep the K best of a pose, compact the rows ----------------
+ * zedo_oil_run takes step_begin / step_end and a row's bits do not depend on the batch it is in, so a run can be cut into
+ * stages that carry fewer and fewer rows.  These two calls are the piece between two stages.  Whether pruning by
+ * reprojection error costs accuracy against ground truth is not measured.
+ * zedo_prune_rank: d_err [H*N] float64, ALL rows (h,n) h-major of the CURRENT slots (no row_offset: a pose's every
+ * hypothesis takes part), e.g. d_err of zedo_min_reproj.  For pose n, slot a comes before slot b iff
+ *   err_a is not NaN and err_b is NaN,  or  neither is NaN and err_a < err_b,
+ *   or neither of these separates them and a < b   (equal values, -0.0 and 0.0, two NaNs: the lower slot first)
+ * - finite ascending, then +inf, then NaN.  NOT zedo_pose_min's "NaN wins": a diverged row is the first to go, as in
+ * zedo_temporal_select.  The kept set is the K first slots of that order; d_keep [K,N] int32, d_keep[r*N + n] = the r-th
+ * kept slot of pose n in ASCENDING SLOT order (K == H: the identity table).
+ * Contract: 1 <= K <= H <= 1024, N >= 1, H*N <= INT_MAX; anything else, or a NULL pointer: ZEDO_E_BADARG, nothing written.
+ * zedo_prune_gather: out of place; with g = keep[r,n]*N + n:  x_out[(r,n)] = x[g] ([.,J,3] fp32),  T_out[(r,n)] = T[g]
+ * ([.,3] fp32),  hyp_out[r,n] = d_hyp ? d_hyp[g] : keep[r,n].  d_hyp [H,N] int32: the ORIGINAL hypothesis id of every
+ * current slot - it chains from stage to stage; NULL: the slots are the hypotheses.  A keep entry outside 0 .. H-1 is never
+ * an address: that output row is NaN in x_out and T_out and its id is -1.  With the identity table the outputs are the
+ * inputs bit for bit.
+ * Contract: any J >= 1, 1 <= K <= H, N >= 1, H*N <= INT_MAX; ZEDO_E_BADARG with nothing written otherwise, for a NULL pointer
+ * other than d_hyp, and for an output pointer equal to an input (x_out == x, T_out == T, hyp_out == d_hyp or d_keep).
+ * Both: allocate nothing, synchronise nothing, enqueue on `stream` only: legal under stream capture; no atomics:
+ * bit-identical from run to run. */
+int zedo_prune_rank(const double *d_err, int H, int N, int K, int *d_keep, void *stream);
+int zedo_prune_gather(const int *d_keep, int H, int K, int N, int J, const float *d_x, const float *d_T, const int *d_hyp,
+                      float *d_x_out, float *d_T_out, int *d_hyp_out, void *stream);
 
 /* The second half of zedo_min_mpjpe on its own: per pose n the minimum of d_err over the hypotheses present in
  * [0,B) and the first hypothesis index that attains it (np.amin / np.argmin, NaN wins: h36m.py:411-412).  For

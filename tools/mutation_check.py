@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: twenty one-line arithmetic mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: twenty-one one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -44,6 +44,9 @@ MUTANTS = [
     ("ZEDO_MUT_JOINT_TIE", "zedo_joint_reproj without d_jerr: the running minimum takes ties, the HIGHER hypothesis wins (zedo_metric.hip joint_reproj_walk_kernel)"),
     # the temporal selection (tests/test_temporal_select_gpu.py, tests/test_select_temporal_driver_gpu.py): leaves every other test green
     ("ZEDO_MUT_TEMPORAL_LAMBDA", "zedo_temporal_select: the motion term enters the recurrence unweighted, lambda is dropped (zedo_temporal.hip temporal_scan_kernel)"),
+    # the pruning between two stages of the loop (tests/test_prune_gpu.py, tests/test_prune_pipeline_gpu.py, tests/test_prune_driver_gpu.py):
+    # leaves every other test green
+    ("ZEDO_MUT_PRUNE_TIE", "zedo_prune_rank: the tie rule a < b becomes a <= b, a slot comes before itself (zedo_prune.hip prune_precedes)"),
 ]
 
 

@@ -873,3 +873,20 @@ extern "C" int zedo_temporal_select(const double *d_unary, const float *d_x, con
                                   (hipStream_t)stream));
     return ZEDO_OK;
 }
+
+// ---- hypothesis pruning between two stages of the loop: the table of kept slots, then the compaction of the rows ----
+extern "C" int zedo_prune_rank(const double *d_err, int H, int N, int K, int *d_keep, void *stream) {
+    if (!d_err || !d_keep || N < 1 || K < 1 || K > H || H > 1024 || (long long)H * N > INT_MAX) return ZEDO_E_BADARG;
+    HIPCHK(launch_prune_rank(d_err, H, N, K, d_keep, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
+extern "C" int zedo_prune_gather(const int *d_keep, int H, int K, int N, int J, const float *d_x, const float *d_T, const int *d_hyp,
+                                 float *d_x_out, float *d_T_out, int *d_hyp_out, void *stream) {
+    if (!d_keep || !d_x || !d_T || !d_x_out || !d_T_out || !d_hyp_out || N < 1 || K < 1 || K > H || J < 1 || J > (INT_MAX - 4) / 3 ||
+        (long long)H * N > INT_MAX)
+        return ZEDO_E_BADARG;
+    if (d_x_out == d_x || d_T_out == d_T || d_hyp_out == d_hyp || d_hyp_out == d_keep) return ZEDO_E_BADARG;    // out of place only
+    HIPCHK(launch_prune_gather(d_keep, H, K, N, J, d_x, d_T, d_hyp, d_x_out, d_T_out, d_hyp_out, (hipStream_t)stream));
+    return ZEDO_OK;
+}

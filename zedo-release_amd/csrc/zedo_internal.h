@@ -239,6 +239,10 @@ hipError_t launch_joint_compose(const float *x, const float *T, const int *joint
 size_t temporal_fixed_bytes(int N, int H);
 hipError_t launch_temporal_select(const double *unary, const float *x, const int *seq_start, int n_seq, int H, int N, int J, double lambda,
                                   void *ws, int chunk, int *path, double *cost, hipStream_t st);
+// hypothesis pruning between two stages of the loop (zedo_prune.hip): keep [K,N], the kept slots of every pose in ascending order
+hipError_t launch_prune_rank(const double *err, int H, int N, int K, int *keep, hipStream_t st);
+hipError_t launch_prune_gather(const int *keep, int H, int K, int N, int J, const float *x, const float *T, const int *hyp, float *x_out,
+                               float *T_out, int *hyp_out, hipStream_t st);
 
 
 // predictor-corrector step kernels (zedo_pc.hip); z: the caller's noise draw, unpadded [B][D]

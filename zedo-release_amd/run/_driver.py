@@ -41,6 +41,11 @@ def build_parser(description, inference=False):
     p.add_argument("--seq_len", type=int, default=None, metavar="L",
                    help="--select temporal: cut the frames into consecutive clips of L (the last one shorter); overrides the dataset's "
                         "seq_start; with --synthetic the only source of clips (default: the dataset's clips, else one clip)")
+    p.add_argument("--prune", type=str, default=None, metavar="PLAN",
+                   help="opt-in: prune hypotheses DURING the loop. PLAN = STEP:KEEP[,STEP:KEEP...], e.g. 100:10 or 0:25,200:5: before OIL "
+                        "step STEP keep, per pose, the KEEP hypotheses with the smallest reprojection error (no ground truth needed) and "
+                        "carry on with KEEP x N rows; step 0 = after IPO.  One rank, the fused pipeline, --select none / reproj.  Whether "
+                        "this costs accuracy is UNMEASURED")
     if inference:
         p.add_argument("--eval", action="store_true", default=None, help="evaluation mode")
         p.add_argument("--data", type=str, default=None, help="npz with db_2d, camera_param[, db_3d] ('wild' dataset)")
@@ -206,6 +211,11 @@ def stepwise_loop(config, model, sde, sample_poses, gt_2d, K, S, device, hypothe
     return (rows, rows_T) if return_T else rows
 
 
+def pruned_path(out):
+    """<out without .npy>_pruned.npz: where run.inference --prune writes which hypotheses survived."""
+    return (out[:-4] if out.endswith(".npy") else out) + "_pruned.npz"
+
+
 def selected_path(out):
     """<out without .npy>_selected.npz: where run.inference --select reproj / joints / temporal writes the pose it keeps per detection."""
     return (out[:-4] if out.endswith(".npy") else out) + "_selected.npz"
@@ -216,13 +226,21 @@ def run(args, inference=False):
     from lib.algorithms.advanced.model import ScoreModelFC_Adv
     from lib.algorithms.ema import ExponentialMovingAverage
     from zedo_hip.pipeline import (Pipeline, ZeDOConfig, barrier, empty_selection, force_dist, gather_row_shards, init_dist,
-                                   local_device_index, reduce_min_over_ranks, shard_hypotheses, shard_rows, take_rows)
+                                   local_device_index, parse_prune_plan, prune_row_steps, reduce_min_over_ranks, shard_hypotheses,
+                                   shard_rows, take_rows)
 
     select = getattr(args, "select", "none") or "none"
     if select != "none" and not inference:
         raise SystemExit(f"--select {select} is honoured by run.inference only: run.opt_main scores every hypothesis against 3D ground "
                          "truth (best of H), and the ground-truth evaluation of a selected pose is printed by run.inference --eval")
     check_select_args(args)
+    prune = getattr(args, "prune", None)
+    if prune is not None and select in ("joints", "temporal"):
+        raise SystemExit(f"--prune with --select {select} is not supported yet (a follow-up): the pruned run keeps different hypotheses "
+                         "per pose; use --select reproj or none")
+    if prune is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--prune runs on one rank only: the rows are sharded by (hypothesis, pose), so the hypotheses of one pose live on "
+                         "several ranks and no rank can rank them; pose-sharded pruning is not built")
     config = load_config(args.config)
     if getattr(args, "math", None):
         os.environ["ZEDO_MATH"] = args.math          # read by zedo_hip.Weights when the model's device copy is built
@@ -270,11 +288,23 @@ def run(args, inference=False):
     H, N = len(sample_poses), len(gt_3d)
     lo, rows = shard_rows(H * N, rank, world)
     why = not_fused_because(config)
+    if prune is not None:
+        if why is not None:
+            raise SystemExit(f"--prune needs the fused pipeline; this configuration steps the per-step sampler surface ({why})")
+        try:
+            plan = parse_prune_plan(prune, H, S)
+        except ValueError as e:
+            raise SystemExit(f"--prune: {e}")
+    hyp = None
     if why is None:
         cfg = ZeDOConfig(z.IPO_iterations, z.IPO_keylist, z.RotAxes, z.IPO_T, z.IPO_minScaleT, z.IPO_maxScaleT, S,
                          z.sampling_eps, sde.T, sde.N, sde.beta_0, sde.beta_1)
         pipe = Pipeline(model.hip_weights(), cfg, device).load(sample_poses, gt_2d, K)
-        x, T = pipe.run(row_offset=lo, rows=rows)
+        if prune is not None:
+            x, T, hyp = pipe.run_pruned(plan)           # [K*N,17,3], [K*N,3], [K,N]: the survivors in ascending hypothesis order
+            H = hyp.shape[0]                            # from here on the survivors are the hypotheses; hyp maps them back
+        else:
+            x, T = pipe.run(row_offset=lo, rows=rows)
     else:
         # the per-step surface runs one hypothesis of ALL poses at a time (a batch of N rows with the global loss
         # normaliser of IPO), so ranks share the hypothesis loop: whole hypotheses, contiguous, unpadded
@@ -289,10 +319,14 @@ def run(args, inference=False):
 
     batch_results = None
     if inference:          # results.npy holds every hypothesis: [N, H, 17, 3] (run/inference.py:233-236)
-        full = gather_row_shards(x, H * N, lo=None if why is None else lo)     # one RCCL all-gather of the row shards
+        # with --prune: the K_final survivors of every pose, [N, K_final, 17, 3], one rank
+        full = x if hyp is not None else gather_row_shards(x, H * N, lo=None if why is None else lo)     # one RCCL all-gather of the row shards
         batch_results = full.reshape(H, N, N_JOINTS, JOINT_DIM).permute(1, 0, 2, 3).cpu().numpy()
         if rank == 0:
             np.save(args.out, batch_results)
+            if hyp is not None:
+                np.savez(pruned_path(args.out), hypothesis=hyp.t().contiguous().cpu().numpy().astype(np.int32),
+                         stage_step=np.array([s for s, _ in plan], np.int32), stage_keep=np.array([k for _, k in plan], np.int32))
     selected = None
     if inference and select == "reproj":
         # per pose the hypothesis whose x + T reprojects closest to the detections (zedo_min_reproj) on this rank's rows, MIN over the
@@ -307,8 +341,10 @@ def run(args, inference=False):
             Kd = torch.tensor(np.ascontiguousarray(K), dtype=torch.float32, device=device)
             _, best, idx = zedo_hip.min_reproj(x, T.contiguous(), d2[:, :, :2].contiguous(), Kd, d2[:, :, 2].contiguous(), N, lo)
         best, idx = reduce_min_over_ranks(best, idx)
-        full_T = gather_row_shards(T.contiguous(), H * N, lo=None if why is None else lo)
-        selected = dict(pose=take_rows(full, idx, H, N).cpu().numpy(), hypothesis=idx.cpu().numpy().astype(np.int32),
+        full_T = T if hyp is not None else gather_row_shards(T.contiguous(), H * N, lo=None if why is None else lo)
+        # with --prune idx is a survivor slot: the file names the original hypothesis
+        kept = idx if hyp is None else take_rows(hyp.reshape(-1), idx, H, N)
+        selected = dict(pose=take_rows(full, idx, H, N).cpu().numpy(), hypothesis=kept.cpu().numpy().astype(np.int32),
                         reproj_px=best.cpu().numpy(), T=take_rows(full_T, idx, H, N).cpu().numpy())
         if rank == 0:
             np.savez(selected_path(args.out), **selected)
@@ -374,6 +410,11 @@ def run(args, inference=False):
         p1 = test_dataset.eval_multi(("rows", x), protocol2=False, print_verbose=rank == 0, row_offset=lo)
         p2 = test_dataset.eval_multi(("rows", x), protocol2=True, print_verbose=rank == 0, row_offset=lo)
         errs = (p1, p2)
+        if hyp is not None and rank == 0:
+            done, total = prune_row_steps(plan, len(sample_poses), S)
+            print(f"best of {H} survivors MPJPE : {p1}")
+            print(f"best of {H} survivors PA-MPJPE : {p2}")
+            print(f"pruned {prune}: row-steps {done * N} of {total * N} ({done / total:.4f})")
         if selected is not None:
             # the selected pose scored as a one-hypothesis set by the same eval_multi (every rank holds all of it: row_offset 0); its
             # own prints are kept off stdout so that the two best-of-H lines above stay the only `mean ...` lines

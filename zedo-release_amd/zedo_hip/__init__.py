@@ -72,6 +72,8 @@ SIGNATURES = {
     "zedo_joint_compose": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "zedo_temporal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_temporal_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _sz, _vp, _vp, _vp]),
+    "zedo_prune_rank": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "zedo_prune_gather": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_pose_min": (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp]),
     "zedo_probe_mfma_peak": (_i, [_i, _vp, _vp, _vp]),
     "zedo_probe_mfma_peak_f16": (_i, [_i, _vp, _vp, _vp]),
@@ -576,6 +578,49 @@ def temporal_select(unary, x_full, seq_start, N=None, lam=100.0, chunk_frames=0)
         _check(_lib.zedo_temporal_select(_p(unary, torch.float64), _p(x_full), _p(seq, torch.int32), seq.numel() - 1, H, N, J, float(lam),
                                          _p(ws, torch.uint8), nbytes, _p(path, torch.int32), _p(cost, torch.float64), _stream(dev)))
     return path, cost
+
+
+def prune_rank(err, N, K):
+    """The table of kept slots between two stages of the loop (zedo_prune_rank): err [H*N] f64 (ALL rows of the current slots, h-major:
+    e.g. err of min_reproj) -> keep [K,N] i32, per pose the K slots with the smallest error in ascending slot order.  Finite errors
+    ascending, then +inf, then NaN, ties to the lower slot: a diverged row is the first to go.  1 <= K <= H <= 1024."""
+    _need_gpu()
+    dev = _device_of(err)
+    N, K = int(N), int(K)
+    if N < 1 or err.dim() != 1 or err.shape[0] % N or err.shape[0] == 0:
+        raise ValueError(f"prune_rank: err [H*N] expected, got {tuple(err.shape)} with N = {N}")
+    H = err.shape[0] // N
+    if not 1 <= K <= H:
+        raise ValueError(f"prune_rank: 1 <= K <= H = {H} expected, got K = {K}")
+    with torch.cuda.device(dev):
+        keep = torch.empty((K, N), dtype=torch.int32, device=dev)
+        _check(_lib.zedo_prune_rank(_p(err, torch.float64), H, N, K, _p(keep, torch.int32), _stream(dev)))
+    return keep
+
+
+def prune_gather(keep, x, T, hyp=None):
+    """The rows of the kept slots, compacted (zedo_prune_gather): keep [K,N] i32 (of prune_rank), x [H*N,J,3] and T [H*N,3] f32 (ALL rows,
+    h-major), hyp [H,N] i32 or None: the original hypothesis id of every current slot (None: the slots are the hypotheses) ->
+    (x_out [K*N,J,3], T_out [K*N,3], hyp_out [K,N] i32); row (r, n) is the input row (keep[r,n], n).  An entry of keep outside the slots
+    gives a NaN row with id -1."""
+    _need_gpu()
+    dev = _device_of(keep, x, T, hyp)
+    if keep.dim() != 2 or x.dim() != 3:
+        raise ValueError(f"prune_gather: keep [K,N] and x [H*N,J,3] expected, got {tuple(keep.shape)} and {tuple(x.shape)}")
+    K, N = keep.shape
+    rows, J = x.shape[0], x.shape[1]
+    H = rows // N if N else 0
+    if (N < 1 or K < 1 or rows % N or K > H or tuple(x.shape) != (rows, J, 3) or tuple(T.shape) != (rows, 3)
+            or (hyp is not None and tuple(hyp.shape) != (H, N))):
+        raise ValueError(f"prune_gather: keep [K,N], x [H*N,J,3], T [H*N,3], hyp [H,N] with K <= H expected, got {tuple(keep.shape)}, "
+                         f"{tuple(x.shape)}, {tuple(T.shape)}, {None if hyp is None else tuple(hyp.shape)}")
+    with torch.cuda.device(dev):
+        x_out = torch.empty((K * N, J, 3), dtype=torch.float32, device=dev)
+        T_out = torch.empty((K * N, 3), dtype=torch.float32, device=dev)
+        hyp_out = torch.empty((K, N), dtype=torch.int32, device=dev)
+        _check(_lib.zedo_prune_gather(_p(keep, torch.int32), H, K, N, J, _p(x), _p(T), _p(hyp, torch.int32), _p(x_out), _p(T_out),
+                                      _p(hyp_out, torch.int32), _stream(dev)))
+    return x_out, T_out, hyp_out
 
 
 def pose_min(err, N, row_offset=0):

@@ -9,6 +9,8 @@ batched as rows (h, n) and every stage running in libzedo_hip.so.
                    or, without ground truth, of the confidence-weighted reprojection error of x + T (select_reproj),
                    or per JOINT of the joint's reprojection distance, the pose assembled from the winners (aggregate_reproj, compose),
                    or along the clips of a video: reprojection error plus a motion cost, by Viterbi (select_temporal)
+    pruning      = opt-in, DURING the loop: at the steps of a plan keep, per pose, the K hypotheses with the smallest reprojection
+                   error and carry on with K x N rows (parse_prune_plan, run_pruned)
 
 Rows may be a contiguous shard of the H*N global rows (one shard per GPU); the only exchange is the final
 MIN over ranks, done by the caller (run/opt_main.py, bench.py) with torch.distributed.
@@ -19,12 +21,45 @@ import numpy as np
 import torch
 
 from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_compose, joint_reproj, min_mpjpe_both, min_reproj, oil_run,
-               reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
+               prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
 def linspace_f32(start, end, steps):
     """torch.linspace(start, end, steps) in fp32 without touching a device (opt_main.py:198)."""
     return torch.linspace(float(start), float(end), int(steps), dtype=torch.float32).numpy()
+
+
+def parse_prune_plan(text, H, S):
+    """"100:10" or "0:25,200:5" -> [(step, keep), ...]: before OIL step `step` the loop keeps, per pose, the `keep` hypotheses with the
+    smallest reprojection error.  Steps strictly ascending in [0, S) (0: after IPO and the initial rotate), keeps strictly descending
+    with 1 <= keep <= H; anything else is a ValueError that names the offending item."""
+    H, S = int(H), int(S)
+    items = [t.strip() for t in str(text).split(",")]
+    plan = []
+    for item in items:
+        parts = item.split(":")
+        if len(parts) != 2 or not all(q.strip().isdigit() for q in parts):
+            raise ValueError(f"prune plan {text!r}: item {item!r} is not STEP:KEEP (two non-negative integers)")
+        step, keep = int(parts[0]), int(parts[1])
+        if step >= S:
+            raise ValueError(f"prune plan {text!r}: item {item!r}: step {step} is outside the loop's steps 0 .. {S - 1}")
+        if not 1 <= keep <= H:
+            raise ValueError(f"prune plan {text!r}: item {item!r}: keep {keep} is outside 1 .. {H} hypotheses")
+        if plan and step <= plan[-1][0]:
+            raise ValueError(f"prune plan {text!r}: item {item!r}: step {step} does not come after step {plan[-1][0]}")
+        if plan and keep >= plan[-1][1]:
+            raise ValueError(f"prune plan {text!r}: item {item!r}: keep {keep} is not below the {plan[-1][1]} already kept")
+        plan.append((step, keep))
+    return plan
+
+
+def prune_row_steps(plan, H, S):
+    """(hypothesis-steps per pose that the loop runs under `plan`, the H * S of the unpruned loop)."""
+    done, begin, cur = 0, 0, int(H)
+    for step, keep in plan:
+        done += cur * (step - begin)
+        begin, cur = step, keep
+    return done + cur * (int(S) - begin), int(H) * int(S)
 
 
 class ZeDOConfig:
@@ -97,6 +132,41 @@ class Pipeline:
             x = rotate_init(self.x0, R, self.N, row_offset)
             oil_run(self.weights, self.sched, x, self.geom, T, 0, S, c.OIL_iterations // 5, row_offset)
         return x, T
+
+    def run_pruned(self, plan, oil_steps=None):
+        """IPO + OIL with hypotheses pruned during the loop -> (x [K*N,17,3], T [K*N,3], hyp [K,N] i32), K the last stage's keep.
+        plan: the text of parse_prune_plan or its [(step, keep), ...].  IPO and the rotate run on all H*N rows; for every stage the loop
+        runs up to the stage's step, zedo_min_reproj scores the current rows against the problem's detections (the current slot count in
+        the role of H), zedo_prune_rank keeps the best `keep` slots per pose and zedo_prune_gather compacts x, T and the ids; the last
+        segment runs to the end.  Row (r, n) of the result is hypothesis hyp[r, n] of pose n, ascending in r.  The switch to the
+        least-squares T stays at OIL_iterations // 5.  No row_offset: a pose's every hypothesis must be on this device.  A row's bits do
+        not depend on the batch it is in, so every surviving row is run()'s row.  Whether pruning by reprojection error costs accuracy
+        is not measured."""
+        c = self.cfg
+        S = c.OIL_iterations if oil_steps is None else int(oil_steps)
+        if not isinstance(plan, str):              # a list goes through the same checks as the text
+            plan = ",".join(f"{int(s)}:{int(k)}" for s, k in plan)
+        plan = parse_prune_plan(plan, self.H, S) if plan else []
+        switch = c.OIL_iterations // 5
+        with torch.cuda.device(self.device):
+            if S > switch and self.singular_poses:     # the loop reaches the least-squares T
+                raise ZedoError(SINGULAR_MSG.format(n=self.singular_poses))
+            B = self.H * self.N
+            R, T = ipo_fit(self.x0, self.uv, self.K, c.IPO_keylist, c.RotAxes, c.IPO_T, c.IPO_minScaleT,
+                           c.IPO_maxScaleT, c.IPO_iterations, self.N * len(c.IPO_keylist) * 2, B, 0)
+            x = rotate_init(self.x0, R, self.N, 0)
+            hyp, begin = None, 0
+            for step, keep in plan:
+                if step > begin:
+                    oil_run(self.weights, self.sched, x, self.geom, T, begin, step, switch, 0)
+                err, _, _ = min_reproj(x, T, self.uv, self.K, self.conf, self.N, 0)
+                x, T, hyp = prune_gather(prune_rank(err, self.N, keep), x, T, hyp)
+                begin = step
+            if S > begin:
+                oil_run(self.weights, self.sched, x, self.geom, T, begin, S, switch, 0)
+            if hyp is None:
+                hyp = torch.arange(self.H, dtype=torch.int32, device=self.device)[:, None].expand(self.H, self.N).contiguous()
+        return x, T, hyp
 
     def select(self, x, gt_centred, row_offset=0):
         """-> dict(p1=(best[N], idx[N]), p2=(best[N], idx[N])) for the local rows (fp64 / int32 tensors)."""
