@@ -9,6 +9,11 @@ import numpy as np
 from _select_ref import select_ref
 
 CASES = [(1, 1, 1), (1, 3, 2), (5, 3, 5), (17, 1, 5), (17, 64, 5), (17, 70, 5), (21, 70, 3), (17, 300, 7)]
+# what the table above stays below (csrc/zedo_metric.hip): the walking kernel has one lane per (pose, joint) - J = 64: a pose's lanes are
+# exactly one wavefront, 65: they straddle two, 33 with N = 70: 2310 lanes, ten workgroups with a tail; the row route hands
+# launch_pose_min N J "poses" - 17 x 483 = 8211 >= POSE_MIN_LANE_N = 8192: the lane-per-pose arg-min on the flattened distances
+BOUNDARY_CASES = [(64, 5, 3), (65, 4, 4), (33, 70, 3), (17, 483, 3)]
+CASES = CASES + BOUNDARY_CASES
 IDS = [f"J{J}-N{N}-H{H}" for J, N, H in CASES]
 
 

@@ -6,14 +6,21 @@ import functools
 
 import numpy as np
 
-RANK_H = (1, 2, 3, 50, 64, 65, 1024)
-RANK_N = (1, 7, 64, 65, 130)
+# H on both sides of every tile size of prune_rank_kernel (csrc/zedo_prune.hip): the small instantiation ends at H = 56, then tiles of
+# P = 64 poses up to H = 256, P = 32 up to 512, P = 16 up to 1024 - 56 | 57, 256 | 257 and 512 | 513 - beside one, two and three slots and
+# the wavefront (64 | 65).  N on both sides of the tiles: 33 is one pose more than a tile of 32, 64 | 65 and 130 the tiles of 64; 1 and 7
+# leave most of a tile empty.  The largest H keeps to N <= 65 (four tiles of 16 and a tail): the reference sorts every column.
+RANK_H = (1, 2, 3, 50, 56, 57, 64, 65, 256, 257, 512, 513, 1024)
+RANK_N = (1, 7, 33, 64, 65, 130)
 RANK_CASES = [(H, N) for H in RANK_H for N in RANK_N if H < 1024 or N <= 65]
+# J of the gather tests: a row is 3 J + 4 words and the 64 lanes of its wavefront copy them 64 at a time - part of one trip (1, 5, 17),
+# exactly one (20: 64 words), a second (21: 67), a third that two lanes take (42: 130), a fourth (64: 196)
+GATHER_J = (1, 5, 17, 20, 21, 42, 64)
 
 
 def rank_ks(H):
-    """K in {1, H-1, H} where those are valid."""
-    return sorted({k for k in (1, H - 1, H) if 1 <= k <= H})
+    """K in {1, H/2, H-1, H} where those are valid: the ends and one K in the middle."""
+    return sorted({k for k in (1, H // 2, H - 1, H) if 1 <= k <= H})
 
 
 def order_ref(err, N):

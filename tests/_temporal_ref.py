@@ -10,10 +10,20 @@ import numpy as np
 # short last clip (70 frames in clips of 9, 130 in clips of 50), a clip longer than a run of the backward pass's LDS staging (300), J != 17.
 CASES = [(1, 1, 1, 1), (1, 7, 2, 7), (5, 12, 3, 4), (17, 64, 5, 64), (17, 70, 50, 35), (17, 70, 64, 9), (21, 40, 65, 40), (17, 300, 7, 300),
          (17, 130, 130, 50)]
-# beyond the issue's table: more hypotheses than the scan kernel keeps in the LDS at once (1024), where D[n-1,.] is walked in pieces
+# more hypotheses than the scan kernel keeps in the LDS at once (TS_CAP = 1024), where D[n-1,.] is walked in pieces
 EXTRA_CASES = [(1, 3, 1030, 3)]
-IDS = [f"J{J}-N{N}-H{H}-L{L}" for J, N, H, L in CASES + EXTRA_CASES]
+# the smallest shapes on the far side of the constants of csrc/zedo_temporal.hip that CASES and EXTRA_CASES stay below:
+#   TT_J = 32 joints per staged piece: 33 (a second piece, one joint long), 64 (two full pieces; H = 17 also crosses the TT_P = 16 tile of
+#   h') and 65 (three pieces);  256 < H <= TS_CAP: H = 300, a lane of the resident scan owns two h and its prefetch serves the first only,
+#   clips of 13 frames end inside the backward pass's runs;  TB_INTS = 8192 ints of staged back rows: H = 4097 stages one frame per run,
+#   H = 8193 walks the table in memory (one frame of transition costs is 537 MB).
+BOUNDARY_CASES = [(33, 9, 5, 9), (64, 6, 17, 3), (65, 5, 3, 5), (17, 40, 300, 13), (1, 4, 4097, 2), (1, 3, 8193, 3)]
+# check_inputs() holds them to the same conditions as the others; with the draws of case() as they are the smallest gap between the best
+# and the second-best candidate over the three lambdas is 6.6e-6 (H = 300), 4.7e-6 (H = 4097) and 1.3e-5 (H = 8193): no other seed needed.
+ALL_CASES = CASES + EXTRA_CASES + BOUNDARY_CASES
+IDS = [f"J{J}-N{N}-H{H}-L{L}" for J, N, H, L in ALL_CASES]
 LAMBDAS = (30.0, 100.0, 300.0)
+REF_BLOCK = 1 << 19                                            # elements of the candidate block the reference holds at a time
 
 
 def clips(N, L):
@@ -47,15 +57,21 @@ def dead_frame_case():
     return x, u.reshape(-1)
 
 
-def motion_ref(x, N, n):
-    """m[n] [H', H] float64 = (1/J) sum_j sqrt(sum_c (x[h,n,j,c] - x[h',n-1,j,c])^2), the sums ascending in c, then in j."""
-    H, J = x.shape[0] // N, x.shape[1]
-    x4 = np.asarray(x, dtype=np.float64).reshape(H, N, J, 3)
-    acc = np.zeros((H, H))
+def motion_block(x4, n, h0, h1):
+    """x4 [H,N,J,3] float64 -> [h1 - h0, H'] float64: m[n, h', h] for h in h0 .. h1-1, h-major (the candidates of one h are contiguous).
+    (1/J) sum_j sqrt(sum_c (x[h,n,j,c] - x[h',n-1,j,c])^2), the sums ascending in c, then in j."""
+    J = x4.shape[2]
+    acc = np.zeros((h1 - h0, x4.shape[0]))
     for j in range(J):
-        d = x4[None, :, n, j, :] - x4[:, None, n - 1, j, :]                                # [h', h, 3]
-        acc = acc + np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2])
+        d0, d1, d2 = (x4[h0:h1, None, n, j, c] - x4[None, :, n - 1, j, c] for c in range(3))
+        acc = acc + np.sqrt(d0 * d0 + d1 * d1 + d2 * d2)
     return acc / J
+
+
+def motion_ref(x, N, n):
+    """m[n] [H', H] float64, all of it at once."""
+    H, J = x.shape[0] // N, x.shape[1]
+    return motion_block(np.asarray(x, dtype=np.float64).reshape(H, N, J, 3), n, 0, H).T
 
 
 def temporal_ref(unary, x, seq_start, lam, N=None):
@@ -66,19 +82,17 @@ def temporal_ref(unary, x, seq_start, lam, N=None):
     H = len(unary) // N
     u = np.asarray(unary, dtype=np.float64).reshape(H, N).T.copy()                         # u[n, h]
     u[~np.isfinite(u)] = np.inf
+    x4 = np.asarray(x, dtype=np.float64).reshape(H, N, x.shape[1], 3)
     dead = ~np.isfinite(u).any(1)
     D, back = np.full((N, H), np.inf), np.full((N, H), -1, np.int32)
     path, cost = np.zeros(N, np.int32), np.full(N, np.inf)
     gap = np.inf
 
-    def second_gap(v, axis):
+    def second_gap(g):
         nonlocal gap
-        if v.shape[axis] > 1:
-            s = np.sort(v, axis=axis)
-            g = np.take(s, 1, axis) - np.take(s, 0, axis)
-            g = g[np.isfinite(g)]
-            if g.size:
-                gap = min(gap, float(g.min()))
+        g = g[np.isfinite(g)]
+        if g.size:
+            gap = min(gap, float(g.min()))
 
     for a, b in zip(seq[:-1], seq[1:]):
         for n in range(a, b):
@@ -87,11 +101,20 @@ def temporal_ref(unary, x, seq_start, lam, N=None):
             if n == a or dead[n - 1]:
                 D[n] = u[n]
                 continue
-            with np.errstate(invalid="ignore"):
-                cand = D[n - 1][:, None] + lam * motion_ref(x, N, n)                        # [h', h]
-            second_gap(cand, 0)
-            back[n] = np.argmin(cand, axis=0)                                              # the lowest h' that attains the minimum
-            D[n] = u[n] + cand[back[n], np.arange(H)]
+            # blocks of hypotheses h, so that 8193 of them need no H x H x 3 array: every element is computed as it would be at once
+            step = max(1, REF_BLOCK // H)
+            for h0 in range(0, H, step):
+                h1 = min(H, h0 + step)
+                k = np.arange(h1 - h0)
+                with np.errstate(invalid="ignore"):
+                    cand = D[n - 1][None, :] + lam * motion_block(x4, n, h0, h1)           # [h, h']
+                back[n, h0:h1] = np.argmin(cand, axis=1)                                   # the lowest h' that attains the minimum
+                first = cand[k, back[n, h0:h1]]
+                D[n, h0:h1] = u[n, h0:h1] + first
+                if H > 1:
+                    cand[k, back[n, h0:h1]] = np.inf
+                    with np.errstate(invalid="ignore"):
+                        second_gap(cand.min(axis=1) - first)
         have = False
         for n in range(b - 1, a - 1, -1):
             if dead[n]:
@@ -101,7 +124,9 @@ def temporal_ref(unary, x, seq_start, lam, N=None):
                 path[n] = back[n + 1, path[n + 1]]
             else:
                 path[n] = int(np.argmin(D[n]))
-                second_gap(D[n], 0)
+                if H > 1:
+                    with np.errstate(invalid="ignore"):
+                        second_gap(np.diff(np.partition(D[n], 1)[:2]))
             cost[n] = D[n, path[n]]
             have = True
     return dict(path=path, cost=cost, D=D, back=back, gap=gap)
@@ -151,7 +176,7 @@ def check_inputs(verbose=True):
     for every case with H >= 5, the selection is not the per-frame one: the path differs from the per-frame arg-min on more than 25 %
     of the frames, switches hypothesis at more than 5 % of the transitions, and at fewer than with lambda = 0."""
     gaps = []
-    for J, N, H, L in CASES + EXTRA_CASES:
+    for J, N, H, L in ALL_CASES:
         x, u = case(J, N, H)
         seq = clips(N, L)
         for lam in LAMBDAS:

@@ -128,14 +128,18 @@ def _combine(parts):
     return best, idx
 
 
-@pytest.mark.parametrize("rows", [True, False], ids=["with_jerr", "walking"])
-def test_shards_are_slices_of_the_whole(zh, rows):
-    """(17, 70, 5) cut at rows 0 / 93 / 211 / 350, on both routes: each shard's jerr is bitwise the slice, the shards' selections combined
-    on the host are bitwise the unsharded selection, and a pose with no row in a shard reports (+inf, -1) for all its joints there."""
-    J, N, H = 17, 70, 5
+@pytest.mark.parametrize("shape,cuts,rows", [((17, 70, 5), [0, 93, 211, 350], True), ((17, 70, 5), [0, 93, 211, 350], False),
+                                             ((17, 483, 3), [0, 93, 700, 1449], True), ((17, 483, 3), [0, 93, 700, 1449], False)],
+                         ids=["with_jerr", "walking", "J17-N483-H3-with_jerr", "J17-N483-H3-walking"])
+def test_shards_are_slices_of_the_whole(zh, shape, cuts, rows):
+    """(17, 70, 5) cut at rows 0 / 93 / 211 / 350 and (17, 483, 3) at 0 / 93 / 700 / 1449 (N J = 8211: the row route's arg-min runs one lane
+    per (pose, joint), with flattened offsets 93 J and 700 J that are no multiple of 64 J), on both routes: each shard's jerr is bitwise
+    the slice, the shards' selections combined on the host are bitwise the unsharded selection, and a pose with no row in a shard reports
+    (+inf, -1) for all its joints there."""
+    J, N, H = shape
     x, T, uv, K, _ = case(J, N, H)
     best, idx, jerr = run(zh, x, T, uv, K)
-    cuts, parts = [0, 93, 211, 350], []
+    parts = []
     for lo, hi in zip(cuts[:-1], cuts[1:]):
         out = run(zh, x[lo:hi], T[lo:hi], uv, K, off=lo, rows=rows)
         if rows:
@@ -148,14 +152,15 @@ def test_shards_are_slices_of_the_whole(zh, rows):
     cb, ci = _combine(parts)
     assert np.array_equal(cb.view(np.int64), best.cpu().numpy().reshape(-1).view(np.int64))
     assert np.array_equal(ci, idx.cpu().numpy().reshape(-1))
-    # rows [93, 120): poses 23 .. 49 only (hypothesis 1), the other 43 report (+inf, -1) for all joints
+    # rows [93, 120): 27 poses of one hypothesis only (N = 70: poses 23 .. 49 of hypothesis 1), the others report (+inf, -1) for all joints
     out = run(zh, x[93:120], T[93:120], uv, K, off=93, rows=rows)
     if rows:
         assert same(out[2], jerr[93:120])
     b, i = out[0], out[1].cpu().numpy()
-    held = (np.arange(N) >= 23) & (np.arange(N) < 50)
-    assert (i[held] == 1).all() and (i[~held] == -1).all() and int((~held).sum()) == 43
-    assert np.isposinf(b.cpu().numpy()[~held]).all() and same(b[23:50], jerr[93:120])
+    p0 = 93 % N
+    held = (np.arange(N) >= p0) & (np.arange(N) < p0 + 27)
+    assert (i[held] == 93 // N).all() and (i[~held] == -1).all() and int((~held).sum()) == N - 27
+    assert np.isposinf(b.cpu().numpy()[~held]).all() and same(b[p0:p0 + 27], jerr[93:120])
 
 
 def test_ties_nan_and_joints_behind_the_camera(zh):
@@ -201,6 +206,20 @@ def test_ties_nan_and_joints_behind_the_camera(zh):
     assert bool(torch.isposinf(b[8, 3])) and i[8, 3].item() == 2
     b2, i2, _ = run(zh, xr[93:], Tr[93:], uv, K, off=93, rows=True)
     assert same(b, b2) and same(i, i2)
+
+
+@pytest.mark.parametrize("J,N,H", CASES, ids=IDS)
+def test_compose_is_the_float64_formula_in_both_frames(zh, J, N, H):
+    """Every case of the table, J up to 65: the camera frame and the frame of the pose-level winner, bitwise compose_ref."""
+    x, T, uv, K, conf = case(J, N, H)
+    xd, Td = dev(x), dev(T)
+    _, idx = zh.joint_reproj(xd, Td, dev(uv), dev(K))
+    _, _, ref = zh.min_reproj(xd, Td, dev(uv), dev(K), dev(conf))
+    jh, rh = idx.cpu().numpy(), ref.cpu().numpy()
+    cam, rel = zh.joint_compose(xd, Td, idx), zh.joint_compose(xd, Td, idx, ref)
+    assert cam.shape == (N, J, 3) and rel.shape == (N, J, 3) and cam.dtype == torch.float32 and rel.dtype == torch.float32
+    assert np.array_equal(cam.cpu().numpy().view(np.int32), compose_ref(x, T, jh).view(np.int32))
+    assert np.array_equal(rel.cpu().numpy().view(np.int32), compose_ref(x, T, jh, rh).view(np.int32))
 
 
 def test_compose(zh):

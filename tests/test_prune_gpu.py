@@ -1,7 +1,8 @@
 """GPU: zedo_prune_rank and zedo_prune_gather - the piece between two stages of a pruned OIL loop.  The table of kept slots against the
 numpy reference of tests/_prune_ref.py (pinned on its own in tests/test_prune_ref.py), the gather against torch indexing; every
-comparison is exact.  Tile tails, one lane, tile boundaries, every tile size of the rank kernel (H = 1024 runs 16 poses per tile), planted
-duplicates, signed zeros, infinities, NaNs; chained stages; out-of-range table entries; guard bands; the refusals of the raw ABI; one
+comparison is exact.  Tile tails, one lane, tile boundaries, every tile size of the rank kernel on both sides of the H at which it changes
+(64 poses per tile up to H = 256, 32 up to 512, 16 up to 1024), planted duplicates, signed zeros, infinities, NaNs; every number of 64-word
+trips along a row of the gather and a second trip of its grid over the rows; chained stages; out-of-range table entries; guard bands; the refusals of the raw ABI; one
 capture of both calls replayed on new input.
 Whether pruning by reprojection error costs accuracy is not measured here or anywhere: these tests hold the arithmetic.  The pruning
 does not depend on the arithmetic mode of the dense layers: one session runs it."""
@@ -10,7 +11,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from _prune_ref import RANK_CASES, case, gather_ref, keep_ref, rank_ks
+from _prune_ref import GATHER_J, RANK_CASES, case, gather_ref, keep_ref, rank_ks
 from _shared import dev, one_arithmetic_mode, zh  # noqa: F401  (fixtures; one_arithmetic_mode is autouse)
 
 pytestmark = pytest.mark.gpu
@@ -63,7 +64,7 @@ def test_the_planted_poses_hold_what_the_case_says():
 
 # ---- 2. the gather -------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("J", [1, 5, 17, 21])
+@pytest.mark.parametrize("J", GATHER_J)
 def test_the_gather_is_torch_indexing_and_stages_chain(zh, J):
     H, N, K1, K2 = 7, 130, 5, 2
     x, T = rows(H, N, J)
@@ -95,7 +96,7 @@ def test_the_gather_is_torch_indexing_and_stages_chain(zh, J):
     assert same(xi, xd) and same(Ti, Td) and same(hi, ident)
 
 
-@pytest.mark.parametrize("J", [1, 17, 21])
+@pytest.mark.parametrize("J", [J for J in GATHER_J if J != 5])
 def test_an_entry_outside_the_slots_is_never_an_address(zh, J):
     """-1 and H planted in the table: those rows are NaN with id -1, every other row is intact, and the guard bands around the three
     outputs (raw ABI, outputs carved from larger buffers) keep their bytes."""
@@ -128,6 +129,35 @@ def test_an_entry_outside_the_slots_is_never_an_address(zh, J):
         assert np.isnan(gx[outside]).all() and np.isnan(gT[outside]).all() and (gh.reshape(-1)[outside] == -1).all()
         assert np.array_equal(gx[~outside].view(np.int32), rx[~outside].view(np.int32))
         assert np.array_equal(gT[~outside].view(np.int32), rT[~outside].view(np.int32)) and np.array_equal(gh, rh)
+
+
+def test_the_gather_walks_the_rows_behind_the_grids_first_trip(zh):
+    """The gather's grid is capped at 2^20 workgroups of four rows: from 4 194 304 output rows up a wavefront takes a second row.  J = 1,
+    H = K = 2, N = 2 097 157: 4 194 314 rows, ten of them behind the first trip.  Outputs pre-filled with a sentinel, compared with torch
+    indexing on the device: all rows, and on their own the rows from 4 194 304 up and the last one."""
+    J, H, K, N = 1, 2, 2, 2097157
+    rows, first_trip = K * N, 4 * (1 << 20)
+    assert rows == first_trip + 10
+    gen = torch.Generator(device="cuda").manual_seed(78)
+    xd = torch.randn((H * N, J, 3), generator=gen, device="cuda")
+    Td = torch.randn((H * N, 3), generator=gen, device="cuda")
+    hd = torch.arange(100, 100 + H * N, dtype=torch.int32, device="cuda").reshape(H, N)
+    # row 0 of the table: slot n % 2, row 1: the other one (not the ascending table of prune_rank: the gather takes any table)
+    first = (torch.arange(N, device="cuda") % 2).to(torch.int32)
+    keep = torch.stack([first, 1 - first]).contiguous()
+    xo = torch.full((rows, J, 3), -7.0, device="cuda")
+    To = torch.full((rows, 3), -7.0, device="cuda")
+    ho = torch.full((K, N), -7, dtype=torch.int32, device="cuda")
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert zh._lib.zedo_prune_gather(P(keep), H, K, N, J, P(xd), P(Td), P(hd), P(xo), P(To), P(ho), st) == 0
+    torch.cuda.synchronize()
+    g = (keep.long() * N + torch.arange(N, device="cuda")[None, :]).reshape(-1)
+    tail = slice(first_trip, rows)
+    for name, out, want in (("x", xo, xd[g]), ("T", To, Td[g]), ("hyp", ho.reshape(-1), hd.reshape(-1)[g])):
+        print(f"gather {rows} rows, {name}: {int((bits(out) != bits(want)).reshape(rows, -1).any(1).sum())} rows differ, "
+              f"{int((out[tail] == -7).reshape(10, -1).all(1).sum())} of the last 10 untouched")
+        assert same(out[tail], want[tail]) and same(out[-1], want[-1]), name
+        assert same(out, want), name
 
 
 # ---- 3. refusals ---------------------------------------------------------------------------------------------------------------------

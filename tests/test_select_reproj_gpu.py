@@ -21,6 +21,11 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 CASES = [(1, 1, 1), (1, 3, 2), (5, 3, 5), (17, 1, 5), (17, 64, 5), (17, 70, 5), (21, 70, 3)]
+# what the table above stays below (csrc/zedo_metric.hip): a 64-row tile of row_reproj17_kernel that wraps round N = 7 poses nine times
+# and one that wraps once, a row short of the tile (N = 63); J above 21, up to the ABI's 64; and N >= POSE_MIN_LANE_N = 8192, where
+# launch_pose_min takes the lane-per-pose arg-min behind both row kernels (J = 17, odd N: every hypothesis starts at another alignment; J = 5)
+BOUNDARY_CASES = [(17, 7, 30), (17, 63, 3), (33, 5, 4), (64, 3, 3), (17, 8219, 2), (5, 8200, 2)]
+CASES = CASES + BOUNDARY_CASES
 IDS = [f"J{J}-N{N}-H{H}" for J, N, H in CASES]
 TOL = 1e-9
 
@@ -92,22 +97,23 @@ def test_row_errors_and_selection_match_the_float64_reference(zh, J, N, H, with_
     assert np.abs(best.cpu().numpy() - rbest).max() <= TOL
 
 
-@pytest.mark.parametrize("N", [64, 70])
-def test_every_path_returns_the_same_bits(zh, N):
+@pytest.mark.parametrize("J,N,H", [(17, 64, 5), (17, 70, 5), (17, 8219, 2), (5, 8200, 2)], ids=["64", "70", "J17-N8219-H2", "J5-N8200-H2"])
+def test_every_path_returns_the_same_bits(zh, J, N, H):
     """J = 17: a view of x one row (204 bytes) into a larger buffer is not 16-byte aligned and takes the generic kernel - the bits of
-    the staged kernel.  No confidences = confidences of one; 5.0 acts as 1.0 and 0.0 as 1e-4, bitwise."""
-    x, T, uv, K, conf = case(17, N, 5)
-    B = 5 * N
+    the staged kernel, also where the lane-per-pose arg-min follows (N = 8219; J = 5 takes the generic kernel either way).
+    No confidences = confidences of one; 5.0 acts as 1.0 and 0.0 as 1e-4, bitwise."""
+    x, T, uv, K, conf = case(J, N, H)
+    B = H * N
     xd, Td, uvd, Kd, cd = dev(x), dev(T), dev(uv), dev(K), dev(conf)
-    buf = torch.empty((B + 1) * 51, dtype=torch.float32, device="cuda")
-    xb = buf[51:].view(B, 17, 3)
+    buf = torch.empty((B + 1) * J * 3, dtype=torch.float32, device="cuda")
+    xb = buf[J * 3:].view(B, J, 3)
     xb.copy_(xd)
     assert xd.data_ptr() % 16 == 0 and xb.data_ptr() % 16 == 12 and xb.is_contiguous()
     for c in (None, cd):
         a, b = zh.min_reproj(xd, Td, uvd, Kd, c), zh.min_reproj(xb, Td, uvd, Kd, c)
         for ta, tb in zip(a, b):
             assert torch.equal(bits(ta), bits(tb))
-    full = lambda v: torch.full((N, 17), v, dtype=torch.float32, device="cuda")
+    full = lambda v: torch.full((N, J), v, dtype=torch.float32, device="cuda")
     for x_ in (xd, xb):
         e_none = zh.min_reproj(x_, Td, uvd, Kd, None)[0]
         e_one = zh.min_reproj(x_, Td, uvd, Kd, full(1.0))[0]
@@ -151,6 +157,30 @@ def test_shards_are_slices_of_the_whole(zh):
     held = (np.arange(N) >= 23) & (np.arange(N) < 50)
     assert np.array_equal(i.cpu().numpy() >= 0, held) and (i.cpu().numpy()[held] == 1).all() and (i.cpu().numpy()[~held] == -1).all()
     assert np.isposinf(b.cpu().numpy()[~held]).all() and torch.equal(bits(b[23:50]), bits(err[93:120]))
+
+
+@pytest.mark.parametrize("J,N,H", [(17, 7, 30), (17, 8219, 2)], ids=["J17-N7-H30", "J17-N8219-H2"])
+@pytest.mark.parametrize("with_conf", [False, True], ids=["noconf", "conf"])
+def test_a_shard_that_starts_inside_the_poses_is_a_slice_of_the_whole(zh, J, N, H, with_conf):
+    """Rows [17, N H - 5), the shard of tests/test_selection_both_gpu.py: the first tile starts at pose 17 % N, not 0 (N = 7: and wraps
+    nine times; N = 8219: the lane-per-pose arg-min counts the hypotheses of poses 0 .. 16 from 1 and loses the last five of h = 1).
+    err is bitwise the slice of the whole; best / idx are select_ref's on the float64 reference of the slice, best bitwise the row it names."""
+    x, T, uv, K, conf = case(J, N, H)
+    c = conf if with_conf else None
+    lo, hi = 17, N * H - 5
+    err = run(zh, x, T, uv, K, c)[0]
+    e, b, i = run(zh, x[lo:hi], T[lo:hi], uv, K, c, off=lo)
+    assert torch.equal(bits(e), bits(err[lo:hi]))
+    rbest, ridx = select_ref(ref(J, N, H, with_conf)[lo:hi], N, lo)
+    local = np.full(H * N, np.inf)
+    local[lo:hi] = ref(J, N, H, with_conf)[lo:hi]
+    s = np.sort(local.reshape(H, N), axis=0)
+    assert np.isfinite(s[0]).all() and (s[1] - s[0]).min() > 1e-6                           # every pose is held, and by no near tie
+    assert np.array_equal(i.cpu().numpy(), ridx) and (ridx >= 0).all()
+    pick = err[i.to(torch.int64) * N + torch.arange(N, device="cuda")]
+    assert torch.equal(bits(b), bits(pick)) and np.abs(b.cpu().numpy() - rbest).max() <= TOL
+    if H == 2:                                                                              # the poses that the cut leaves one hypothesis
+        assert (ridx[:lo] == 1).all() and (ridx[N - 5:] == 0).all()
 
 
 def test_ties_nan_and_points_behind_the_camera(zh):

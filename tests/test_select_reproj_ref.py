@@ -66,3 +66,10 @@ def test_select_ref_is_amin_and_argmin_per_pose():
     assert list(best) == [2.0, 1.0, np.inf] and list(idx) == [1, 0, 0]                             # a tie and an all-inf pose: the first
     best, idx = select_ref(err[4:6], 3, row_offset=4)
     assert list(best) == [np.inf, 1.0, np.inf] and list(idx) == [-1, 1, 1]                         # pose 0 holds no row of this shard
+
+
+def test_the_inputs_of_the_gpu_cases_are_what_the_bounds_assume():
+    """The conditions tests/test_select_reproj_gpu.py asserts on its case table before it compares anything - depth above 1 m, finite errors
+    of tens to hundreds of pixels, no best-to-second gap under 1e-6 px - hold on the reference alone, without a GPU."""
+    import test_select_reproj_gpu as gpu
+    gpu.test_the_inputs_are_what_the_bounds_assume()

@@ -16,7 +16,7 @@ import pytest
 from _joint_ref import case as reproj_case
 from _select_ref import reproj_ref, select_ref
 from _shared import dev, one_arithmetic_mode, problem, zh  # noqa: F401  (fixtures; one_arithmetic_mode is autouse)
-from _temporal_ref import (CASES, EXTRA_CASES, IDS, LAMBDAS, case, check_inputs, clips, cost_bound, dead_frame_case, reference,
+from _temporal_ref import (ALL_CASES, IDS, LAMBDAS, case, check_inputs, clips, cost_bound, dead_frame_case, reference,
                            temporal_ref)
 
 pytestmark = pytest.mark.gpu
@@ -39,7 +39,7 @@ def test_the_inputs_are_what_the_exact_comparison_assumes():
     check_inputs()
 
 
-@pytest.mark.parametrize("J,N,H,L", CASES + EXTRA_CASES, ids=IDS)
+@pytest.mark.parametrize("J,N,H,L", ALL_CASES, ids=IDS)
 def test_path_and_cost_match_the_float64_reference(zh, J, N, H, L):
     x, u = case(J, N, H)
     worst = 0.0
@@ -56,10 +56,13 @@ def test_path_and_cost_match_the_float64_reference(zh, J, N, H, L):
     print(f"worst relative cost error over the three lambdas: {worst:.3e}")
 
 
-@pytest.mark.parametrize("J,N,H,L", [(17, 70, 50, 35), (17, 130, 130, 50), (21, 40, 65, 40), (17, 300, 7, 300)], ids=lambda v: str(v))
+@pytest.mark.parametrize("J,N,H,L", [(17, 70, 50, 35), (17, 130, 130, 50), (21, 40, 65, 40), (17, 300, 7, 300), (33, 9, 5, 9), (17, 40, 300, 13)],
+                         ids=lambda v: str(v))
 def test_the_bits_do_not_depend_on_the_chunk_the_workspace_or_the_stream(zh, J, N, H, L):
-    """Chunks of 1, 2 and 7 frames (forced through the workspace size) against the default; a workspace pre-filled with NaN bytes at
-    the raw ABI; a side stream; one call captured into a graph and replayed twice."""
+    """Chunks of 1, 2 and 7 frames (forced through the workspace size) against the default (all N frames); a workspace pre-filled with
+    NaN bytes at the raw ABI; a side stream; one call captured into a graph and replayed twice.  (33, 9, 5, 9): the accumulators of the
+    transition kernel carried over a second joint piece; (17, 40, 300, 13): two h per lane of the resident scan, whose first frame of
+    every chunk fetches D[n-1,.] from the table."""
     x, u = case(J, N, H)
     xd, ud, seq = dev(x), dev(u, torch.float64), clips(N, L)
     lam = 100.0

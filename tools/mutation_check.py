@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: twenty-one one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: twenty-six one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -47,6 +47,13 @@ MUTANTS = [
     # the pruning between two stages of the loop (tests/test_prune_gpu.py, tests/test_prune_pipeline_gpu.py, tests/test_prune_driver_gpu.py):
     # leaves every other test green
     ("ZEDO_MUT_PRUNE_TIE", "zedo_prune_rank: the tie rule a < b becomes a <= b, a slot comes before itself (zedo_prune.hip prune_precedes)"),
+    # tile tails and dispatch branches of the selection, pruning and video kernels (profiles/mutation_boundaries.txt): each leaves the
+    # tests of these entry points green as they stood before their case tables crossed the constants named here
+    ("ZEDO_MUT_TT_PIECE", "zedo_temporal_select: joint pieces after the first (J > TT_J = 32) stage joints 0.. of the pose again (zedo_temporal.hip temporal_transition_kernel)"),
+    ("ZEDO_MUT_TB_WALK", "zedo_temporal_select: the walk in memory (H > TB_INTS = 8192) reads back row n instead of n + 1 (zedo_temporal.hip temporal_backtrack_kernel)"),
+    ("ZEDO_MUT_PR_P32", "zedo_prune_rank: tiles of 32 poses (256 < H <= 512) count the kept slots below a - 1 for the output position (zedo_prune.hip prune_rank_kernel)"),
+    ("ZEDO_MUT_PG_TRIP", "zedo_prune_gather: the grid-stride loop over the rows stops after its first trip (zedo_prune.hip prune_gather_kernel)"),
+    ("ZEDO_MUT_PMIN_LANE_H", "lane-per-pose arg-min (N >= 8192): reports h - h0, the hypothesis counted from the shard's first (zedo_metric.hip pose_min_kernel)"),
 ]
 
 

@@ -256,7 +256,11 @@ __global__ void pose_min_kernel(const double *__restrict__ err, int B, int N, lo
         if (min_takes(v, (int)h, e, hi)) { e = v; hi = (int)h; }
     }
     best[n] = (hi >= 0) ? e : __builtin_huge_val();
+#ifdef ZEDO_MUT_PMIN_LANE_H   // tools/mutation_check.py only: the hypothesis is counted from the shard's first one
+    best_h[n] = hi >= 0 ? hi - (int)h0 : hi;
+#else
     best_h[n] = hi;
+#endif
 }
 
 // Many poses (N >= POSE_MIN_LANE_N), J = 17, round 6: the row errors POSE-MAJOR.  One wave per (64 consecutive poses, chunk of the local

@@ -52,7 +52,11 @@ __global__ __launch_bounds__(PR_T) void prune_rank_kernel(const double *__restri
     for (int a = g; a < H; a += G) {
         if (!skept[a * P + p]) continue;
         int r = 0;
+#ifdef ZEDO_MUT_PR_P32   // tools/mutation_check.py only: tiles of 32 poses count the kept slots below a - 1 (r stays within 0 .. K-1)
+        for (int b = 0; b < (P == 32 ? a - 1 : a); ++b) r += skept[b * P + p];
+#else
         for (int b = 0; b < a; ++b) r += skept[b * P + p];
+#endif
         keep[(size_t)r * N + n] = a;                              // r < K: exactly K slots of a pose are kept
     }
 }
@@ -94,6 +98,9 @@ __global__ __launch_bounds__(PG_T) void prune_gather_kernel(const int *__restric
             else if (c < J3 + 3) T_out[(size_t)row * 3 + (c - J3)] = ok ? T[g * 3 + (c - J3)] : nan;
             else hyp_out[row] = !ok ? -1 : (hyp ? hyp[g] : h);
         }
+#ifdef ZEDO_MUT_PG_TRIP   // tools/mutation_check.py only: the rows behind the grid's first trip are never written
+        break;
+#endif
     }
 }
 

@@ -48,14 +48,19 @@ __global__ __launch_bounds__(TT_T) void temporal_transition_kernel(const float *
     for (int k = 0; k < TT_K; ++k) acc[k] = 0.0;
     for (int j0 = 0; j0 < J; j0 += TT_J) {
         const int ne = min(TT_J, J - j0) * 3;                      // floats of this piece per pose
+#ifdef ZEDO_MUT_TT_PIECE   // tools/mutation_check.py only: every piece stages joints 0 .. of the pose again (valid addresses: ne <= 3 J)
+        const int js = 0;
+#else
+        const int js = j0;
+#endif
         __syncthreads();                                           // the previous piece has been read by every lane
         for (int q = tid; q < nh * ne; q += TT_T) {
             const int r = q / ne, e = q - r * ne;
-            sc[r * TT_LD + e] = x[(size_t)(h0 + r) * hs + ((size_t)n * J + j0) * 3 + e];
+            sc[r * TT_LD + e] = x[(size_t)(h0 + r) * hs + ((size_t)n * J + js) * 3 + e];
         }
         for (int q = tid; q < np * ne; q += TT_T) {
             const int r = q / ne, e = q - r * ne;
-            sp[r * TT_LD + e] = x[(size_t)(p0 + r) * hs + ((size_t)(n - 1) * J + j0) * 3 + e];
+            sp[r * TT_LD + e] = x[(size_t)(p0 + r) * hs + ((size_t)(n - 1) * J + js) * 3 + e];
         }
         __syncthreads();                                           // the lanes read what other lanes have staged
         if (lh < nh) {
@@ -251,7 +256,11 @@ __global__ __launch_bounds__(256) void temporal_backtrack_kernel(const int *__re
             for (int i = len - 1; i >= 0; --i) {
                 if (sdead[i]) { p = 0; have = 0; }
                 else {
+#ifdef ZEDO_MUT_TB_WALK   // tools/mutation_check.py only: the walk in memory reads the row of the frame itself (a row of the clip: <= b - 1)
+                    p = have ? (staged ? sb[i * H + p] : back[(size_t)min(r0 + i, b - 1) * H + p]) : send[i];
+#else
                     p = have ? (staged ? sb[i * H + p] : back[(size_t)(r0 + i + 1) * H + p]) : send[i];
+#endif
                     p = clampi(p, 0, H - 1);
                     have = 1;
                 }
