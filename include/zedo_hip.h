@@ -45,7 +45,8 @@ extern "C" {
                               * still 5 (additive): + zedo_min_reproj;
                               * still 5 (additive): + zedo_joint_reproj, zedo_joint_compose;
                               * still 5 (additive): + zedo_temporal_workspace_bytes, zedo_temporal_select;
-                              * still 5 (additive): + zedo_prune_rank, zedo_prune_gather */
+                              * still 5 (additive): + zedo_prune_rank, zedo_prune_gather;
+                              * still 5 (additive): + zedo_joint_temporal_workspace_bytes, zedo_joint_temporal_select */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -367,6 +368,44 @@ int zedo_joint_compose(const float *d_x, const float *d_T, const int *d_joint_h,
 size_t zedo_temporal_workspace_bytes(int N, int H, int chunk_frames);
 int zedo_temporal_select(const double *d_unary, const float *d_x, const int *d_seq_start, int n_seq, int H, int N, int J,
                          double lambda, void *d_workspace, size_t workspace_bytes, int *d_path_h, double *d_cost, void *stream);
+
+/* ---- joint-wise selection along a video WITHOUT ground truth: one Viterbi chain per joint ------------------------------
+ * zedo_joint_reproj decides every joint of every frame on its own, zedo_temporal_select keeps whole hypotheses and its motion
+ * term is a mean over all joints.  This is their product: for every joint of every clip the hypothesis path that minimises
+ * that joint's own cost plus lambda times that joint's displacement to the previous frame's choice, in the camera frame
+ * (x + T) - the frame zedo_joint_compose assembles in - exactly, by dynamic programming over each clip, independently for
+ * every joint.  Whether this lowers the error against ground truth on real video is not measured.
+ * d_junary [H*N,J] float64, rows (h,n) h-major, ALL rows (no row_offset): any per-(row, joint) cost, e.g. d_jerr of
+ * zedo_joint_reproj (pixels).  d_x [H*N,J,3] fp32 and d_T [H*N,3] fp32, the same rows (metres); d_T may be NULL: the motion
+ * term is then taken on x alone.  lambda: cost units per metre.  d_seq_start [n_seq+1] int32 ON THE DEVICE, the rules of
+ * zedo_temporal_select: every entry is clamped to 0 .. N before use and is never an address.
+ * All arithmetic in float64 on the inputs as given, independent for every joint j:
+ *   X[n,h,j,c]   = (double)x[h*N+n,j,c] + (d_T ? (double)T[h*N+n,c] : 0.0)
+ *   u[n,j,h]     = junary[(h*N+n)*J + j] if finite, else +inf (NaN and +-inf: the hypothesis is excluded for that joint);
+ *                  (n,j) is DEAD if no u[n,j,h] is finite
+ *   m[n,j,h',h]  = sqrt(d0^2 + d1^2 + d2^2),  d_c = X[n,h,j,c] - X[n-1,h',j,c]          (products, then the sum ascending in c)
+ *   chain start (n first of its clip, or (n-1,j) dead):  D[n,j,h] = u[n,j,h], back[n,j,h] = -1
+ *   otherwise:  D[n,j,h] = u[n,j,h] + min_h' (D[n-1,j,h'] + lambda m[n,j,h',h]),  back[n,j,h] = the lowest h' that attains the minimum
+ *   dead (n,j): D[n,j,.] = +inf
+ * Backwards per (clip, joint): at the last frame of a chain (the clip's last frame, or (n+1,j) is dead) path[n,j] = the lowest h
+ * that minimises D[n,j,.]; inside a chain path[n,j] = back[n+1,j, path[n+1,j]].
+ * d_path_h [N,J] int32; d_cost [N,J] float64 = D[n,j, path[n,j]]; a dead (frame, joint) reports hypothesis 0 and cost +inf and
+ * splits only that joint's chain.  With d_T == NULL and J == 1 the outputs are the bits of zedo_temporal_select on the same
+ * unaries and x (the same statements on the same operands).
+ * (x and T are taken to be finite: a non-finite coordinate makes the affected minima unspecified, never an address.)
+ * Workspace (8-byte aligned, need not be initialised): D [N,J,H] float64, back [N,J,H] int32, two int32 flags per (frame,
+ * joint) - zedo_joint_temporal_workspace_bytes(N, H, J); 0 for sizes the call refuses.  There is no H x H table: a transition
+ * cost is one square root of three terms and is computed where the recurrence consumes it.
+ * Contract: J >= 1, N >= 1, 1 <= n_seq <= N, 1 <= H <= 1024 (one joint's X[n-1,.] and D[n-1,.] stay in the LDS), N*J*H <=
+ * INT_MAX, finite lambda >= 0; ZEDO_E_BADARG with nothing written for a NULL pointer other than d_T, a non-positive size,
+ * H > 1024, n_seq > N, N*J*H above INT_MAX, a negative or non-finite lambda, or a workspace that is not 8-byte aligned;
+ * ZEDO_E_WORKSPACE with nothing written if workspace_bytes is too small; allocates nothing, synchronises nothing, enqueues on
+ * `stream` only: legal under stream capture; no atomics: bit-identical from run to run.  One workgroup per (clip, joint): a
+ * single long clip is serial in time on J CUs. */
+size_t zedo_joint_temporal_workspace_bytes(int N, int H, int J);
+int zedo_joint_temporal_select(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
+                               int H, int N, int J, double lambda, void *d_workspace, size_t workspace_bytes,
+                               int *d_path_h, double *d_cost, void *stream);
 
 /* ---- pruning hypotheses DURING the loop, without ground truth: keep the K best of a pose, compact the rows ----------------
  * zedo_oil_run takes step_begin / step_end and a row's bits do not depend on the batch it is in, so a run can be cut into

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: twenty-six one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: twenty-seven one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -54,6 +54,9 @@ MUTANTS = [
     ("ZEDO_MUT_PR_P32", "zedo_prune_rank: tiles of 32 poses (256 < H <= 512) count the kept slots below a - 1 for the output position (zedo_prune.hip prune_rank_kernel)"),
     ("ZEDO_MUT_PG_TRIP", "zedo_prune_gather: the grid-stride loop over the rows stops after its first trip (zedo_prune.hip prune_gather_kernel)"),
     ("ZEDO_MUT_PMIN_LANE_H", "lane-per-pose arg-min (N >= 8192): reports h - h0, the hypothesis counted from the shard's first (zedo_metric.hip pose_min_kernel)"),
+    # the joint-wise temporal selection (tests/test_joint_temporal_gpu.py, tests/test_select_joints_temporal_driver_gpu.py): leaves every
+    # other test green
+    ("ZEDO_MUT_JT_NO_T", "zedo_joint_temporal_select: the motion term is taken on x alone although d_T was given (zedo_joint_temporal.hip joint_temporal_scan_kernel)"),
 ]
 
 

@@ -874,6 +874,26 @@ extern "C" int zedo_temporal_select(const double *d_unary, const float *d_x, con
     return ZEDO_OK;
 }
 
+// ---- joint-wise temporal selection: one chain per (clip, joint), no table of transition costs ----
+extern "C" size_t zedo_joint_temporal_workspace_bytes(int N, int H, int J) {
+    if (N < 1 || H < 1 || J < 1 || H > 1024 || (long long)N * J > INT_MAX || (long long)N * J * H > INT_MAX) return 0;
+    return joint_temporal_bytes(N, H, J);
+}
+
+extern "C" int zedo_joint_temporal_select(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
+                                          int H, int N, int J, double lambda, void *d_workspace, size_t workspace_bytes, int *d_path_h,
+                                          double *d_cost, void *stream) {
+    if (!d_junary || !d_x || !d_seq_start || !d_workspace || !d_path_h || !d_cost || H < 1 || N < 1 || J < 1 || n_seq < 1 || n_seq > N)
+        return ZEDO_E_BADARG;
+    if (H > 1024 || (long long)N * J > INT_MAX || (long long)N * J * H > INT_MAX) return ZEDO_E_BADARG;
+    if (!std::isfinite(lambda) || lambda < 0.0) return ZEDO_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(d_workspace) & 7) return ZEDO_E_BADARG;              // the tables are float64
+    if (workspace_bytes < joint_temporal_bytes(N, H, J)) return ZEDO_E_WORKSPACE;
+    HIPCHK(launch_joint_temporal_select(d_junary, d_x, d_T, d_seq_start, n_seq, H, N, J, lambda, d_workspace, d_path_h, d_cost,
+                                        (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
 // ---- hypothesis pruning between two stages of the loop: the table of kept slots, then the compaction of the rows ----
 extern "C" int zedo_prune_rank(const double *d_err, int H, int N, int K, int *d_keep, void *stream) {
     if (!d_err || !d_keep || N < 1 || K < 1 || K > H || H > 1024 || (long long)H * N > INT_MAX) return ZEDO_E_BADARG;

@@ -239,6 +239,10 @@ hipError_t launch_joint_compose(const float *x, const float *T, const int *joint
 size_t temporal_fixed_bytes(int N, int H);
 hipError_t launch_temporal_select(const double *unary, const float *x, const int *seq_start, int n_seq, int H, int N, int J, double lambda,
                                   void *ws, int chunk, int *path, double *cost, hipStream_t st);
+// joint-wise temporal selection (zedo_joint_temporal.hip); ws: joint_temporal_bytes(N, H, J) of tables, H <= 1024
+size_t joint_temporal_bytes(int N, int H, int J);
+hipError_t launch_joint_temporal_select(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,
+                                        int J, double lambda, void *ws, int *path, double *cost, hipStream_t st);
 // hypothesis pruning between two stages of the loop (zedo_prune.hip): keep [K,N], the kept slots of every pose in ascending order
 hipError_t launch_prune_rank(const double *err, int H, int N, int K, int *keep, hipStream_t st);
 hipError_t launch_prune_gather(const int *keep, int H, int K, int N, int J, const float *x, const float *T, const int *hyp, float *x_out,

@@ -72,6 +72,8 @@ SIGNATURES = {
     "zedo_joint_compose": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "zedo_temporal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_temporal_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _sz, _vp, _vp, _vp]),
+    "zedo_joint_temporal_workspace_bytes": (_sz, [_i, _i, _i]),
+    "zedo_joint_temporal_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _sz, _vp, _vp, _vp]),
     "zedo_prune_rank": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "zedo_prune_gather": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_pose_min": (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp]),
@@ -577,6 +579,43 @@ def temporal_select(unary, x_full, seq_start, N=None, lam=100.0, chunk_frames=0)
         cost = torch.empty((N,), dtype=torch.float64, device=dev)
         _check(_lib.zedo_temporal_select(_p(unary, torch.float64), _p(x_full), _p(seq, torch.int32), seq.numel() - 1, H, N, J, float(lam),
                                          _p(ws, torch.uint8), nbytes, _p(path, torch.int32), _p(cost, torch.float64), _stream(dev)))
+    return path, cost
+
+
+def joint_temporal_select(junary, x_full, T_full, seq_start, N=None, lam=100.0):
+    """Joint-wise selection along a video without ground truth (zedo_joint_temporal_select): junary [H*N,J] f64 (ALL rows, h-major: e.g.
+    jerr of joint_reproj(return_rows=True), pixels), x_full [H*N,J,3] f32, T_full [H*N,3] f32 or None (the motion term on x alone),
+    seq_start [n_seq+1] (a sequence or an int tensor: strictly ascending from 0 to N) -> (path [N,J] i32, cost [N,J] f64): per (clip,
+    joint) the hypothesis sequence that minimises the sum of that joint's unaries plus lam times that joint's displacement in the camera
+    frame (x + T) between consecutive choices (Viterbi, fp64, one chain per joint).  lam is in cost units per metre; the default of 100 is
+    untuned.  At most 1024 hypotheses.  Whether the joint-wise temporal paths are closer to ground truth than the per-frame joint-wise
+    arg-min is not measured."""
+    _need_gpu()
+    dev = _device_of(junary, x_full, T_full, seq_start if isinstance(seq_start, torch.Tensor) and seq_start.is_cuda else None)
+    rows, J = x_full.shape[0], x_full.shape[1]
+    if isinstance(seq_start, torch.Tensor):
+        if seq_start.dtype not in (torch.int32, torch.int64) or seq_start.dim() != 1:
+            raise ValueError(f"joint_temporal_select: seq_start must be a 1-D int tensor, got {seq_start.dtype} {tuple(seq_start.shape)}")
+        seq = seq_start.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        seq = torch.tensor([int(v) for v in seq_start], dtype=torch.int32, device=dev)
+    if N is None:
+        N = int(seq[-1].item()) if seq.numel() else 0
+    N = int(N)
+    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J) or seq.numel() < 2
+            or (T_full is not None and tuple(T_full.shape) != (rows, 3))):
+        raise ValueError(f"joint_temporal_select: junary [H*N,J], x [H*N,J,3], T [H*N,3], seq_start [n_seq+1] expected, got "
+                         f"{tuple(junary.shape)}, {tuple(x_full.shape)}, {None if T_full is None else tuple(T_full.shape)}, {tuple(seq.shape)} "
+                         f"with N = {N}")
+    H = rows // N
+    with torch.cuda.device(dev):
+        nbytes = int(_lib.zedo_joint_temporal_workspace_bytes(N, H, J))
+        ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+        path = torch.empty((N, J), dtype=torch.int32, device=dev)
+        cost = torch.empty((N, J), dtype=torch.float64, device=dev)
+        _check(_lib.zedo_joint_temporal_select(_p(junary, torch.float64), _p(x_full), _p(T_full), _p(seq, torch.int32), seq.numel() - 1, H, N,
+                                               J, float(lam), _p(ws, torch.uint8), nbytes, _p(path, torch.int32), _p(cost, torch.float64),
+                                               _stream(dev)))
     return path, cost
 
 

@@ -8,7 +8,8 @@ batched as rows (h, n) and every stage running in libzedo_hip.so.
     selection    = per-pose min over hypotheses of (PA-)MPJPE     (eval_multi)
                    or, without ground truth, of the confidence-weighted reprojection error of x + T (select_reproj),
                    or per JOINT of the joint's reprojection distance, the pose assembled from the winners (aggregate_reproj, compose),
-                   or along the clips of a video: reprojection error plus a motion cost, by Viterbi (select_temporal)
+                   or along the clips of a video: reprojection error plus a motion cost, by Viterbi (select_temporal),
+                   or both: per joint along the clips, one Viterbi chain per joint (select_joints_temporal, compose)
     pruning      = opt-in, DURING the loop: at the steps of a plan keep, per pose, the K hypotheses with the smallest reprojection
                    error and carry on with K x N rows (parse_prune_plan, run_pruned)
 
@@ -20,8 +21,8 @@ import os
 import numpy as np
 import torch
 
-from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_compose, joint_reproj, min_mpjpe_both, min_reproj, oil_run,
-               prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
+from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_compose, joint_reproj, joint_temporal_select, min_mpjpe_both,
+               min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
 def linspace_f32(start, end, steps):
@@ -218,6 +219,19 @@ class Pipeline:
             err, _, _ = min_reproj(x, T, self.uv, self.K, self.conf, self.N, 0)
             path, cost = temporal_select(err, x, seq_start, self.N, lam)
         return path, cost, err
+
+    def select_joints_temporal(self, x, T, seq_start, lam=100.0):
+        """Joint-wise selection along a video without ground truth on the problem of load(): x [H*N,17,3] and T [H*N,3], ALL rows,
+        seq_start = the first frame of every clip and N -> (joint_path [N,17] i32, joint_cost [N,17] f64, jerr [H*N,17] f64): the unaries
+        are zedo_joint_reproj's per-(row, joint) distances (pixels), each joint's path minimises them plus lam (pixels per metre, default
+        untuned) times that joint's displacement in the camera frame between consecutive choices (zedo_joint_temporal_select).
+        compose(x, T, joint_path, ref) assembles the pose."""
+        if x.shape[0] != self.H * self.N:
+            raise ValueError(f"select_joints_temporal: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        with torch.cuda.device(self.device):
+            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
+            path, cost = joint_temporal_select(jerr, x, T, seq_start, self.N, lam)
+        return path, cost, jerr
 
     def take(self, rows_full, idx):
         """The winning row of every pose: rows_full [H*N, ...] (all global rows, h-major), idx [N] -> rows_full.view(H, N, ...)[idx, arange(N)].
