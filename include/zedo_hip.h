@@ -46,7 +46,8 @@ extern "C" {
                               * still 5 (additive): + zedo_joint_reproj, zedo_joint_compose;
                               * still 5 (additive): + zedo_temporal_workspace_bytes, zedo_temporal_select;
                               * still 5 (additive): + zedo_prune_rank, zedo_prune_gather;
-                              * still 5 (additive): + zedo_joint_temporal_workspace_bytes, zedo_joint_temporal_select */
+                              * still 5 (additive): + zedo_joint_temporal_workspace_bytes, zedo_joint_temporal_select;
+                              * still 5 (additive): + zedo_joint_marginal_workspace_bytes, zedo_joint_marginal */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -406,6 +407,49 @@ size_t zedo_joint_temporal_workspace_bytes(int N, int H, int J);
 int zedo_joint_temporal_select(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
                                int H, int N, int J, double lambda, void *d_workspace, size_t workspace_bytes,
                                int *d_path_h, double *d_cost, void *stream);
+
+/* ---- fusing hypotheses along a video WITHOUT ground truth: per-joint posterior mean and spread ------------------------------
+ * zedo_joint_temporal_select answers with one hypothesis per (frame, joint) and says nothing of the others.  This is the
+ * sum-product twin of its max-product recurrence: the same energy read as a probability at a temperature tau,
+ *   p(path of joint j over a chain) proportional to exp(-(sum_n u[n,j,h_n] + lambda sum_n m[n,j,h_{n-1},h_n]) / tau),
+ * and from it, exactly (forward-backward in the log domain), the posterior marginal of every hypothesis of every (frame,
+ * joint), the posterior mean position, its covariance - the spread of the hypotheses in metres, weighted by what the model
+ * believes - and the most probable hypothesis with its probability.  Whether the fused pose is closer to ground truth than a
+ * selected one on real video is not measured.
+ * Inputs: exactly those of zedo_joint_temporal_select - d_junary [H*N,J] float64 rows (h,n) ALL rows, d_x [H*N,J,3] and d_T
+ * [H*N,3] fp32 (d_T may be NULL), d_seq_start [n_seq+1] int32 ON THE DEVICE, every entry clamped to 0 .. N before use and
+ * never an address - and tau > 0, the temperature in cost units (pixels on zedo_joint_reproj's distances).
+ * All arithmetic in float64.  X, u, m, DEAD and "chain start" are those of zedo_joint_temporal_select, word for word: a
+ * non-finite unary excludes that hypothesis for that joint; a (frame, joint) with no finite unary is dead and splits only that
+ * joint's chain.  With l[n,j,h] = -u[n,j,h] / tau (-inf when excluded), c = lambda / tau, LSE the log of a sum of exponentials:
+ *   forward   chain start:  A[n,j,h] = l[n,j,h]
+ *             otherwise:    A[n,j,h] = l[n,j,h] + LSE_h' (A[n-1,j,h'] - c m[n,j,h',h])
+ *   backward  chain end (the clip's last frame, or (n+1,j) dead):  B[n,j,h] = 0  and  logZ = LSE_h A[n,j,h]
+ *             otherwise:    B[n,j,h] = LSE_h' (l[n+1,j,h'] + B[n+1,j,h'] - c m[n+1,j,h,h'])
+ *   marginal  w[n,j,h] = exp(A[n,j,h] + B[n,j,h] - logZ);  an excluded hypothesis has w = 0 exactly
+ * Every LSE is evaluated shifted by the TRUE maximum of its terms (two walks over the terms; where the h' are split over parts
+ * of a workgroup, each part shifts by its own maximum and the parts are combined shifted by the largest): safe for any finite
+ * c m, and at a small tau the largest term contributes exactly 1.  (lambda / tau and u / tau are taken to be finite.)
+ * Outputs (all required but d_w):
+ *   d_mean [N,J,3]  sum_h w X, camera frame (metres)
+ *   d_cov  [N,J,6]  sum_h w (X - mean)(X - mean)^T in the order xx, xy, xz, yy, yz, zz (m^2), from the centred differences
+ *   d_hmax [N,J] int32  the lowest h with the largest marginal;  d_wmax [N,J]  that marginal
+ *   d_logz [N,J]    the chain's log-partition value logZ, repeated on every frame of the chain
+ *   d_w    [N,J,H]  optional (NULL: not written): the marginals
+ * A dead (frame, joint) reports NaN in mean and cov, hypothesis 0, wmax = 0, logz = -inf and a row of zeros in d_w.
+ * Workspace (8-byte aligned, need not be initialised): A [N,J,H] float64 and one int32 flag per (frame, joint) -
+ * zedo_joint_marginal_workspace_bytes(N, H, J); 0 for sizes the call refuses.  B never leaves the LDS.
+ * Contract: that of zedo_joint_temporal_select - J >= 1, N >= 1, 1 <= n_seq <= N, 1 <= H <= 1024, N*J*H <= INT_MAX, finite
+ * lambda >= 0 - and finite tau > 0; ZEDO_E_BADARG with nothing written for a NULL pointer other than d_T and d_w, a
+ * non-positive size, H > 1024, n_seq > N, N*J*H above INT_MAX, a negative or non-finite lambda, tau <= 0 or not finite, or a
+ * workspace that is not 8-byte aligned; ZEDO_E_WORKSPACE with nothing written if workspace_bytes is too small; allocates
+ * nothing, synchronises nothing, enqueues on `stream` only: legal under stream capture; no atomics, every sum in a fixed
+ * order: bit-identical from run to run, for any alignment of d_x and any workspace content, with and without d_w.  One
+ * workgroup per (clip, joint), twice: a single long clip is serial in time on J CUs. */
+size_t zedo_joint_marginal_workspace_bytes(int N, int H, int J);
+int zedo_joint_marginal(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
+                        int H, int N, int J, double lambda, double tau, void *d_workspace, size_t workspace_bytes,
+                        double *d_mean, double *d_cov, int *d_hmax, double *d_wmax, double *d_logz, double *d_w, void *stream);
 
 /* ---- pruning hypotheses DURING the loop, without ground truth: keep the K best of a pose, compact the rows ----------------
  * zedo_oil_run takes step_begin / step_end and a row's bits do not depend on the batch it is in, so a run can be cut into

@@ -894,6 +894,28 @@ extern "C" int zedo_joint_temporal_select(const double *d_junary, const float *d
     return ZEDO_OK;
 }
 
+// ---- posterior marginals of the joint-wise chain model: forward-backward per (clip, joint), A in the workspace ----
+extern "C" size_t zedo_joint_marginal_workspace_bytes(int N, int H, int J) {
+    if (N < 1 || H < 1 || J < 1 || H > 1024 || (long long)N * J > INT_MAX || (long long)N * J * H > INT_MAX) return 0;
+    return joint_marginal_bytes(N, H, J);
+}
+
+extern "C" int zedo_joint_marginal(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq, int H,
+                                   int N, int J, double lambda, double tau, void *d_workspace, size_t workspace_bytes, double *d_mean,
+                                   double *d_cov, int *d_hmax, double *d_wmax, double *d_logz, double *d_w, void *stream) {
+    if (!d_junary || !d_x || !d_seq_start || !d_workspace || !d_mean || !d_cov || !d_hmax || !d_wmax || !d_logz || H < 1 || N < 1 ||
+        J < 1 || n_seq < 1 || n_seq > N)
+        return ZEDO_E_BADARG;
+    if (H > 1024 || (long long)N * J > INT_MAX || (long long)N * J * H > INT_MAX) return ZEDO_E_BADARG;
+    if (!std::isfinite(lambda) || lambda < 0.0) return ZEDO_E_BADARG;
+    if (!std::isfinite(tau) || !(tau > 0.0)) return ZEDO_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(d_workspace) & 7) return ZEDO_E_BADARG;              // A is float64
+    if (workspace_bytes < joint_marginal_bytes(N, H, J)) return ZEDO_E_WORKSPACE;
+    HIPCHK(launch_joint_marginal(d_junary, d_x, d_T, d_seq_start, n_seq, H, N, J, lambda / tau, tau, d_workspace, d_mean, d_cov, d_hmax,
+                                 d_wmax, d_logz, d_w, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
 // ---- hypothesis pruning between two stages of the loop: the table of kept slots, then the compaction of the rows ----
 extern "C" int zedo_prune_rank(const double *d_err, int H, int N, int K, int *d_keep, void *stream) {
     if (!d_err || !d_keep || N < 1 || K < 1 || K > H || H > 1024 || (long long)H * N > INT_MAX) return ZEDO_E_BADARG;

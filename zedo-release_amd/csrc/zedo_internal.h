@@ -243,6 +243,12 @@ hipError_t launch_temporal_select(const double *unary, const float *x, const int
 size_t joint_temporal_bytes(int N, int H, int J);
 hipError_t launch_joint_temporal_select(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,
                                         int J, double lambda, void *ws, int *path, double *cost, hipStream_t st);
+hipError_t launch_joint_temporal_dead(const double *junary, int H, int NJ, int *dead, hipStream_t st);
+// posterior marginals of the same chain model (zedo_joint_marginal.hip); ws: joint_marginal_bytes(N, H, J), H <= 1024; c = lambda / tau
+size_t joint_marginal_bytes(int N, int H, int J);
+hipError_t launch_joint_marginal(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N, int J,
+                                 double c, double tau, void *ws, double *mean, double *cov, int *hmax, double *wmax, double *logz, double *w,
+                                 hipStream_t st);
 // hypothesis pruning between two stages of the loop (zedo_prune.hip): keep [K,N], the kept slots of every pose in ascending order
 hipError_t launch_prune_rank(const double *err, int H, int N, int K, int *keep, hipStream_t st);
 hipError_t launch_prune_gather(const int *keep, int H, int K, int N, int J, const float *x, const float *T, const int *hyp, float *x_out,

@@ -213,6 +213,12 @@ size_t joint_temporal_bytes(int N, int H, int J) {
     return njh * 8 + (((njh + 2 * nj) * 4 + 7) & ~(size_t)7);
 }
 
+// the dead flags on their own, for the other chain model on the same unaries (zedo_joint_marginal.hip)
+hipError_t launch_joint_temporal_dead(const double *junary, int H, int NJ, int *dead, hipStream_t st) {
+    hipLaunchKernelGGL(joint_temporal_dead_kernel, dim3((unsigned)(((size_t)NJ + 255) / 256)), dim3(256), 0, st, junary, H, NJ, dead);
+    return hipGetLastError();
+}
+
 hipError_t launch_joint_temporal_select(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,
                                         int J, double lambda, void *ws, int *path, double *cost, hipStream_t st) {
     const size_t nj = (size_t)N * J, njh = nj * H;

@@ -29,20 +29,27 @@ def build_parser(description, inference=False):
     p.add_argument("--math", choices=("f32", "f16x3"), default=None,
                    help="arithmetic of the dense layers: f32 = exact fp32 MFMA (default), f16x3 = split-fp16 operands on the fp16 "
                         "matrix pipe at fp32-level accuracy, ~2x faster (same as the ZEDO_MATH environment variable)")
-    p.add_argument("--select", choices=("none", "reproj", "joints", "temporal", "joints-temporal"), default="none",
+    p.add_argument("--select", choices=("none", "reproj", "joints", "temporal", "joints-temporal", "joints-fused"), default="none",
                    help="run.inference only: reproj = also keep, per pose, the hypothesis whose x + T reprojects closest to the 2D "
                         "detections (confidence-weighted, no ground truth needed) -> <out>_selected.npz; joints = keep, per JOINT, the "
                         "hypothesis whose joint reprojects closest to its detection and assemble the pose from those joints; temporal = "
                         "the frames are a video: per clip the hypothesis sequence that minimises reprojection error plus --smooth times "
                         "the mean joint displacement between consecutive frames (Viterbi); joints-temporal = both: per clip and per JOINT the "
                         "hypothesis sequence that minimises that joint's reprojection distance plus --smooth times that joint's displacement "
-                        "in the camera frame (one Viterbi chain per joint), the pose assembled from those joints")
+                        "in the camera frame (one Viterbi chain per joint), the pose assembled from those joints; joints-fused = the soft "
+                        "answer of the same chain model at --temperature: per joint the posterior mean position over the hypotheses, its "
+                        "covariance (the depth ambiguity in metres) and the most probable hypothesis with its probability")
     p.add_argument("--smooth", type=float, default=None, metavar="LAMBDA",
                    help="--select temporal: weight of the motion cost in pixels per metre (default 100: a mean joint jump of 1 cm costs as "
                         "much as 1 px of reprojection error; the default is UNTUNED - its effect on accuracy has not been measured); "
-                        "--select joints-temporal: the same, in pixels per metre of that joint's displacement (default 100, UNTUNED as well)")
+                        "--select joints-temporal: the same, in pixels per metre of that joint's displacement (default 100, UNTUNED as well); "
+                        "--select joints-fused: as for joints-temporal")
+    p.add_argument("--temperature", type=float, default=None, metavar="TAU",
+                   help="--select joints-fused only: the temperature of the chain model in pixels - a path that costs TAU more is e times less "
+                        "probable (default 1.0, UNTUNED: its effect on accuracy has not been measured); towards 0 the fused pose becomes the "
+                        "pose of --select joints-temporal")
     p.add_argument("--seq_len", type=int, default=None, metavar="L",
-                   help="--select temporal / joints-temporal: cut the frames into consecutive clips of L (the last one shorter); overrides the dataset's "
+                   help="--select temporal / joints-temporal / joints-fused: cut the frames into consecutive clips of L (the last one shorter); overrides the dataset's "
                         "seq_start; with --synthetic the only source of clips (default: the dataset's clips, else one clip)")
     p.add_argument("--prune", type=str, default=None, metavar="PLAN",
                    help="opt-in: prune hypotheses DURING the loop. PLAN = STEP:KEEP[,STEP:KEEP...], e.g. 100:10 or 0:25,200:5: before OIL "
@@ -57,10 +64,19 @@ def build_parser(description, inference=False):
 
 
 def check_select_args(args):
-    """--smooth / --seq_len belong to --select temporal and --select joints-temporal; --smooth defaults to 100 there."""
+    """--smooth / --seq_len belong to --select temporal, joints-temporal and joints-fused; --smooth defaults to 100 there.  --temperature
+    belongs to --select joints-fused and defaults to 1 there."""
     select = getattr(args, "select", "none") or "none"
     smooth, seq_len = getattr(args, "smooth", None), getattr(args, "seq_len", None)
-    if select not in ("temporal", "joints-temporal"):
+    temperature = getattr(args, "temperature", None)
+    if select != "joints-fused":
+        if temperature is not None:
+            raise SystemExit("--temperature is a switch of --select joints-fused")
+    elif temperature is None:
+        args.temperature = 1.0
+    elif not (np.isfinite(temperature) and temperature > 0):
+        raise SystemExit(f"--temperature {temperature}: a finite temperature > 0 expected")
+    if select not in ("temporal", "joints-temporal", "joints-fused"):
         if smooth is not None or seq_len is not None:
             raise SystemExit("--smooth and --seq_len are switches of --select temporal and --select joints-temporal")
         return
@@ -220,7 +236,7 @@ def pruned_path(out):
 
 
 def selected_path(out):
-    """<out without .npy>_selected.npz: where run.inference --select reproj / joints / temporal / joints-temporal writes the pose it keeps per detection."""
+    """<out without .npy>_selected.npz: where run.inference --select reproj / joints / temporal / joints-temporal / joints-fused writes the pose it keeps per detection."""
     return (out[:-4] if out.endswith(".npy") else out) + "_selected.npz"
 
 
@@ -238,7 +254,7 @@ def run(args, inference=False):
                          "truth (best of H), and the ground-truth evaluation of a selected pose is printed by run.inference --eval")
     check_select_args(args)
     prune = getattr(args, "prune", None)
-    if prune is not None and select in ("joints", "temporal", "joints-temporal"):
+    if prune is not None and select in ("joints", "temporal", "joints-temporal", "joints-fused"):
         raise SystemExit(f"--prune with --select {select} is not supported yet (a follow-up): the pruned run keeps different hypotheses "
                          "per pose; use --select reproj or none")
     if prune is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -407,11 +423,11 @@ def run(args, inference=False):
                         T=take_rows(full_T, path, H, N).cpu().numpy(), seq_start=seq.astype(np.int32), smooth=np.float64(args.smooth))
         if rank == 0:
             np.savez(selected_path(args.out), **selected)
-    if inference and select == "joints-temporal":
-        # the frames are a video and the pose is assembled joint by joint: each rank evaluates zedo_joint_reproj (the route that writes every
-        # row's per-joint distances) and zedo_min_reproj on its own rows; the distances, the errors and T are gathered like the rows; every
-        # rank runs the pose-level Viterbi (zedo_temporal_select: the frame the pose is written in is itself consistent along the clip) and
-        # the J joint-wise ones (zedo_joint_temporal_select) on the full arrays and ends with the same arrays, rank 0 writes them
+
+    def video_joint_inputs():
+        # what --select joints-temporal and joints-fused share: the clips; each rank evaluates zedo_joint_reproj (the route that writes every
+        # row's per-joint distances) and zedo_min_reproj on its own rows; the distances, the errors and T are gathered like the rows, so that
+        # every rank holds the full arrays.  -> (seq, uvd, Kd, cfd, full_err, full_jerr, full_T, full rows, what --select joints keeps)
         import zedo_hip
         if args.seq_len is not None:
             seq = np.array(list(range(0, N, args.seq_len)) + [N], np.int32)
@@ -434,7 +450,15 @@ def run(args, inference=False):
         full_err = gather_row_shards(err, H * N, lo=glo).contiguous()
         full_jerr = gather_row_shards(jerr, H * N, lo=glo).contiguous()
         full_T = gather_row_shards(T.contiguous(), H * N, lo=glo).contiguous()
-        full = full.contiguous()
+        return seq, uvd, Kd, cfd, full_err, full_jerr, full_T, full.contiguous(), jidx0
+
+    if inference and select == "joints-temporal":
+        # the frames are a video and the pose is assembled joint by joint: each rank evaluates zedo_joint_reproj (the route that writes every
+        # row's per-joint distances) and zedo_min_reproj on its own rows; the distances, the errors and T are gathered like the rows; every
+        # rank runs the pose-level Viterbi (zedo_temporal_select: the frame the pose is written in is itself consistent along the clip) and
+        # the J joint-wise ones (zedo_joint_temporal_select) on the full arrays and ends with the same arrays, rank 0 writes them
+        import zedo_hip
+        seq, uvd, Kd, cfd, full_err, full_jerr, full_T, full, jidx0 = video_joint_inputs()
         idx, _ = zedo_hip.temporal_select(full_err, full, seq, N, args.smooth)
         jpath, jcost = zedo_hip.joint_temporal_select(full_jerr, full, full_T, seq, N, args.smooth)
         pose = zedo_hip.joint_compose(full, full_T, jpath.contiguous(), idx.contiguous(), N)
@@ -446,6 +470,25 @@ def run(args, inference=False):
                         joint_path_cost=jcost.cpu().numpy(), hypothesis=idx.cpu().numpy().astype(np.int32), T=T_sel.cpu().numpy(),
                         reproj_px=px.cpu().numpy(), reproj_px_pose_level=take_rows(full_err, idx, H, N).cpu().numpy(),
                         seq_start=seq.astype(np.int32), smooth=np.float64(args.smooth))
+        if rank == 0:
+            np.savez(selected_path(args.out), **selected)
+    if inference and select == "joints-fused":
+        # the soft answer of the chain model of joints-temporal: the same unaries, errors and T gathered the same way; every rank runs the
+        # pose-level Viterbi (the frame the pose is written in), the J forward-backward passes (zedo_joint_marginal) and, for comparison,
+        # the J joint-wise Viterbi chains on the full arrays and ends with the same arrays, rank 0 writes them
+        import zedo_hip
+        seq, uvd, Kd, cfd, full_err, full_jerr, full_T, full, _ = video_joint_inputs()
+        idx, _ = zedo_hip.temporal_select(full_err, full, seq, N, args.smooth)
+        mean, cov, hmax, wmax, logz = zedo_hip.joint_marginal(full_jerr, full, full_T, seq, N, args.smooth, args.temperature)
+        jpath, _ = zedo_hip.joint_temporal_select(full_jerr, full, full_T, seq, N, args.smooth)
+        T_sel = take_rows(full_T, idx, H, N).contiguous()
+        pose = (mean - T_sel.to(torch.float64)[:, None, :]).to(torch.float32)     # in the frame --select joints-temporal writes in
+        spread = (cov[:, :, 0] + cov[:, :, 3] + cov[:, :, 5]).sqrt()
+        selected = dict(pose=pose.cpu().numpy(), joint_cov=cov.cpu().numpy(), joint_spread_m=spread.cpu().numpy(),
+                        joint_hypothesis=hmax.cpu().numpy().astype(np.int32), joint_weight=wmax.cpu().numpy(), joint_logz=logz.cpu().numpy(),
+                        joint_hypothesis_viterbi=jpath.cpu().numpy().astype(np.int32), hypothesis=idx.cpu().numpy().astype(np.int32),
+                        T=T_sel.cpu().numpy(), reproj_px_pose_level=take_rows(full_err, idx, H, N).cpu().numpy(),
+                        seq_start=seq.astype(np.int32), smooth=np.float64(args.smooth), temperature=np.float64(args.temperature))
         if rank == 0:
             np.savez(selected_path(args.out), **selected)
     errs = None
@@ -469,7 +512,7 @@ def run(args, inference=False):
                 s1 = test_dataset.eval_multi(("rows", sel_rows), protocol2=False, print_verbose=False, row_offset=0)
                 s2 = test_dataset.eval_multi(("rows", sel_rows), protocol2=True, print_verbose=False, row_offset=0)
             if rank == 0:
-                label = {"joints": "joints-aggregated", "temporal": "temporal-selected", "joints-temporal": "joints-temporal"}.get(select, "reproj-selected")
+                label = {"joints": "joints-aggregated", "temporal": "temporal-selected", "joints-temporal": "joints-temporal", "joints-fused": "joints-fused"}.get(select, "reproj-selected")
                 print(f"{label} MPJPE : {s1}")
                 print(f"{label} PA-MPJPE : {s2}")
             errs = (p1, p2, s1, s2)

@@ -74,6 +74,8 @@ SIGNATURES = {
     "zedo_temporal_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _sz, _vp, _vp, _vp]),
     "zedo_joint_temporal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_temporal_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _sz, _vp, _vp, _vp]),
+    "zedo_joint_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
+    "zedo_joint_marginal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_prune_rank": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "zedo_prune_gather": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_pose_min": (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp]),
@@ -617,6 +619,48 @@ def joint_temporal_select(junary, x_full, T_full, seq_start, N=None, lam=100.0):
                                                J, float(lam), _p(ws, torch.uint8), nbytes, _p(path, torch.int32), _p(cost, torch.float64),
                                                _stream(dev)))
     return path, cost
+
+
+def joint_marginal(junary, x_full, T_full, seq_start, N=None, lam=100.0, tau=1.0, return_weights=False):
+    """Fusing hypotheses along a video without ground truth (zedo_joint_marginal): the inputs of joint_temporal_select and a temperature
+    tau > 0 in cost units -> (mean [N,J,3] f64, cov [N,J,6] f64, hmax [N,J] i32, wmax [N,J] f64, logz [N,J] f64[, w [N,J,H] f64]): per
+    (clip, joint) the posterior marginals w of the hypotheses under p(path) ~ exp(-(unaries + lam * displacements) / tau), the chain
+    model joint_temporal_select optimises (forward-backward, fp64), and from them the posterior mean position in the camera frame, its
+    covariance (xx, xy, xz, yy, yz, zz; m^2), the most probable hypothesis, its probability and the chain's log-partition value.  A dead
+    (frame, joint) reports NaN, 0, 0 and -inf.  lam = 100 and tau = 1 are untuned.  At most 1024 hypotheses.  Whether the fused pose is
+    closer to ground truth than a selected one is not measured."""
+    _need_gpu()
+    dev = _device_of(junary, x_full, T_full, seq_start if isinstance(seq_start, torch.Tensor) and seq_start.is_cuda else None)
+    rows, J = x_full.shape[0], x_full.shape[1]
+    if isinstance(seq_start, torch.Tensor):
+        if seq_start.dtype not in (torch.int32, torch.int64) or seq_start.dim() != 1:
+            raise ValueError(f"joint_marginal: seq_start must be a 1-D int tensor, got {seq_start.dtype} {tuple(seq_start.shape)}")
+        seq = seq_start.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        seq = torch.tensor([int(v) for v in seq_start], dtype=torch.int32, device=dev)
+    if N is None:
+        N = int(seq[-1].item()) if seq.numel() else 0
+    N = int(N)
+    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J) or seq.numel() < 2
+            or (T_full is not None and tuple(T_full.shape) != (rows, 3))):
+        raise ValueError(f"joint_marginal: junary [H*N,J], x [H*N,J,3], T [H*N,3], seq_start [n_seq+1] expected, got "
+                         f"{tuple(junary.shape)}, {tuple(x_full.shape)}, {None if T_full is None else tuple(T_full.shape)}, {tuple(seq.shape)} "
+                         f"with N = {N}")
+    H = rows // N
+    with torch.cuda.device(dev):
+        nbytes = int(_lib.zedo_joint_marginal_workspace_bytes(N, H, J))
+        ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+        mean = torch.empty((N, J, 3), dtype=torch.float64, device=dev)
+        cov = torch.empty((N, J, 6), dtype=torch.float64, device=dev)
+        hmax = torch.empty((N, J), dtype=torch.int32, device=dev)
+        wmax = torch.empty((N, J), dtype=torch.float64, device=dev)
+        logz = torch.empty((N, J), dtype=torch.float64, device=dev)
+        w = torch.empty((N, J, H), dtype=torch.float64, device=dev) if return_weights else None
+        _check(_lib.zedo_joint_marginal(_p(junary, torch.float64), _p(x_full), _p(T_full), _p(seq, torch.int32), seq.numel() - 1, H, N, J,
+                                        float(lam), float(tau), _p(ws, torch.uint8), nbytes, _p(mean, torch.float64),
+                                        _p(cov, torch.float64), _p(hmax, torch.int32), _p(wmax, torch.float64), _p(logz, torch.float64),
+                                        _p(w, torch.float64), _stream(dev)))
+    return (mean, cov, hmax, wmax, logz, w) if return_weights else (mean, cov, hmax, wmax, logz)
 
 
 def prune_rank(err, N, K):

@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_compose, joint_reproj, joint_temporal_select, min_mpjpe_both,
+from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_compose, joint_marginal, joint_reproj, joint_temporal_select, min_mpjpe_both,
                min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
@@ -232,6 +232,19 @@ class Pipeline:
             _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
             path, cost = joint_temporal_select(jerr, x, T, seq_start, self.N, lam)
         return path, cost, jerr
+
+    def fuse_joints_temporal(self, x, T, seq_start, lam=100.0, tau=1.0):
+        """Joint-wise fusion along a video without ground truth on the problem of load(): x [H*N,17,3] and T [H*N,3], ALL rows, seq_start =
+        the first frame of every clip and N -> (mean [N,17,3] f64, cov [N,17,6] f64, hmax [N,17] i32, wmax [N,17] f64, logz [N,17] f64,
+        jerr [H*N,17] f64): the unaries are zedo_joint_reproj's per-(row, joint) distances (pixels); the posterior mean position of every
+        joint in the camera frame, its covariance, the most probable hypothesis and its probability under the chain model
+        select_joints_temporal optimises, at the temperature tau in pixels (zedo_joint_marginal; lam and tau untuned)."""
+        if x.shape[0] != self.H * self.N:
+            raise ValueError(f"fuse_joints_temporal: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        with torch.cuda.device(self.device):
+            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
+            out = joint_marginal(jerr, x, T, seq_start, self.N, lam, tau)
+        return out + (jerr,)
 
     def take(self, rows_full, idx):
         """The winning row of every pose: rows_full [H*N, ...] (all global rows, h-major), idx [N] -> rows_full.view(H, N, ...)[idx, arange(N)].
