@@ -47,7 +47,8 @@ extern "C" {
                               * still 5 (additive): + zedo_temporal_workspace_bytes, zedo_temporal_select;
                               * still 5 (additive): + zedo_prune_rank, zedo_prune_gather;
                               * still 5 (additive): + zedo_joint_temporal_workspace_bytes, zedo_joint_temporal_select;
-                              * still 5 (additive): + zedo_joint_marginal_workspace_bytes, zedo_joint_marginal */
+                              * still 5 (additive): + zedo_joint_marginal_workspace_bytes, zedo_joint_marginal;
+                              * still 5 (additive): + zedo_joint_accel_workspace_bytes, zedo_joint_accel_select */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -450,6 +451,47 @@ size_t zedo_joint_marginal_workspace_bytes(int N, int H, int J);
 int zedo_joint_marginal(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
                         int H, int N, int J, double lambda, double tau, void *d_workspace, size_t workspace_bytes,
                         double *d_mean, double *d_cov, int *d_hmax, double *d_wmax, double *d_logz, double *d_w, void *stream);
+
+/* ---- joint-wise selection along a video WITHOUT ground truth: a second-order motion model ----------------------------------
+ * zedo_joint_temporal_select charges lambda times the DISPLACEMENT of a joint between consecutive choices: a zero-velocity
+ * prior.  Real motion is common to all hypotheses and enters under the square root, so the faster a limb moves the cheaper a
+ * switch between hypotheses becomes.  This call adds lambda_a times the SECOND DIFFERENCE X[n] - 2 X[n-1] + X[n-2], which is
+ * blind to a constant velocity.  The state of a chain is then a PAIR of hypotheses: H^2 states and H^3 transitions per
+ * (frame, joint).  Whether this lowers the error against ground truth on real video is not measured.
+ * Inputs: exactly those of zedo_joint_temporal_select - d_junary [H*N,J] float64 rows (h,n) ALL rows, d_x [H*N,J,3] and d_T
+ * [H*N,3] fp32 (d_T may be NULL), d_seq_start [n_seq+1] int32 ON THE DEVICE, every entry clamped to 0 .. N before use and
+ * never an address - and two weights in cost units per metre: lambda_v on the displacement, lambda_a on the second difference.
+ * All arithmetic in float64, independent for every joint j.  X, u, m and DEAD are those of zedo_joint_temporal_select, word
+ * for word; a CHAIN is a maximal run c0 .. c1-1 of frames of one clip at which (n,j) is not dead.
+ *   a[n,j,h'',h',h] = sqrt(e0^2 + e1^2 + e2^2),  e_c = (X[n,h,j,c] - 2 X[n-1,h',j,c]) + X[n-2,h'',j,c]
+ *                     (the product by 2, the difference, the sum; then the squares and their sum ascending in c)
+ *   c1 - c0 == 1:  path[c0] = the lowest h that minimises u[c0,j,.]
+ *   n == c0+1:     E[n][h',h] = u[n-1,j,h'] + (u[n,j,h] + lambda_v m[n,j,h',h])
+ *   n >= c0+2:     E[n][h',h] = u[n,j,h] + (lambda_v m[n,j,h',h] + min_h'' (E[n-1][h'',h'] + lambda_a a[n,j,h'',h',h])),
+ *                  back2[n][h',h] = the lowest h'' that attains the minimum (strict comparison, h'' ascending)
+ *   end of chain:  (h',h) = the pair with the smallest E[c1-1], ties to the lowest h' H + h;  path[c1-1] = h, path[c1-2] = h',
+ *                  and downwards path[n-2] = back2[n][path[n-1], path[n]]
+ * d_path_h [N,J] int32.  d_cost [N,J] float64 is the cost of the kept path RE-ACCUMULATED along it, with p_n = path[n,j]:
+ *   cost[c0] = u[c0,j,p]
+ *   cost[c0+1] = cost[c0] + (u[n,j,p_n] + lambda_v m[n,j,p_{n-1},p_n])
+ *   cost[n] = cost[n-1] + (u[n,j,p_n] + (lambda_v m[n,j,p_{n-1},p_n] + lambda_a a[n,j,p_{n-2},p_{n-1},p_n]))   for n >= c0+2
+ * - E is not kept for all frames (that would be 8 N J H^2 bytes), so cost[c1-1] equals the minimum of E[c1-1] up to the
+ * rounding of a different order of the same additions.  A dead (frame, joint) reports hypothesis 0 and cost +inf and splits
+ * only that joint's chain.  With lambda_a == 0 the paths are those of zedo_joint_temporal_select wherever its minima are
+ * unique beyond rounding.  (x and T are taken to be finite, as there.)
+ * Workspace (8-byte aligned, need not be initialised): back2 as one byte per (frame, joint, h', h), rounded up to 4 bytes, and
+ * two int32 flags per (frame, joint) - zedo_joint_accel_workspace_bytes(N, H, J); 0 for sizes the call refuses.  That is 43 MB
+ * at 1 015 frames x 17 joints x 50^2 and 3.0 GB at 70 880 frames: cut a long recording into calls of whole clips.
+ * Contract: J >= 1, N >= 1, 1 <= n_seq <= N, 1 <= H <= 64 (the pair table of one joint, 8 H^2 bytes, stays in the LDS), N*J*H
+ * <= INT_MAX, finite lambda_v >= 0 and lambda_a >= 0; ZEDO_E_BADARG with nothing written for a NULL pointer other than d_T, a
+ * non-positive size, H > 64, n_seq > N, N*J*H above INT_MAX, a negative or non-finite lambda_v or lambda_a, or a workspace
+ * that is not 8-byte aligned; ZEDO_E_WORKSPACE with nothing written if workspace_bytes is too small; allocates nothing,
+ * synchronises nothing, enqueues on `stream` only: legal under stream capture; no atomics: bit-identical from run to run.
+ * One workgroup per (clip, joint): a single long clip is serial in time on J CUs. */
+size_t zedo_joint_accel_workspace_bytes(int N, int H, int J);
+int zedo_joint_accel_select(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
+                            int H, int N, int J, double lambda_v, double lambda_a, void *d_workspace, size_t workspace_bytes,
+                            int *d_path_h, double *d_cost, void *stream);
 
 /* ---- pruning hypotheses DURING the loop, without ground truth: keep the K best of a pose, compact the rows ----------------
  * zedo_oil_run takes step_begin / step_end and a row's bits do not depend on the batch it is in, so a run can be cut into

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: twenty-eight one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: twenty-nine one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -59,6 +59,9 @@ MUTANTS = [
     ("ZEDO_MUT_JT_NO_T", "zedo_joint_temporal_select: the motion term is taken on x alone although d_T was given (zedo_joint_temporal.hip joint_temporal_scan_kernel)"),
     # the joint-wise fusion (tests/test_joint_marginal_gpu.py, tests/test_select_joints_fused_driver_gpu.py): leaves every other test green
     ("ZEDO_MUT_JM_NO_BACKWARD", "zedo_joint_marginal: B = 0 on every frame - the filtering marginals, not the smoothed ones (zedo_joint_marginal.hip joint_marginal_backward_kernel)"),
+    # the second-order joint-wise selection (tests/test_joint_accel_gpu.py, tests/test_select_joints_accel_driver_gpu.py): leaves every other
+    # test green
+    ("ZEDO_MUT_JA_FIRST_DIFF", "zedo_joint_accel_select: the second difference is taken as X[n] - X[n-1] + X[n-2], the factor 2 is dropped (zedo_joint_accel.hip joint_accel_scan_kernel and joint_accel_cost_kernel)"),
 ]
 
 

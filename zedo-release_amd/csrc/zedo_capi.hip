@@ -916,6 +916,26 @@ extern "C" int zedo_joint_marginal(const double *d_junary, const float *d_x, con
     return ZEDO_OK;
 }
 
+// ---- joint-wise selection with a second-order motion model: one chain over pairs per (clip, joint), the pair table in the LDS ----
+extern "C" size_t zedo_joint_accel_workspace_bytes(int N, int H, int J) {
+    if (N < 1 || H < 1 || J < 1 || H > 64 || (long long)N * J > INT_MAX || (long long)N * J * H > INT_MAX) return 0;
+    return joint_accel_bytes(N, H, J);
+}
+
+extern "C" int zedo_joint_accel_select(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq, int H,
+                                       int N, int J, double lambda_v, double lambda_a, void *d_workspace, size_t workspace_bytes,
+                                       int *d_path_h, double *d_cost, void *stream) {
+    if (!d_junary || !d_x || !d_seq_start || !d_workspace || !d_path_h || !d_cost || H < 1 || N < 1 || J < 1 || n_seq < 1 || n_seq > N)
+        return ZEDO_E_BADARG;
+    if (H > 64 || (long long)N * J > INT_MAX || (long long)N * J * H > INT_MAX) return ZEDO_E_BADARG;
+    if (!std::isfinite(lambda_v) || lambda_v < 0.0 || !std::isfinite(lambda_a) || lambda_a < 0.0) return ZEDO_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(d_workspace) & 7) return ZEDO_E_BADARG;              // as for the other chain models
+    if (workspace_bytes < joint_accel_bytes(N, H, J)) return ZEDO_E_WORKSPACE;
+    HIPCHK(launch_joint_accel_select(d_junary, d_x, d_T, d_seq_start, n_seq, H, N, J, lambda_v, lambda_a, d_workspace, d_path_h, d_cost,
+                                     (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
 // ---- hypothesis pruning between two stages of the loop: the table of kept slots, then the compaction of the rows ----
 extern "C" int zedo_prune_rank(const double *d_err, int H, int N, int K, int *d_keep, void *stream) {
     if (!d_err || !d_keep || N < 1 || K < 1 || K > H || H > 1024 || (long long)H * N > INT_MAX) return ZEDO_E_BADARG;

@@ -249,6 +249,10 @@ size_t joint_marginal_bytes(int N, int H, int J);
 hipError_t launch_joint_marginal(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N, int J,
                                  double c, double tau, void *ws, double *mean, double *cov, int *hmax, double *wmax, double *logz, double *w,
                                  hipStream_t st);
+// joint-wise selection with a second-order motion model (zedo_joint_accel.hip); ws: joint_accel_bytes(N, H, J), H <= 64
+size_t joint_accel_bytes(int N, int H, int J);
+hipError_t launch_joint_accel_select(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,
+                                     int J, double lambda_v, double lambda_a, void *ws, int *path, double *cost, hipStream_t st);
 // hypothesis pruning between two stages of the loop (zedo_prune.hip): keep [K,N], the kept slots of every pose in ascending order
 hipError_t launch_prune_rank(const double *err, int H, int N, int K, int *keep, hipStream_t st);
 hipError_t launch_prune_gather(const int *keep, int H, int K, int N, int J, const float *x, const float *T, const int *hyp, float *x_out,

@@ -44,6 +44,13 @@ def build_parser(description, inference=False):
                         "much as 1 px of reprojection error; the default is UNTUNED - its effect on accuracy has not been measured); "
                         "--select joints-temporal: the same, in pixels per metre of that joint's displacement (default 100, UNTUNED as well); "
                         "--select joints-fused: as for joints-temporal")
+    p.add_argument("--accel", type=float, default=None, metavar="LAMBDA2",
+                   help="--select joints-temporal only: add a second-order motion term - LAMBDA2 pixels per metre of that joint's second "
+                        "difference X[n] - 2 X[n-1] + X[n-2] in the camera frame, which is blind to a constant velocity - to every joint's "
+                        "chain (a chain over pairs of hypotheses, at most 64 of them); --smooth stays the weight of the displacement and "
+                        "still drives the pose-level path whose frame the pose is written in.  --smooth 0 --accel L is the pure "
+                        "second-order chain; the pose-level path is then the per-frame one.  No default; any value is UNTUNED - its effect on "
+                        "accuracy has not been measured")
     p.add_argument("--temperature", type=float, default=None, metavar="TAU",
                    help="--select joints-fused only: the temperature of the chain model in pixels - a path that costs TAU more is e times less "
                         "probable (default 1.0, UNTUNED: its effect on accuracy has not been measured); towards 0 the fused pose becomes the "
@@ -65,8 +72,14 @@ def build_parser(description, inference=False):
 
 def check_select_args(args):
     """--smooth / --seq_len belong to --select temporal, joints-temporal and joints-fused; --smooth defaults to 100 there.  --temperature
-    belongs to --select joints-fused and defaults to 1 there."""
+    belongs to --select joints-fused and defaults to 1 there.  --accel belongs to --select joints-temporal and has no default."""
     select = getattr(args, "select", "none") or "none"
+    accel = getattr(args, "accel", None)
+    if accel is not None:
+        if select != "joints-temporal":
+            raise SystemExit("--accel is a switch of --select joints-temporal")
+        if not (np.isfinite(accel) and accel >= 0):
+            raise SystemExit(f"--accel {accel}: a finite weight >= 0 expected")
     smooth, seq_len = getattr(args, "smooth", None), getattr(args, "seq_len", None)
     temperature = getattr(args, "temperature", None)
     if select != "joints-fused":
@@ -460,7 +473,11 @@ def run(args, inference=False):
         import zedo_hip
         seq, uvd, Kd, cfd, full_err, full_jerr, full_T, full, jidx0 = video_joint_inputs()
         idx, _ = zedo_hip.temporal_select(full_err, full, seq, N, args.smooth)
-        jpath, jcost = zedo_hip.joint_temporal_select(full_jerr, full, full_T, seq, N, args.smooth)
+        accel = getattr(args, "accel", None)
+        if accel is None:
+            jpath, jcost = zedo_hip.joint_temporal_select(full_jerr, full, full_T, seq, N, args.smooth)
+        else:                                                                     # the second-order chain (zedo_joint_accel_select)
+            jpath, jcost = zedo_hip.joint_accel_select(full_jerr, full, full_T, seq, N, args.smooth, accel)
         pose = zedo_hip.joint_compose(full, full_T, jpath.contiguous(), idx.contiguous(), N)
         T_sel = take_rows(full_T, idx, H, N).contiguous()
         _, px, _ = zedo_hip.min_reproj(pose, T_sel, uvd, Kd, cfd, N, 0)           # the assembled poses as a one-hypothesis problem
@@ -470,6 +487,8 @@ def run(args, inference=False):
                         joint_path_cost=jcost.cpu().numpy(), hypothesis=idx.cpu().numpy().astype(np.int32), T=T_sel.cpu().numpy(),
                         reproj_px=px.cpu().numpy(), reproj_px_pose_level=take_rows(full_err, idx, H, N).cpu().numpy(),
                         seq_start=seq.astype(np.int32), smooth=np.float64(args.smooth))
+        if accel is not None:
+            selected["accel"] = np.float64(accel)
         if rank == 0:
             np.savez(selected_path(args.out), **selected)
     if inference and select == "joints-fused":

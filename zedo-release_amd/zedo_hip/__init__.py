@@ -74,6 +74,8 @@ SIGNATURES = {
     "zedo_temporal_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _sz, _vp, _vp, _vp]),
     "zedo_joint_temporal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_temporal_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _sz, _vp, _vp, _vp]),
+    "zedo_joint_accel_workspace_bytes": (_sz, [_i, _i, _i]),
+    "zedo_joint_accel_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp]),
     "zedo_joint_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_marginal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_prune_rank": (_i, [_vp, _i, _i, _i, _vp, _vp]),
@@ -618,6 +620,43 @@ def joint_temporal_select(junary, x_full, T_full, seq_start, N=None, lam=100.0):
         _check(_lib.zedo_joint_temporal_select(_p(junary, torch.float64), _p(x_full), _p(T_full), _p(seq, torch.int32), seq.numel() - 1, H, N,
                                                J, float(lam), _p(ws, torch.uint8), nbytes, _p(path, torch.int32), _p(cost, torch.float64),
                                                _stream(dev)))
+    return path, cost
+
+
+def joint_accel_select(junary, x_full, T_full, seq_start, N=None, lam=100.0, accel=100.0):
+    """Joint-wise selection along a video with a second-order motion model (zedo_joint_accel_select): the inputs of joint_temporal_select
+    and a second weight -> (path [N,J] i32, cost [N,J] f64): per (clip, joint) the hypothesis sequence that minimises the sum of that
+    joint's unaries plus lam times its displacement plus accel times its second difference X[n] - 2 X[n-1] + X[n-2] in the camera frame
+    (x + T) - a term that is blind to a constant velocity (Viterbi over pairs of hypotheses, fp64, one chain per joint).  cost is the
+    cost of the kept path re-accumulated along it.  lam and accel are in cost units per metre; the defaults of 100 are untuned; lam = 0
+    is the pure second-order chain.  At most 64 hypotheses; the workspace is one byte per (frame, joint, pair).  Whether these paths are
+    closer to ground truth than joint_temporal_select's is not measured."""
+    _need_gpu()
+    dev = _device_of(junary, x_full, T_full, seq_start if isinstance(seq_start, torch.Tensor) and seq_start.is_cuda else None)
+    rows, J = x_full.shape[0], x_full.shape[1]
+    if isinstance(seq_start, torch.Tensor):
+        if seq_start.dtype not in (torch.int32, torch.int64) or seq_start.dim() != 1:
+            raise ValueError(f"joint_accel_select: seq_start must be a 1-D int tensor, got {seq_start.dtype} {tuple(seq_start.shape)}")
+        seq = seq_start.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        seq = torch.tensor([int(v) for v in seq_start], dtype=torch.int32, device=dev)
+    if N is None:
+        N = int(seq[-1].item()) if seq.numel() else 0
+    N = int(N)
+    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J) or seq.numel() < 2
+            or (T_full is not None and tuple(T_full.shape) != (rows, 3))):
+        raise ValueError(f"joint_accel_select: junary [H*N,J], x [H*N,J,3], T [H*N,3], seq_start [n_seq+1] expected, got "
+                         f"{tuple(junary.shape)}, {tuple(x_full.shape)}, {None if T_full is None else tuple(T_full.shape)}, {tuple(seq.shape)} "
+                         f"with N = {N}")
+    H = rows // N
+    with torch.cuda.device(dev):
+        nbytes = int(_lib.zedo_joint_accel_workspace_bytes(N, H, J))
+        ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+        path = torch.empty((N, J), dtype=torch.int32, device=dev)
+        cost = torch.empty((N, J), dtype=torch.float64, device=dev)
+        _check(_lib.zedo_joint_accel_select(_p(junary, torch.float64), _p(x_full), _p(T_full), _p(seq, torch.int32), seq.numel() - 1, H, N,
+                                            J, float(lam), float(accel), _p(ws, torch.uint8), nbytes, _p(path, torch.int32),
+                                            _p(cost, torch.float64), _stream(dev)))
     return path, cost
 
 

@@ -21,8 +21,8 @@ import os
 import numpy as np
 import torch
 
-from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_compose, joint_marginal, joint_reproj, joint_temporal_select, min_mpjpe_both,
-               min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
+from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
+               joint_temporal_select, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
 def linspace_f32(start, end, steps):
@@ -231,6 +231,18 @@ class Pipeline:
         with torch.cuda.device(self.device):
             _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
             path, cost = joint_temporal_select(jerr, x, T, seq_start, self.N, lam)
+        return path, cost, jerr
+
+    def select_joints_accel(self, x, T, seq_start, lam=100.0, accel=100.0):
+        """select_joints_temporal with a second-order motion model: the same inputs and outputs, each joint's path minimises its unaries
+        plus lam times its displacement plus accel (pixels per metre, default untuned) times its second difference X[n] - 2 X[n-1] +
+        X[n-2] in the camera frame, which is blind to a constant velocity (zedo_joint_accel_select; at most 64 hypotheses).  joint_cost
+        is the cost of the kept path re-accumulated along it."""
+        if x.shape[0] != self.H * self.N:
+            raise ValueError(f"select_joints_accel: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        with torch.cuda.device(self.device):
+            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
+            path, cost = joint_accel_select(jerr, x, T, seq_start, self.N, lam, accel)
         return path, cost, jerr
 
     def fuse_joints_temporal(self, x, T, seq_start, lam=100.0, tau=1.0):
