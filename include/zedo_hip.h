@@ -493,6 +493,57 @@ int zedo_joint_accel_select(const double *d_junary, const float *d_x, const floa
                             int H, int N, int J, double lambda_v, double lambda_a, void *d_workspace, size_t workspace_bytes,
                             int *d_path_h, double *d_cost, void *stream);
 
+/* ---- skeleton-coupled joint-wise aggregation WITHOUT ground truth: exact min-sum over the bone tree ------------------------
+ * zedo_joint_reproj picks every joint of a pose on its own, and the chain models above couple a joint to itself along time.
+ * A pose assembled by zedo_joint_compose can therefore take the two ends of a bone from different depth solutions; the bone
+ * then has a length no hypothesis has.  This call couples a joint to its neighbours in the skeleton, per pose: the assembled
+ * bone should be as long as the two hypotheses that supply its ends say this bone is.  A pose taken whole from one hypothesis
+ * pays nothing.  The skeleton is a tree, so the minimum is exact: min-sum dynamic programming from the leaves to the roots.
+ * Whether this lowers the error against ground truth is not measured.
+ * Inputs: d_junary [H*N,J] float64, rows (h,n) h-major, ALL rows: any per-(row, joint) cost, e.g. d_jerr of zedo_joint_reproj
+ * (pixels).  d_x [H*N,J,3] fp32 and d_T [H*N,3] fp32 or NULL, the same rows (metres).  d_weight [N,J] fp32 or NULL: a
+ * confidence per (pose, joint).  h_parent [J] int32 ON THE HOST, read during the call (as h_keylist of zedo_ipo_fit is): any
+ * forest - parent[j] in -1 .. J-1, never j itself, no cycle, at least one -1.  The host derives the processing order
+ * (post-order, children in ascending index) and hands it to the kernel by value: no device allocation, no copy.  mu: cost
+ * units per metre of bone mismatch.
+ * Per pose n, independent of every other pose, all arithmetic in float64 on the inputs as given:
+ *   X[n,h,j,c]  = (double)x[h*N+n,j,c] + (d_T ? (double)T[h*N+n,c] : 0.0)
+ *   w[n,j]      = d_weight ? (double)clamp(weight[n,j], 1e-4f, 1.0f) : 1.0   (the clamp in fp32, as zedo_min_reproj takes it)
+ *   u[n,j,h]    = w[n,j] * junary[(h*N+n)*J+j] if that product is finite, else +inf (the hypothesis is excluded for that joint);
+ *                 (n,j) is DEAD if no u[n,j,h] is finite
+ * For a joint g with parent p = parent[g] >= 0:
+ *   own[n,g,h]      = sqrt(e0^2+e1^2+e2^2),  e_c = X[n,h,g,c]  - X[n,h,p,c]        (products, then the sum ascending in c)
+ *   mix[n,g,hp,hc]  = sqrt(d0^2+d1^2+d2^2),  d_c = X[n,hc,g,c] - X[n,hp,p,c]
+ *   b[n,g,hp,hc]    = | mix[n,g,hp,hc] - 0.5 * (own[n,g,hc] + own[n,g,hp]) |        metres; exactly 0 when hc == hp
+ *   energy(assignment h_.) = sum_j u[n,j,h_j] + mu * sum_{g: parent live} b[n,g,h_p,h_g]
+ * The recurrence, children before parents and siblings in ascending index:
+ *   S[j,h] starts as u[n,j,h]
+ *   for a live g with a live parent p:  M_g[hp] = min_hc (S[g,hc] + mu * b[n,g,hp,hc]),  back[g,hp] = the lowest hc that
+ *       attains it,  S[p,hp] += M_g[hp]
+ *   a ROOT is a live joint with parent -1 or with a dead parent:  h_root = the lowest arg-min of S[root,.]
+ *   downwards:  h_g = back[g, h_parent]
+ * A dead joint reports hypothesis 0 and bone 0, sends nothing to its parent and turns its children into roots: it cuts the
+ * tree there and nowhere else.
+ * Outputs, all required: d_joint_h [N,J] int32, the kept assignment;  d_cost [N] float64 = the sum over the roots, in
+ * ascending index, of min S[root,.], +inf if the pose has no live joint;  d_bone [N,J] float64 = b[n,g,h_p,h_g] at the kept
+ * assignment, 0 for roots and dead joints.
+ * Two limits hold by construction: at mu = 0 with d_weight == NULL d_joint_h is bit for bit d_best_h of zedo_joint_reproj on
+ * the same rows; as mu grows the assignment becomes one whole hypothesis per pose, the arg-min over h of sum_j u[n,j,h].
+ * (x and T are taken to be finite: a non-finite coordinate makes the affected minima unspecified and is never an address.)
+ * There is no workspace: S, back and the positions live in the LDS of the pose's workgroup, which bounds the sizes:
+ *   34 J H + 16 H + 4096 <= 163840 bytes, the 160 KiB of a gfx950 CU
+ *   (24 J H of positions, 8 J H of S, 2 J H of back as 16-bit entries, 16 H of bone lengths, 4096 of minima and flags),
+ * and 1 <= J <= 64 (the cap of the network entry points), 1 <= H <= 1024.  That admits H <= 268 at J = 17, H <= 72 at J = 64,
+ * H <= 1024 for J <= 4.
+ * Contract: N >= 1, the caps above, H*N*J <= INT_MAX, finite mu >= 0; ZEDO_E_BADARG with nothing written for a NULL pointer
+ * other than d_T / d_weight, a non-positive size, a size above the caps, H*N*J above INT_MAX, a parent array that breaks the
+ * rules, or a negative or non-finite mu; allocates nothing, synchronises nothing, enqueues on `stream` only: legal under
+ * stream capture; no atomics, every sum in a fixed order (S[p,.] takes its children in ascending index whatever the launch
+ * shape): bit-identical from run to run.  One workgroup of 256 lanes per pose, one launch. */
+int zedo_joint_tree_select(const double *d_junary, const float *d_x, const float *d_T, const float *d_weight,
+                           const int *h_parent, int H, int N, int J, double mu,
+                           int *d_joint_h, double *d_cost, double *d_bone, void *stream);
+
 /* ---- pruning hypotheses DURING the loop, without ground truth: keep the K best of a pose, compact the rows ----------------
  * zedo_oil_run takes step_begin / step_end and a row's bits do not depend on the batch it is in, so a run can be cut into
  * stages that carry fewer and fewer rows.  These two calls are the piece between two stages.  Whether pruning by

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: twenty-nine one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: thirty one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -62,6 +62,8 @@ MUTANTS = [
     # the second-order joint-wise selection (tests/test_joint_accel_gpu.py, tests/test_select_joints_accel_driver_gpu.py): leaves every other
     # test green
     ("ZEDO_MUT_JA_FIRST_DIFF", "zedo_joint_accel_select: the second difference is taken as X[n] - X[n-1] + X[n-2], the factor 2 is dropped (zedo_joint_accel.hip joint_accel_scan_kernel and joint_accel_cost_kernel)"),
+    # the skeleton-coupled aggregation (tests/test_joint_tree_gpu.py, tests/test_select_joints_tree_driver_gpu.py): leaves every other test green
+    ("ZEDO_MUT_TREE_NO_HALF", "zedo_joint_tree_select: the bone term compares the assembled length with the SUM of the two hypotheses' lengths, the 0.5 is dropped (zedo_joint_tree.hip tr_bone: the recurrence and bone[n,.])"),
 ]
 
 

@@ -936,6 +936,18 @@ extern "C" int zedo_joint_accel_select(const double *d_junary, const float *d_x,
     return ZEDO_OK;
 }
 
+// ---- skeleton-coupled joint-wise aggregation: min-sum over the bone tree, one workgroup per pose, no workspace ----
+extern "C" int zedo_joint_tree_select(const double *d_junary, const float *d_x, const float *d_T, const float *d_weight, const int *h_parent,
+                                      int H, int N, int J, double mu, int *d_joint_h, double *d_cost, double *d_bone, void *stream) {
+    if (!d_junary || !d_x || !h_parent || !d_joint_h || !d_cost || !d_bone || H < 1 || N < 1 || J < 1) return ZEDO_E_BADARG;
+    if (J > TR_JMAX || H > TR_HMAX || joint_tree_lds_bytes(H, J) > TR_LDS || (long long)H * N * J > INT_MAX) return ZEDO_E_BADARG;
+    if (!std::isfinite(mu) || mu < 0.0) return ZEDO_E_BADARG;
+    TreeOrder tr;
+    if (!joint_tree_order(h_parent, J, &tr)) return ZEDO_E_BADARG;
+    HIPCHK(launch_joint_tree_select(d_junary, d_x, d_T, d_weight, tr, H, N, J, mu, d_joint_h, d_cost, d_bone, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
 // ---- hypothesis pruning between two stages of the loop: the table of kept slots, then the compaction of the rows ----
 extern "C" int zedo_prune_rank(const double *d_err, int H, int N, int K, int *d_keep, void *stream) {
     if (!d_err || !d_keep || N < 1 || K < 1 || K > H || H > 1024 || (long long)H * N > INT_MAX) return ZEDO_E_BADARG;

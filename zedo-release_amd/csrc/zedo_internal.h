@@ -253,6 +253,19 @@ hipError_t launch_joint_marginal(const double *junary, const float *x, const flo
 size_t joint_accel_bytes(int N, int H, int J);
 hipError_t launch_joint_accel_select(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,
                                      int J, double lambda_v, double lambda_a, void *ws, int *path, double *cost, hipStream_t st);
+// skeleton-coupled joint-wise aggregation (zedo_joint_tree.hip): min-sum over the bone tree, one workgroup per pose, everything in the
+// LDS - joint_tree_lds_bytes(H, J) = 34 J H + 16 H + 4096 of the CU's TR_LDS bytes.  The host derives the post-order of the bones
+// (joint_tree_order: false for a parent array that is not a forest) and hands it to the kernel by value.
+constexpr int TR_T = 256, TR_JMAX = 64, TR_HMAX = 1024;
+constexpr size_t TR_LDS = 160 * 1024;
+struct TreeOrder {
+    signed char parent[TR_JMAX];      // -1: a root
+    unsigned char order[TR_JMAX];     // the joints, children before parents, siblings in ascending index
+};
+size_t joint_tree_lds_bytes(int H, int J);
+bool joint_tree_order(const int *parent, int J, TreeOrder *out);
+hipError_t launch_joint_tree_select(const double *junary, const float *x, const float *T, const float *weight, const TreeOrder &tr, int H,
+                                    int N, int J, double mu, int *joint_h, double *cost, double *bone, hipStream_t st);
 // hypothesis pruning between two stages of the loop (zedo_prune.hip): keep [K,N], the kept slots of every pose in ascending order
 hipError_t launch_prune_rank(const double *err, int H, int N, int K, int *keep, hipStream_t st);
 hipError_t launch_prune_gather(const int *keep, int H, int K, int N, int J, const float *x, const float *T, const int *hyp, float *x_out,

@@ -1,0 +1,225 @@
+// Skeleton-coupled joint-wise aggregation for gfx950 (zedo_joint_tree_select): per pose the assignment of one hypothesis to every joint
+// that minimises the joints' unary costs plus mu times, for every bone, the mismatch between the assembled bone's length and the length
+// the two hypotheses that supply its ends give that bone - exact min-sum dynamic programming over the bone tree, fp64, one launch.
+// One workgroup of 256 lanes serves one pose; everything lives in the LDS, sized to the case:
+//   X    [J][H][3] f64   the pose's camera-frame positions, staged once: H runs of 12 J bytes at a stride of N J 3 floats (neighbouring
+//                        poses are neighbours in memory, and neighbours in the grid run at the same time).  Joint-major: the lanes of a
+//                        wave read X[j][h] of consecutive h - fp64 triples at a stride of 6 dwords, which 32 lanes spread over the 64
+//                        banks without a conflict (ds_read_b64 is served in groups of 32 lanes, bank = dword address mod 64) - or all the
+//                        same h: a broadcast
+//   S    [J][H]    f64   u, then u plus the messages of the children
+//   back [J][H]    u16   the arg-min of a bone's message
+//   own  [2][H]    f64   the bone's own length in every hypothesis, formed once per bone, double-buffered over consecutive bones
+// 34 J H + 16 H + 4096 bytes in all (the parts' minima, the roots and the flags are the 4096).
+// The bones are walked in the host's post-order (children before parents, siblings ascending), handed over by value.  For one bone the
+// H^2 pairs are dealt as in joint_temporal_scan_kernel: 256 lanes as P parts x 256 / P slots, P = 4 (H <= 64), 2 (H <= 128) or 1; the
+// lane (part, slot) owns hp = slot (+ 256, .. when P = 1 and H > 256) and walks one part of the hc in lockstep with its wave, so
+// S[g][hc], own[hc] and X[g][hc] are broadcast reads; the parts' minima meet in the LDS and part 0 combines them in ascending part
+// order with a strict comparison - the lowest hc still wins.  S[p][.] takes its children's messages in the order of the walk, i.e. in
+// ascending child index whatever the launch shape.  One barrier per bone (two where the hc are split).  The roots' minima, the downward
+// pass and bone[n,.] end the same launch.  No atomics, no scratch.
+#include "zedo_internal.h"
+
+namespace zedo {
+
+__device__ __forceinline__ bool tr_finite64(double v) { return fabs(v) < __builtin_huge_val(); }   // false for NaN and +-inf
+
+// sqrt(d0^2 + d1^2 + d2^2), d = a - b: products, then the sum ascending in c
+__device__ __forceinline__ double tr_dist(const double *a, double b0, double b1, double b2) {
+    const double d0 = a[0] - b0, d1 = a[1] - b1, d2 = a[2] - b2;
+    return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+}
+// the bone term of one pair, in metres: exactly 0 when both ends come from one hypothesis (mix and both own are then the same bits)
+__device__ __forceinline__ double tr_bone(double mix, double own_c, double own_p) {
+#ifdef ZEDO_MUT_TREE_NO_HALF   // tools/mutation_check.py only: the two hypotheses' lengths are summed, not averaged
+    return fabs(mix - (own_c + own_p));
+#else
+    return fabs(mix - 0.5 * (own_c + own_p));
+#endif
+}
+
+__global__ __launch_bounds__(TR_T) void joint_tree_kernel(const double *__restrict__ junary, const float *__restrict__ x,
+                                                          const float *__restrict__ Tr, const float *__restrict__ weight, const TreeOrder tr,
+                                                          int H, int N, int J, double mu, int *__restrict__ joint_h, double *__restrict__ cost,
+                                                          double *__restrict__ bone) {
+    extern __shared__ double tr_lds[];
+    const int JH = J * H;
+    double *const sX = tr_lds, *const sS = sX + 3 * JH, *const sOwn = sS + JH, *const sPv = sOwn + 2 * H, *const sRmin = sPv + TR_T;
+    int *const sPi = reinterpret_cast<int *>(sRmin + TR_JMAX), *const sSel = sPi + TR_T, *const sLive = sSel + TR_JMAX;
+    unsigned short *const sBack = reinterpret_cast<unsigned short *>(sLive + TR_JMAX);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t n = blockIdx.x;
+    const double inf = __builtin_huge_val();
+
+    // the pose's positions and unaries, once: consecutive lanes read consecutive floats of a row
+    const int J3 = 3 * J;
+    for (int e = tid; e < 3 * JH; e += TR_T) {
+        const int h = e / J3, r = e - h * J3, j = r / 3, c = r - 3 * j;
+        const size_t row = (size_t)h * N + n;
+        sX[(j * H + h) * 3 + c] = (double)x[row * J3 + r] + (Tr ? (double)Tr[row * 3 + c] : 0.0);
+    }
+    for (int e = tid; e < JH; e += TR_T) {
+        const int h = e / J, j = e - h * J;
+        double w = 1.0;
+        if (weight) {                                              // the clamp of zedo_min_reproj, taken in fp32 (NaN stays NaN)
+            float c = weight[n * J + j];
+            if (c > 1.0f) c = 1.0f;
+            if (c < 1e-4f) c = 1e-4f;
+            w = (double)c;
+        }
+        const double u = w * junary[((size_t)h * N + n) * J + j];
+        sS[j * H + h] = tr_finite64(u) ? u : inf;
+    }
+    __syncthreads();
+    for (int j = wave; j < J; j += TR_T / 64) {                    // a wave per joint: does it have a finite unary at all?
+        int any = 0;
+        for (int h = lane; h < H; h += 64) any |= tr_finite64(sS[j * H + h]) ? 1 : 0;
+        const bool live = __ballot(any) != 0;
+        if (lane == 0) sLive[j] = live ? 1 : 0;
+    }
+    __syncthreads();
+
+    // upwards: the message of every live bone with a live parent, in the host's order
+    const int P = H <= TR_T / 4 ? 4 : (H <= TR_T / 2 ? 2 : 1), SLOTS = TR_T / P;
+    const int part = tid / SLOTS, slot = tid - part * SLOTS;
+    const int per = (H + P - 1) / P, q0 = min(H, part * per), q1 = min(H, q0 + per);      // this lane's hc (part 0 is never empty)
+    int nb = 0;
+    for (int i = 0; i < J; ++i) {
+        const int g = tr.order[i], p = tr.parent[g];
+        if (p < 0 || !sLive[g] || !sLive[p]) continue;             // (workgroup-uniform) a root, dead, or cut off by a dead parent
+        double *const own = sOwn + (nb & 1) * H;
+        ++nb;
+        const double *const Xg = sX + (size_t)g * H * 3, *const Xp = sX + (size_t)p * H * 3, *const Sg = sS + g * H;
+        for (int h = tid; h < H; h += TR_T) own[h] = tr_dist(Xg + h * 3, Xp[h * 3], Xp[h * 3 + 1], Xp[h * 3 + 2]);
+        __syncthreads();                                           // A: own[] is there; the previous bone's sums are in S
+        for (int hp = slot; hp < H; hp += SLOTS) {
+            const double p0 = Xp[hp * 3], p1 = Xp[hp * 3 + 1], p2 = Xp[hp * 3 + 2], op = own[hp];
+            double best = inf;
+            int bi = q0;
+#pragma unroll 2
+            for (int hc = q0; hc < q1; ++hc) {
+                const double c = Sg[hc] + mu * tr_bone(tr_dist(Xg + hc * 3, p0, p1, p2), own[hc], op);
+                if (c < best) { best = c; bi = hc; }               // strict: the lowest hc that attains the minimum
+            }
+            if (P == 1) {
+                sBack[g * H + hp] = (unsigned short)bi;
+                sS[p * H + hp] += best;
+            } else {
+                sPv[tid] = best;
+                sPi[tid] = bi;
+            }
+        }
+        if (P > 1) {
+            __syncthreads();                                       // B: the parts' minima are in the LDS
+            if (part == 0 && slot < H) {
+                double best = sPv[slot];
+                int bi = sPi[slot];
+                const int np = (H + per - 1) / per;                // the parts that are not empty
+                for (int q = 1; q < np; ++q) {
+                    const double c = sPv[q * SLOTS + slot];
+                    if (c < best) { best = c; bi = sPi[q * SLOTS + slot]; }
+                }
+                sBack[g * H + slot] = (unsigned short)bi;
+                sS[p * H + slot] += best;
+            }
+        }
+    }
+    __syncthreads();
+
+    // the roots: a live joint without a live parent; a wave per root takes the lowest arg-min of S[root][.]
+    for (int j = wave; j < J; j += TR_T / 64) {
+        const int p = tr.parent[j];
+        if (!sLive[j] || (p >= 0 && sLive[p])) continue;           // (wave-uniform)
+        double v = inf;
+        int vh = 0x7fffffff;
+        for (int h = lane; h < H; h += 64) {
+            const double c = sS[j * H + h];
+            if (c < v) { v = c; vh = h; }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double ov = __shfl_xor(v, off);
+            const int oh = __shfl_xor(vh, off);
+            if (ov < v || (ov == v && oh < vh)) { v = ov; vh = oh; }
+        }
+        if (lane == 0) { sRmin[j] = v; sSel[j] = vh == 0x7fffffff ? 0 : vh; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double c = 0.0;
+        int roots = 0;
+        for (int j = 0; j < J; ++j) {                              // ascending root index
+            const int p = tr.parent[j];
+            if (sLive[j] && !(p >= 0 && sLive[p])) { c += sRmin[j]; ++roots; }
+        }
+        cost[n] = roots ? c : inf;
+        for (int i = J - 1; i >= 0; --i) {                         // downwards: parents before children
+            const int g = tr.order[i], p = tr.parent[g];
+            if (!sLive[g]) sSel[g] = 0;
+            else if (p >= 0 && sLive[p]) sSel[g] = sBack[g * H + sSel[p]];
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < J; j += TR_T) {
+        const int p = tr.parent[j], hc = sSel[j];
+        double b = 0.0;
+        if (sLive[j] && p >= 0 && sLive[p]) {
+            const int hp = sSel[p];
+            const double *const Xj = sX + (size_t)j * H * 3, *const Xp = sX + (size_t)p * H * 3;
+            const double own_c = tr_dist(Xj + hc * 3, Xp[hc * 3], Xp[hc * 3 + 1], Xp[hc * 3 + 2]);
+            const double own_p = tr_dist(Xj + hp * 3, Xp[hp * 3], Xp[hp * 3 + 1], Xp[hp * 3 + 2]);
+            b = tr_bone(tr_dist(Xj + hc * 3, Xp[hp * 3], Xp[hp * 3 + 1], Xp[hp * 3 + 2]), own_c, own_p);
+        }
+        joint_h[n * J + j] = hc;
+        bone[n * J + j] = b;
+    }
+}
+
+size_t joint_tree_lds_bytes(int H, int J) { return (size_t)34 * J * H + (size_t)16 * H + 4096; }
+
+// parent [J] -> the post-order with children in ascending index; false for anything that is not a forest
+bool joint_tree_order(const int *parent, int J, TreeOrder *out) {
+    if (J < 1 || J > TR_JMAX) return false;
+    int first[TR_JMAX], next[TR_JMAX], stack[TR_JMAX], roots = 0;
+    for (int j = 0; j < J; ++j) {
+        if (parent[j] < -1 || parent[j] >= J || parent[j] == j) return false;
+        first[j] = next[j] = -1;
+        roots += parent[j] < 0;
+    }
+    if (!roots) return false;
+    for (int j = J - 1; j >= 0; --j)                                // prepend in descending index: the lists come out ascending
+        if (parent[j] >= 0) { next[j] = first[parent[j]]; first[parent[j]] = j; }
+    int cnt = 0;
+    for (int r = 0; r < J; ++r) {
+        if (parent[r] >= 0) continue;
+        int sp = 0;
+        stack[sp++] = r;
+        while (sp) {
+            const int v = stack[sp - 1];
+            if (first[v] >= 0) {                                   // descend into the next child, consuming it
+                const int c = first[v];
+                first[v] = next[c];
+                stack[sp++] = c;
+            } else {
+                out->order[cnt++] = (unsigned char)v;
+                --sp;
+            }
+        }
+    }
+    if (cnt != J) return false;                                    // what no root reaches sits on a cycle
+    for (int j = 0; j < J; ++j) out->parent[j] = (signed char)parent[j];
+    for (int j = J; j < TR_JMAX; ++j) { out->parent[j] = -1; out->order[j] = 0; }
+    return true;
+}
+
+hipError_t launch_joint_tree_select(const double *junary, const float *x, const float *T, const float *weight, const TreeOrder &tr, int H,
+                                    int N, int J, double mu, int *joint_h, double *cost, double *bone, hipStream_t st) {
+    static std::atomic<bool> lds_ok[MAX_DEVICES];
+    hipError_t e = allow_lds(reinterpret_cast<const void *>(joint_tree_kernel), TR_LDS, lds_ok);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(joint_tree_kernel, dim3((unsigned)N), dim3(TR_T), joint_tree_lds_bytes(H, J), st, junary, x, T, weight, tr, H, N, J, mu,
+                       joint_h, cost, bone);
+    return hipGetLastError();
+}
+
+}  // namespace zedo

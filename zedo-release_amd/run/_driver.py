@@ -29,7 +29,7 @@ def build_parser(description, inference=False):
     p.add_argument("--math", choices=("f32", "f16x3"), default=None,
                    help="arithmetic of the dense layers: f32 = exact fp32 MFMA (default), f16x3 = split-fp16 operands on the fp16 "
                         "matrix pipe at fp32-level accuracy, ~2x faster (same as the ZEDO_MATH environment variable)")
-    p.add_argument("--select", choices=("none", "reproj", "joints", "temporal", "joints-temporal", "joints-fused"), default="none",
+    p.add_argument("--select", choices=("none", "reproj", "joints", "temporal", "joints-temporal", "joints-fused", "joints-tree"), default="none",
                    help="run.inference only: reproj = also keep, per pose, the hypothesis whose x + T reprojects closest to the 2D "
                         "detections (confidence-weighted, no ground truth needed) -> <out>_selected.npz; joints = keep, per JOINT, the "
                         "hypothesis whose joint reprojects closest to its detection and assemble the pose from those joints; temporal = "
@@ -38,7 +38,10 @@ def build_parser(description, inference=False):
                         "hypothesis sequence that minimises that joint's reprojection distance plus --smooth times that joint's displacement "
                         "in the camera frame (one Viterbi chain per joint), the pose assembled from those joints; joints-fused = the soft "
                         "answer of the same chain model at --temperature: per joint the posterior mean position over the hypotheses, its "
-                        "covariance (the depth ambiguity in metres) and the most probable hypothesis with its probability")
+                        "covariance (the depth ambiguity in metres) and the most probable hypothesis with its probability; joints-tree = "
+                        "joints with the skeleton as a coupling: per pose the assignment of a hypothesis to every joint that minimises the "
+                        "joints' confidence-weighted reprojection distances plus --bone times, for every bone, the difference between the "
+                        "assembled bone's length and the length its two hypotheses give that bone (exact min-sum over the bone tree)")
     p.add_argument("--smooth", type=float, default=None, metavar="LAMBDA",
                    help="--select temporal: weight of the motion cost in pixels per metre (default 100: a mean joint jump of 1 cm costs as "
                         "much as 1 px of reprojection error; the default is UNTUNED - its effect on accuracy has not been measured); "
@@ -55,6 +58,10 @@ def build_parser(description, inference=False):
                    help="--select joints-fused only: the temperature of the chain model in pixels - a path that costs TAU more is e times less "
                         "probable (default 1.0, UNTUNED: its effect on accuracy has not been measured); towards 0 the fused pose becomes the "
                         "pose of --select joints-temporal")
+    p.add_argument("--bone", type=float, default=None, metavar="MU",
+                   help="--select joints-tree only: weight of the bone term in pixels per metre (default 100: 1 cm of bone mismatch costs as "
+                        "much as 1 px of one joint's weighted reprojection distance; the default is UNTUNED - its effect on accuracy has not "
+                        "been measured); 0 is --select joints, a large value one whole hypothesis per pose")
     p.add_argument("--seq_len", type=int, default=None, metavar="L",
                    help="--select temporal / joints-temporal / joints-fused: cut the frames into consecutive clips of L (the last one shorter); overrides the dataset's "
                         "seq_start; with --synthetic the only source of clips (default: the dataset's clips, else one clip)")
@@ -72,8 +79,17 @@ def build_parser(description, inference=False):
 
 def check_select_args(args):
     """--smooth / --seq_len belong to --select temporal, joints-temporal and joints-fused; --smooth defaults to 100 there.  --temperature
-    belongs to --select joints-fused and defaults to 1 there.  --accel belongs to --select joints-temporal and has no default."""
+    belongs to --select joints-fused and defaults to 1 there.  --accel belongs to --select joints-temporal and has no default.  --bone
+    belongs to --select joints-tree and defaults to 100 there."""
     select = getattr(args, "select", "none") or "none"
+    bone = getattr(args, "bone", None)
+    if select != "joints-tree":
+        if bone is not None:
+            raise SystemExit("--bone is a switch of --select joints-tree")
+    elif bone is None:
+        args.bone = 100.0
+    elif not (np.isfinite(bone) and bone >= 0):
+        raise SystemExit(f"--bone {bone}: a finite weight >= 0 expected")
     accel = getattr(args, "accel", None)
     if accel is not None:
         if select != "joints-temporal":
@@ -249,7 +265,7 @@ def pruned_path(out):
 
 
 def selected_path(out):
-    """<out without .npy>_selected.npz: where run.inference --select reproj / joints / temporal / joints-temporal / joints-fused writes the pose it keeps per detection."""
+    """<out without .npy>_selected.npz: where run.inference --select reproj / joints / temporal / joints-temporal / joints-fused / joints-tree writes the pose it keeps per detection."""
     return (out[:-4] if out.endswith(".npy") else out) + "_selected.npz"
 
 
@@ -267,7 +283,7 @@ def run(args, inference=False):
                          "truth (best of H), and the ground-truth evaluation of a selected pose is printed by run.inference --eval")
     check_select_args(args)
     prune = getattr(args, "prune", None)
-    if prune is not None and select in ("joints", "temporal", "joints-temporal", "joints-fused"):
+    if prune is not None and select in ("joints", "temporal", "joints-temporal", "joints-fused", "joints-tree"):
         raise SystemExit(f"--prune with --select {select} is not supported yet (a follow-up): the pruned run keeps different hypotheses "
                          "per pose; use --select reproj or none")
     if prune is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -410,6 +426,43 @@ def run(args, inference=False):
                         reproj_px_pose_level=best.cpu().numpy())
         if rank == 0:
             np.savez(selected_path(args.out), **selected)
+    if inference and select == "joints-tree":
+        # --select joints with the skeleton as a coupling, step for step: each rank evaluates zedo_min_reproj and zedo_joint_reproj (the
+        # route that writes every row's per-joint distances) on its own rows, both MIN over the ranks; the distances and T are gathered
+        # like the rows; every rank runs the same min-sum over the bone tree (zedo_joint_tree_select, the confidences as weights) on the
+        # full arrays and ends with the same arrays, rank 0 writes them
+        import zedo_hip
+        if why is None:
+            uvd, Kd, cfd = pipe.uv, pipe.K, pipe.conf
+        else:
+            d2 = torch.tensor(np.ascontiguousarray(gt_2d), dtype=torch.float32, device=device)
+            uvd, Kd, cfd = d2[:, :, :2].contiguous(), torch.tensor(np.ascontiguousarray(K), dtype=torch.float32, device=device), d2[:, :, 2].contiguous()
+        if rows == 0:
+            best, idx = empty_selection(N, device)
+            jerr = torch.empty((0, N_JOINTS), dtype=torch.float64, device=device)
+            jbest0, jidx0 = (t.reshape(N, N_JOINTS) for t in empty_selection(N * N_JOINTS, device))
+        else:
+            _, best, idx = zedo_hip.min_reproj(x, T.contiguous(), uvd, Kd, cfd, N, lo)
+            jbest0, jidx0, jerr = zedo_hip.joint_reproj(x, T.contiguous(), uvd, Kd, N, lo, return_rows=True)
+        best, idx = reduce_min_over_ranks(best, idx)
+        jbest0, jidx0 = reduce_min_over_ranks(jbest0, jidx0)                       # what --select joints keeps
+        glo = None if why is None else lo
+        full_jerr = gather_row_shards(jerr, H * N, lo=glo).contiguous()
+        full_T = gather_row_shards(T.contiguous(), H * N, lo=glo).contiguous()
+        skeleton = test_dataset.get_skeleton() if hasattr(test_dataset, "get_skeleton") else zedo_hip.H36M_EDGES
+        parent = zedo_hip.skeleton_parents(skeleton, N_JOINTS)
+        jidx, tcost, jbone = zedo_hip.joint_tree_select(full_jerr, full.contiguous(), full_T, parent, N, args.bone, cfd)
+        pose = zedo_hip.joint_compose(full.contiguous(), full_T, jidx.contiguous(), idx.contiguous(), N)
+        T_sel = take_rows(full_T, idx, H, N).contiguous()
+        _, px, _ = zedo_hip.min_reproj(pose, T_sel, uvd, Kd, cfd, N, 0)           # the assembled poses as a one-hypothesis problem
+        jpx = full_jerr.reshape(H, N, N_JOINTS).gather(0, jidx.to(torch.int64)[None])[0]
+        selected = dict(pose=pose.cpu().numpy(), joint_hypothesis=jidx.cpu().numpy().astype(np.int32),
+                        joint_hypothesis_per_joint=jidx0.cpu().numpy().astype(np.int32), joint_reproj_px=jpx.cpu().numpy(),
+                        joint_bone_m=jbone.cpu().numpy(), tree_cost=tcost.cpu().numpy(), hypothesis=idx.cpu().numpy().astype(np.int32),
+                        T=T_sel.cpu().numpy(), reproj_px=px.cpu().numpy(), reproj_px_pose_level=best.cpu().numpy(),
+                        bone=np.float64(args.bone))
+        if rank == 0:
+            np.savez(selected_path(args.out), **selected)
     if inference and select == "temporal":
         # the frames are a video: each rank evaluates zedo_min_reproj on its own rows, the per-row errors and T are gathered like the rows,
         # every rank runs the same Viterbi (zedo_temporal_select) on the full arrays and ends with the same arrays, rank 0 writes them
@@ -531,7 +584,7 @@ def run(args, inference=False):
                 s1 = test_dataset.eval_multi(("rows", sel_rows), protocol2=False, print_verbose=False, row_offset=0)
                 s2 = test_dataset.eval_multi(("rows", sel_rows), protocol2=True, print_verbose=False, row_offset=0)
             if rank == 0:
-                label = {"joints": "joints-aggregated", "temporal": "temporal-selected", "joints-temporal": "joints-temporal", "joints-fused": "joints-fused"}.get(select, "reproj-selected")
+                label = {"joints": "joints-aggregated", "temporal": "temporal-selected", "joints-temporal": "joints-temporal", "joints-fused": "joints-fused", "joints-tree": "joints-tree"}.get(select, "reproj-selected")
                 print(f"{label} MPJPE : {s1}")
                 print(f"{label} PA-MPJPE : {s2}")
             errs = (p1, p2, s1, s2)

@@ -78,6 +78,7 @@ SIGNATURES = {
     "zedo_joint_accel_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp]),
     "zedo_joint_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_marginal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "zedo_joint_tree_select": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp, _vp]),
     "zedo_prune_rank": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "zedo_prune_gather": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_pose_min": (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp]),
@@ -658,6 +659,67 @@ def joint_accel_select(junary, x_full, T_full, seq_start, N=None, lam=100.0, acc
                                             J, float(lam), float(accel), _p(ws, torch.uint8), nbytes, _p(path, torch.int32),
                                             _p(cost, torch.float64), _stream(dev)))
     return path, cost
+
+
+# the 16 bones every ported dataset's get_skeleton() returns (H36M's 17 joints)
+H36M_EDGES = ((0, 1), (1, 2), (2, 3), (0, 4), (4, 5), (5, 6), (0, 7), (7, 8), (8, 9), (9, 10), (8, 11), (11, 12), (12, 13), (8, 14), (14, 15),
+              (15, 16))
+
+
+def skeleton_parents(edges, J, root=0):
+    """The parent array of a skeleton: edges = J - 1 undirected bones (a, b) as get_skeleton() lists them -> [J] ints, parent[root] = -1,
+    by breadth-first search from `root`.  ValueError for an edge list that is not a spanning tree of the J joints (a wrong number of
+    bones, a joint outside 0 .. J-1, a bone from a joint to itself, a cycle, or a joint the root does not reach)."""
+    J, root = int(J), int(root)
+    edges = [(int(a), int(b)) for a, b in edges]
+    if J < 1 or not 0 <= root < J:
+        raise ValueError(f"skeleton_parents: root {root} is not one of {J} joints")
+    if len(edges) != J - 1 or any(a == b or not (0 <= a < J and 0 <= b < J) for a, b in edges):
+        raise ValueError(f"skeleton_parents: {J - 1} bones between two different joints in 0 .. {J - 1} expected, got {len(edges)}: not a spanning tree")
+    nbr = [[] for _ in range(J)]
+    for a, b in edges:
+        nbr[a].append(b)
+        nbr[b].append(a)
+    parent, seen, queue = [-1] * J, [False] * J, [root]
+    seen[root] = True
+    for v in queue:
+        for c in nbr[v]:
+            if not seen[c]:
+                seen[c], parent[c] = True, v
+                queue.append(c)
+    if len(queue) != J:                       # J - 1 bones that leave a joint out close a cycle elsewhere
+        raise ValueError(f"skeleton_parents: the bones do not connect all {J} joints to joint {root} (a cycle or a disconnected part): not a spanning tree")
+    return parent
+
+
+def joint_tree_select(junary, x_full, T_full, parent, N=None, mu=100.0, weight=None):
+    """Skeleton-coupled joint-wise aggregation without ground truth (zedo_joint_tree_select): junary [H*N,J] f64 (ALL rows, h-major: e.g.
+    jerr of joint_reproj(return_rows=True), pixels), x_full [H*N,J,3] f32, T_full [H*N,3] f32 or None, parent [J] ints (a forest: -1 for a
+    root; skeleton_parents builds it from a get_skeleton() edge list), weight [N,J] f32 or None (confidences, clamped to 1e-4 .. 1 as
+    min_reproj clamps them) -> (joint_h [N,J] i32, cost [N] f64, bone [N,J] f64): per pose the assignment of a hypothesis to every joint
+    that minimises the sum of the weighted unaries plus mu times, over the bones, the difference between the assembled bone's length and
+    the mean of the lengths its two hypotheses give that bone (exact min-sum over the tree, fp64); bone is that difference in metres at
+    the kept assignment.  mu is in cost units per metre; the default of 100 is untuned.  mu = 0 is joint_reproj's arg-min, a large mu one
+    whole hypothesis per pose.  Whether the coupled pose is closer to ground truth than the per-joint arg-min is not measured."""
+    _need_gpu()
+    dev = _device_of(junary, x_full, T_full, weight)
+    rows, J = x_full.shape[0], x_full.shape[1]
+    par = np.ascontiguousarray(np.asarray(parent.cpu() if isinstance(parent, torch.Tensor) else parent).astype(np.int32))
+    N = (0 if weight is None else weight.shape[0]) if N is None else int(N)      # without N the weights say how many poses there are
+    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J) or par.shape != (J,)
+            or (T_full is not None and tuple(T_full.shape) != (rows, 3)) or (weight is not None and tuple(weight.shape) != (N, J))):
+        raise ValueError(f"joint_tree_select: junary [H*N,J], x [H*N,J,3], T [H*N,3], parent [J], weight [N,J] expected, got "
+                         f"{tuple(junary.shape)}, {tuple(x_full.shape)}, {None if T_full is None else tuple(T_full.shape)}, {par.shape}, "
+                         f"{None if weight is None else tuple(weight.shape)} with N = {N}")
+    H = rows // N
+    with torch.cuda.device(dev):
+        joint_h = torch.empty((N, J), dtype=torch.int32, device=dev)
+        cost = torch.empty((N,), dtype=torch.float64, device=dev)
+        bone = torch.empty((N, J), dtype=torch.float64, device=dev)
+        _check(_lib.zedo_joint_tree_select(_p(junary, torch.float64), _p(x_full), _p(T_full), _p(weight), par.ctypes.data_as(ctypes.c_void_p),
+                                           H, N, J, float(mu), _p(joint_h, torch.int32), _p(cost, torch.float64), _p(bone, torch.float64),
+                                           _stream(dev)))
+    return joint_h, cost, bone
 
 
 def joint_marginal(junary, x_full, T_full, seq_start, N=None, lam=100.0, tau=1.0, return_weights=False):

@@ -21,8 +21,8 @@ import os
 import numpy as np
 import torch
 
-from . import (SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
-               joint_temporal_select, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
+from . import (H36M_EDGES, SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
+               joint_temporal_select, joint_tree_select, skeleton_parents, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
 def linspace_f32(start, end, steps):
@@ -198,6 +198,22 @@ class Pipeline:
             return best.reshape(self.N, J), idx.reshape(self.N, J)
         with torch.cuda.device(self.device):
             return joint_reproj(x, T, self.uv, self.K, self.N, row_offset)
+
+    def aggregate_tree(self, x, T, mu=100.0, parent=None):
+        """aggregate_reproj with the skeleton as a coupling, on the problem of load(): x [H*N,17,3] and T [H*N,3], ALL rows (a pose's every
+        hypothesis takes part) -> (joint_h [N,17] i32, cost [N] f64, bone [N,17] f64, jerr [H*N,17] f64): the unaries are
+        zedo_joint_reproj's per-(row, joint) distances (pixels) weighted by the pipeline's confidences; the assignment minimises them plus
+        mu (pixels per metre, default untuned) times every bone's mismatch between its assembled length and the length its two hypotheses
+        give it (zedo_joint_tree_select, exact min-sum over the tree).  parent [17]: the bone tree, default H36M's.
+        compose(x, T, joint_h, ref) assembles the pose."""
+        if x.shape[0] != self.H * self.N:
+            raise ValueError(f"aggregate_tree: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        if parent is None:
+            parent = skeleton_parents(H36M_EDGES, self.uv.shape[1])
+        with torch.cuda.device(self.device):
+            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
+            joint_h, cost, bone = joint_tree_select(jerr, x, T, parent, self.N, mu, self.conf)
+        return joint_h, cost, bone, jerr
 
     def compose(self, x_full, T_full, joint_idx, ref_idx=None):
         """The pose assembled from the joints aggregate_reproj selected: x_full [H*N,17,3], T_full [H*N,3] (all global rows), joint_idx
