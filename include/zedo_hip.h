@@ -544,6 +544,59 @@ int zedo_joint_tree_select(const double *d_junary, const float *d_x, const float
                            const int *h_parent, int H, int N, int J, double mu,
                            int *d_joint_h, double *d_cost, double *d_bone, void *stream);
 
+/* ---- skeleton-coupled FUSION per pose WITHOUT ground truth: exact sum-product over the bone tree --------------------------
+ * The soft answer of zedo_joint_tree_select, as zedo_joint_marginal is the soft answer of zedo_joint_temporal_select: the same
+ * energy read as a probability at a temperature tau.  From one image (no clip is needed) every joint gets a fused position, an
+ * error bar and the probability of its likeliest hypothesis.  The skeleton is a tree, so the marginals are exact: one pass from
+ * the leaves to the roots, one back.  Whether the fused pose is closer to ground truth is not measured.
+ * Inputs: those of zedo_joint_tree_select, word for word - rows (h,n) h-major, ALL rows; d_T and d_weight may be NULL;
+ * h_parent [J] int32 ON THE HOST, any forest, validated by the same rules, the host derives the same post-order and passes
+ * it by value - and tau: finite, > 0, in cost units (an assignment that costs tau more is e times less probable).
+ * X, the clamp of the weights, u, DEAD, own, mix and b are those of zedo_joint_tree_select, statement for statement.
+ * Per pose n, all arithmetic in float64:
+ *   p(assignment h_.) ~ exp(-(sum_j u[n,j,h_j] + mu * sum_{g: live, parent live} b[n,g,h_p,h_g]) / tau)
+ * With l[j,h] = -u[n,j,h] / tau (-inf where the hypothesis is excluded) and c = mu / tau:
+ *   upwards, children before parents and siblings in ascending index:  S[j,.] starts as l[j,.];  for a live g with a live parent p
+ *       M_g[hp] = LSE_hc (S[g,hc] - c * b[n,g,hp,hc]),  S[p,hp] += M_g[hp]
+ *   a ROOT is a live joint with parent -1 or with a dead parent:  logZ_root = LSE_h S[root,h],  Dn[root,.] = 0
+ *   downwards, parents before children:  E_g[hp] = l[p,hp] + sum_{children k != g of p} M_k[hp] + Dn[p,hp], formed as
+ *       S[p,hp] - M_g[hp] + Dn[p,hp];  Dn[g,hc] = LSE_hp (E_g[hp] - c * b[n,g,hp,hc])
+ *   w[j,h] = exp(S[j,h] + Dn[j,h] - logZ of j's component): exactly 0 for an excluded hypothesis
+ *   pi[g,hp,hc] = exp(E_g[hp] - c * b[n,g,hp,hc] + S[g,hc] - logZ): the pair marginal of a bone, never stored
+ * Every LSE is shifted by the TRUE maximum of its terms (two walks over them; the bone term is recomputed, not kept), so a
+ * small tau underflows nothing that matters.  Where the inner index is split over parts of the workgroup each part shifts
+ * by its own maximum and the parts combine in ascending order, shifted by the largest.
+ * Outputs, all required but d_w:
+ *   d_mean [N,J,3] float64 = sum_h w X (camera frame, metres);
+ *   d_cov  [N,J,6] float64 = sum_h w (X - mean)(X - mean)^T in the order xx, xy, xz, yy, yz, zz, from centred differences;
+ *   d_hmax [N,J] int32 = the lowest h with the largest marginal;  d_wmax [N,J] float64 = that marginal;
+ *   d_logz [N,J] float64 = the log-partition value of the joint's component (the tree after dead joints cut it), repeated on
+ *       every joint of that component;
+ *   d_bone [N,J] float64 = sum_{hp,hc} pi[g,hp,hc] * b[n,g,hp,hc], the EXPECTED bone mismatch in metres, 0 for roots and dead
+ *       joints;
+ *   d_w [N,J,H] float64 or NULL: the marginals.
+ * A dead joint reports NaN in mean and cov, hypothesis 0, wmax 0, logz -inf, bone 0 and a row of zeros in d_w; it sends
+ * nothing up and turns its children into roots, as in zedo_joint_tree_select.
+ * Limits that hold by construction: as tau -> 0 d_hmax becomes d_joint_h of zedo_joint_tree_select and d_bone its d_bone; at
+ * mu = 0 the marginals are the per-joint softmax of -u / tau.
+ * (x and T are taken to be finite, as in zedo_joint_tree_select.)
+ * There is no workspace: X, S, the messages M and Dn and the bone lengths live in the LDS of the pose's workgroup:
+ *   48 J H + 16 H + 8192 <= 163840 bytes, the 160 KiB of a gfx950 CU
+ *   (24 J H of positions, 8 J H each of S, M and Dn, 16 H of bone lengths and E_g, 8192 of the parts' sums, logZ and flags),
+ * and 1 <= J <= 64, 1 <= H <= 1024.  zedo_joint_tree_marginal_max_h(J) returns the largest H this admits at J - 187 at
+ * J = 17, 50 at J = 64, 1024 for J <= 2 - and 0 for a J outside 1 .. 64.
+ * Contract: N >= 1, H <= zedo_joint_tree_marginal_max_h(J), H*N*J <= INT_MAX, finite mu >= 0, finite tau > 0, finite mu / tau;
+ * ZEDO_E_BADARG with nothing written for a NULL pointer other than d_T / d_weight / d_w, a non-positive size, a size above
+ * the caps, H*N*J above INT_MAX, a parent array that breaks the rules, a negative or non-finite mu, tau <= 0 or not finite,
+ * or mu / tau not finite; allocates nothing, synchronises nothing, enqueues on `stream` only: legal under stream capture; no
+ * atomics, every sum in a fixed order: bit-identical from run to run and with or without d_w.  One workgroup of 256 lanes
+ * per pose, one launch. */
+int zedo_joint_tree_marginal_max_h(int J);
+int zedo_joint_tree_marginal(const double *d_junary, const float *d_x, const float *d_T, const float *d_weight,
+                             const int *h_parent, int H, int N, int J, double mu, double tau,
+                             double *d_mean, double *d_cov, int *d_hmax, double *d_wmax, double *d_logz,
+                             double *d_bone, double *d_w, void *stream);
+
 /* ---- pruning hypotheses DURING the loop, without ground truth: keep the K best of a pose, compact the rows ----------------
  * zedo_oil_run takes step_begin / step_end and a row's bits do not depend on the batch it is in, so a run can be cut into
  * stages that carry fewer and fewer rows.  These two calls are the piece between two stages.  Whether pruning by

@@ -948,6 +948,23 @@ extern "C" int zedo_joint_tree_select(const double *d_junary, const float *d_x, 
     return ZEDO_OK;
 }
 
+// ---- skeleton-coupled fusion per pose: sum-product over the bone tree, one workgroup per pose, no workspace ----
+extern "C" int zedo_joint_tree_marginal_max_h(int J) { return joint_tree_marginal_max_h(J); }
+
+extern "C" int zedo_joint_tree_marginal(const double *d_junary, const float *d_x, const float *d_T, const float *d_weight, const int *h_parent,
+                                        int H, int N, int J, double mu, double tau, double *d_mean, double *d_cov, int *d_hmax, double *d_wmax,
+                                        double *d_logz, double *d_bone, double *d_w, void *stream) {
+    if (!d_junary || !d_x || !h_parent || !d_mean || !d_cov || !d_hmax || !d_wmax || !d_logz || !d_bone || H < 1 || N < 1 || J < 1)
+        return ZEDO_E_BADARG;
+    if (J > TR_JMAX || H > joint_tree_marginal_max_h(J) || (long long)H * N * J > INT_MAX) return ZEDO_E_BADARG;
+    if (!std::isfinite(mu) || mu < 0.0 || !std::isfinite(tau) || !(tau > 0.0) || !std::isfinite(mu / tau)) return ZEDO_E_BADARG;
+    TreeOrder tr;
+    if (!joint_tree_order(h_parent, J, &tr)) return ZEDO_E_BADARG;
+    HIPCHK(launch_joint_tree_marginal(d_junary, d_x, d_T, d_weight, tr, H, N, J, mu / tau, tau, d_mean, d_cov, d_hmax, d_wmax, d_logz, d_bone,
+                                      d_w, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
 // ---- hypothesis pruning between two stages of the loop: the table of kept slots, then the compaction of the rows ----
 extern "C" int zedo_prune_rank(const double *d_err, int H, int N, int K, int *d_keep, void *stream) {
     if (!d_err || !d_keep || N < 1 || K < 1 || K > H || H > 1024 || (long long)H * N > INT_MAX) return ZEDO_E_BADARG;

@@ -266,6 +266,29 @@ size_t joint_tree_lds_bytes(int H, int J);
 bool joint_tree_order(const int *parent, int J, TreeOrder *out);
 hipError_t launch_joint_tree_select(const double *junary, const float *x, const float *T, const float *weight, const TreeOrder &tr, int H,
                                     int N, int J, double mu, int *joint_h, double *cost, double *bone, hipStream_t st);
+// the statements of the bone term, shared by the min-sum kernel and its sum-product twin (zedo_joint_tree_marginal.hip)
+__device__ __forceinline__ bool tr_finite64(double v) { return fabs(v) < __builtin_huge_val(); }   // false for NaN and +-inf
+// sqrt(d0^2 + d1^2 + d2^2), d = a - b: products, then the sum ascending in c
+__device__ __forceinline__ double tr_dist(const double *a, double b0, double b1, double b2) {
+    const double d0 = a[0] - b0, d1 = a[1] - b1, d2 = a[2] - b2;
+    return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+}
+// the bone term of one pair, in metres: exactly 0 when both ends come from one hypothesis (mix and both own are then the same bits)
+__device__ __forceinline__ double tr_bone(double mix, double own_c, double own_p) {
+#ifdef ZEDO_MUT_TREE_NO_HALF   // tools/mutation_check.py only: the two hypotheses' lengths are summed, not averaged
+    return fabs(mix - (own_c + own_p));
+#else
+    return fabs(mix - 0.5 * (own_c + own_p));
+#endif
+}
+// posterior marginals of the same energy (zedo_joint_tree_marginal.hip): sum-product over the bone tree, one workgroup per pose, everything
+// in the LDS - joint_tree_marginal_lds_bytes(H, J) = 48 J H + 16 H + 8192 of the CU's TR_LDS bytes; c = mu / tau.
+// joint_tree_marginal_max_h(J): the largest H that fits (at most TR_HMAX), 0 for a J outside 1 .. TR_JMAX.
+size_t joint_tree_marginal_lds_bytes(int H, int J);
+int joint_tree_marginal_max_h(int J);
+hipError_t launch_joint_tree_marginal(const double *junary, const float *x, const float *T, const float *weight, const TreeOrder &tr, int H,
+                                      int N, int J, double c, double tau, double *mean, double *cov, int *hmax, double *wmax, double *logz,
+                                      double *bone, double *w, hipStream_t st);
 // hypothesis pruning between two stages of the loop (zedo_prune.hip): keep [K,N], the kept slots of every pose in ascending order
 hipError_t launch_prune_rank(const double *err, int H, int N, int K, int *keep, hipStream_t st);
 hipError_t launch_prune_gather(const int *keep, int H, int K, int N, int J, const float *x, const float *T, const int *hyp, float *x_out,

@@ -22,21 +22,7 @@
 
 namespace zedo {
 
-__device__ __forceinline__ bool tr_finite64(double v) { return fabs(v) < __builtin_huge_val(); }   // false for NaN and +-inf
-
-// sqrt(d0^2 + d1^2 + d2^2), d = a - b: products, then the sum ascending in c
-__device__ __forceinline__ double tr_dist(const double *a, double b0, double b1, double b2) {
-    const double d0 = a[0] - b0, d1 = a[1] - b1, d2 = a[2] - b2;
-    return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-}
-// the bone term of one pair, in metres: exactly 0 when both ends come from one hypothesis (mix and both own are then the same bits)
-__device__ __forceinline__ double tr_bone(double mix, double own_c, double own_p) {
-#ifdef ZEDO_MUT_TREE_NO_HALF   // tools/mutation_check.py only: the two hypotheses' lengths are summed, not averaged
-    return fabs(mix - (own_c + own_p));
-#else
-    return fabs(mix - 0.5 * (own_c + own_p));
-#endif
-}
+// (tr_finite64, tr_dist and tr_bone - the statements this kernel shares with its sum-product twin - are in zedo_internal.h)
 
 __global__ __launch_bounds__(TR_T) void joint_tree_kernel(const double *__restrict__ junary, const float *__restrict__ x,
                                                           const float *__restrict__ Tr, const float *__restrict__ weight, const TreeOrder tr,

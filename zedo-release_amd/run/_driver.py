@@ -29,7 +29,8 @@ def build_parser(description, inference=False):
     p.add_argument("--math", choices=("f32", "f16x3"), default=None,
                    help="arithmetic of the dense layers: f32 = exact fp32 MFMA (default), f16x3 = split-fp16 operands on the fp16 "
                         "matrix pipe at fp32-level accuracy, ~2x faster (same as the ZEDO_MATH environment variable)")
-    p.add_argument("--select", choices=("none", "reproj", "joints", "temporal", "joints-temporal", "joints-fused", "joints-tree"), default="none",
+    p.add_argument("--select", choices=("none", "reproj", "joints", "temporal", "joints-temporal", "joints-fused", "joints-tree", "joints-tree-fused"),
+                   default="none",
                    help="run.inference only: reproj = also keep, per pose, the hypothesis whose x + T reprojects closest to the 2D "
                         "detections (confidence-weighted, no ground truth needed) -> <out>_selected.npz; joints = keep, per JOINT, the "
                         "hypothesis whose joint reprojects closest to its detection and assemble the pose from those joints; temporal = "
@@ -41,7 +42,10 @@ def build_parser(description, inference=False):
                         "covariance (the depth ambiguity in metres) and the most probable hypothesis with its probability; joints-tree = "
                         "joints with the skeleton as a coupling: per pose the assignment of a hypothesis to every joint that minimises the "
                         "joints' confidence-weighted reprojection distances plus --bone times, for every bone, the difference between the "
-                        "assembled bone's length and the length its two hypotheses give that bone (exact min-sum over the bone tree)")
+                        "assembled bone's length and the length its two hypotheses give that bone (exact min-sum over the bone tree); "
+                        "joints-tree-fused = the soft answer of the same skeleton model at --temperature, from one image: per joint the "
+                        "posterior mean position over the hypotheses, its covariance, the most probable hypothesis with its probability "
+                        "and every bone's expected mismatch (exact sum-product over the bone tree)")
     p.add_argument("--smooth", type=float, default=None, metavar="LAMBDA",
                    help="--select temporal: weight of the motion cost in pixels per metre (default 100: a mean joint jump of 1 cm costs as "
                         "much as 1 px of reprojection error; the default is UNTUNED - its effect on accuracy has not been measured); "
@@ -57,11 +61,13 @@ def build_parser(description, inference=False):
     p.add_argument("--temperature", type=float, default=None, metavar="TAU",
                    help="--select joints-fused only: the temperature of the chain model in pixels - a path that costs TAU more is e times less "
                         "probable (default 1.0, UNTUNED: its effect on accuracy has not been measured); towards 0 the fused pose becomes the "
-                        "pose of --select joints-temporal")
+                        "pose of --select joints-temporal; --select joints-tree-fused: the temperature of the skeleton model, in pixels "
+                        "as well (default 1.0, UNTUNED); towards 0 the fused pose becomes the pose of --select joints-tree")
     p.add_argument("--bone", type=float, default=None, metavar="MU",
                    help="--select joints-tree only: weight of the bone term in pixels per metre (default 100: 1 cm of bone mismatch costs as "
                         "much as 1 px of one joint's weighted reprojection distance; the default is UNTUNED - its effect on accuracy has not "
-                        "been measured); 0 is --select joints, a large value one whole hypothesis per pose")
+                        "been measured); 0 is --select joints, a large value one whole hypothesis per pose; --select joints-tree-fused: the same "
+                        "weight in the model the marginals are taken of (default 100, UNTUNED as well)")
     p.add_argument("--seq_len", type=int, default=None, metavar="L",
                    help="--select temporal / joints-temporal / joints-fused: cut the frames into consecutive clips of L (the last one shorter); overrides the dataset's "
                         "seq_start; with --synthetic the only source of clips (default: the dataset's clips, else one clip)")
@@ -80,10 +86,11 @@ def build_parser(description, inference=False):
 def check_select_args(args):
     """--smooth / --seq_len belong to --select temporal, joints-temporal and joints-fused; --smooth defaults to 100 there.  --temperature
     belongs to --select joints-fused and defaults to 1 there.  --accel belongs to --select joints-temporal and has no default.  --bone
-    belongs to --select joints-tree and defaults to 100 there."""
+    belongs to --select joints-tree and defaults to 100 there.  --select joints-tree-fused takes --bone and --temperature with the same
+    defaults and checks."""
     select = getattr(args, "select", "none") or "none"
     bone = getattr(args, "bone", None)
-    if select != "joints-tree":
+    if select not in ("joints-tree", "joints-tree-fused"):
         if bone is not None:
             raise SystemExit("--bone is a switch of --select joints-tree")
     elif bone is None:
@@ -98,7 +105,7 @@ def check_select_args(args):
             raise SystemExit(f"--accel {accel}: a finite weight >= 0 expected")
     smooth, seq_len = getattr(args, "smooth", None), getattr(args, "seq_len", None)
     temperature = getattr(args, "temperature", None)
-    if select != "joints-fused":
+    if select not in ("joints-fused", "joints-tree-fused"):
         if temperature is not None:
             raise SystemExit("--temperature is a switch of --select joints-fused")
     elif temperature is None:
@@ -265,7 +272,7 @@ def pruned_path(out):
 
 
 def selected_path(out):
-    """<out without .npy>_selected.npz: where run.inference --select reproj / joints / temporal / joints-temporal / joints-fused / joints-tree writes the pose it keeps per detection."""
+    """<out without .npy>_selected.npz: where run.inference --select reproj / joints / temporal / joints-temporal / joints-fused / joints-tree / joints-tree-fused writes the pose it keeps per detection."""
     return (out[:-4] if out.endswith(".npy") else out) + "_selected.npz"
 
 
@@ -283,7 +290,7 @@ def run(args, inference=False):
                          "truth (best of H), and the ground-truth evaluation of a selected pose is printed by run.inference --eval")
     check_select_args(args)
     prune = getattr(args, "prune", None)
-    if prune is not None and select in ("joints", "temporal", "joints-temporal", "joints-fused", "joints-tree"):
+    if prune is not None and select in ("joints", "temporal", "joints-temporal", "joints-fused", "joints-tree", "joints-tree-fused"):
         raise SystemExit(f"--prune with --select {select} is not supported yet (a follow-up): the pruned run keeps different hypotheses "
                          "per pose; use --select reproj or none")
     if prune is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -334,6 +341,12 @@ def run(args, inference=False):
     z = config.ZeDO
     S = args.oil_iterations or z.OIL_iterations
     H, N = len(sample_poses), len(gt_3d)
+    if select == "joints-tree-fused":
+        import zedo_hip
+        cap = zedo_hip.joint_tree_marginal_max_h(N_JOINTS)
+        if H > cap:
+            raise SystemExit(f"--select joints-tree-fused admits at most {cap} hypotheses per pose at {N_JOINTS} joints (the model of a pose lives "
+                             f"in the LDS of one workgroup), --hypo {H} given: use fewer hypotheses, or --select joints-tree")
     lo, rows = shard_rows(H * N, rank, world)
     why = not_fused_because(config)
     if prune is not None:
@@ -426,11 +439,12 @@ def run(args, inference=False):
                         reproj_px_pose_level=best.cpu().numpy())
         if rank == 0:
             np.savez(selected_path(args.out), **selected)
-    if inference and select == "joints-tree":
-        # --select joints with the skeleton as a coupling, step for step: each rank evaluates zedo_min_reproj and zedo_joint_reproj (the
-        # route that writes every row's per-joint distances) on its own rows, both MIN over the ranks; the distances and T are gathered
-        # like the rows; every rank runs the same min-sum over the bone tree (zedo_joint_tree_select, the confidences as weights) on the
-        # full arrays and ends with the same arrays, rank 0 writes them
+
+    def tree_inputs():
+        # what --select joints-tree and joints-tree-fused share, --select joints step for step: each rank evaluates zedo_min_reproj and
+        # zedo_joint_reproj (the route that writes every row's per-joint distances) on its own rows, both MIN over the ranks; the
+        # distances and T are gathered like the rows, so that every rank holds the full arrays; the bone tree is the dataset's.
+        # -> (uvd, Kd, cfd, pose-level best and idx, what --select joints keeps, full_jerr, full_T, parent)
         import zedo_hip
         if why is None:
             uvd, Kd, cfd = pipe.uv, pipe.K, pipe.conf
@@ -450,7 +464,13 @@ def run(args, inference=False):
         full_jerr = gather_row_shards(jerr, H * N, lo=glo).contiguous()
         full_T = gather_row_shards(T.contiguous(), H * N, lo=glo).contiguous()
         skeleton = test_dataset.get_skeleton() if hasattr(test_dataset, "get_skeleton") else zedo_hip.H36M_EDGES
-        parent = zedo_hip.skeleton_parents(skeleton, N_JOINTS)
+        return uvd, Kd, cfd, best, idx, jidx0, full_jerr, full_T, zedo_hip.skeleton_parents(skeleton, N_JOINTS)
+
+    if inference and select == "joints-tree":
+        # --select joints with the skeleton as a coupling: on the arrays of tree_inputs() every rank runs the same min-sum over the bone
+        # tree (zedo_joint_tree_select, the confidences as weights) and ends with the same arrays, rank 0 writes them
+        import zedo_hip
+        uvd, Kd, cfd, best, idx, jidx0, full_jerr, full_T, parent = tree_inputs()
         jidx, tcost, jbone = zedo_hip.joint_tree_select(full_jerr, full.contiguous(), full_T, parent, N, args.bone, cfd)
         pose = zedo_hip.joint_compose(full.contiguous(), full_T, jidx.contiguous(), idx.contiguous(), N)
         T_sel = take_rows(full_T, idx, H, N).contiguous()
@@ -461,6 +481,25 @@ def run(args, inference=False):
                         joint_bone_m=jbone.cpu().numpy(), tree_cost=tcost.cpu().numpy(), hypothesis=idx.cpu().numpy().astype(np.int32),
                         T=T_sel.cpu().numpy(), reproj_px=px.cpu().numpy(), reproj_px_pose_level=best.cpu().numpy(),
                         bone=np.float64(args.bone))
+        if rank == 0:
+            np.savez(selected_path(args.out), **selected)
+    if inference and select == "joints-tree-fused":
+        # the soft answer of the skeleton model of joints-tree, on the same arrays (tree_inputs()): every rank runs the same sum-product
+        # over the bone tree (zedo_joint_tree_marginal, the confidences as weights) and, for comparison, the min-sum of joints-tree at the
+        # same weight and ends with the same arrays, rank 0 writes them
+        import zedo_hip
+        _, _, cfd, best, idx, _, full_jerr, full_T, parent = tree_inputs()
+        mean, cov, hmax, wmax, logz, ebone = zedo_hip.joint_tree_marginal(full_jerr, full.contiguous(), full_T, parent, N, args.bone,
+                                                                          args.temperature, cfd)
+        jtree, _, _ = zedo_hip.joint_tree_select(full_jerr, full.contiguous(), full_T, parent, N, args.bone, cfd)
+        T_sel = take_rows(full_T, idx, H, N).contiguous()
+        pose = (mean - T_sel.to(torch.float64)[:, None, :]).to(torch.float32)     # in the frame --select joints-tree writes in
+        spread = (cov[:, :, 0] + cov[:, :, 3] + cov[:, :, 5]).sqrt()
+        selected = dict(pose=pose.cpu().numpy(), joint_cov=cov.cpu().numpy(), joint_spread_m=spread.cpu().numpy(),
+                        joint_hypothesis=hmax.cpu().numpy().astype(np.int32), joint_weight=wmax.cpu().numpy(), joint_logz=logz.cpu().numpy(),
+                        joint_bone_m=ebone.cpu().numpy(), joint_hypothesis_tree=jtree.cpu().numpy().astype(np.int32),
+                        hypothesis=idx.cpu().numpy().astype(np.int32), T=T_sel.cpu().numpy(), reproj_px_pose_level=best.cpu().numpy(),
+                        bone=np.float64(args.bone), temperature=np.float64(args.temperature))
         if rank == 0:
             np.savez(selected_path(args.out), **selected)
     if inference and select == "temporal":
@@ -584,7 +623,8 @@ def run(args, inference=False):
                 s1 = test_dataset.eval_multi(("rows", sel_rows), protocol2=False, print_verbose=False, row_offset=0)
                 s2 = test_dataset.eval_multi(("rows", sel_rows), protocol2=True, print_verbose=False, row_offset=0)
             if rank == 0:
-                label = {"joints": "joints-aggregated", "temporal": "temporal-selected", "joints-temporal": "joints-temporal", "joints-fused": "joints-fused", "joints-tree": "joints-tree"}.get(select, "reproj-selected")
+                label = {"joints": "joints-aggregated", "temporal": "temporal-selected", "joints-temporal": "joints-temporal", "joints-fused": "joints-fused", "joints-tree": "joints-tree",
+                         "joints-tree-fused": "joints-tree-fused"}.get(select, "reproj-selected")
                 print(f"{label} MPJPE : {s1}")
                 print(f"{label} PA-MPJPE : {s2}")
             errs = (p1, p2, s1, s2)

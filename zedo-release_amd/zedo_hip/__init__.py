@@ -79,6 +79,8 @@ SIGNATURES = {
     "zedo_joint_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_marginal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_joint_tree_select": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp, _vp]),
+    "zedo_joint_tree_marginal_max_h": (_i, [_i]),
+    "zedo_joint_tree_marginal": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_prune_rank": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "zedo_prune_gather": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_pose_min": (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp]),
@@ -720,6 +722,47 @@ def joint_tree_select(junary, x_full, T_full, parent, N=None, mu=100.0, weight=N
                                            H, N, J, float(mu), _p(joint_h, torch.int32), _p(cost, torch.float64), _p(bone, torch.float64),
                                            _stream(dev)))
     return joint_h, cost, bone
+
+
+def joint_tree_marginal_max_h(J):
+    """The largest number of hypotheses joint_tree_marginal admits at J joints (zedo_joint_tree_marginal_max_h): what fits the LDS of one
+    workgroup, 48 J H + 16 H + 8192 <= 163840 bytes, at most 1024; 0 for a J outside 1 .. 64."""
+    return int(_lib.zedo_joint_tree_marginal_max_h(int(J)))
+
+
+def joint_tree_marginal(junary, x_full, T_full, parent, N=None, mu=100.0, tau=1.0, weight=None, return_weights=False):
+    """Skeleton-coupled fusion per pose without ground truth (zedo_joint_tree_marginal): the inputs of joint_tree_select and a temperature
+    tau > 0 in cost units -> (mean [N,J,3] f64, cov [N,J,6] f64, hmax [N,J] i32, wmax [N,J] f64, logz [N,J] f64, bone [N,J] f64[, w
+    [N,J,H] f64]): per pose the exact posterior marginals w of every joint's hypotheses under p(assignment) ~ exp(-(weighted unaries +
+    mu * bone mismatches) / tau), the energy joint_tree_select minimises (sum-product over the bone tree, fp64), and from them the
+    posterior mean position in the camera frame, its covariance (xx, xy, xz, yy, yz, zz; m^2), the most probable hypothesis, its
+    probability, the log-partition value of the joint's component and the expected mismatch of the bone to the parent (metres).  A dead
+    joint reports NaN, 0, 0, -inf and 0.  mu = 100 and tau = 1 are untuned.  At most joint_tree_marginal_max_h(J) hypotheses.  Whether the
+    fused pose is closer to ground truth than a selected one is not measured."""
+    _need_gpu()
+    dev = _device_of(junary, x_full, T_full, weight)
+    rows, J = x_full.shape[0], x_full.shape[1]
+    par = np.ascontiguousarray(np.asarray(parent.cpu() if isinstance(parent, torch.Tensor) else parent).astype(np.int32))
+    N = (0 if weight is None else weight.shape[0]) if N is None else int(N)      # without N the weights say how many poses there are
+    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J) or par.shape != (J,)
+            or (T_full is not None and tuple(T_full.shape) != (rows, 3)) or (weight is not None and tuple(weight.shape) != (N, J))):
+        raise ValueError(f"joint_tree_marginal: junary [H*N,J], x [H*N,J,3], T [H*N,3], parent [J], weight [N,J] expected, got "
+                         f"{tuple(junary.shape)}, {tuple(x_full.shape)}, {None if T_full is None else tuple(T_full.shape)}, {par.shape}, "
+                         f"{None if weight is None else tuple(weight.shape)} with N = {N}")
+    H = rows // N
+    with torch.cuda.device(dev):
+        mean = torch.empty((N, J, 3), dtype=torch.float64, device=dev)
+        cov = torch.empty((N, J, 6), dtype=torch.float64, device=dev)
+        hmax = torch.empty((N, J), dtype=torch.int32, device=dev)
+        wmax = torch.empty((N, J), dtype=torch.float64, device=dev)
+        logz = torch.empty((N, J), dtype=torch.float64, device=dev)
+        bone = torch.empty((N, J), dtype=torch.float64, device=dev)
+        w = torch.empty((N, J, H), dtype=torch.float64, device=dev) if return_weights else None
+        _check(_lib.zedo_joint_tree_marginal(_p(junary, torch.float64), _p(x_full), _p(T_full), _p(weight), par.ctypes.data_as(ctypes.c_void_p),
+                                             H, N, J, float(mu), float(tau), _p(mean, torch.float64), _p(cov, torch.float64),
+                                             _p(hmax, torch.int32), _p(wmax, torch.float64), _p(logz, torch.float64), _p(bone, torch.float64),
+                                             _p(w, torch.float64), _stream(dev)))
+    return (mean, cov, hmax, wmax, logz, bone, w) if return_weights else (mean, cov, hmax, wmax, logz, bone)
 
 
 def joint_marginal(junary, x_full, T_full, seq_start, N=None, lam=100.0, tau=1.0, return_weights=False):

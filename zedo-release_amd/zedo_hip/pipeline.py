@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import (H36M_EDGES, SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
-               joint_temporal_select, joint_tree_select, skeleton_parents, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
+               joint_temporal_select, joint_tree_marginal, joint_tree_select, skeleton_parents, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
 def linspace_f32(start, end, steps):
@@ -214,6 +214,22 @@ class Pipeline:
             _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
             joint_h, cost, bone = joint_tree_select(jerr, x, T, parent, self.N, mu, self.conf)
         return joint_h, cost, bone, jerr
+
+    def fuse_tree(self, x, T, mu=100.0, tau=1.0, parent=None):
+        """The soft answer of aggregate_tree, on the problem of load(): x [H*N,17,3] and T [H*N,3], ALL rows -> (mean [N,17,3] f64, cov
+        [N,17,6] f64, hmax [N,17] i32, wmax [N,17] f64, logz [N,17] f64, bone [N,17] f64, jerr [H*N,17] f64): the unaries and the weights
+        are aggregate_tree's - zedo_joint_reproj's per-(row, joint) distances (pixels) and the pipeline's confidences - and the outputs
+        the exact posterior marginals of the same energy at the temperature tau (pixels), read as a fused position, its covariance, the
+        most probable hypothesis, its probability, the component's log-partition value and every bone's expected mismatch
+        (zedo_joint_tree_marginal, sum-product over the tree).  mu and tau: defaults untuned.  parent [17]: the bone tree, default H36M's."""
+        if x.shape[0] != self.H * self.N:
+            raise ValueError(f"fuse_tree: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        if parent is None:
+            parent = skeleton_parents(H36M_EDGES, self.uv.shape[1])
+        with torch.cuda.device(self.device):
+            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
+            out = joint_tree_marginal(jerr, x, T, parent, self.N, mu, tau, self.conf)
+        return out + (jerr,)
 
     def compose(self, x_full, T_full, joint_idx, ref_idx=None):
         """The pose assembled from the joints aggregate_reproj selected: x_full [H*N,17,3], T_full [H*N,3] (all global rows), joint_idx
