@@ -64,7 +64,7 @@ MUTANTS = [
     ("ZEDO_MUT_JA_FIRST_DIFF", "zedo_joint_accel_select: the second difference is taken as X[n] - X[n-1] + X[n-2], the factor 2 is dropped (zedo_joint_accel.hip joint_accel_scan_kernel and joint_accel_cost_kernel)"),
     # the skeleton-coupled aggregation (tests/test_joint_tree_gpu.py, tests/test_select_joints_tree_driver_gpu.py) and, since its sum-product
     # twin shares the statement, the skeleton-coupled fusion's tests: leaves every other test green
-    ("ZEDO_MUT_TREE_NO_HALF", "zedo_joint_tree_select and zedo_joint_tree_marginal: the bone term compares the assembled length with the SUM of the two hypotheses' lengths, the 0.5 is dropped (zedo_internal.h tr_bone: the recurrences and bone[n,.])"),
+    ("ZEDO_MUT_TREE_NO_HALF", "zedo_joint_tree_select and zedo_joint_tree_marginal: the bone term compares the assembled length with the SUM of the two hypotheses' lengths, the 0.5 is dropped (zedo_chain.h tr_bone: the recurrences and bone[n,.])"),
     # the skeleton-coupled fusion (tests/test_joint_tree_marginal_gpu.py, tests/test_select_joints_tree_fused_driver_gpu.py): leaves every other
     # test green
     ("ZEDO_MUT_TREEMARG_NO_DOWN", "zedo_joint_tree_marginal: Dn = 0 on every joint - the downward pass is dropped, a joint hears from its subtree only (zedo_joint_tree_marginal.hip joint_tree_marginal_kernel)"),

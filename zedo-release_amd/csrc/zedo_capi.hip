@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <vector>
@@ -874,92 +875,109 @@ extern "C" int zedo_temporal_select(const double *d_unary, const float *d_x, con
     return ZEDO_OK;
 }
 
-// ---- joint-wise temporal selection: one chain per (clip, joint), no table of transition costs ----
+// ---- the joint-wise chain models: one chain per (clip, joint); the tables of a call live in the caller's workspace ----
+// the shapes an entry point and its *_workspace_bytes accept: at most h_cap hypotheses, N J and N J H within int
+static bool chain_dims_ok(int N, int H, int J, int h_cap) {
+    return N >= 1 && H >= 1 && J >= 1 && H <= h_cap && (long long)N * J <= INT_MAX && (long long)N * J * H <= INT_MAX;
+}
+
+// ZEDO_OK, or what the call returns: null pointers and ranges, the H cap and the int products, the weights (finite, >= 0) and the
+// temperature (finite, > 0; 1 where the model has none), the alignment of the workspace - the tables are float64 - (all ZEDO_E_BADARG),
+// then its size (ZEDO_E_WORKSPACE).
+static int chain_args_ok(std::initializer_list<const void *> required, int n_seq, int N, int H, int J, int h_cap,
+                         std::initializer_list<double> weights, double tau, const void *workspace, size_t workspace_bytes,
+                         size_t (*bytes)(int, int, int)) {
+    for (const void *p : required)
+        if (!p) return ZEDO_E_BADARG;
+    if (!workspace || n_seq < 1 || n_seq > N || !chain_dims_ok(N, H, J, h_cap)) return ZEDO_E_BADARG;
+    for (const double w : weights)
+        if (!std::isfinite(w) || w < 0.0) return ZEDO_E_BADARG;
+    if (!std::isfinite(tau) || !(tau > 0.0)) return ZEDO_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(workspace) & 7) return ZEDO_E_BADARG;
+    return workspace_bytes < bytes(N, H, J) ? ZEDO_E_WORKSPACE : ZEDO_OK;
+}
+
+constexpr int JOINT_CHAIN_HMAX = 1024, JOINT_ACCEL_HMAX = 64;      // the pair table of the second-order model is H x H in the LDS
+
 extern "C" size_t zedo_joint_temporal_workspace_bytes(int N, int H, int J) {
-    if (N < 1 || H < 1 || J < 1 || H > 1024 || (long long)N * J > INT_MAX || (long long)N * J * H > INT_MAX) return 0;
-    return joint_temporal_bytes(N, H, J);
+    return chain_dims_ok(N, H, J, JOINT_CHAIN_HMAX) ? joint_temporal_bytes(N, H, J) : 0;
 }
 
 extern "C" int zedo_joint_temporal_select(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
                                           int H, int N, int J, double lambda, void *d_workspace, size_t workspace_bytes, int *d_path_h,
                                           double *d_cost, void *stream) {
-    if (!d_junary || !d_x || !d_seq_start || !d_workspace || !d_path_h || !d_cost || H < 1 || N < 1 || J < 1 || n_seq < 1 || n_seq > N)
-        return ZEDO_E_BADARG;
-    if (H > 1024 || (long long)N * J > INT_MAX || (long long)N * J * H > INT_MAX) return ZEDO_E_BADARG;
-    if (!std::isfinite(lambda) || lambda < 0.0) return ZEDO_E_BADARG;
-    if (reinterpret_cast<uintptr_t>(d_workspace) & 7) return ZEDO_E_BADARG;              // the tables are float64
-    if (workspace_bytes < joint_temporal_bytes(N, H, J)) return ZEDO_E_WORKSPACE;
+    const int rc = chain_args_ok({d_junary, d_x, d_seq_start, d_path_h, d_cost}, n_seq, N, H, J, JOINT_CHAIN_HMAX, {lambda}, 1.0, d_workspace,
+                                 workspace_bytes, joint_temporal_bytes);
+    if (rc != ZEDO_OK) return rc;
     HIPCHK(launch_joint_temporal_select(d_junary, d_x, d_T, d_seq_start, n_seq, H, N, J, lambda, d_workspace, d_path_h, d_cost,
                                         (hipStream_t)stream));
     return ZEDO_OK;
 }
 
-// ---- posterior marginals of the joint-wise chain model: forward-backward per (clip, joint), A in the workspace ----
+// posterior marginals of the same chain model: forward-backward per (clip, joint), A in the workspace
 extern "C" size_t zedo_joint_marginal_workspace_bytes(int N, int H, int J) {
-    if (N < 1 || H < 1 || J < 1 || H > 1024 || (long long)N * J > INT_MAX || (long long)N * J * H > INT_MAX) return 0;
-    return joint_marginal_bytes(N, H, J);
+    return chain_dims_ok(N, H, J, JOINT_CHAIN_HMAX) ? joint_marginal_bytes(N, H, J) : 0;
 }
 
 extern "C" int zedo_joint_marginal(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq, int H,
                                    int N, int J, double lambda, double tau, void *d_workspace, size_t workspace_bytes, double *d_mean,
                                    double *d_cov, int *d_hmax, double *d_wmax, double *d_logz, double *d_w, void *stream) {
-    if (!d_junary || !d_x || !d_seq_start || !d_workspace || !d_mean || !d_cov || !d_hmax || !d_wmax || !d_logz || H < 1 || N < 1 ||
-        J < 1 || n_seq < 1 || n_seq > N)
-        return ZEDO_E_BADARG;
-    if (H > 1024 || (long long)N * J > INT_MAX || (long long)N * J * H > INT_MAX) return ZEDO_E_BADARG;
-    if (!std::isfinite(lambda) || lambda < 0.0) return ZEDO_E_BADARG;
-    if (!std::isfinite(tau) || !(tau > 0.0)) return ZEDO_E_BADARG;
-    if (reinterpret_cast<uintptr_t>(d_workspace) & 7) return ZEDO_E_BADARG;              // A is float64
-    if (workspace_bytes < joint_marginal_bytes(N, H, J)) return ZEDO_E_WORKSPACE;
+    const int rc = chain_args_ok({d_junary, d_x, d_seq_start, d_mean, d_cov, d_hmax, d_wmax, d_logz}, n_seq, N, H, J, JOINT_CHAIN_HMAX,
+                                 {lambda}, tau, d_workspace, workspace_bytes, joint_marginal_bytes);
+    if (rc != ZEDO_OK) return rc;
     HIPCHK(launch_joint_marginal(d_junary, d_x, d_T, d_seq_start, n_seq, H, N, J, lambda / tau, tau, d_workspace, d_mean, d_cov, d_hmax,
                                  d_wmax, d_logz, d_w, (hipStream_t)stream));
     return ZEDO_OK;
 }
 
-// ---- joint-wise selection with a second-order motion model: one chain over pairs per (clip, joint), the pair table in the LDS ----
+// the second-order motion model: one chain over pairs of hypotheses per (clip, joint)
 extern "C" size_t zedo_joint_accel_workspace_bytes(int N, int H, int J) {
-    if (N < 1 || H < 1 || J < 1 || H > 64 || (long long)N * J > INT_MAX || (long long)N * J * H > INT_MAX) return 0;
-    return joint_accel_bytes(N, H, J);
+    return chain_dims_ok(N, H, J, JOINT_ACCEL_HMAX) ? joint_accel_bytes(N, H, J) : 0;
 }
 
 extern "C" int zedo_joint_accel_select(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq, int H,
                                        int N, int J, double lambda_v, double lambda_a, void *d_workspace, size_t workspace_bytes,
                                        int *d_path_h, double *d_cost, void *stream) {
-    if (!d_junary || !d_x || !d_seq_start || !d_workspace || !d_path_h || !d_cost || H < 1 || N < 1 || J < 1 || n_seq < 1 || n_seq > N)
-        return ZEDO_E_BADARG;
-    if (H > 64 || (long long)N * J > INT_MAX || (long long)N * J * H > INT_MAX) return ZEDO_E_BADARG;
-    if (!std::isfinite(lambda_v) || lambda_v < 0.0 || !std::isfinite(lambda_a) || lambda_a < 0.0) return ZEDO_E_BADARG;
-    if (reinterpret_cast<uintptr_t>(d_workspace) & 7) return ZEDO_E_BADARG;              // as for the other chain models
-    if (workspace_bytes < joint_accel_bytes(N, H, J)) return ZEDO_E_WORKSPACE;
+    const int rc = chain_args_ok({d_junary, d_x, d_seq_start, d_path_h, d_cost}, n_seq, N, H, J, JOINT_ACCEL_HMAX, {lambda_v, lambda_a}, 1.0,
+                                 d_workspace, workspace_bytes, joint_accel_bytes);
+    if (rc != ZEDO_OK) return rc;
     HIPCHK(launch_joint_accel_select(d_junary, d_x, d_T, d_seq_start, n_seq, H, N, J, lambda_v, lambda_a, d_workspace, d_path_h, d_cost,
                                      (hipStream_t)stream));
     return ZEDO_OK;
 }
 
-// ---- skeleton-coupled joint-wise aggregation: min-sum over the bone tree, one workgroup per pose, no workspace ----
+// ---- the skeleton-coupled models: one workgroup per pose over the bone tree, everything in the LDS, no workspace ----
+// true, with the post-order of the bones in *tr, or the call is ZEDO_E_BADARG: null pointers and ranges, J, whether the kernel's tables
+// of H hypotheses (lds_bytes) fit the LDS, the int product, mu (finite, >= 0), tau (finite, > 0; 1 where the model has none) and their
+// ratio, a parent array that is not a forest.
+static bool tree_args_ok(std::initializer_list<const void *> required, const int *h_parent, int H, int N, int J,
+                         size_t (*lds_bytes)(int, int), double mu, double tau, TreeOrder *tr) {
+    for (const void *p : required)
+        if (!p) return false;
+    if (!h_parent || H < 1 || N < 1 || J < 1 || J > TR_JMAX || H > TR_HMAX || (long long)H * N * J > INT_MAX) return false;
+    if (lds_bytes(H, J) > TR_LDS) return false;
+    if (!std::isfinite(mu) || mu < 0.0 || !std::isfinite(tau) || !(tau > 0.0) || !std::isfinite(mu / tau)) return false;
+    return joint_tree_order(h_parent, J, tr);
+}
+
 extern "C" int zedo_joint_tree_select(const double *d_junary, const float *d_x, const float *d_T, const float *d_weight, const int *h_parent,
                                       int H, int N, int J, double mu, int *d_joint_h, double *d_cost, double *d_bone, void *stream) {
-    if (!d_junary || !d_x || !h_parent || !d_joint_h || !d_cost || !d_bone || H < 1 || N < 1 || J < 1) return ZEDO_E_BADARG;
-    if (J > TR_JMAX || H > TR_HMAX || joint_tree_lds_bytes(H, J) > TR_LDS || (long long)H * N * J > INT_MAX) return ZEDO_E_BADARG;
-    if (!std::isfinite(mu) || mu < 0.0) return ZEDO_E_BADARG;
     TreeOrder tr;
-    if (!joint_tree_order(h_parent, J, &tr)) return ZEDO_E_BADARG;
+    if (!tree_args_ok({d_junary, d_x, d_joint_h, d_cost, d_bone}, h_parent, H, N, J, joint_tree_lds_bytes, mu, 1.0, &tr)) return ZEDO_E_BADARG;
     HIPCHK(launch_joint_tree_select(d_junary, d_x, d_T, d_weight, tr, H, N, J, mu, d_joint_h, d_cost, d_bone, (hipStream_t)stream));
     return ZEDO_OK;
 }
 
-// ---- skeleton-coupled fusion per pose: sum-product over the bone tree, one workgroup per pose, no workspace ----
+// sum-product over the same tree
 extern "C" int zedo_joint_tree_marginal_max_h(int J) { return joint_tree_marginal_max_h(J); }
 
 extern "C" int zedo_joint_tree_marginal(const double *d_junary, const float *d_x, const float *d_T, const float *d_weight, const int *h_parent,
                                         int H, int N, int J, double mu, double tau, double *d_mean, double *d_cov, int *d_hmax, double *d_wmax,
                                         double *d_logz, double *d_bone, double *d_w, void *stream) {
-    if (!d_junary || !d_x || !h_parent || !d_mean || !d_cov || !d_hmax || !d_wmax || !d_logz || !d_bone || H < 1 || N < 1 || J < 1)
-        return ZEDO_E_BADARG;
-    if (J > TR_JMAX || H > joint_tree_marginal_max_h(J) || (long long)H * N * J > INT_MAX) return ZEDO_E_BADARG;
-    if (!std::isfinite(mu) || mu < 0.0 || !std::isfinite(tau) || !(tau > 0.0) || !std::isfinite(mu / tau)) return ZEDO_E_BADARG;
     TreeOrder tr;
-    if (!joint_tree_order(h_parent, J, &tr)) return ZEDO_E_BADARG;
+    if (!tree_args_ok({d_junary, d_x, d_mean, d_cov, d_hmax, d_wmax, d_logz, d_bone}, h_parent, H, N, J, joint_tree_marginal_lds_bytes, mu, tau,
+                      &tr))
+        return ZEDO_E_BADARG;
     HIPCHK(launch_joint_tree_marginal(d_junary, d_x, d_T, d_weight, tr, H, N, J, mu / tau, tau, d_mean, d_cov, d_hmax, d_wmax, d_logz, d_bone,
                                       d_w, (hipStream_t)stream));
     return ZEDO_OK;

@@ -1,0 +1,206 @@
+// What the label-free selection and fusion kernels share (zedo_temporal.hip, zedo_joint_temporal.hip, zedo_joint_marginal.hip,
+// zedo_joint_accel.hip, zedo_joint_tree.hip, zedo_joint_tree_marginal.hip): the one copy of their lane layout, their reductions and their
+// staging.  The rules every user relies on live here and nowhere else:
+//   - a tie goes to the lowest index (strict comparisons, parts and waves combined in ascending order);
+//   - a sum is a butterfly inside each wave, then the waves in ascending order: a fixed order, no atomics;
+//   - a lane past H reads row H-1 and stores nothing;
+//   - an offset read from seq_start is clamped to 0 .. N before it is an address.
+// The recurrences themselves - what is minimised or summed - stay in their own files.
+#pragma once
+#include "zedo_internal.h"
+
+#include <climits>
+#include <cstdint>
+#include <type_traits>
+
+namespace zedo {
+
+constexpr int CHAIN_T = 256, CHAIN_W = CHAIN_T / 64;               // the workgroup of every kernel of this family: four waves
+
+__device__ __forceinline__ bool finite64(double v) { return fabs(v) < __builtin_huge_val(); }   // false for NaN and +-inf
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// X[n,h,j,.] in the camera frame: (double)x + (T ? (double)T : 0) of row g = h N + n
+__device__ __forceinline__ void load_cam(const float *__restrict__ x, const float *__restrict__ T, size_t g, int J, int j, double out[3]) {
+    const float *px = x + (g * J + j) * 3;
+    const float *pt = T ? T + g * 3 : nullptr;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c] = (double)px[c] + (pt ? (double)pt[c] : 0.0);
+}
+
+// Workgroup w of a grid of n_seq J serves clip s = w / J, joint j = w % J (the J chains of a clip are neighbours in the grid), frames
+// a .. b-1.  An empty clip (a >= b) is workgroup-uniform: the kernel returns.
+struct ClipJoint { int s, j, a, b; };
+__device__ __forceinline__ ClipJoint clip_joint(const int *__restrict__ seq_start, int N, int J) {
+    const int s = blockIdx.x / J;
+    return {s, (int)blockIdx.x - s * J, clampi(seq_start[s], 0, N), clampi(seq_start[s + 1], 0, N)};
+}
+
+// ---- the lane split: CHAIN_T lanes as P parts x CHAIN_T / P slots ----
+// The lane (part, slot) owns the outer index slot (+ SLOTS, .. : K of them) and walks ONE part of the inner index, q0 .. q1-1 of
+// 0 .. H-1 (ceil(H / P) consecutive ones; part 0 is never empty, np parts are not).  The parts' results meet in the LDS and part 0
+// combines them in ascending part order.  H -> P: 4 (H <= 64), 2 (H <= 128), else 1, and then K = 1 (H <= 256), 2 (H <= 512) or 4 (H <=
+// 1024): no lane walks for an index nobody owns beyond the last, partly filled group.  chain_parts and dispatch_pk are the only places
+// that know these numbers.
+__host__ __device__ constexpr int chain_parts(int H) { return H <= CHAIN_T / 4 ? 4 : (H <= CHAIN_T / 2 ? 2 : 1); }
+
+struct Lanes {
+    int slots, part, slot, q0, q1, np;
+    __device__ __forceinline__ Lanes(int tid, int H, int P) : slots(CHAIN_T / P), part(tid / slots), slot(tid - part * slots) {
+        const int per = (H + P - 1) / P;
+        q0 = min(H, part * per);
+        q1 = min(H, q0 + per);
+        np = (H + per - 1) / per;
+    }
+};
+// P fixed by the instantiation; a kernel whose H is only known at run time (the tree kernels) uses Lanes(tid, H, chain_parts(H))
+template <int P, int K>
+struct ChainLanes : Lanes {
+    static_assert(P == 1 || K == 1, "a lane owns several hypotheses only where the inner index is not split");
+    static constexpr int SLOTS = CHAIN_T / P, CAP = K * SLOTS;     // CAP: the hypotheses the instantiation holds in the LDS
+    __device__ __forceinline__ ChainLanes(int tid, int H) : Lanes(tid, H, P) {}
+};
+
+// f(integral_constant<int, P>, integral_constant<int, K>) of the instantiation that serves H <= 4 CHAIN_T
+template <int V>
+using IntC = std::integral_constant<int, V>;
+template <class F>
+inline void dispatch_pk(int H, F &&f) {
+    const int P = chain_parts(H);
+    if (P == 4) f(IntC<4>(), IntC<1>());
+    else if (P == 2) f(IntC<2>(), IntC<1>());
+    else if (H <= CHAIN_T) f(IntC<1>(), IntC<1>());
+    else if (H <= 2 * CHAIN_T) f(IntC<1>(), IntC<2>());
+    else f(IntC<1>(), IntC<4>());
+}
+
+// ---- reductions ----
+// The best v (MAX: the largest, otherwise the smallest) and the lowest h that holds it; h = INT_MAX: no entry.  Every lane gets both.
+template <bool MAX>
+__device__ __forceinline__ bool arg_better(double ov, int oh, double v, int h) {
+    return (MAX ? ov > v : ov < v) || (ov == v && oh < h);
+}
+template <bool MAX>
+__device__ __forceinline__ void wave_arg(double &v, int &h) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ov = __shfl_xor(v, off);
+        const int oh = __shfl_xor(h, off);
+        if (arg_better<MAX>(ov, oh, v, h)) { v = ov; h = oh; }
+    }
+}
+// over the workgroup's nw waves, in ascending wave order; sred, sredi: nw entries of the LDS.  One barrier; the caller puts another
+// between this and its next write to sred / sredi (the barriers of the next frame do where a kernel reduces once per frame).
+template <bool MAX>
+__device__ __forceinline__ void block_arg(double &v, int &h, double *sred, int *sredi, int tid, int nw = CHAIN_W) {
+    wave_arg<MAX>(v, h);
+    if ((tid & 63) == 0) { sred[tid >> 6] = v; sredi[tid >> 6] = h; }
+    __syncthreads();
+    v = sred[0];
+    h = sredi[0];
+    for (int w = 1; w < nw; ++w)
+        if (arg_better<MAX>(sred[w], sredi[w], v, h)) { v = sred[w]; h = sredi[w]; }
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    return v;
+}
+// the sum of v over the wave, a butterfly: every lane gets it
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+// sums of NV values over the CHAIN_W waves of the workgroup: a butterfly inside each wave, then the waves ascending; every lane gets
+// the sums.  sred: CHAIN_W NV doubles of the LDS, free again on return.
+template <int NV>
+__device__ __forceinline__ void block_sum(double (&v)[NV], double *sred, int tid) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
+    if ((tid & 63) == 0)
+#pragma unroll
+        for (int i = 0; i < NV; ++i) sred[(tid >> 6) * NV + i] = v[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        double s = sred[i];
+        for (int w = 1; w < CHAIN_W; ++w) s += sred[w * NV + i];
+        v[i] = s;
+    }
+    __syncthreads();
+}
+
+// ---- the bone tree: one workgroup per pose, everything in the LDS ----
+// sqrt(d0^2 + d1^2 + d2^2), d = a - b: products, then the sum ascending in c
+__device__ __forceinline__ double tr_dist(const double *a, double b0, double b1, double b2) {
+    const double d0 = a[0] - b0, d1 = a[1] - b1, d2 = a[2] - b2;
+    return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+}
+// the bone term of one pair, in metres: exactly 0 when both ends come from one hypothesis (mix and both own are then the same bits)
+__device__ __forceinline__ double tr_bone(double mix, double own_c, double own_p) {
+#ifdef ZEDO_MUT_TREE_NO_HALF   // tools/mutation_check.py only: the two hypotheses' lengths are summed, not averaged
+    return fabs(mix - (own_c + own_p));
+#else
+    return fabs(mix - 0.5 * (own_c + own_p));
+#endif
+}
+// Pose n's tables, staged once.  sX [J][H][3]: the camera-frame positions - H runs of 12 J bytes at a stride of N J 3 floats, consecutive
+// lanes read consecutive floats of a row.  Joint-major, so the lanes of a wave read X[j][h] of consecutive h - fp64 triples at a stride of
+// 6 dwords, which 32 lanes spread over the 64 banks without a conflict (ds_read_b64 is served in groups of 32 lanes, bank = dword address
+// mod 64) - or all the same h: a broadcast.  sS [J][H]: score(w u) of the unary u weighted by the confidence w (the clamp of
+// zedo_min_reproj, taken in fp32: NaN stays NaN), `excluded` where w u is not finite.  sLive [J]: does the joint have a hypothesis that
+// is not excluded - a wave per joint, by ballot.  sZero (may be null): a table [J][H] zeroed in the same pass.  Ends WITHOUT a barrier:
+// sLive is visible after the caller's next one.
+template <class Score>
+__device__ __forceinline__ void tree_stage(const double *__restrict__ junary, const float *__restrict__ x, const float *__restrict__ Tr,
+                                           const float *__restrict__ weight, size_t n, int H, int N, int J, double excluded, Score score,
+                                           double *sX, double *sS, int *sLive, double *sZero = nullptr) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, JH = J * H, J3 = 3 * J;
+    for (int e = tid; e < 3 * JH; e += CHAIN_T) {
+        const int h = e / J3, r = e - h * J3, j = r / 3, c = r - 3 * j;
+        const size_t row = (size_t)h * N + n;
+        sX[(j * H + h) * 3 + c] = (double)x[row * J3 + r] + (Tr ? (double)Tr[row * 3 + c] : 0.0);
+    }
+    for (int e = tid; e < JH; e += CHAIN_T) {
+        const int h = e / J, j = e - h * J;
+        double w = 1.0;
+        if (weight) {
+            float c = weight[n * J + j];
+            if (c > 1.0f) c = 1.0f;
+            if (c < 1e-4f) c = 1e-4f;
+            w = (double)c;
+        }
+        const double u = w * junary[((size_t)h * N + n) * J + j];
+        sS[j * H + h] = finite64(u) ? score(u) : excluded;
+        if (sZero) sZero[j * H + h] = 0.0;
+    }
+    __syncthreads();
+    for (int j = wave; j < J; j += CHAIN_W) {
+        int any = 0;
+        for (int h = lane; h < H; h += 64) any |= sS[j * H + h] != excluded ? 1 : 0;
+        const bool live = __ballot(any) != 0;
+        if (lane == 0) sLive[j] = live ? 1 : 0;
+    }
+}
+
+// ---- the workspace of an entry point, carved in ONE place: its size is where the carving ends ----
+// take<T>(n): n elements of T at the next offset aligned for T.  With ws = nullptr only bytes() means anything.  A layout struct holds
+// a Carve as its FIRST member and initialises its tables from it in the order they are declared.
+class Carve {
+    uintptr_t base_;
+    size_t off_ = 0;
+
+public:
+    explicit Carve(void *ws) : base_(reinterpret_cast<uintptr_t>(ws)) {}
+    template <class T>
+    T *take(size_t n) {
+        off_ = (off_ + alignof(T) - 1) & ~(alignof(T) - 1);
+        T *const p = reinterpret_cast<T *>(base_ + off_);
+        off_ += n * sizeof(T);
+        return p;
+    }
+    size_t bytes(size_t align = 1) const { return (off_ + align - 1) & ~(align - 1); }
+};
+
+}  // namespace zedo

@@ -256,7 +256,7 @@ hipError_t launch_joint_accel_select(const double *junary, const float *x, const
 // skeleton-coupled joint-wise aggregation (zedo_joint_tree.hip): min-sum over the bone tree, one workgroup per pose, everything in the
 // LDS - joint_tree_lds_bytes(H, J) = 34 J H + 16 H + 4096 of the CU's TR_LDS bytes.  The host derives the post-order of the bones
 // (joint_tree_order: false for a parent array that is not a forest) and hands it to the kernel by value.
-constexpr int TR_T = 256, TR_JMAX = 64, TR_HMAX = 1024;
+constexpr int TR_JMAX = 64, TR_HMAX = 1024;
 constexpr size_t TR_LDS = 160 * 1024;
 struct TreeOrder {
     signed char parent[TR_JMAX];      // -1: a root
@@ -266,21 +266,6 @@ size_t joint_tree_lds_bytes(int H, int J);
 bool joint_tree_order(const int *parent, int J, TreeOrder *out);
 hipError_t launch_joint_tree_select(const double *junary, const float *x, const float *T, const float *weight, const TreeOrder &tr, int H,
                                     int N, int J, double mu, int *joint_h, double *cost, double *bone, hipStream_t st);
-// the statements of the bone term, shared by the min-sum kernel and its sum-product twin (zedo_joint_tree_marginal.hip)
-__device__ __forceinline__ bool tr_finite64(double v) { return fabs(v) < __builtin_huge_val(); }   // false for NaN and +-inf
-// sqrt(d0^2 + d1^2 + d2^2), d = a - b: products, then the sum ascending in c
-__device__ __forceinline__ double tr_dist(const double *a, double b0, double b1, double b2) {
-    const double d0 = a[0] - b0, d1 = a[1] - b1, d2 = a[2] - b2;
-    return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-}
-// the bone term of one pair, in metres: exactly 0 when both ends come from one hypothesis (mix and both own are then the same bits)
-__device__ __forceinline__ double tr_bone(double mix, double own_c, double own_p) {
-#ifdef ZEDO_MUT_TREE_NO_HALF   // tools/mutation_check.py only: the two hypotheses' lengths are summed, not averaged
-    return fabs(mix - (own_c + own_p));
-#else
-    return fabs(mix - 0.5 * (own_c + own_p));
-#endif
-}
 // posterior marginals of the same energy (zedo_joint_tree_marginal.hip): sum-product over the bone tree, one workgroup per pose, everything
 // in the LDS - joint_tree_marginal_lds_bytes(H, J) = 48 J H + 16 H + 8192 of the CU's TR_LDS bytes; c = mu / tau.
 // joint_tree_marginal_max_h(J): the largest H that fits (at most TR_HMAX), 0 for a J outside 1 .. TR_JMAX.

@@ -8,21 +8,11 @@
 //   joint_accel_backtrack_kernel  the backward pass, one workgroup per (clip, joint), runs of back2 staged through the LDS
 //   joint_accel_cost_kernel       the cost of the kept path re-accumulated along it, one workgroup per (clip, joint): the terms of a run of
 //                                 frames in parallel, their sum by one lane in ascending frame order
-// Workgroup w serves clip w / J, joint w % J, as in zedo_joint_temporal.hip.  E is never stored for all frames.  No atomics.
-#include "zedo_internal.h"
+// The (clip, joint) of a workgroup, the camera-frame load and the arg-min reduction are zedo_chain.h's.  E is never stored for all
+// frames.  No atomics.
+#include "zedo_chain.h"
 
 namespace zedo {
-
-__device__ __forceinline__ bool ja_finite64(double v) { return fabs(v) < __builtin_huge_val(); }   // false for NaN and +-inf
-__device__ __forceinline__ int ja_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// X[n,h,j,.] = (double)x + (d_T ? (double)T : 0) of row g = h N + n
-__device__ __forceinline__ void ja_load_x(const float *__restrict__ x, const float *__restrict__ Tr, size_t g, int J, int j, double out[3]) {
-    const float *px = x + (g * J + j) * 3;
-    const float *pt = Tr ? Tr + g * 3 : nullptr;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[c] = (double)px[c] + (pt ? (double)pt[c] : 0.0);
-}
 
 // The forward recurrence of one (clip, joint).  The H^2 pairs q = h' H + h are dealt to the 256 lanes round robin: lane t owns the KA
 // pairs q = t, t + 256, ..; KA = 1 (H <= 16), 2 (H <= 22), 4 (H <= 32), 7 (H <= 42), 10 (H <= 50), 13 (H <= 57) or 16 (H <= JA_CAP = 64):
@@ -37,26 +27,26 @@ __device__ __forceinline__ void ja_load_x(const float *__restrict__ x, const flo
 //   second (n-1 is a start):  E[n][h',h] = u[n-1,h'] + (u[n,h] + lambda_v m[n,h',h])
 //   otherwise:  E[n][h',h] = u[n,h] + (lambda_v m[n,h',h] + min_h'' (E[n-1][h'',h'] + lambda_a a[n,h'',h',h])), back2 = the lowest h''
 // A frame that ends a chain also gets endq: the lowest q = h' H + h that minimises E[n] (of a one-frame chain: the lowest h).
-constexpr int JA_T = 256, JA_CAP = 64;
+constexpr int JA_CAP = 64;
 template <int KA>
-__global__ __launch_bounds__(JA_T) void joint_accel_scan_kernel(const double *__restrict__ junary, const float *__restrict__ x,
+__global__ __launch_bounds__(CHAIN_T) void joint_accel_scan_kernel(const double *__restrict__ junary, const float *__restrict__ x,
                                                                 const float *__restrict__ Tr, const int *__restrict__ seq_start,
                                                                 const int *__restrict__ dead, int H, int N, int J, double lambda_v,
                                                                 double lambda_a, unsigned char *__restrict__ back2, int *__restrict__ endq) {
     __shared__ double sE[JA_CAP * JA_CAP];
     __shared__ double sX[3][JA_CAP * 3], sU[2][JA_CAP];
-    __shared__ double rv[JA_T / 64];
-    __shared__ int rq[JA_T / 64];
+    __shared__ double rv[CHAIN_W];
+    __shared__ int rq[CHAIN_W];
     const int tid = threadIdx.x, HH = H * H;
-    const int s = blockIdx.x / J, j = blockIdx.x - s * J;
-    const int a = ja_clampi(seq_start[s], 0, N), b = ja_clampi(seq_start[s + 1], 0, N);
+    const ClipJoint cj = clip_joint(seq_start, N, J);
+    const int j = cj.j, a = cj.a, b = cj.b;
     if (a >= b) return;                                            // (workgroup-uniform)
     const double inf = __builtin_huge_val();
     // this lane's pairs (a pair past H^2 is computed as pair H^2 - 1 and stored nowhere)
     int qh1[KA], qh0[KA];                                          // h' and h of pair k
 #pragma unroll
     for (int k = 0; k < KA; ++k) {
-        const int q = min(tid + k * JA_T, HH - 1);
+        const int q = min(tid + k * CHAIN_T, HH - 1);
         qh1[k] = q / H;
         qh0[k] = q - qh1[k] * H;
     }
@@ -64,9 +54,9 @@ __global__ __launch_bounds__(JA_T) void joint_accel_scan_kernel(const double *__
     double xn[3], un;
     auto fetch = [&](int n) {
         const size_t g = (size_t)min(tid, H - 1) * N + n;
-        ja_load_x(x, Tr, g, J, j, xn);
+        load_cam(x, Tr, g, J, j, xn);
         const double u0 = junary[g * J + j];
-        un = ja_finite64(u0) ? u0 : inf;
+        un = finite64(u0) ? u0 : inf;
     };
     int s0 = 0, s1 = 2, s2 = 1;                                    // the slots of X[n], X[n-1], X[n-2]
     fetch(a);
@@ -127,17 +117,17 @@ __global__ __launch_bounds__(JA_T) void joint_accel_scan_kernel(const double *__
             }
         }
         double v = inf;                                            // a chain of one frame: the candidates are u[n,.]
-        int vq = 0x7fffffff;
+        int vq = INT_MAX;
         if (ends && start && tid < H) { v = U0[tid]; vq = tid; }
         __syncthreads();                                           // B: the LDS of frame n has been read by every lane
         if (scan) {
 #pragma unroll
             for (int k = 0; k < KA; ++k) {
-                const int q = tid + k * JA_T;
+                const int q = tid + k * CHAIN_T;
                 if (q < HH) {
                     sE[q] = en[k];                                 // E[n][h',h] at h' H + h: the next frame reads it h''-major
                     if (!second) back_j[(size_t)n * HH + q] = (unsigned char)bn[k];
-                    if (en[k] < v || (en[k] == v && q < vq)) { v = en[k]; vq = q; }      // (q ascends with k)
+                    if (arg_better<false>(en[k], q, v, vq)) { v = en[k]; vq = q; }       // (q ascends with k)
                 }
             }
         }
@@ -147,19 +137,8 @@ __global__ __launch_bounds__(JA_T) void joint_accel_scan_kernel(const double *__
         }
         { const int t = s2; s2 = s1; s1 = s0; s0 = t; }
         if (ends) {                                                // (workgroup-uniform) the lowest arg-min, from the owners' registers
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                const double ov = __shfl_xor(v, off);
-                const int oq = __shfl_xor(vq, off);
-                if (ov < v || (ov == v && oq < vq)) { v = ov; vq = oq; }
-            }
-            if ((tid & 63) == 0) { rv[tid >> 6] = v; rq[tid >> 6] = vq; }
-            __syncthreads();
-            if (tid == 0) {
-                for (int w = 1; w < JA_T / 64; ++w)
-                    if (rv[w] < v || (rv[w] == v && rq[w] < vq)) { v = rv[w]; vq = rq[w]; }
-                endq[nj] = vq == 0x7fffffff ? 0 : vq;
-            }
+            block_arg<false>(v, vq, rv, rq, tid);
+            if (tid == 0) endq[nj] = vq == INT_MAX ? 0 : vq;
         }
     }
 }
@@ -178,8 +157,8 @@ __global__ __launch_bounds__(256) void joint_accel_backtrack_kernel(const int *_
     __shared__ int sdead[JAB_RUN + 1], send[JAB_RUN], spath[JAB_RUN];
     __shared__ int carry[4];                                       // lane 0's state between runs: known successors, path[n+1], path[n+2], h'
     const int tid = threadIdx.x, T = blockDim.x, HH = H * H;
-    const int s = blockIdx.x / J, j = blockIdx.x - s * J;
-    const int a = ja_clampi(seq_start[s], 0, N), b = ja_clampi(seq_start[s + 1], 0, N);
+    const ClipJoint cj = clip_joint(seq_start, N, J);
+    const int j = cj.j, a = cj.a, b = cj.b;
     if (a >= b) return;
     const int R = min(JAB_RUN, JAB_BYTES / HH);
     const unsigned char *const back_j = back2 + (size_t)j * N * HH;
@@ -203,15 +182,15 @@ __global__ __launch_bounds__(256) void joint_accel_backtrack_kernel(const int *_
                 if (sdead[i + 1]) have = 0;
                 else {
                     if (have == 0) {                               // the last frame of a chain
-                        if (sdead[i]) p = ja_clampi(send[i], 0, H - 1);          // .. of one frame
+                        if (sdead[i]) p = clampi(send[i], 0, H - 1);          // .. of one frame
                         else {
-                            const int q = ja_clampi(send[i], 0, HH - 1);
+                            const int q = clampi(send[i], 0, HH - 1);
                             pend = q / H;
                             p = q - pend * H;
                             have = 1;
                         }
                     } else if (have == 1) { p = pend; have = 2; }
-                    else p = ja_clampi(sb[i * HH + pa * H + pb], 0, H - 1);
+                    else p = clampi(sb[i * HH + pa * H + pb], 0, H - 1);
                     pb = pa;
                     pa = p;
                 }
@@ -234,8 +213,8 @@ __global__ __launch_bounds__(256) void joint_accel_cost_kernel(const double *__r
     __shared__ double st[256];
     __shared__ int sk[256];                                        // 0 dead, 1 start, 2 inside a chain
     const int tid = threadIdx.x;
-    const int s = blockIdx.x / J, j = blockIdx.x - s * J;
-    const int a = ja_clampi(seq_start[s], 0, N), b = ja_clampi(seq_start[s + 1], 0, N);
+    const ClipJoint cj = clip_joint(seq_start, N, J);
+    const int j = cj.j, a = cj.a, b = cj.b;
     if (a >= b) return;
     const double inf = __builtin_huge_val();
     double acc = 0.0;                                              // lane 0: cost[n-1]
@@ -249,21 +228,21 @@ __global__ __launch_bounds__(256) void joint_accel_cost_kernel(const double *__r
             if (!dead[nj]) {
                 const bool start = (n > a ? dead[nj - J] : 1) != 0;
                 const bool second = !start && (n - 1 > a ? dead[nj - 2 * (size_t)J] : 1) != 0;
-                const int p0 = ja_clampi(path[nj], 0, H - 1);
+                const int p0 = clampi(path[nj], 0, H - 1);
                 const double u0 = junary[((size_t)p0 * N + n) * J + j];
-                t = ja_finite64(u0) ? u0 : inf;
+                t = finite64(u0) ? u0 : inf;
                 kind = 1;
                 if (!start) {
-                    const int p1 = ja_clampi(path[nj - J], 0, H - 1);
+                    const int p1 = clampi(path[nj - J], 0, H - 1);
                     double X0[3], X1[3];
-                    ja_load_x(x, Tr, (size_t)p0 * N + n, J, j, X0);
-                    ja_load_x(x, Tr, (size_t)p1 * N + n - 1, J, j, X1);
+                    load_cam(x, Tr, (size_t)p0 * N + n, J, j, X0);
+                    load_cam(x, Tr, (size_t)p1 * N + n - 1, J, j, X1);
                     const double d0 = X0[0] - X1[0], d1 = X0[1] - X1[1], d2 = X0[2] - X1[2];
                     double w = lambda_v * sqrt(d0 * d0 + d1 * d1 + d2 * d2);
                     if (!second) {
-                        const int p2 = ja_clampi(path[nj - 2 * (size_t)J], 0, H - 1);
+                        const int p2 = clampi(path[nj - 2 * (size_t)J], 0, H - 1);
                         double X2[3];
-                        ja_load_x(x, Tr, (size_t)p2 * N + n - 2, J, j, X2);
+                        load_cam(x, Tr, (size_t)p2 * N + n - 2, J, j, X2);
 #ifdef ZEDO_MUT_JA_FIRST_DIFF
                         const double e0 = (X0[0] - X1[0]) + X2[0], e1 = (X0[1] - X1[1]) + X2[1], e2 = (X0[2] - X1[2]) + X2[2];
 #else
@@ -292,33 +271,36 @@ __global__ __launch_bounds__(256) void joint_accel_cost_kernel(const double *__r
 }
 
 // Workspace: back2 [J,N,H,H] u8 (padded to 4 bytes) | dead [N,J] i32, endq [N,J] i32
-size_t joint_accel_bytes(int N, int H, int J) {
-    const size_t nj = (size_t)N * J;
-    return ((nj * H * H + 3) & ~(size_t)3) + nj * 8;
-}
+struct JointAccelWs {
+    Carve c;
+    unsigned char *back2;
+    int *dead, *endq;
+    size_t bytes;
+    JointAccelWs(void *ws, size_t nj, size_t H)
+        : c(ws), back2(c.take<unsigned char>(nj * H * H)), dead(c.take<int>(nj)), endq(c.take<int>(nj)), bytes(c.bytes()) {}
+};
+size_t joint_accel_bytes(int N, int H, int J) { return JointAccelWs(nullptr, (size_t)N * J, H).bytes; }
 
 hipError_t launch_joint_accel_select(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,
                                      int J, double lambda_v, double lambda_a, void *ws, int *path, double *cost, hipStream_t st) {
-    const size_t nj = (size_t)N * J;
-    unsigned char *back2 = static_cast<unsigned char *>(ws);
-    int *dead = reinterpret_cast<int *>(back2 + ((nj * H * H + 3) & ~(size_t)3)), *endq = dead + nj;
+    const JointAccelWs w(ws, (size_t)N * J, H);
     const dim3 grid((unsigned)n_seq * (unsigned)J);                // n_seq <= N and N J H <= INT_MAX
-    const hipError_t e = launch_joint_temporal_dead(junary, H, (int)nj, dead, st);
+    const hipError_t e = launch_joint_temporal_dead(junary, H, N * J, w.dead, st);
     if (e != hipSuccess) return e;
 #define ZEDO_JA_SCAN(KA)                                                                                                               \
-    hipLaunchKernelGGL((joint_accel_scan_kernel<KA>), grid, dim3(JA_T), 0, st, junary, x, T, seq_start, dead, H, N, J, lambda_v, lambda_a, \
-                       back2, endq)
+    hipLaunchKernelGGL((joint_accel_scan_kernel<KA>), grid, dim3(CHAIN_T), 0, st, junary, x, T, seq_start, w.dead, H, N, J, lambda_v, lambda_a, \
+                       w.back2, w.endq)
     const int HH = H * H;
-    if (HH <= JA_T) ZEDO_JA_SCAN(1);
-    else if (HH <= 2 * JA_T) ZEDO_JA_SCAN(2);
-    else if (HH <= 4 * JA_T) ZEDO_JA_SCAN(4);
-    else if (HH <= 7 * JA_T) ZEDO_JA_SCAN(7);
-    else if (HH <= 10 * JA_T) ZEDO_JA_SCAN(10);
-    else if (HH <= 13 * JA_T) ZEDO_JA_SCAN(13);
+    if (HH <= CHAIN_T) ZEDO_JA_SCAN(1);
+    else if (HH <= 2 * CHAIN_T) ZEDO_JA_SCAN(2);
+    else if (HH <= 4 * CHAIN_T) ZEDO_JA_SCAN(4);
+    else if (HH <= 7 * CHAIN_T) ZEDO_JA_SCAN(7);
+    else if (HH <= 10 * CHAIN_T) ZEDO_JA_SCAN(10);
+    else if (HH <= 13 * CHAIN_T) ZEDO_JA_SCAN(13);
     else ZEDO_JA_SCAN(16);
 #undef ZEDO_JA_SCAN
-    hipLaunchKernelGGL(joint_accel_backtrack_kernel, grid, dim3(256), 0, st, seq_start, dead, endq, back2, H, N, J, path);
-    hipLaunchKernelGGL(joint_accel_cost_kernel, grid, dim3(256), 0, st, junary, x, T, seq_start, dead, path, H, N, J, lambda_v, lambda_a,
+    hipLaunchKernelGGL(joint_accel_backtrack_kernel, grid, dim3(256), 0, st, seq_start, w.dead, w.endq, w.back2, H, N, J, path);
+    hipLaunchKernelGGL(joint_accel_cost_kernel, grid, dim3(256), 0, st, junary, x, T, seq_start, w.dead, path, H, N, J, lambda_v, lambda_a,
                        cost);
     return hipGetLastError();
 }

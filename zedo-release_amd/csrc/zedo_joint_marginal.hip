@@ -6,21 +6,16 @@
 //   joint_marginal_forward_kernel   A[n,j,.], one workgroup per (clip, joint), written to the workspace
 //   joint_marginal_backward_kernel  B[n,j,.] from the clip's end, one workgroup per (clip, joint); B never leaves the LDS: the marginals,
 //                                   the mean, the covariance and the arg-max of a frame are formed where its B is
-// Both recurrences are the scan kernel's with (min, +) replaced by (log-sum-exp, +): the same P parts x 256 / P slots, the same K
-// hypotheses per lane, the same two barriers per frame and the same fetch of the next frame before the first of them.  A log-sum-exp
+// Both recurrences are a Viterbi scan with (min, +) replaced by (log-sum-exp, +), on the lane split of zedo_chain.h (whose clip
+// prologue and reductions they use as well): two barriers per frame, the next frame fetched before the first of them.  A log-sum-exp
 // takes two walks over the h': the first finds the largest term, the second adds exp(term - largest) in ascending h' - shifted by
 // the TRUE maximum of the terms, so at a small tau the largest term contributes exactly 1 and nothing that matters underflows.  The
 // transition cost of a pair is recomputed in the second walk (one square root of three terms) rather than kept.  With P > 1 every part
 // shifts by its own maximum and part 0 combines (max_p, sum_p) in ascending part order.  Sums over the hypotheses of a frame (log Z, the
-// mean, the covariance) are a butterfly inside each wave, then the four waves in ascending order: a fixed order, no atomics.
-#include "zedo_internal.h"
+// mean, the covariance) are block_sum's: a fixed order, no atomics.
+#include "zedo_chain.h"
 
 namespace zedo {
-
-__device__ __forceinline__ bool jm_finite64(double v) { return fabs(v) < __builtin_huge_val(); }   // false for NaN and +-inf
-__device__ __forceinline__ int jm_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-constexpr int JM_T = 256, JM_W = JM_T / 64;                        // H <= 4 JM_T = 1024: a lane owns at most four hypotheses
 
 // One lane's share of LSE_h' (sV[h'] - c |xc[k] - sX[h']|) over h' = q0 .. q1-1, for each of its K hypotheses: mx = the largest term
 // (-inf if the share has none above -inf), sm = sum exp(term - mx) ascending in h' (shifted by 0 where mx is -inf: every exp is 0).
@@ -76,73 +71,34 @@ __device__ __forceinline__ double jm_combine(double mx, double sm, const double 
     return mx + log(sm);
 }
 
-// Sums of NV values over the workgroup in a fixed order: a butterfly inside each wave, then the waves ascending; every lane gets the sums.
-template <int NV>
-__device__ __forceinline__ void jm_block_sum(double (&v)[NV], double *sred, int tid) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) v[i] += __shfl_xor(v[i], off);
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int i = 0; i < NV; ++i) sred[(tid >> 6) * NV + i] = v[i];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        double s = sred[i];
-        for (int w = 1; w < JM_W; ++w) s += sred[w * NV + i];
-        v[i] = s;
-    }
-    __syncthreads();
-}
-
-// The largest v of the workgroup and the lowest h that holds it (h = INT_MAX: no entry); every lane gets both.
-__device__ __forceinline__ void jm_block_max(double &v, int &h, double *sred, int *sredi, int tid) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double ov = __shfl_xor(v, off);
-        const int oh = __shfl_xor(h, off);
-        if (ov > v || (ov == v && oh < h)) { v = ov; h = oh; }
-    }
-    if ((tid & 63) == 0) { sred[tid >> 6] = v; sredi[tid >> 6] = h; }
-    __syncthreads();
-    v = sred[0];
-    h = sredi[0];
-    for (int w = 1; w < JM_W; ++w)
-        if (sred[w] > v || (sred[w] == v && sredi[w] < h)) { v = sred[w]; h = sredi[w]; }
-    __syncthreads();
-}
-
-// The forward recurrence of one (clip, joint); the lane layout, the barriers and the prefetch are joint_temporal_scan_kernel's.
+// The forward recurrence of one (clip, joint) on ChainLanes<P, K>: the lane (part, slot) owns h = slot + k SLOTS of frame n and walks its
+// part of the h' of frame n-1, which sits in the LDS.  (A lane past H reads hypothesis H-1 and stores nothing.)
 //   l[n,j,h] = -u[n,j,h] / tau, -inf where the unary is not finite
 //   chain start (first frame of the clip, or (n-1, j) dead):  A[n,j,h] = l[n,j,h]
 //   otherwise:  A[n,j,h] = l[n,j,h] + LSE_h' (A[n-1,j,h'] - c m[n,j,h',h]),  c = lambda / tau
 //   dead (n, j): A[n,j,.] = -inf
 template <int P, int K>
-__global__ __launch_bounds__(JM_T) void joint_marginal_forward_kernel(const double *__restrict__ junary, const float *__restrict__ x,
+__global__ __launch_bounds__(CHAIN_T) void joint_marginal_forward_kernel(const double *__restrict__ junary, const float *__restrict__ x,
                                                                       const float *__restrict__ Tr, const int *__restrict__ seq_start,
                                                                       const int *__restrict__ dead, int H, int N, int J, double c, double tau,
                                                                       double *__restrict__ A) {
-    constexpr int SLOTS = JM_T / P, CAP = K * SLOTS;
-    static_assert(P == 1 || K == 1, "a lane owns several hypotheses only where the h' are not split");
-    __shared__ double sX[CAP * 3], sV[CAP];
-    __shared__ double sPm[JM_T], sPs[JM_T];                        // the parts' maxima and sums (P > 1)
-    const int tid = threadIdx.x, part = tid / SLOTS, slot = tid - part * SLOTS;
-    const int s = blockIdx.x / J, j = blockIdx.x - s * J;
-    const int a = jm_clampi(seq_start[s], 0, N), b = jm_clampi(seq_start[s + 1], 0, N);
+    using L = ChainLanes<P, K>;
+    constexpr int SLOTS = L::SLOTS;
+    __shared__ double sX[L::CAP * 3], sV[L::CAP];
+    __shared__ double sPm[CHAIN_T], sPs[CHAIN_T];                        // the parts' maxima and sums (P > 1)
+    const int tid = threadIdx.x;
+    const L ln(tid, H);
+    const int part = ln.part, slot = ln.slot;
+    const ClipJoint cj = clip_joint(seq_start, N, J);
+    const int j = cj.j, a = cj.a, b = cj.b;
     if (a >= b) return;                                            // (workgroup-uniform)
     const double ninf = -__builtin_huge_val();
-    const int per = (H + P - 1) / P, q0 = min(H, part * per), q1 = min(H, q0 + per);      // this lane's h' (part 0 is never empty)
-    const int np = (H + per - 1) / per;                            // the parts that are not empty
     double xn[K][3], un[K] = {};
-    auto fetch = [&](int n) {                                      // a lane past H reads hypothesis H-1 and stores nothing
+    auto fetch = [&](int n) {
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const size_t g = (size_t)min(slot + k * SLOTS, H - 1) * N + n;
-            const float *px = x + (g * J + j) * 3;
-            const float *pt = Tr ? Tr + g * 3 : nullptr;
-#pragma unroll
-            for (int cc = 0; cc < 3; ++cc) xn[k][cc] = (double)px[cc] + (pt ? (double)pt[cc] : 0.0);
+            load_cam(x, Tr, g, J, j, xn[k]);
             if (P == 1 || part == 0) un[k] = junary[g * J + j];    // only the owners use the unary
         }
     };
@@ -162,7 +118,7 @@ __global__ __launch_bounds__(JM_T) void joint_marginal_forward_kernel(const doub
         double mx[K], sm[K];
         __syncthreads();                                           // A: X[n-1,.] and A[n-1,.] are in the LDS
         if (chain) {
-            jm_walk<K>(sX, sV, q0, q1, xc, c, mx, sm);
+            jm_walk<K>(sX, sV, ln.q0, ln.q1, xc, c, mx, sm);
             if (P > 1) { sPm[tid] = mx[0]; sPs[tid] = sm[0]; }
         }
         __syncthreads();                                           // B: frame n-1 has been read by every lane
@@ -171,8 +127,8 @@ __global__ __launch_bounds__(JM_T) void joint_marginal_forward_kernel(const doub
             for (int k = 0; k < K; ++k) {
                 const int h = slot + k * SLOTS;
                 if (h < H) {
-                    const double l = jm_finite64(uc[k]) ? -uc[k] / tau : ninf;
-                    const double v = is_dead ? ninf : (chain ? l + jm_combine<P>(mx[k], sm[k], sPm, sPs, SLOTS, slot, np) : l);
+                    const double l = finite64(uc[k]) ? -uc[k] / tau : ninf;
+                    const double v = is_dead ? ninf : (chain ? l + jm_combine<P>(mx[k], sm[k], sPm, sPs, SLOTS, slot, ln.np) : l);
                     A[nj * H + h] = v;
                     sV[h] = v;
                     sX[h * 3] = xc[k][0]; sX[h * 3 + 1] = xc[k][1]; sX[h * 3 + 2] = xc[k][2];
@@ -189,36 +145,33 @@ __global__ __launch_bounds__(JM_T) void joint_marginal_forward_kernel(const doub
 //   w[n,j,h] = exp(A[n,j,h] + B[n,j,h] - log Z): exactly 0 for an excluded hypothesis (A = -inf)
 //   mean = sum_h w X;  cov = sum_h w (X - mean)(X - mean)^T, from the centred differences;  hmax = the lowest h with the largest w
 template <int P, int K>
-__global__ __launch_bounds__(JM_T) void joint_marginal_backward_kernel(const double *__restrict__ junary, const float *__restrict__ x,
+__global__ __launch_bounds__(CHAIN_T) void joint_marginal_backward_kernel(const double *__restrict__ junary, const float *__restrict__ x,
                                                                        const float *__restrict__ Tr, const int *__restrict__ seq_start,
                                                                        const int *__restrict__ dead, const double *__restrict__ A, int H,
                                                                        int N, int J, double c, double tau, double *__restrict__ mean,
                                                                        double *__restrict__ cov, int *__restrict__ hmax,
                                                                        double *__restrict__ wmax, double *__restrict__ logz,
                                                                        double *__restrict__ wout) {
-    constexpr int SLOTS = JM_T / P, CAP = K * SLOTS;
-    static_assert(P == 1 || K == 1, "a lane owns several hypotheses only where the h' are not split");
-    __shared__ double sX[CAP * 3], sV[CAP];
-    __shared__ double sPm[JM_T], sPs[JM_T];
-    __shared__ double sred[JM_W * 6];
-    __shared__ int sredi[JM_W];
-    const int tid = threadIdx.x, part = tid / SLOTS, slot = tid - part * SLOTS;
-    const int s = blockIdx.x / J, j = blockIdx.x - s * J;
-    const int a = jm_clampi(seq_start[s], 0, N), b = jm_clampi(seq_start[s + 1], 0, N);
+    using L = ChainLanes<P, K>;
+    constexpr int SLOTS = L::SLOTS;
+    __shared__ double sX[L::CAP * 3], sV[L::CAP];
+    __shared__ double sPm[CHAIN_T], sPs[CHAIN_T];
+    __shared__ double sred[CHAIN_W * 6];
+    __shared__ int sredi[CHAIN_W];
+    const int tid = threadIdx.x;
+    const L ln(tid, H);
+    const int part = ln.part, slot = ln.slot;
+    const ClipJoint cj = clip_joint(seq_start, N, J);
+    const int j = cj.j, a = cj.a, b = cj.b;
     if (a >= b) return;                                            // (workgroup-uniform)
     const double ninf = -__builtin_huge_val(), qnan = __builtin_nan("");
-    const int per = (H + P - 1) / P, q0 = min(H, part * per), q1 = min(H, q0 + per);
-    const int np = (H + per - 1) / per;
     double xn[K][3], un[K] = {}, an[K] = {};
     auto fetch = [&](int n) {
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int h = min(slot + k * SLOTS, H - 1);
             const size_t g = (size_t)h * N + n;
-            const float *px = x + (g * J + j) * 3;
-            const float *pt = Tr ? Tr + g * 3 : nullptr;
-#pragma unroll
-            for (int cc = 0; cc < 3; ++cc) xn[k][cc] = (double)px[cc] + (pt ? (double)pt[cc] : 0.0);
+            load_cam(x, Tr, g, J, j, xn[k]);
             if (P == 1 || part == 0) {                             // only the owners use the unary and A: the other parts walk with X alone
                 un[k] = junary[g * J + j];
                 an[k] = A[((size_t)n * J + j) * H + h];
@@ -243,7 +196,7 @@ __global__ __launch_bounds__(JM_T) void joint_marginal_backward_kernel(const dou
         double mx[K], sm[K];
         __syncthreads();                                           // A: X[n+1,.] and (l + B)[n+1,.] are in the LDS
         if (chain) {
-            jm_walk<K>(sX, sV, q0, q1, xc, c, mx, sm);
+            jm_walk<K>(sX, sV, ln.q0, ln.q1, xc, c, mx, sm);
             if (P > 1) { sPm[tid] = mx[0]; sPs[tid] = sm[0]; }
         }
         __syncthreads();                                           // B: frame n+1 has been read by every lane
@@ -255,12 +208,11 @@ __global__ __launch_bounds__(JM_T) void joint_marginal_backward_kernel(const dou
             for (int k = 0; k < K; ++k) {
                 const int h = slot + k * SLOTS;
                 if (h < H) {
-                    const double l = jm_finite64(uc[k]) ? -uc[k] / tau : ninf;
+                    const double l = finite64(uc[k]) ? -uc[k] / tau : ninf;
 #ifdef ZEDO_MUT_JM_NO_BACKWARD   // tools/mutation_check.py only: B = 0 on every frame - the filtering marginals, not the smoothed ones
                     const double Bv = 0.0;
-                    (void)np;
 #else
-                    const double Bv = chain ? jm_combine<P>(mx[k], sm[k], sPm, sPs, SLOTS, slot, np) : 0.0;
+                    const double Bv = chain ? jm_combine<P>(mx[k], sm[k], sPm, sPs, SLOTS, slot, ln.np) : 0.0;
 #endif
                     sV[h] = is_dead ? ninf : l + Bv;
                     sX[h * 3] = xc[k][0]; sX[h * 3 + 1] = xc[k][1]; sX[h * 3 + 2] = xc[k][2];
@@ -280,19 +232,20 @@ __global__ __launch_bounds__(JM_T) void joint_marginal_backward_kernel(const dou
         }
         if (ends) {                                                // (workgroup-uniform) B = 0: log Z = LSE_h A[n,j,h], shifted by the largest A
             double v = ninf;
-            int vh = 0x7fffffff;
+            int vh = INT_MAX;
 #pragma unroll
             for (int k = 0; k < K; ++k)
                 if (ab[k] > v) { v = ab[k]; vh = slot + k * SLOTS; }
-            jm_block_max(v, vh, sred, sredi, tid);
+            block_arg<true>(v, vh, sred, sredi, tid);
+            __syncthreads();                                       // sred is block_sum's next
             double e[1] = {0.0};
 #pragma unroll
             for (int k = 0; k < K; ++k) e[0] += exp(ab[k] - v);    // exp(-inf) = 0 for what is excluded or nobody's
-            jm_block_sum<1>(e, sred, tid);
+            block_sum<1>(e, sred, tid);
             lz = v + log(e[0]);
         }
         double wk[K], m3[3] = {0.0, 0.0, 0.0}, bw = ninf;
-        int bh = 0x7fffffff;
+        int bh = INT_MAX;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int h = slot + k * SLOTS;
@@ -305,8 +258,9 @@ __global__ __launch_bounds__(JM_T) void joint_marginal_backward_kernel(const dou
                 for (int cc = 0; cc < 3; ++cc) m3[cc] += wk[k] * xc[k][cc];
             }
         }
-        jm_block_max(bw, bh, sred, sredi, tid);
-        jm_block_sum<3>(m3, sred, tid);
+        block_arg<true>(bw, bh, sred, sredi, tid);
+        __syncthreads();
+        block_sum<3>(m3, sred, tid);
         double c6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -314,40 +268,36 @@ __global__ __launch_bounds__(JM_T) void joint_marginal_backward_kernel(const dou
             c6[0] += wk[k] * (d0 * d0); c6[1] += wk[k] * (d0 * d1); c6[2] += wk[k] * (d0 * d2);
             c6[3] += wk[k] * (d1 * d1); c6[4] += wk[k] * (d1 * d2); c6[5] += wk[k] * (d2 * d2);
         }
-        jm_block_sum<6>(c6, sred, tid);
+        block_sum<6>(c6, sred, tid);
         if (tid < 3) mean[nj * 3 + tid] = m3[tid];
         if (tid < 6) cov[nj * 6 + tid] = c6[tid];
-        if (tid == 0) { hmax[nj] = bh == 0x7fffffff ? 0 : bh; wmax[nj] = bh == 0x7fffffff ? 0.0 : bw; logz[nj] = lz; }
+        if (tid == 0) { hmax[nj] = bh == INT_MAX ? 0 : bh; wmax[nj] = bh == INT_MAX ? 0.0 : bw; logz[nj] = lz; }
     }
 }
 
 // Workspace: A [N,J,H] f64 | dead [N,J] i32 (padded to 8 bytes)
-size_t joint_marginal_bytes(int N, int H, int J) {
-    const size_t nj = (size_t)N * J;
-    return nj * H * 8 + ((nj * 4 + 7) & ~(size_t)7);
-}
+struct JointMarginalWs {
+    Carve c;
+    double *A;
+    int *dead;
+    size_t bytes;
+    JointMarginalWs(void *ws, size_t nj, size_t H) : c(ws), A(c.take<double>(nj * H)), dead(c.take<int>(nj)), bytes(c.bytes(8)) {}
+};
+size_t joint_marginal_bytes(int N, int H, int J) { return JointMarginalWs(nullptr, (size_t)N * J, H).bytes; }
 
 hipError_t launch_joint_marginal(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N, int J,
                                  double c, double tau, void *ws, double *mean, double *cov, int *hmax, double *wmax, double *logz, double *w,
                                  hipStream_t st) {
-    const size_t nj = (size_t)N * J;
-    double *A = static_cast<double *>(ws);
-    int *dead = reinterpret_cast<int *>(A + nj * H);
+    const JointMarginalWs t(ws, (size_t)N * J, H);
     const dim3 grid((unsigned)n_seq * (unsigned)J);                // n_seq <= N and N J H <= INT_MAX
-    const hipError_t e = launch_joint_temporal_dead(junary, H, (int)nj, dead, st);
+    const hipError_t e = launch_joint_temporal_dead(junary, H, N * J, t.dead, st);
     if (e != hipSuccess) return e;
-#define ZEDO_JM(P, K)                                                                                                                   \
-    do {                                                                                                                                \
-        hipLaunchKernelGGL((joint_marginal_forward_kernel<P, K>), grid, dim3(JM_T), 0, st, junary, x, T, seq_start, dead, H, N, J, c, tau, A); \
-        hipLaunchKernelGGL((joint_marginal_backward_kernel<P, K>), grid, dim3(JM_T), 0, st, junary, x, T, seq_start, dead, A, H, N, J, c, tau, \
-                           mean, cov, hmax, wmax, logz, w);                                                                             \
-    } while (0)
-    if (H <= JM_T / 4) ZEDO_JM(4, 1);
-    else if (H <= JM_T / 2) ZEDO_JM(2, 1);
-    else if (H <= JM_T) ZEDO_JM(1, 1);
-    else if (H <= 2 * JM_T) ZEDO_JM(1, 2);
-    else ZEDO_JM(1, 4);
-#undef ZEDO_JM
+    dispatch_pk(H, [&](auto P, auto K) {
+        hipLaunchKernelGGL((joint_marginal_forward_kernel<P(), K()>), grid, dim3(CHAIN_T), 0, st, junary, x, T, seq_start, t.dead, H, N, J, c,
+                           tau, t.A);
+        hipLaunchKernelGGL((joint_marginal_backward_kernel<P(), K()>), grid, dim3(CHAIN_T), 0, st, junary, x, T, seq_start, t.dead, t.A, H, N, J,
+                           c, tau, mean, cov, hmax, wmax, logz, w);
+    });
     return hipGetLastError();
 }
 

@@ -5,32 +5,24 @@
 //   joint_temporal_scan_kernel       the forward recurrence, one workgroup per (clip, joint); the transition cost of a pair (h', h) is one
 //                                    square root of three terms and is computed where the recurrence consumes it - there is no H x H table
 //   joint_temporal_backtrack_kernel  the backward pass, one workgroup per (clip, joint), runs of the back table staged through the LDS
-// Workgroup w serves clip w / J, joint w % J: the J chains of a clip are neighbours in the grid.  A chain reads 12 bytes of x per
-// (frame, hypothesis), at a stride of N J 3 floats across h; the other joints of the same pose row sit in the same few 128-byte
-// lines, and neighbours in the grid run at the same time, so a line fetched from HBM for one chain serves the others from the L2.
-// No atomics.
-#include "zedo_internal.h"
+// The (clip, joint) of a workgroup, the lane split and the reductions are zedo_chain.h's.  A chain reads 12 bytes of x per (frame,
+// hypothesis), at a stride of N J 3 floats across h; the other joints of the same pose row sit in the same few 128-byte lines, and
+// neighbours in the grid run at the same time, so a line fetched from HBM for one chain serves the others from the L2.  No atomics.
+#include "zedo_chain.h"
 
 namespace zedo {
-
-__device__ __forceinline__ bool jt_finite64(double v) { return fabs(v) < __builtin_huge_val(); }   // false for NaN and +-inf
-__device__ __forceinline__ int jt_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(256) void joint_temporal_dead_kernel(const double *__restrict__ junary, int H, int NJ, int *__restrict__ dead) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;           // i = n J + j: junary[(h N + n) J + j] = junary[h NJ + i]
     if (i >= NJ) return;
     int any = 0;
-    for (int h = 0; h < H; ++h) any |= jt_finite64(junary[(size_t)h * NJ + i]) ? 1 : 0;   // a wave reads 512 contiguous bytes per hypothesis
+    for (int h = 0; h < H; ++h) any |= finite64(junary[(size_t)h * NJ + i]) ? 1 : 0;      // a wave reads 512 contiguous bytes per hypothesis
     dead[i] = any ? 0 : 1;
 }
 
-// The forward recurrence of one (clip, joint).  256 lanes as P parts x 256 / P slots:
-//   P = 4 (H <= 64) and P = 2 (H <= 128): lane (part, slot) owns h = slot and walks ONE part of the h' (ceil(H / P) consecutive ones);
-//       the parts' minima meet in the LDS and part 0 combines them in ascending part order with a strict comparison - the tie still
-//       goes to the lowest h';
-//   P = 1 (H <= JT_CAP = 1024): lane t owns K hypotheses h = t, t + 256, .. and walks all h'; one LDS read of (X[n-1,h'], D[n-1,h'])
-//       serves the lane's every h.  K = 1 (H <= 256), 2 (H <= 512) or 4: no lane evaluates square roots for a hypothesis nobody owns
-//       beyond the last, partly filled group of 256.
+// The forward recurrence of one (clip, joint), on ChainLanes<P, K>: the lane (part, slot) owns the hypotheses h = slot + k SLOTS of frame
+// n and walks its part of the h' of frame n-1; with P > 1 part 0 combines the parts' minima with a strict comparison - the tie still
+// goes to the lowest h'.  With P = 1 one LDS read of (X[n-1,h'], D[n-1,h']) serves the lane's every h.
 // X[n-1,.] (fp64 triples) and D[n-1,.] sit in the LDS; every lane of a wave reads the same h' - a broadcast.  Two barriers per frame:
 // A - frame n-1 is in the LDS; B - every lane has read it (and the parts' minima are in the LDS), the owners replace it with frame n,
 // which they hold in registers.  What does not depend on D - x, T and junary of frame n+1 - is fetched BEFORE barrier A of frame n.
@@ -39,31 +31,33 @@ __global__ __launch_bounds__(256) void joint_temporal_dead_kernel(const double *
 //   dead (n, j): D[n,j,.] = +inf
 // A frame that ends a chain (last of the clip, or (n+1, j) dead) also gets the lowest arg-min of D[n,j,.] (endh): the backward pass
 // starts there.
-constexpr int JT_T = 256, JT_CAP = 1024;
+constexpr int JT_CAP = 4 * CHAIN_T;
 template <int P, int K>
-__global__ __launch_bounds__(JT_T) void joint_temporal_scan_kernel(const double *__restrict__ junary, const float *__restrict__ x,
-                                                                   const float *__restrict__ Tr, const int *__restrict__ seq_start,
-                                                                   const int *__restrict__ dead, int H, int N, int J, double lambda,
-                                                                   double *__restrict__ D, int *__restrict__ back, int *__restrict__ endh) {
-    constexpr int SLOTS = JT_T / P, CAP = K * SLOTS;
-    static_assert(P == 1 || K == 1, "a lane owns several hypotheses only where the h' are not split");
-    __shared__ double sX[CAP * 3], sD[CAP];
-    __shared__ double sPv[JT_T];                                   // the parts' minima (P > 1)
-    __shared__ int sPi[JT_T];
-    __shared__ double rv[JT_T / 64];
-    __shared__ int rh[JT_T / 64];
-    const int tid = threadIdx.x, part = tid / SLOTS, slot = tid - part * SLOTS;
-    const int s = blockIdx.x / J, j = blockIdx.x - s * J;
-    const int a = jt_clampi(seq_start[s], 0, N), b = jt_clampi(seq_start[s + 1], 0, N);
+__global__ __launch_bounds__(CHAIN_T) void joint_temporal_scan_kernel(const double *__restrict__ junary, const float *__restrict__ x,
+                                                                      const float *__restrict__ Tr, const int *__restrict__ seq_start,
+                                                                      const int *__restrict__ dead, int H, int N, int J, double lambda,
+                                                                      double *__restrict__ D, int *__restrict__ back, int *__restrict__ endh) {
+    using L = ChainLanes<P, K>;
+    constexpr int SLOTS = L::SLOTS;
+    __shared__ double sX[L::CAP * 3], sD[L::CAP];
+    __shared__ double sPv[CHAIN_T];                                // the parts' minima (P > 1)
+    __shared__ int sPi[CHAIN_T];
+    __shared__ double rv[CHAIN_W];
+    __shared__ int rh[CHAIN_W];
+    const int tid = threadIdx.x;
+    const L ln(tid, H);
+    const ClipJoint cj = clip_joint(seq_start, N, J);
+    const int j = cj.j, a = cj.a, b = cj.b;
     if (a >= b) return;                                            // (workgroup-uniform)
     const double inf = __builtin_huge_val();
-    const int per = (H + P - 1) / P, q0 = min(H, part * per), q1 = min(H, q0 + per);      // this lane's h' (part 0 is never empty)
-    // X[n,h,j,.] and u[n,j,h] of this lane's h (a lane past H reads hypothesis H-1 and stores nothing)
+    // X[n,h,j,.] and u[n,j,h] of this lane's h.  load_cam's statements in place, not a call of it: through the function the compiler
+    // joins the three loads of x into one and converts it before the branch on T, i.e. waits for the prefetch ahead of barrier A - a
+    // call without T on one clip of 1 015 frames (J = 17, H = 50) measured 2 875 us against 2 778 us.
     double xn[K][3], un[K];
     auto fetch = [&](int n) {
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            const size_t g = (size_t)min(slot + k * SLOTS, H - 1) * N + n;
+            const size_t g = (size_t)min(ln.slot + k * SLOTS, H - 1) * N + n;
             const float *px = x + (g * J + j) * 3;
 #ifdef ZEDO_MUT_JT_NO_T   // tools/mutation_check.py only: the motion term is taken on x alone although T was given
             const float *pt = nullptr;
@@ -96,31 +90,30 @@ __global__ __launch_bounds__(JT_T) void joint_temporal_scan_kernel(const double 
 #pragma unroll
             for (int k = 0; k < K; ++k) { dn[k] = inf; bn[k] = 0; }
 #pragma unroll 4
-            for (int hp = q0; hp < q1; ++hp) {
+            for (int hp = ln.q0; hp < ln.q1; ++hp) {
                 const double p0 = sX[hp * 3], p1 = sX[hp * 3 + 1], p2 = sX[hp * 3 + 2], pd = sD[hp];
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     const double d0 = xc[k][0] - p0, d1 = xc[k][1] - p1, d2 = xc[k][2] - p2;
                     const double c = pd + lambda * sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-                    if (hp == q0 || c < dn[k]) { dn[k] = c; bn[k] = hp; }   // strict: the lowest h' that attains the minimum
+                    if (hp == ln.q0 || c < dn[k]) { dn[k] = c; bn[k] = hp; }   // strict: the lowest h' that attains the minimum
                 }
             }
             if (P > 1) { sPv[tid] = dn[0]; sPi[tid] = bn[0]; }
         }
         __syncthreads();                                           // B: frame n-1 has been read by every lane
-        if (part == 0) {
+        if (ln.part == 0) {
             if (chain && P > 1) {
-                const int np = (H + per - 1) / per;                // the parts that are not empty
-                for (int p = 1; p < np; ++p) {
-                    const double c = sPv[p * SLOTS + slot];
-                    if (c < dn[0]) { dn[0] = c; bn[0] = sPi[p * SLOTS + slot]; }
+                for (int p = 1; p < ln.np; ++p) {
+                    const double c = sPv[p * SLOTS + ln.slot];
+                    if (c < dn[0]) { dn[0] = c; bn[0] = sPi[p * SLOTS + ln.slot]; }
                 }
             }
 #pragma unroll
             for (int k = 0; k < K; ++k) {
-                const int h = slot + k * SLOTS;
+                const int h = ln.slot + k * SLOTS;
                 if (h < H) {
-                    const double u0 = jt_finite64(uc[k]) ? uc[k] : inf;
+                    const double u0 = finite64(uc[k]) ? uc[k] : inf;
                     const double d = chain ? u0 + dn[k] : (is_dead ? inf : u0);
                     dn[k] = d;
                     D[nj * H + h] = d;
@@ -132,27 +125,16 @@ __global__ __launch_bounds__(JT_T) void joint_temporal_scan_kernel(const double 
         }
         if (ends) {                                                // (workgroup-uniform) the lowest arg-min of D[n,j,.], from the owners' registers
             double v = inf;
-            int vh = 0x7fffffff;
-            if (part == 0) {
+            int vh = INT_MAX;
+            if (ln.part == 0) {
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
-                    const int h = slot + k * SLOTS;
-                    if (h < H && (dn[k] < v || (dn[k] == v && h < vh))) { v = dn[k]; vh = h; }
+                    const int h = ln.slot + k * SLOTS;
+                    if (h < H && arg_better<false>(dn[k], h, v, vh)) { v = dn[k]; vh = h; }
                 }
             }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                const double ov = __shfl_xor(v, off);
-                const int oh = __shfl_xor(vh, off);
-                if (ov < v || (ov == v && oh < vh)) { v = ov; vh = oh; }
-            }
-            if ((tid & 63) == 0) { rv[tid >> 6] = v; rh[tid >> 6] = vh; }
-            __syncthreads();
-            if (tid == 0) {
-                for (int w = 1; w < JT_T / 64; ++w)
-                    if (rv[w] < v || (rv[w] == v && rh[w] < vh)) { v = rv[w]; vh = rh[w]; }
-                endh[nj] = vh == 0x7fffffff ? 0 : vh;
-            }
+            block_arg<false>(v, vh, rv, rh, tid);
+            if (tid == 0) endh[nj] = vh == INT_MAX ? 0 : vh;
         }
     }
 }
@@ -170,8 +152,8 @@ __global__ __launch_bounds__(256) void joint_temporal_backtrack_kernel(const int
     __shared__ int sb[JB_INTS], sdead[JB_RUN], send[JB_RUN], spath[JB_RUN];
     __shared__ int carry[2];                                       // lane 0's state between runs: have a successor in the chain, its h
     const int tid = threadIdx.x, T = blockDim.x;
-    const int s = blockIdx.x / J, j = blockIdx.x - s * J;
-    const int a = jt_clampi(seq_start[s], 0, N), b = jt_clampi(seq_start[s + 1], 0, N);
+    const ClipJoint cj = clip_joint(seq_start, N, J);
+    const int j = cj.j, a = cj.a, b = cj.b;
     if (a >= b) return;
     const int R = min(JB_RUN, JB_INTS / H);
     if (tid == 0) { carry[0] = 0; carry[1] = 0; }
@@ -190,7 +172,7 @@ __global__ __launch_bounds__(256) void joint_temporal_backtrack_kernel(const int
             for (int i = len - 1; i >= 0; --i) {
                 if (sdead[i]) { p = 0; have = 0; }
                 else {
-                    p = jt_clampi(have ? sb[i * H + p] : send[i], 0, H - 1);
+                    p = clampi(have ? sb[i * H + p] : send[i], 0, H - 1);
                     have = 1;
                 }
                 spath[i] = p;
@@ -208,12 +190,17 @@ __global__ __launch_bounds__(256) void joint_temporal_backtrack_kernel(const int
 }
 
 // Workspace: D [N,J,H] f64 | back [N,J,H] i32, dead [N,J] i32, endh [N,J] i32 (padded to 8 bytes)
-size_t joint_temporal_bytes(int N, int H, int J) {
-    const size_t nj = (size_t)N * J, njh = nj * H;
-    return njh * 8 + (((njh + 2 * nj) * 4 + 7) & ~(size_t)7);
-}
+struct JointTemporalWs {
+    Carve c;
+    double *D;
+    int *back, *dead, *endh;
+    size_t bytes;
+    JointTemporalWs(void *ws, size_t nj, size_t H)
+        : c(ws), D(c.take<double>(nj * H)), back(c.take<int>(nj * H)), dead(c.take<int>(nj)), endh(c.take<int>(nj)), bytes(c.bytes(8)) {}
+};
+size_t joint_temporal_bytes(int N, int H, int J) { return JointTemporalWs(nullptr, (size_t)N * J, H).bytes; }
 
-// the dead flags on their own, for the other chain model on the same unaries (zedo_joint_marginal.hip)
+// the dead flags on their own, for the other chain models on the same unaries
 hipError_t launch_joint_temporal_dead(const double *junary, int H, int NJ, int *dead, hipStream_t st) {
     hipLaunchKernelGGL(joint_temporal_dead_kernel, dim3((unsigned)(((size_t)NJ + 255) / 256)), dim3(256), 0, st, junary, H, NJ, dead);
     return hipGetLastError();
@@ -221,21 +208,14 @@ hipError_t launch_joint_temporal_dead(const double *junary, int H, int NJ, int *
 
 hipError_t launch_joint_temporal_select(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,
                                         int J, double lambda, void *ws, int *path, double *cost, hipStream_t st) {
-    const size_t nj = (size_t)N * J, njh = nj * H;
-    double *D = static_cast<double *>(ws);
-    int *back = reinterpret_cast<int *>(D + njh), *dead = back + njh, *endh = dead + nj;
+    const JointTemporalWs w(ws, (size_t)N * J, H);
     const dim3 grid((unsigned)n_seq * (unsigned)J);                // n_seq <= N and N J H <= INT_MAX
-    hipLaunchKernelGGL(joint_temporal_dead_kernel, dim3((unsigned)((nj + 255) / 256)), dim3(256), 0, st, junary, H, (int)nj, dead);
-#define ZEDO_JT_SCAN(P, K)                                                                                                          \
-    hipLaunchKernelGGL((joint_temporal_scan_kernel<P, K>), grid, dim3(JT_T), 0, st, junary, x, T, seq_start, dead, H, N, J, lambda, D, back, \
-                       endh)
-    if (H <= JT_T / 4) ZEDO_JT_SCAN(4, 1);
-    else if (H <= JT_T / 2) ZEDO_JT_SCAN(2, 1);
-    else if (H <= JT_T) ZEDO_JT_SCAN(1, 1);
-    else if (H <= 2 * JT_T) ZEDO_JT_SCAN(1, 2);
-    else ZEDO_JT_SCAN(1, 4);
-#undef ZEDO_JT_SCAN
-    hipLaunchKernelGGL(joint_temporal_backtrack_kernel, grid, dim3(256), 0, st, seq_start, dead, endh, back, D, H, N, J, path, cost);
+    hipLaunchKernelGGL(joint_temporal_dead_kernel, dim3((unsigned)(((size_t)N * J + 255) / 256)), dim3(256), 0, st, junary, H, N * J, w.dead);
+    dispatch_pk(H, [&](auto P, auto K) {
+        hipLaunchKernelGGL((joint_temporal_scan_kernel<P(), K()>), grid, dim3(CHAIN_T), 0, st, junary, x, T, seq_start, w.dead, H, N, J, lambda,
+                           w.D, w.back, w.endh);
+    });
+    hipLaunchKernelGGL(joint_temporal_backtrack_kernel, grid, dim3(256), 0, st, seq_start, w.dead, w.endh, w.back, w.D, H, N, J, path, cost);
     return hipGetLastError();
 }
 

@@ -2,73 +2,43 @@
 // that minimises the joints' unary costs plus mu times, for every bone, the mismatch between the assembled bone's length and the length
 // the two hypotheses that supply its ends give that bone - exact min-sum dynamic programming over the bone tree, fp64, one launch.
 // One workgroup of 256 lanes serves one pose; everything lives in the LDS, sized to the case:
-//   X    [J][H][3] f64   the pose's camera-frame positions, staged once: H runs of 12 J bytes at a stride of N J 3 floats (neighbouring
-//                        poses are neighbours in memory, and neighbours in the grid run at the same time).  Joint-major: the lanes of a
-//                        wave read X[j][h] of consecutive h - fp64 triples at a stride of 6 dwords, which 32 lanes spread over the 64
-//                        banks without a conflict (ds_read_b64 is served in groups of 32 lanes, bank = dword address mod 64) - or all the
-//                        same h: a broadcast
+//   X    [J][H][3] f64   the pose's camera-frame positions, joint-major (tree_stage of zedo_chain.h stages X, S and the live flags;
+//                        neighbouring poses are neighbours in memory, and neighbours in the grid run at the same time)
 //   S    [J][H]    f64   u, then u plus the messages of the children
 //   back [J][H]    u16   the arg-min of a bone's message
 //   own  [2][H]    f64   the bone's own length in every hypothesis, formed once per bone, double-buffered over consecutive bones
 // 34 J H + 16 H + 4096 bytes in all (the parts' minima, the roots and the flags are the 4096).
 // The bones are walked in the host's post-order (children before parents, siblings ascending), handed over by value.  For one bone the
-// H^2 pairs are dealt as in joint_temporal_scan_kernel: 256 lanes as P parts x 256 / P slots, P = 4 (H <= 64), 2 (H <= 128) or 1; the
-// lane (part, slot) owns hp = slot (+ 256, .. when P = 1 and H > 256) and walks one part of the hc in lockstep with its wave, so
+// H^2 pairs are dealt by the lane split of zedo_chain.h with P = chain_parts(H): the lane (part, slot) owns hp = slot (+ 256, .. when
+// P = 1 and H > 256) and walks one part of the hc in lockstep with its wave, so
 // S[g][hc], own[hc] and X[g][hc] are broadcast reads; the parts' minima meet in the LDS and part 0 combines them in ascending part
 // order with a strict comparison - the lowest hc still wins.  S[p][.] takes its children's messages in the order of the walk, i.e. in
 // ascending child index whatever the launch shape.  One barrier per bone (two where the hc are split).  The roots' minima, the downward
 // pass and bone[n,.] end the same launch.  No atomics, no scratch.
-#include "zedo_internal.h"
+#include "zedo_chain.h"
 
 namespace zedo {
 
-// (tr_finite64, tr_dist and tr_bone - the statements this kernel shares with its sum-product twin - are in zedo_internal.h)
-
-__global__ __launch_bounds__(TR_T) void joint_tree_kernel(const double *__restrict__ junary, const float *__restrict__ x,
+__global__ __launch_bounds__(CHAIN_T) void joint_tree_kernel(const double *__restrict__ junary, const float *__restrict__ x,
                                                           const float *__restrict__ Tr, const float *__restrict__ weight, const TreeOrder tr,
                                                           int H, int N, int J, double mu, int *__restrict__ joint_h, double *__restrict__ cost,
                                                           double *__restrict__ bone) {
     extern __shared__ double tr_lds[];
     const int JH = J * H;
-    double *const sX = tr_lds, *const sS = sX + 3 * JH, *const sOwn = sS + JH, *const sPv = sOwn + 2 * H, *const sRmin = sPv + TR_T;
-    int *const sPi = reinterpret_cast<int *>(sRmin + TR_JMAX), *const sSel = sPi + TR_T, *const sLive = sSel + TR_JMAX;
+    double *const sX = tr_lds, *const sS = sX + 3 * JH, *const sOwn = sS + JH, *const sPv = sOwn + 2 * H, *const sRmin = sPv + CHAIN_T;
+    int *const sPi = reinterpret_cast<int *>(sRmin + TR_JMAX), *const sSel = sPi + CHAIN_T, *const sLive = sSel + TR_JMAX;
     unsigned short *const sBack = reinterpret_cast<unsigned short *>(sLive + TR_JMAX);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t n = blockIdx.x;
     const double inf = __builtin_huge_val();
 
-    // the pose's positions and unaries, once: consecutive lanes read consecutive floats of a row
-    const int J3 = 3 * J;
-    for (int e = tid; e < 3 * JH; e += TR_T) {
-        const int h = e / J3, r = e - h * J3, j = r / 3, c = r - 3 * j;
-        const size_t row = (size_t)h * N + n;
-        sX[(j * H + h) * 3 + c] = (double)x[row * J3 + r] + (Tr ? (double)Tr[row * 3 + c] : 0.0);
-    }
-    for (int e = tid; e < JH; e += TR_T) {
-        const int h = e / J, j = e - h * J;
-        double w = 1.0;
-        if (weight) {                                              // the clamp of zedo_min_reproj, taken in fp32 (NaN stays NaN)
-            float c = weight[n * J + j];
-            if (c > 1.0f) c = 1.0f;
-            if (c < 1e-4f) c = 1e-4f;
-            w = (double)c;
-        }
-        const double u = w * junary[((size_t)h * N + n) * J + j];
-        sS[j * H + h] = tr_finite64(u) ? u : inf;
-    }
-    __syncthreads();
-    for (int j = wave; j < J; j += TR_T / 64) {                    // a wave per joint: does it have a finite unary at all?
-        int any = 0;
-        for (int h = lane; h < H; h += 64) any |= tr_finite64(sS[j * H + h]) ? 1 : 0;
-        const bool live = __ballot(any) != 0;
-        if (lane == 0) sLive[j] = live ? 1 : 0;
-    }
+    tree_stage(junary, x, Tr, weight, n, H, N, J, inf, [](double u) { return u; }, sX, sS, sLive);
     __syncthreads();
 
     // upwards: the message of every live bone with a live parent, in the host's order
-    const int P = H <= TR_T / 4 ? 4 : (H <= TR_T / 2 ? 2 : 1), SLOTS = TR_T / P;
-    const int part = tid / SLOTS, slot = tid - part * SLOTS;
-    const int per = (H + P - 1) / P, q0 = min(H, part * per), q1 = min(H, q0 + per);      // this lane's hc (part 0 is never empty)
+    const int P = chain_parts(H);
+    const Lanes ln(tid, H, P);
+    const int SLOTS = ln.slots, part = ln.part, slot = ln.slot, q0 = ln.q0, q1 = ln.q1;   // q0 .. q1-1: this lane's hc
     int nb = 0;
     for (int i = 0; i < J; ++i) {
         const int g = tr.order[i], p = tr.parent[g];
@@ -76,7 +46,7 @@ __global__ __launch_bounds__(TR_T) void joint_tree_kernel(const double *__restri
         double *const own = sOwn + (nb & 1) * H;
         ++nb;
         const double *const Xg = sX + (size_t)g * H * 3, *const Xp = sX + (size_t)p * H * 3, *const Sg = sS + g * H;
-        for (int h = tid; h < H; h += TR_T) own[h] = tr_dist(Xg + h * 3, Xp[h * 3], Xp[h * 3 + 1], Xp[h * 3 + 2]);
+        for (int h = tid; h < H; h += CHAIN_T) own[h] = tr_dist(Xg + h * 3, Xp[h * 3], Xp[h * 3 + 1], Xp[h * 3 + 2]);
         __syncthreads();                                           // A: own[] is there; the previous bone's sums are in S
         for (int hp = slot; hp < H; hp += SLOTS) {
             const double p0 = Xp[hp * 3], p1 = Xp[hp * 3 + 1], p2 = Xp[hp * 3 + 2], op = own[hp];
@@ -100,8 +70,7 @@ __global__ __launch_bounds__(TR_T) void joint_tree_kernel(const double *__restri
             if (part == 0 && slot < H) {
                 double best = sPv[slot];
                 int bi = sPi[slot];
-                const int np = (H + per - 1) / per;                // the parts that are not empty
-                for (int q = 1; q < np; ++q) {
+                for (int q = 1; q < ln.np; ++q) {
                     const double c = sPv[q * SLOTS + slot];
                     if (c < best) { best = c; bi = sPi[q * SLOTS + slot]; }
                 }
@@ -113,22 +82,17 @@ __global__ __launch_bounds__(TR_T) void joint_tree_kernel(const double *__restri
     __syncthreads();
 
     // the roots: a live joint without a live parent; a wave per root takes the lowest arg-min of S[root][.]
-    for (int j = wave; j < J; j += TR_T / 64) {
+    for (int j = wave; j < J; j += CHAIN_T / 64) {
         const int p = tr.parent[j];
         if (!sLive[j] || (p >= 0 && sLive[p])) continue;           // (wave-uniform)
         double v = inf;
-        int vh = 0x7fffffff;
+        int vh = INT_MAX;
         for (int h = lane; h < H; h += 64) {
             const double c = sS[j * H + h];
             if (c < v) { v = c; vh = h; }
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double ov = __shfl_xor(v, off);
-            const int oh = __shfl_xor(vh, off);
-            if (ov < v || (ov == v && oh < vh)) { v = ov; vh = oh; }
-        }
-        if (lane == 0) { sRmin[j] = v; sSel[j] = vh == 0x7fffffff ? 0 : vh; }
+        wave_arg<false>(v, vh);
+        if (lane == 0) { sRmin[j] = v; sSel[j] = vh == INT_MAX ? 0 : vh; }
     }
     __syncthreads();
     if (tid == 0) {
@@ -146,7 +110,7 @@ __global__ __launch_bounds__(TR_T) void joint_tree_kernel(const double *__restri
         }
     }
     __syncthreads();
-    for (int j = tid; j < J; j += TR_T) {
+    for (int j = tid; j < J; j += CHAIN_T) {
         const int p = tr.parent[j], hc = sSel[j];
         double b = 0.0;
         if (sLive[j] && p >= 0 && sLive[p]) {
@@ -203,7 +167,7 @@ hipError_t launch_joint_tree_select(const double *junary, const float *x, const 
     static std::atomic<bool> lds_ok[MAX_DEVICES];
     hipError_t e = allow_lds(reinterpret_cast<const void *>(joint_tree_kernel), TR_LDS, lds_ok);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(joint_tree_kernel, dim3((unsigned)N), dim3(TR_T), joint_tree_lds_bytes(H, J), st, junary, x, T, weight, tr, H, N, J, mu,
+    hipLaunchKernelGGL(joint_tree_kernel, dim3((unsigned)N), dim3(CHAIN_T), joint_tree_lds_bytes(H, J), st, junary, x, T, weight, tr, H, N, J, mu,
                        joint_h, cost, bone);
     return hipGetLastError();
 }

@@ -3,16 +3,15 @@
 // one back give every joint's exact marginals over its hypotheses - in the log domain, fp64 - and from them the posterior mean position,
 // its covariance, the most probable hypothesis, the log-partition value and every bone's expected mismatch.  One launch, one workgroup
 // of 256 lanes per pose, everything in the LDS, sized to the case:
-//   X    [J][H][3] f64   the pose's camera-frame positions, staged as joint_tree_kernel stages them (joint-major: the lanes of a wave read
-//                        X[j][h] of consecutive h - fp64 triples at a stride of 6 dwords, no bank conflict - or all the same h: a broadcast)
+//   X    [J][H][3] f64   the pose's camera-frame positions, joint-major (tree_stage of zedo_chain.h stages X, S and the live flags)
 //   S    [J][H]    f64   l = -u / tau, then l plus the messages of the children
 //   M    [J][H]    f64   M_g[hp], the message bone g sends up (the downward pass needs it); once Dn[g] is formed, the slot holds
 //                        sum_hp pi[g,hp,hc] b[g,hp,hc] of every hc instead: the terms of bone[n,g]
 //   Dn   [J][H]    f64   the message from above; at the end the marginal w[j,h] itself
 //   own  [H], E [H] f64  the bone's own length in every hypothesis, and E_g[hp] = S[p,hp] - M_g[hp] + Dn[p,hp] of the downward pass
 // 48 J H + 16 H + 8192 bytes in all (the parts' maxima, sums and bone sums, log Z of every joint and the flags are the 8192).
-// The bones are walked in the host's post-order upwards and in its reverse downwards.  For one bone the H^2 pairs are dealt as in
-// joint_tree_kernel: P parts x 256 / P slots, P = 4 (H <= 64), 2 (H <= 128) or 1; a lane owns the OUTER index (hp upwards, hc downwards;
+// The bones are walked in the host's post-order upwards and in its reverse downwards.  For one bone the H^2 pairs are dealt by the lane
+// split of zedo_chain.h with P = chain_parts(H); a lane owns the OUTER index (hp upwards, hc downwards;
 // + 256, .. when P = 1 and H > 256) and walks one part of the inner index in lockstep with its wave, so the inner index's value, own
 // length and position are broadcast reads in both roles, and the owner's position is read once, at the conflict-free stride above.  A
 // log-sum-exp takes two walks: the first finds the largest term, the second adds exp(term - largest) in ascending inner index; the bone
@@ -20,7 +19,7 @@
 // own maximum and part 0 combines the parts in ascending order, shifted by the largest.  Downwards the second walk also adds
 // exp(term - largest) b: the pair marginals are consumed where they are formed.  The roots' log Z, the marginals, the mean, the
 // covariance, the arg-max and bone[n,.] end the same launch, a wave per joint.  No atomics, no scratch, every sum in a fixed order.
-#include "zedo_internal.h"
+#include "zedo_chain.h"
 
 namespace zedo {
 
@@ -74,14 +73,7 @@ __device__ __forceinline__ void tm_combine(double &mx, double &sm, double &sb, c
     sb = B;
 }
 
-// the sum of v over the wave, a butterfly: every lane gets it
-__device__ __forceinline__ double tm_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-__global__ __launch_bounds__(TR_T) void joint_tree_marginal_kernel(const double *__restrict__ junary, const float *__restrict__ x,
+__global__ __launch_bounds__(CHAIN_T) void joint_tree_marginal_kernel(const double *__restrict__ junary, const float *__restrict__ x,
                                                                    const float *__restrict__ Tr, const float *__restrict__ weight,
                                                                    const TreeOrder tr, int H, int N, int J, double c, double tau,
                                                                    double *__restrict__ mean, double *__restrict__ cov, int *__restrict__ hmax,
@@ -90,44 +82,18 @@ __global__ __launch_bounds__(TR_T) void joint_tree_marginal_kernel(const double 
     extern __shared__ double tm_lds[];
     const int JH = J * H;
     double *const sX = tm_lds, *const sS = sX + 3 * JH, *const sM = sS + JH, *const sD = sM + JH, *const sOwn = sD + JH, *const sE = sOwn + H;
-    double *const sPm = sE + H, *const sPs = sPm + TR_T, *const sPb = sPs + TR_T, *const sLz = sPb + TR_T;
+    double *const sPm = sE + H, *const sPs = sPm + CHAIN_T, *const sPb = sPs + CHAIN_T, *const sLz = sPb + CHAIN_T;
     int *const sLive = reinterpret_cast<int *>(sLz + TR_JMAX);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t n = blockIdx.x;
     const double ninf = -__builtin_huge_val(), qnan = __builtin_nan("");
 
-    // the pose's positions and l = -u / tau, once: consecutive lanes read consecutive floats of a row
-    const int J3 = 3 * J;
-    for (int e = tid; e < 3 * JH; e += TR_T) {
-        const int h = e / J3, r = e - h * J3, j = r / 3, cc = r - 3 * j;
-        const size_t row = (size_t)h * N + n;
-        sX[(j * H + h) * 3 + cc] = (double)x[row * J3 + r] + (Tr ? (double)Tr[row * 3 + cc] : 0.0);
-    }
-    for (int e = tid; e < JH; e += TR_T) {
-        const int h = e / J, j = e - h * J;
-        double w = 1.0;
-        if (weight) {                                              // the clamp of zedo_min_reproj, taken in fp32 (NaN stays NaN)
-            float cf = weight[n * J + j];
-            if (cf > 1.0f) cf = 1.0f;
-            if (cf < 1e-4f) cf = 1e-4f;
-            w = (double)cf;
-        }
-        const double u = w * junary[((size_t)h * N + n) * J + j];
-        sS[j * H + h] = tr_finite64(u) ? -u / tau : ninf;
-        sD[j * H + h] = 0.0;                                       // Dn of a root; every other live joint's is written on the way down
-    }
-    __syncthreads();
-    for (int j = wave; j < J; j += TR_T / 64) {                    // a wave per joint: does it have a finite unary at all?
-        int any = 0;
-        for (int h = lane; h < H; h += 64) any |= sS[j * H + h] > ninf ? 1 : 0;
-        const bool live = __ballot(any) != 0;
-        if (lane == 0) sLive[j] = live ? 1 : 0;
-    }
+    // l = -u / tau; sD = 0: Dn of a root - every other live joint's is written on the way down
+    tree_stage(junary, x, Tr, weight, n, H, N, J, ninf, [tau](double u) { return -u / tau; }, sX, sS, sLive, sD);
 
-    const int P = H <= TR_T / 4 ? 4 : (H <= TR_T / 2 ? 2 : 1), SLOTS = TR_T / P;
-    const int part = tid / SLOTS, slot = tid - part * SLOTS;
-    const int per = (H + P - 1) / P, q0 = min(H, part * per), q1 = min(H, q0 + per);      // this lane's inner indices (part 0 is never empty)
-    const int np = (H + per - 1) / per;                            // the parts that are not empty
+    const int P = chain_parts(H);
+    const Lanes ln(tid, H, P);
+    const int SLOTS = ln.slots, part = ln.part, slot = ln.slot, q0 = ln.q0, q1 = ln.q1, np = ln.np;       // q0 .. q1-1: this lane's inner indices
 
     // upwards: the message of every live bone with a live parent, in the host's order
     for (int i = 0; i < J; ++i) {
@@ -135,7 +101,7 @@ __global__ __launch_bounds__(TR_T) void joint_tree_marginal_kernel(const double 
         const int g = tr.order[i], p = tr.parent[g];
         if (p < 0 || !sLive[g] || !sLive[p]) continue;             // (workgroup-uniform) a root, dead, or cut off by a dead parent
         const double *const Xg = sX + (size_t)g * H * 3, *const Xp = sX + (size_t)p * H * 3;
-        for (int h = tid; h < H; h += TR_T) sOwn[h] = tr_dist(Xg + h * 3, Xp[h * 3], Xp[h * 3 + 1], Xp[h * 3 + 2]);
+        for (int h = tid; h < H; h += CHAIN_T) sOwn[h] = tr_dist(Xg + h * 3, Xp[h * 3], Xp[h * 3 + 1], Xp[h * 3 + 2]);
         __syncthreads();                                           // A: own[] is there
         for (int hp = slot; hp < H; hp += SLOTS) {
             const double xo[3] = {Xp[hp * 3], Xp[hp * 3 + 1], Xp[hp * 3 + 2]};
@@ -164,16 +130,15 @@ __global__ __launch_bounds__(TR_T) void joint_tree_marginal_kernel(const double 
     __syncthreads();
 
     // the roots: a live joint without a live parent; a wave per root takes log Z = LSE_h S[root,h], shifted by the largest
-    for (int j = wave; j < J; j += TR_T / 64) {
+    for (int j = wave; j < J; j += CHAIN_T / 64) {
         const int p = tr.parent[j];
         if (!sLive[j] || (p >= 0 && sLive[p])) continue;           // (wave-uniform)
         double v = ninf;
         for (int h = lane; h < H; h += 64) v = fmax(v, sS[j * H + h]);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+        v = wave_max(v);
         double e = 0.0;
         for (int h = lane; h < H; h += 64) e += exp(sS[j * H + h] - v);
-        e = tm_wave_sum(e);
+        e = wave_sum(e);
         if (lane == 0) sLz[j] = v + log(e);
     }
     __syncthreads();
@@ -190,7 +155,7 @@ __global__ __launch_bounds__(TR_T) void joint_tree_marginal_kernel(const double 
         const int g = tr.order[i], p = tr.parent[g];
         if (p < 0 || !sLive[g] || !sLive[p]) continue;             // (workgroup-uniform)
         const double *const Xg = sX + (size_t)g * H * 3, *const Xp = sX + (size_t)p * H * 3;
-        for (int h = tid; h < H; h += TR_T) {
+        for (int h = tid; h < H; h += CHAIN_T) {
             sOwn[h] = tr_dist(Xg + h * 3, Xp[h * 3], Xp[h * 3 + 1], Xp[h * 3 + 2]);
             sE[h] = sS[p * H + h] - sM[g * H + h] + sD[p * H + h];
         }
@@ -226,7 +191,7 @@ __global__ __launch_bounds__(TR_T) void joint_tree_marginal_kernel(const double 
     __syncthreads();
 
     // what is read off the marginals, a wave per joint: every sum lane by lane in ascending h, then a butterfly over the wave
-    for (int j = wave; j < J; j += TR_T / 64) {
+    for (int j = wave; j < J; j += CHAIN_T / 64) {
         const size_t nj = n * J + j;
         if (!sLive[j]) {                                           // (wave-uniform) NaN, hypothesis 0, weight 0, log Z = -inf, bone 0, a row of zeros
             if (lane < 3) mean[nj * 3 + lane] = qnan;
@@ -241,7 +206,7 @@ __global__ __launch_bounds__(TR_T) void joint_tree_marginal_kernel(const double 
         const double lz = sLz[j];
         const double *const Xj = sX + (size_t)j * H * 3;
         double m0 = 0.0, m1 = 0.0, m2 = 0.0, bs = 0.0, bw = ninf;
-        int bh = 0x7fffffff;
+        int bh = INT_MAX;
         for (int h = lane; h < H; h += 64) {
             const double w = exp(sS[j * H + h] + sD[j * H + h] - lz);                     // exactly 0 for an excluded hypothesis (S = -inf)
             sD[j * H + h] = w;                                     // (read back by this lane only)
@@ -250,13 +215,8 @@ __global__ __launch_bounds__(TR_T) void joint_tree_marginal_kernel(const double 
             m0 += w * Xj[h * 3]; m1 += w * Xj[h * 3 + 1]; m2 += w * Xj[h * 3 + 2];
             if (coupled) bs += sM[j * H + h];
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double ov = __shfl_xor(bw, off);
-            const int oh = __shfl_xor(bh, off);
-            if (ov > bw || (ov == bw && oh < bh)) { bw = ov; bh = oh; }
-        }
-        m0 = tm_wave_sum(m0); m1 = tm_wave_sum(m1); m2 = tm_wave_sum(m2); bs = tm_wave_sum(bs);
+        wave_arg<true>(bw, bh);
+        m0 = wave_sum(m0); m1 = wave_sum(m1); m2 = wave_sum(m2); bs = wave_sum(bs);
         double c6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         for (int h = lane; h < H; h += 64) {
             const double w = sD[j * H + h], d0 = Xj[h * 3] - m0, d1 = Xj[h * 3 + 1] - m1, d2 = Xj[h * 3 + 2] - m2;
@@ -264,13 +224,13 @@ __global__ __launch_bounds__(TR_T) void joint_tree_marginal_kernel(const double 
             c6[3] += w * (d1 * d1); c6[4] += w * (d1 * d2); c6[5] += w * (d2 * d2);
         }
 #pragma unroll
-        for (int k = 0; k < 6; ++k) c6[k] = tm_wave_sum(c6[k]);
+        for (int k = 0; k < 6; ++k) c6[k] = wave_sum(c6[k]);
         if (lane == 0) {
             mean[nj * 3] = m0; mean[nj * 3 + 1] = m1; mean[nj * 3 + 2] = m2;
 #pragma unroll
             for (int k = 0; k < 6; ++k) cov[nj * 6 + k] = c6[k];
-            hmax[nj] = bh == 0x7fffffff ? 0 : bh;
-            wmax[nj] = bh == 0x7fffffff ? 0.0 : bw;
+            hmax[nj] = bh == INT_MAX ? 0 : bh;
+            wmax[nj] = bh == INT_MAX ? 0.0 : bw;
             logz[nj] = lz;
             bone[nj] = bs;
         }
@@ -292,7 +252,7 @@ hipError_t launch_joint_tree_marginal(const double *junary, const float *x, cons
     static std::atomic<bool> lds_ok[MAX_DEVICES];
     hipError_t e = allow_lds(reinterpret_cast<const void *>(joint_tree_marginal_kernel), TR_LDS, lds_ok);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(joint_tree_marginal_kernel, dim3((unsigned)N), dim3(TR_T), joint_tree_marginal_lds_bytes(H, J), st, junary, x, T, weight,
+    hipLaunchKernelGGL(joint_tree_marginal_kernel, dim3((unsigned)N), dim3(CHAIN_T), joint_tree_marginal_lds_bytes(H, J), st, junary, x, T, weight,
                        tr, H, N, J, c, tau, mean, cov, hmax, wmax, logz, bone, w);
     return hipGetLastError();
 }

@@ -7,15 +7,13 @@
 //   temporal_scan_kernel        the forward recurrence, one workgroup per clip, one lane per hypothesis h (lanes loop beyond the workgroup)
 //   temporal_backtrack_kernel   the backward pass, one workgroup per clip, runs of the back table staged through the LDS
 // The host cuts the frames into chunks of C (whatever transition costs the caller's workspace holds) and launches the transition and the
-// scan kernel per chunk; D and back live in the workspace for all frames, so the result does not depend on C.  No atomics.
-#include "zedo_internal.h"
+// scan kernel per chunk; D and back live in the workspace for all frames, so the result does not depend on C.  No atomics.  The arg-min
+// reduction and the workspace carving are zedo_chain.h's.
+#include "zedo_chain.h"
 
 #include <algorithm>
 
 namespace zedo {
-
-__device__ __forceinline__ bool finite64(double v) { return fabs(v) < __builtin_huge_val(); }   // false for NaN and +-inf
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(256) void temporal_dead_kernel(const double *__restrict__ unary, int H, int N, int *__restrict__ dead) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -203,24 +201,13 @@ __global__ __launch_bounds__(256) void temporal_scan_kernel(const double *__rest
         if (ends) {                                                // (workgroup-uniform) the lowest arg-min of D[n,.]
             __syncthreads();                                       // D[n,.] of every lane is in sD[cur] / in the table
             double v = inf;
-            int vh = 0x7fffffff;
+            int vh = INT_MAX;
             for (int h = tid; h < H; h += T) {
                 const double d = RESIDENT ? sD[cur * TS_CAP + h] : D[(size_t)n * H + h];
-                if (d < v || (d == v && h < vh)) { v = d; vh = h; }
+                if (arg_better<false>(d, h, v, vh)) { v = d; vh = h; }
             }
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                const double ov = __shfl_xor(v, off);
-                const int oh = __shfl_xor(vh, off);
-                if (ov < v || (ov == v && oh < vh)) { v = ov; vh = oh; }
-            }
-            if ((tid & 63) == 0) { rv[tid >> 6] = v; rh[tid >> 6] = vh; }
-            __syncthreads();
-            if (tid == 0) {
-                for (int w = 1; w < (T + 63) / 64; ++w)
-                    if (rv[w] < v || (rv[w] == v && rh[w] < vh)) { v = rv[w]; vh = rh[w]; }
-                endh[n] = vh == 0x7fffffff ? 0 : vh;
-            }
+            block_arg<false>(v, vh, rv, rh, tid, (T + 63) / 64);
+            if (tid == 0) endh[n] = vh == INT_MAX ? 0 : vh;
         }
     }
 }
@@ -278,34 +265,38 @@ __global__ __launch_bounds__(256) void temporal_backtrack_kernel(const int *__re
 }
 
 // Workspace: D [N,H] f64 | back [N,H] i32, dead [N] i32, endh [N] i32 (padded to 8 bytes) | M [C,H,H] f64
-size_t temporal_fixed_bytes(int N, int H) {
-    const size_t nh = (size_t)N * H;
-    return nh * 8 + (((nh + 2 * (size_t)N) * 4 + 7) & ~(size_t)7);
-}
+struct TemporalWs {
+    Carve c;
+    double *D;
+    int *back, *dead, *endh;
+    double *M;
+    size_t fixed_bytes;                                            // everything but M
+    TemporalWs(void *ws, size_t N, size_t H)
+        : c(ws), D(c.take<double>(N * H)), back(c.take<int>(N * H)), dead(c.take<int>(N)), endh(c.take<int>(N)), M(c.take<double>(0)),
+          fixed_bytes(c.bytes()) {}
+};
+size_t temporal_fixed_bytes(int N, int H) { return TemporalWs(nullptr, N, H).fixed_bytes; }
 
 hipError_t launch_temporal_select(const double *unary, const float *x, const int *seq_start, int n_seq, int H, int N, int J, double lambda,
                                   void *ws, int chunk, int *path, double *cost, hipStream_t st) {
-    const size_t nh = (size_t)N * H;
-    double *D = static_cast<double *>(ws);
-    int *back = reinterpret_cast<int *>(D + nh), *dead = back + nh, *endh = dead + N;
-    double *M = reinterpret_cast<double *>(static_cast<char *>(ws) + temporal_fixed_bytes(N, H));
-    hipLaunchKernelGGL(temporal_dead_kernel, dim3((N + 255) / 256), dim3(256), 0, st, unary, H, N, dead);
+    const TemporalWs w(ws, N, H);
+    hipLaunchKernelGGL(temporal_dead_kernel, dim3((N + 255) / 256), dim3(256), 0, st, unary, H, N, w.dead);
     const int T = std::min(256, (H + 63) / 64 * 64);
     for (int c0 = 0; c0 < N; c0 += chunk) {
         const int cnt = std::min(chunk, N - c0);
         if (c0 + cnt > 1)
             hipLaunchKernelGGL(temporal_transition_kernel, dim3(cnt, (H + TT_H - 1) / TT_H, (H + TT_P - 1) / TT_P), dim3(TT_T), 0, st, x, H, N,
-                               J, c0, M);
+                               J, c0, w.M);
         if (H <= TS_CAP)
-            hipLaunchKernelGGL(temporal_scan_kernel<true>, dim3(n_seq), dim3(T), 0, st, unary, M, seq_start, dead, H, N, lambda, c0, cnt, D,
-                               back, endh);
+            hipLaunchKernelGGL(temporal_scan_kernel<true>, dim3(n_seq), dim3(T), 0, st, unary, w.M, seq_start, w.dead, H, N, lambda, c0, cnt,
+                               w.D, w.back, w.endh);
         else
-            hipLaunchKernelGGL(temporal_scan_kernel<false>, dim3(n_seq), dim3(T), 0, st, unary, M, seq_start, dead, H, N, lambda, c0, cnt, D,
-                               back, endh);
+            hipLaunchKernelGGL(temporal_scan_kernel<false>, dim3(n_seq), dim3(T), 0, st, unary, w.M, seq_start, w.dead, H, N, lambda, c0, cnt,
+                               w.D, w.back, w.endh);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(temporal_backtrack_kernel, dim3(n_seq), dim3(256), 0, st, seq_start, dead, endh, back, D, H, N, path, cost);
+    hipLaunchKernelGGL(temporal_backtrack_kernel, dim3(n_seq), dim3(256), 0, st, seq_start, w.dead, w.endh, w.back, w.D, H, N, path, cost);
     return hipGetLastError();
 }
 

@@ -556,6 +556,62 @@ def joint_compose(x_full, T_full, joint_idx, ref_idx=None, N=None):
     return pose
 
 
+def _chain_inputs(name, unary, x_full, T_full, seq_start, N, joint_wise):
+    """What the selection and fusion calls along a video share: the device, seq_start as an int32 tensor on it, N (read off seq_start's
+    last entry - one synchronisation - when the caller did not give it), H and J, with the shapes checked: unary [H*N,J] (joint_wise) or
+    [H*N], x [H*N,J,3], T [H*N,3] or None.  `name`: the public function the ValueError speaks for."""
+    _need_gpu()
+    dev = _device_of(unary, x_full, T_full, seq_start if isinstance(seq_start, torch.Tensor) and seq_start.is_cuda else None)
+    rows, J = x_full.shape[0], x_full.shape[1]
+    if isinstance(seq_start, torch.Tensor):
+        if seq_start.dtype not in (torch.int32, torch.int64) or seq_start.dim() != 1:
+            raise ValueError(f"{name}: seq_start must be a 1-D int tensor, got {seq_start.dtype} {tuple(seq_start.shape)}")
+        seq = seq_start.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        seq = torch.tensor([int(v) for v in seq_start], dtype=torch.int32, device=dev)
+    if N is None:
+        N = int(seq[-1].item()) if seq.numel() else 0
+    N = int(N)
+    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(unary.shape) != ((rows, J) if joint_wise else (rows,))
+            or seq.numel() < 2 or (T_full is not None and tuple(T_full.shape) != (rows, 3))):
+        if joint_wise:
+            raise ValueError(f"{name}: junary [H*N,J], x [H*N,J,3], T [H*N,3], seq_start [n_seq+1] expected, got "
+                             f"{tuple(unary.shape)}, {tuple(x_full.shape)}, {None if T_full is None else tuple(T_full.shape)}, {tuple(seq.shape)} "
+                             f"with N = {N}")
+        raise ValueError(f"{name}: unary [H*N], x [H*N,J,3], seq_start [n_seq+1] expected, got {tuple(unary.shape)}, "
+                         f"{tuple(x_full.shape)}, {tuple(seq.shape)} with N = {N}")
+    return dev, seq, N, rows // N, J
+
+
+def _tree_inputs(name, junary, x_full, T_full, parent, N, weight):
+    """What the skeleton-coupled calls share: the device, the parent array as contiguous int32 on the host, N (the weights say how many
+    poses there are when the caller did not), H and J, with the shapes checked."""
+    _need_gpu()
+    dev = _device_of(junary, x_full, T_full, weight)
+    rows, J = x_full.shape[0], x_full.shape[1]
+    par = np.ascontiguousarray(np.asarray(parent.cpu() if isinstance(parent, torch.Tensor) else parent).astype(np.int32))
+    N = (0 if weight is None else weight.shape[0]) if N is None else int(N)
+    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J) or par.shape != (J,)
+            or (T_full is not None and tuple(T_full.shape) != (rows, 3)) or (weight is not None and tuple(weight.shape) != (N, J))):
+        raise ValueError(f"{name}: junary [H*N,J], x [H*N,J,3], T [H*N,3], parent [J], weight [N,J] expected, got "
+                         f"{tuple(junary.shape)}, {tuple(x_full.shape)}, {None if T_full is None else tuple(T_full.shape)}, {par.shape}, "
+                         f"{None if weight is None else tuple(weight.shape)} with N = {N}")
+    return dev, par, N, rows // N, J
+
+
+def _marginal_outputs(N, J, H, dev, return_weights):
+    """mean [N,J,3], cov [N,J,6], hmax [N,J] i32, wmax [N,J], logz [N,J] and, on request, w [N,J,H] (else None); f64 unless noted."""
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+    return (f64(N, J, 3), f64(N, J, 6), torch.empty((N, J), dtype=torch.int32, device=dev), f64(N, J), f64(N, J),
+            f64(N, J, H) if return_weights else None)
+
+
+def _workspace(bytes_fn, dev, *shape):
+    """(the bytes the entry point asks for at this shape, a uint8 tensor of at least that and at least 8)"""
+    nbytes = int(bytes_fn(*shape))
+    return nbytes, torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+
+
 def temporal_select(unary, x_full, seq_start, N=None, lam=100.0, chunk_frames=0):
     """Selection along a video without ground truth (zedo_temporal_select): unary [H*N] f64 (ALL rows, h-major: e.g. err of min_reproj,
     pixels), x_full [H*N,J,3] f32, seq_start [n_seq+1] (a sequence or an int tensor: strictly ascending from 0 to N, the first frame of
@@ -563,25 +619,9 @@ def temporal_select(unary, x_full, seq_start, N=None, lam=100.0, chunk_frames=0)
     the mean joint displacement between consecutive choices (Viterbi, fp64).  lam is in cost units per metre; the default of 100 (1 cm of
     mean joint jump costs as much as 1 px) is untuned.  chunk_frames: frames of transition costs held at once (0: at most 256 MB); the
     result does not depend on it.  Whether the temporal path is closer to ground truth than the per-frame arg-min is not measured."""
-    _need_gpu()
-    dev = _device_of(unary, x_full, seq_start if isinstance(seq_start, torch.Tensor) and seq_start.is_cuda else None)
-    rows, J = x_full.shape[0], x_full.shape[1]
-    if isinstance(seq_start, torch.Tensor):
-        if seq_start.dtype not in (torch.int32, torch.int64) or seq_start.dim() != 1:
-            raise ValueError(f"temporal_select: seq_start must be a 1-D int tensor, got {seq_start.dtype} {tuple(seq_start.shape)}")
-        seq = seq_start.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        seq = torch.tensor([int(v) for v in seq_start], dtype=torch.int32, device=dev)
-    if N is None:
-        N = int(seq[-1].item()) if seq.numel() else 0
-    N = int(N)
-    if N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(unary.shape) != (rows,) or seq.numel() < 2:
-        raise ValueError(f"temporal_select: unary [H*N], x [H*N,J,3], seq_start [n_seq+1] expected, got {tuple(unary.shape)}, "
-                         f"{tuple(x_full.shape)}, {tuple(seq.shape)} with N = {N}")
-    H = rows // N
+    dev, seq, N, H, J = _chain_inputs("temporal_select", unary, x_full, None, seq_start, N, joint_wise=False)
     with torch.cuda.device(dev):
-        nbytes = int(_lib.zedo_temporal_workspace_bytes(N, H, int(chunk_frames)))
-        ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+        nbytes, ws = _workspace(_lib.zedo_temporal_workspace_bytes, dev, N, H, int(chunk_frames))
         path = torch.empty((N,), dtype=torch.int32, device=dev)
         cost = torch.empty((N,), dtype=torch.float64, device=dev)
         _check(_lib.zedo_temporal_select(_p(unary, torch.float64), _p(x_full), _p(seq, torch.int32), seq.numel() - 1, H, N, J, float(lam),
@@ -597,27 +637,9 @@ def joint_temporal_select(junary, x_full, T_full, seq_start, N=None, lam=100.0):
     frame (x + T) between consecutive choices (Viterbi, fp64, one chain per joint).  lam is in cost units per metre; the default of 100 is
     untuned.  At most 1024 hypotheses.  Whether the joint-wise temporal paths are closer to ground truth than the per-frame joint-wise
     arg-min is not measured."""
-    _need_gpu()
-    dev = _device_of(junary, x_full, T_full, seq_start if isinstance(seq_start, torch.Tensor) and seq_start.is_cuda else None)
-    rows, J = x_full.shape[0], x_full.shape[1]
-    if isinstance(seq_start, torch.Tensor):
-        if seq_start.dtype not in (torch.int32, torch.int64) or seq_start.dim() != 1:
-            raise ValueError(f"joint_temporal_select: seq_start must be a 1-D int tensor, got {seq_start.dtype} {tuple(seq_start.shape)}")
-        seq = seq_start.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        seq = torch.tensor([int(v) for v in seq_start], dtype=torch.int32, device=dev)
-    if N is None:
-        N = int(seq[-1].item()) if seq.numel() else 0
-    N = int(N)
-    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J) or seq.numel() < 2
-            or (T_full is not None and tuple(T_full.shape) != (rows, 3))):
-        raise ValueError(f"joint_temporal_select: junary [H*N,J], x [H*N,J,3], T [H*N,3], seq_start [n_seq+1] expected, got "
-                         f"{tuple(junary.shape)}, {tuple(x_full.shape)}, {None if T_full is None else tuple(T_full.shape)}, {tuple(seq.shape)} "
-                         f"with N = {N}")
-    H = rows // N
+    dev, seq, N, H, J = _chain_inputs("joint_temporal_select", junary, x_full, T_full, seq_start, N, joint_wise=True)
     with torch.cuda.device(dev):
-        nbytes = int(_lib.zedo_joint_temporal_workspace_bytes(N, H, J))
-        ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+        nbytes, ws = _workspace(_lib.zedo_joint_temporal_workspace_bytes, dev, N, H, J)
         path = torch.empty((N, J), dtype=torch.int32, device=dev)
         cost = torch.empty((N, J), dtype=torch.float64, device=dev)
         _check(_lib.zedo_joint_temporal_select(_p(junary, torch.float64), _p(x_full), _p(T_full), _p(seq, torch.int32), seq.numel() - 1, H, N,
@@ -634,27 +656,9 @@ def joint_accel_select(junary, x_full, T_full, seq_start, N=None, lam=100.0, acc
     cost of the kept path re-accumulated along it.  lam and accel are in cost units per metre; the defaults of 100 are untuned; lam = 0
     is the pure second-order chain.  At most 64 hypotheses; the workspace is one byte per (frame, joint, pair).  Whether these paths are
     closer to ground truth than joint_temporal_select's is not measured."""
-    _need_gpu()
-    dev = _device_of(junary, x_full, T_full, seq_start if isinstance(seq_start, torch.Tensor) and seq_start.is_cuda else None)
-    rows, J = x_full.shape[0], x_full.shape[1]
-    if isinstance(seq_start, torch.Tensor):
-        if seq_start.dtype not in (torch.int32, torch.int64) or seq_start.dim() != 1:
-            raise ValueError(f"joint_accel_select: seq_start must be a 1-D int tensor, got {seq_start.dtype} {tuple(seq_start.shape)}")
-        seq = seq_start.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        seq = torch.tensor([int(v) for v in seq_start], dtype=torch.int32, device=dev)
-    if N is None:
-        N = int(seq[-1].item()) if seq.numel() else 0
-    N = int(N)
-    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J) or seq.numel() < 2
-            or (T_full is not None and tuple(T_full.shape) != (rows, 3))):
-        raise ValueError(f"joint_accel_select: junary [H*N,J], x [H*N,J,3], T [H*N,3], seq_start [n_seq+1] expected, got "
-                         f"{tuple(junary.shape)}, {tuple(x_full.shape)}, {None if T_full is None else tuple(T_full.shape)}, {tuple(seq.shape)} "
-                         f"with N = {N}")
-    H = rows // N
+    dev, seq, N, H, J = _chain_inputs("joint_accel_select", junary, x_full, T_full, seq_start, N, joint_wise=True)
     with torch.cuda.device(dev):
-        nbytes = int(_lib.zedo_joint_accel_workspace_bytes(N, H, J))
-        ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
+        nbytes, ws = _workspace(_lib.zedo_joint_accel_workspace_bytes, dev, N, H, J)
         path = torch.empty((N, J), dtype=torch.int32, device=dev)
         cost = torch.empty((N, J), dtype=torch.float64, device=dev)
         _check(_lib.zedo_joint_accel_select(_p(junary, torch.float64), _p(x_full), _p(T_full), _p(seq, torch.int32), seq.numel() - 1, H, N,
@@ -703,17 +707,7 @@ def joint_tree_select(junary, x_full, T_full, parent, N=None, mu=100.0, weight=N
     the mean of the lengths its two hypotheses give that bone (exact min-sum over the tree, fp64); bone is that difference in metres at
     the kept assignment.  mu is in cost units per metre; the default of 100 is untuned.  mu = 0 is joint_reproj's arg-min, a large mu one
     whole hypothesis per pose.  Whether the coupled pose is closer to ground truth than the per-joint arg-min is not measured."""
-    _need_gpu()
-    dev = _device_of(junary, x_full, T_full, weight)
-    rows, J = x_full.shape[0], x_full.shape[1]
-    par = np.ascontiguousarray(np.asarray(parent.cpu() if isinstance(parent, torch.Tensor) else parent).astype(np.int32))
-    N = (0 if weight is None else weight.shape[0]) if N is None else int(N)      # without N the weights say how many poses there are
-    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J) or par.shape != (J,)
-            or (T_full is not None and tuple(T_full.shape) != (rows, 3)) or (weight is not None and tuple(weight.shape) != (N, J))):
-        raise ValueError(f"joint_tree_select: junary [H*N,J], x [H*N,J,3], T [H*N,3], parent [J], weight [N,J] expected, got "
-                         f"{tuple(junary.shape)}, {tuple(x_full.shape)}, {None if T_full is None else tuple(T_full.shape)}, {par.shape}, "
-                         f"{None if weight is None else tuple(weight.shape)} with N = {N}")
-    H = rows // N
+    dev, par, N, H, J = _tree_inputs("joint_tree_select", junary, x_full, T_full, parent, N, weight)
     with torch.cuda.device(dev):
         joint_h = torch.empty((N, J), dtype=torch.int32, device=dev)
         cost = torch.empty((N,), dtype=torch.float64, device=dev)
@@ -739,25 +733,10 @@ def joint_tree_marginal(junary, x_full, T_full, parent, N=None, mu=100.0, tau=1.
     probability, the log-partition value of the joint's component and the expected mismatch of the bone to the parent (metres).  A dead
     joint reports NaN, 0, 0, -inf and 0.  mu = 100 and tau = 1 are untuned.  At most joint_tree_marginal_max_h(J) hypotheses.  Whether the
     fused pose is closer to ground truth than a selected one is not measured."""
-    _need_gpu()
-    dev = _device_of(junary, x_full, T_full, weight)
-    rows, J = x_full.shape[0], x_full.shape[1]
-    par = np.ascontiguousarray(np.asarray(parent.cpu() if isinstance(parent, torch.Tensor) else parent).astype(np.int32))
-    N = (0 if weight is None else weight.shape[0]) if N is None else int(N)      # without N the weights say how many poses there are
-    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J) or par.shape != (J,)
-            or (T_full is not None and tuple(T_full.shape) != (rows, 3)) or (weight is not None and tuple(weight.shape) != (N, J))):
-        raise ValueError(f"joint_tree_marginal: junary [H*N,J], x [H*N,J,3], T [H*N,3], parent [J], weight [N,J] expected, got "
-                         f"{tuple(junary.shape)}, {tuple(x_full.shape)}, {None if T_full is None else tuple(T_full.shape)}, {par.shape}, "
-                         f"{None if weight is None else tuple(weight.shape)} with N = {N}")
-    H = rows // N
+    dev, par, N, H, J = _tree_inputs("joint_tree_marginal", junary, x_full, T_full, parent, N, weight)
     with torch.cuda.device(dev):
-        mean = torch.empty((N, J, 3), dtype=torch.float64, device=dev)
-        cov = torch.empty((N, J, 6), dtype=torch.float64, device=dev)
-        hmax = torch.empty((N, J), dtype=torch.int32, device=dev)
-        wmax = torch.empty((N, J), dtype=torch.float64, device=dev)
-        logz = torch.empty((N, J), dtype=torch.float64, device=dev)
+        mean, cov, hmax, wmax, logz, w = _marginal_outputs(N, J, H, dev, return_weights)
         bone = torch.empty((N, J), dtype=torch.float64, device=dev)
-        w = torch.empty((N, J, H), dtype=torch.float64, device=dev) if return_weights else None
         _check(_lib.zedo_joint_tree_marginal(_p(junary, torch.float64), _p(x_full), _p(T_full), _p(weight), par.ctypes.data_as(ctypes.c_void_p),
                                              H, N, J, float(mu), float(tau), _p(mean, torch.float64), _p(cov, torch.float64),
                                              _p(hmax, torch.int32), _p(wmax, torch.float64), _p(logz, torch.float64), _p(bone, torch.float64),
@@ -773,33 +752,10 @@ def joint_marginal(junary, x_full, T_full, seq_start, N=None, lam=100.0, tau=1.0
     covariance (xx, xy, xz, yy, yz, zz; m^2), the most probable hypothesis, its probability and the chain's log-partition value.  A dead
     (frame, joint) reports NaN, 0, 0 and -inf.  lam = 100 and tau = 1 are untuned.  At most 1024 hypotheses.  Whether the fused pose is
     closer to ground truth than a selected one is not measured."""
-    _need_gpu()
-    dev = _device_of(junary, x_full, T_full, seq_start if isinstance(seq_start, torch.Tensor) and seq_start.is_cuda else None)
-    rows, J = x_full.shape[0], x_full.shape[1]
-    if isinstance(seq_start, torch.Tensor):
-        if seq_start.dtype not in (torch.int32, torch.int64) or seq_start.dim() != 1:
-            raise ValueError(f"joint_marginal: seq_start must be a 1-D int tensor, got {seq_start.dtype} {tuple(seq_start.shape)}")
-        seq = seq_start.to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        seq = torch.tensor([int(v) for v in seq_start], dtype=torch.int32, device=dev)
-    if N is None:
-        N = int(seq[-1].item()) if seq.numel() else 0
-    N = int(N)
-    if (N < 1 or rows % N or tuple(x_full.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J) or seq.numel() < 2
-            or (T_full is not None and tuple(T_full.shape) != (rows, 3))):
-        raise ValueError(f"joint_marginal: junary [H*N,J], x [H*N,J,3], T [H*N,3], seq_start [n_seq+1] expected, got "
-                         f"{tuple(junary.shape)}, {tuple(x_full.shape)}, {None if T_full is None else tuple(T_full.shape)}, {tuple(seq.shape)} "
-                         f"with N = {N}")
-    H = rows // N
+    dev, seq, N, H, J = _chain_inputs("joint_marginal", junary, x_full, T_full, seq_start, N, joint_wise=True)
     with torch.cuda.device(dev):
-        nbytes = int(_lib.zedo_joint_marginal_workspace_bytes(N, H, J))
-        ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
-        mean = torch.empty((N, J, 3), dtype=torch.float64, device=dev)
-        cov = torch.empty((N, J, 6), dtype=torch.float64, device=dev)
-        hmax = torch.empty((N, J), dtype=torch.int32, device=dev)
-        wmax = torch.empty((N, J), dtype=torch.float64, device=dev)
-        logz = torch.empty((N, J), dtype=torch.float64, device=dev)
-        w = torch.empty((N, J, H), dtype=torch.float64, device=dev) if return_weights else None
+        nbytes, ws = _workspace(_lib.zedo_joint_marginal_workspace_bytes, dev, N, H, J)
+        mean, cov, hmax, wmax, logz, w = _marginal_outputs(N, J, H, dev, return_weights)
         _check(_lib.zedo_joint_marginal(_p(junary, torch.float64), _p(x_full), _p(T_full), _p(seq, torch.int32), seq.numel() - 1, H, N, J,
                                         float(lam), float(tau), _p(ws, torch.uint8), nbytes, _p(mean, torch.float64),
                                         _p(cov, torch.float64), _p(hmax, torch.int32), _p(wmax, torch.float64), _p(logz, torch.float64),
