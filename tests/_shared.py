@@ -9,6 +9,8 @@ import hashlib
 import json
 import os
 import socket
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -242,6 +244,61 @@ def report_env(rec):
     if os.environ.get("ZEDO_PARITY_REPORT"):
         with open(os.environ["ZEDO_PARITY_REPORT"], "a") as f:
             f.write(json.dumps(rec) + "\n")
+
+
+# The driver tests (tests/test_select_*_driver_gpu.py, tests/test_prune_driver_gpu.py)
+
+def _inference(argv, capsys):
+    """run.inference in this process -> (results, errs, what it printed)."""
+    import run.inference as inf
+    capsys.readouterr()
+    res, errs = inf.main(inf.parse_args(["prog"] + argv))
+    return res, errs, capsys.readouterr().out
+
+
+def _problem(n, cfg=None):
+    """The detections of the driver's synthetic run of n poses (seeded by the configuration file cfg, default pw3d's): uv, K, conf."""
+    from lib.dataset import synthetic as syn
+    from run._driver import load_config
+    d = syn.make_poses(n, seed=load_config(cfg or cfg_path("pw3d")).seed)
+    return d["db_2d"][:, :, :2], d["camera_param"], d["db_2d"][:, :, 2]
+
+
+def _rows_and_T(n, h, s):
+    """The fused loop of the driver's synthetic pw3d run again: x [h n,17,3], T [h n,3] on the device (same kernels, same bits)."""
+    from lib.dataset import synthetic as syn
+    from run._driver import load_config
+    from zedo_hip.pipeline import Pipeline, ZeDOConfig
+    cfg = load_config(cfg_path("pw3d"))
+    z = cfg.ZeDO
+    uv, K, conf = _problem(n)
+    pipe = Pipeline(syn.make_weights(seed=cfg.seed), ZeDOConfig(z.IPO_iterations, z.IPO_keylist, z.RotAxes, z.IPO_T, z.IPO_minScaleT, z.IPO_maxScaleT,
+                                                                s, z.sampling_eps, 0.1, 1000, 0.1, 20.0), "cuda")
+    pipe.load(syn.make_clusters(h, seed=cfg.seed), np.concatenate([uv, conf[:, :, None]], -1), K)
+    return pipe.run()
+
+
+def _sel(runs, name):
+    """<out>_selected.npz of a `runs` fixture's entry name -> (results, path of the out file, stdout)."""
+    return np.load(str(runs[name][1])[:-4] + "_selected.npz")
+
+
+def run_two_ranks(argv, cwd):
+    """python -m run.inference argv as two fresh processes in cwd: two members of one gloo process group on device 0, each on its own
+    row shard, each under its own time limit -> [(stdout, stderr, returncode)] by rank, every exit status asserted 0 first."""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "ZEDO_FORCE_DIST", "ZEDO_BENCH_FORCE_DIST"):
+        env.pop(k, None)
+    env.update(ZEDO_SHARE_DEVICE="1", ZEDO_DIST_BACKEND="gloo", ZEDO_NO_BUILD="1", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1",
+               MASTER_PORT=str(free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0",
+               PYTHONPATH=os.path.join(ROOT, "zedo-release_amd") + os.pathsep + env.get("PYTHONPATH", ""))
+    cmd = ["timeout", "-k", "10", "300", sys.executable, "-m", "run.inference"] + argv
+    procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), cwd=str(cwd), stdout=subprocess.PIPE,
+                              stderr=subprocess.PIPE, text=True) for r in range(2)]
+    done = [p.communicate() + (p.returncode,) for p in procs]
+    for r, (out, err, rc) in enumerate(done):                       # every exit status, before anything else is looked at
+        assert rc == 0, (r, rc, out[-2000:], err[-4000:])
+    return done
 
 
 # Fixtures: a test module imports the ones it uses by name (W needs zh beside it).  A module-scope fixture is built once per

@@ -10,20 +10,13 @@ import sys
 import numpy as np
 import pytest
 
-from _shared import ROOT, cfg_path, free_port, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
+from _shared import ROOT, _inference, cfg_path, free_port, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 N, H, S, PLAN, KF = 9, 6, 40, "7:4,8:2", 2
 BASE = ["--config", cfg_path("pw3d"), "--synthetic", str(N), "--hypo", str(H), "--oil_iterations", str(S)]
-
-
-def _inference(argv, capsys):
-    import run.inference as inf
-    capsys.readouterr()
-    res, errs = inf.main(inf.parse_args(["prog"] + argv))
-    return res, errs, capsys.readouterr().out
 
 
 @pytest.fixture(scope="module")
@@ -131,6 +124,7 @@ def test_the_refusals(tmp_path):
 
 def test_two_ranks_refuse_the_switch(tmp_path):
     """Two fresh processes of a gloo launch: both end at once with the message, before a process group or a GPU is touched."""
+    # not _shared.run_two_ranks: that launcher asserts exit status 0 of both ranks, this launch must end with status 1
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "ZEDO_FORCE_DIST", "ZEDO_BENCH_FORCE_DIST"):
         env.pop(k, None)

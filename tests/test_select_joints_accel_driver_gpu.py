@@ -11,7 +11,7 @@ import pytest
 
 from _joint_accel_ref import cost_bound, joint_accel_ref
 from _joint_ref import joint_reproj_ref
-from _shared import cfg_path, dev, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
+from _shared import _problem, _rows_and_T, cfg_path, dev, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
 from _temporal_ref import clips
 
 pytestmark = pytest.mark.gpu
@@ -22,27 +22,6 @@ BASE = ["--config", cfg_path("pw3d"), "--synthetic", str(N), "--hypo", str(H), "
 JT = ["--select", "joints-temporal", "--seq_len", str(L), "--smooth", "100"]
 JT_ARRAYS = ("pose", "joint_hypothesis", "joint_hypothesis_per_frame", "joint_reproj_px", "joint_path_cost", "hypothesis", "T", "reproj_px",
              "reproj_px_pose_level", "seq_start", "smooth")
-
-
-def _problem():
-    from lib.dataset import synthetic as syn
-    from run._driver import load_config
-    d = syn.make_poses(N, seed=load_config(cfg_path("pw3d")).seed)
-    return d["db_2d"][:, :, :2], d["camera_param"], d["db_2d"][:, :, 2]
-
-
-def _rows_and_T():
-    """The fused loop of the driver's synthetic pw3d run again: x [H N,17,3], T [H N,3] on the device (same kernels, same bits)."""
-    from lib.dataset import synthetic as syn
-    from run._driver import load_config
-    from zedo_hip.pipeline import Pipeline, ZeDOConfig
-    cfg = load_config(cfg_path("pw3d"))
-    z = cfg.ZeDO
-    uv, K, conf = _problem()
-    pipe = Pipeline(syn.make_weights(seed=cfg.seed), ZeDOConfig(z.IPO_iterations, z.IPO_keylist, z.RotAxes, z.IPO_T, z.IPO_minScaleT, z.IPO_maxScaleT,
-                                                                S, z.sampling_eps, 0.1, 1000, 0.1, 20.0), "cuda")
-    pipe.load(syn.make_clusters(H, seed=cfg.seed), np.concatenate([uv, conf[:, :, None]], -1), K)
-    return pipe.run()
 
 
 @pytest.fixture(scope="module")
@@ -70,9 +49,9 @@ def test_selected_npz_gains_accel_beside_an_unchanged_results_file(runs):
     for k in ("joint_hypothesis_per_frame", "hypothesis", "T", "reproj_px_pose_level", "seq_start", "smooth"):
         assert sel[k].dtype == first[k].dtype and sel[k].tobytes() == first[k].tobytes(), k
     # the joint paths and their costs: the binding on the run's own rows
-    x, Tall = _rows_and_T()
+    x, Tall = _rows_and_T(N, H, S)
     assert np.array_equal(x.reshape(H, N, 17, 3).permute(1, 0, 2, 3).cpu().numpy(), a)
-    uv, K, conf = (dev(v) for v in _problem())
+    uv, K, conf = (dev(v) for v in _problem(N))
     jerr = zh.joint_reproj(x, Tall, uv, K, return_rows=True)[2]
     jpath, jcost = zh.joint_accel_select(jerr, x, Tall, seq, N, LAM, ACC)
     jh, jpc, hyp = sel["joint_hypothesis"], sel["joint_path_cost"], sel["hypothesis"]

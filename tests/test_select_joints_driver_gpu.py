@@ -5,14 +5,12 @@ errors.  Fused and step-wise route, --eval, the refusal of run.opt_main, and two
 the one-rank run.  Whether the assembled pose is closer to ground truth on real data is not measured: the inputs here are synthetic.
 The selection does not depend on the arithmetic mode of the dense layers: one session runs it."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from _joint_ref import compose_ref
-from _shared import ROOT, cfg_path, dev, free_port, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
+from _shared import _inference, _problem, _rows_and_T, cfg_path, dev, run_two_ranks, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -20,20 +18,6 @@ torch = pytest.importorskip("torch")
 N, H, S = 8, 3, 10
 BASE = ["--config", cfg_path("pw3d"), "--synthetic", str(N), "--hypo", str(H), "--oil_iterations", str(S)]
 ARRAYS = ("pose", "joint_hypothesis", "joint_reproj_px", "hypothesis", "T", "reproj_px", "reproj_px_pose_level")
-
-
-def _inference(argv, capsys):
-    import run.inference as inf
-    capsys.readouterr()
-    res, errs = inf.main(inf.parse_args(["prog"] + argv))
-    return res, errs, capsys.readouterr().out
-
-
-def _problem(n=N, cfg=None):
-    from lib.dataset import synthetic as syn
-    from run._driver import load_config
-    d = syn.make_poses(n, seed=load_config(cfg or cfg_path("pw3d")).seed)
-    return d["db_2d"][:, :, :2], d["camera_param"], d["db_2d"][:, :, 2]
 
 
 def _check_selected(sel, sel_reproj, results, uv, K, conf, n=N, h=H):
@@ -59,20 +43,6 @@ def _check_selected(sel, sel_reproj, results, uv, K, conf, n=N, h=H):
     return pose, jh, jpx, hyp, T
 
 
-def _rows_and_T(n=N, h=H, s=S):
-    """The fused loop of the driver's synthetic pw3d run again: x [h n,17,3], T [h n,3] on the device (same kernels, same bits)."""
-    from lib.dataset import synthetic as syn
-    from run._driver import load_config
-    from zedo_hip.pipeline import Pipeline, ZeDOConfig
-    cfg = load_config(cfg_path("pw3d"))
-    z = cfg.ZeDO
-    uv, K, conf = _problem(n)
-    pipe = Pipeline(syn.make_weights(seed=cfg.seed), ZeDOConfig(z.IPO_iterations, z.IPO_keylist, z.RotAxes, z.IPO_T, z.IPO_minScaleT, z.IPO_maxScaleT,
-                                                                s, z.sampling_eps, 0.1, 1000, 0.1, 20.0), "cuda")
-    pipe.load(syn.make_clusters(h, seed=cfg.seed), np.concatenate([uv, conf[:, :, None]], -1), K)
-    return pipe.run()
-
-
 @pytest.fixture(scope="module")
 def one_rank(tmp_path_factory):
     """The one-rank runs with --select joints and --select reproj (in this process), shared by the tests below: (directory, results)."""
@@ -93,11 +63,11 @@ def test_selected_npz_beside_an_unchanged_results_file(one_rank, tmp_path, capsy
     assert np.array_equal(res_b, res) and np.array_equal(res, plain)
     a, b = np.load(d / "results.npy"), np.load(tmp_path / "results.npy")
     assert a.shape == (N, H, 17, 3) and a.tobytes() == b.tobytes() and a.tobytes() == np.load(d / "reproj.npy").tobytes()
-    uv, K, conf = _problem()
+    uv, K, conf = _problem(N)
     sel = np.load(d / "results_selected.npz")
     pose, jh, jpx, hyp, T = _check_selected(sel, np.load(d / "reproj_selected.npz"), a, uv, K, conf)
     # pose recomputed from results.npy + every row's T gives joint_hypothesis again through zh.joint_reproj
-    x, Tall = _rows_and_T()
+    x, Tall = _rows_and_T(N, H, S)
     assert np.array_equal(x.reshape(H, N, 17, 3).permute(1, 0, 2, 3).cpu().numpy(), a)
     rows = dev(np.ascontiguousarray(a.transpose(1, 0, 2, 3)).reshape(H * N, 17, 3))
     best, idx = zh.joint_reproj(rows, Tall, dev(uv), dev(K))
@@ -160,18 +130,7 @@ def test_two_ranks_on_one_gpu_write_the_one_rank_file(one_rank, tmp_path):
     """Two fresh processes, two members of one gloo process group on device 0, each on its own row shard (12 rows each of 24): rank 0's
     _selected.npz is byte for byte the one-rank run's in all seven arrays, results.npy as well."""
     d, _ = one_rank
-    env = dict(os.environ)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "ZEDO_FORCE_DIST", "ZEDO_BENCH_FORCE_DIST"):
-        env.pop(k, None)
-    env.update(ZEDO_SHARE_DEVICE="1", ZEDO_DIST_BACKEND="gloo", ZEDO_NO_BUILD="1", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1",
-               MASTER_PORT=str(free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0",
-               PYTHONPATH=os.path.join(ROOT, "zedo-release_amd") + os.pathsep + env.get("PYTHONPATH", ""))
-    cmd = ["timeout", "-k", "10", "300", sys.executable, "-m", "run.inference"] + BASE + ["--out", str(tmp_path / "results.npy"), "--select", "joints"]
-    procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), cwd=str(tmp_path), stdout=subprocess.PIPE,
-                              stderr=subprocess.PIPE, text=True) for r in range(2)]
-    done = [p.communicate() + (p.returncode,) for p in procs]
-    for r, (out, err, rc) in enumerate(done):                       # every exit status, before anything else is looked at
-        assert rc == 0, (r, rc, out[-2000:], err[-4000:])
+    run_two_ranks(BASE + ["--out", str(tmp_path / "results.npy"), "--select", "joints"], tmp_path)
     assert np.load(tmp_path / "results.npy").tobytes() == np.load(d / "results.npy").tobytes()
     one, two = np.load(d / "results_selected.npz"), np.load(tmp_path / "results_selected.npz")
     assert sorted(two.files) == sorted(ARRAYS)

@@ -8,13 +8,11 @@ The spreads and the probabilities are PRINTED, not asserted: whether the fused p
 measured at all - the inputs here are synthetic and the weights random.  The fusion does not depend on the arithmetic mode of the dense
 layers: one session runs it."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from _shared import ROOT, cfg_path, dev, free_port, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
+from _shared import _inference, _problem, _rows_and_T, cfg_path, dev, run_two_ranks, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
 from _temporal_ref import clips
 
 pytestmark = pytest.mark.gpu
@@ -25,34 +23,6 @@ BASE = ["--config", cfg_path("pw3d"), "--synthetic", str(N), "--hypo", str(H), "
 JF = ["--select", "joints-fused", "--seq_len", str(L), "--smooth", "100"]
 ARRAYS = ("pose", "joint_cov", "joint_spread_m", "joint_hypothesis", "joint_weight", "joint_logz", "joint_hypothesis_viterbi", "hypothesis",
           "T", "reproj_px_pose_level", "seq_start", "smooth", "temperature")
-
-
-def _inference(argv, capsys):
-    import run.inference as inf
-    capsys.readouterr()
-    res, errs = inf.main(inf.parse_args(["prog"] + argv))
-    return res, errs, capsys.readouterr().out
-
-
-def _problem(n=N):
-    from lib.dataset import synthetic as syn
-    from run._driver import load_config
-    d = syn.make_poses(n, seed=load_config(cfg_path("pw3d")).seed)
-    return d["db_2d"][:, :, :2], d["camera_param"], d["db_2d"][:, :, 2]
-
-
-def _rows_and_T(n=N, h=H, s=S):
-    """The fused loop of the driver's synthetic pw3d run again: x [h n,17,3], T [h n,3] on the device (same kernels, same bits)."""
-    from lib.dataset import synthetic as syn
-    from run._driver import load_config
-    from zedo_hip.pipeline import Pipeline, ZeDOConfig
-    cfg = load_config(cfg_path("pw3d"))
-    z = cfg.ZeDO
-    uv, K, conf = _problem(n)
-    pipe = Pipeline(syn.make_weights(seed=cfg.seed), ZeDOConfig(z.IPO_iterations, z.IPO_keylist, z.RotAxes, z.IPO_T, z.IPO_minScaleT, z.IPO_maxScaleT,
-                                                                s, z.sampling_eps, 0.1, 1000, 0.1, 20.0), "cuda")
-    pipe.load(syn.make_clusters(h, seed=cfg.seed), np.concatenate([uv, conf[:, :, None]], -1), K)
-    return pipe.run()
 
 
 @pytest.fixture(scope="module")
@@ -88,9 +58,9 @@ def test_selected_npz_beside_an_unchanged_results_file(runs):
     for v, want in ((smooth, LAM), (temperature, 1.0)):
         assert v.dtype == np.float64 and v.shape == () and float(v) == want
     # every array again through the binding, from results.npy's rows and the loop's translations
-    x, Tall = _rows_and_T()
+    x, Tall = _rows_and_T(N, H, S)
     assert np.array_equal(x.reshape(H, N, 17, 3).permute(1, 0, 2, 3).cpu().numpy(), a)
-    uv, K, conf = (dev(v) for v in _problem())
+    uv, K, conf = (dev(v) for v in _problem(N))
     jerr = zh.joint_reproj(x, Tall, uv, K, return_rows=True)[2]
     err = zh.min_reproj(x, Tall, uv, K, conf)[0]
     path, _ = zh.temporal_select(err, x, seq, N, LAM)
@@ -158,18 +128,7 @@ def test_two_ranks_on_one_gpu_write_the_one_rank_file(runs, tmp_path):
     """Two fresh processes, two members of one gloo process group on device 0, each on its own row shard: rank 0's _selected.npz is byte
     for byte the one-rank run's in all thirteen arrays, results.npy as well."""
     d, _, _ = runs
-    env = dict(os.environ)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "ZEDO_FORCE_DIST", "ZEDO_BENCH_FORCE_DIST"):
-        env.pop(k, None)
-    env.update(ZEDO_SHARE_DEVICE="1", ZEDO_DIST_BACKEND="gloo", ZEDO_NO_BUILD="1", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1",
-               MASTER_PORT=str(free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0",
-               PYTHONPATH=os.path.join(ROOT, "zedo-release_amd") + os.pathsep + env.get("PYTHONPATH", ""))
-    cmd = ["timeout", "-k", "10", "300", sys.executable, "-m", "run.inference"] + BASE + ["--out", str(tmp_path / "results.npy")] + JF
-    procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), cwd=str(tmp_path), stdout=subprocess.PIPE,
-                              stderr=subprocess.PIPE, text=True) for r in range(2)]
-    done = [p.communicate() + (p.returncode,) for p in procs]
-    for r, (out, err, rc) in enumerate(done):                       # every exit status, before anything else is looked at
-        assert rc == 0, (r, rc, out[-2000:], err[-4000:])
+    run_two_ranks(BASE + ["--out", str(tmp_path / "results.npy")] + JF, tmp_path)
     assert np.load(tmp_path / "results.npy").tobytes() == np.load(d / "results.npy").tobytes()
     one, two = np.load(d / "results_selected.npz"), np.load(tmp_path / "results_selected.npz")
     assert sorted(two.files) == sorted(ARRAYS)

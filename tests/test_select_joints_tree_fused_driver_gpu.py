@@ -12,7 +12,7 @@ import pytest
 
 import _joint_tree_marginal_ref as M
 import _joint_tree_ref as R
-from _shared import cfg_path, dev, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
+from _shared import _inference, _problem, _rows_and_T, _sel, cfg_path, dev, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -23,34 +23,6 @@ KEYS = ("pose", "joint_cov", "joint_spread_m", "joint_hypothesis", "joint_weight
         "hypothesis", "T", "reproj_px_pose_level", "bone", "temperature")
 RUNS = {"none": [], "tree": ["--select", "joints-tree"], "fused": ["--select", "joints-tree-fused"],
         "cold": ["--select", "joints-tree-fused", "--temperature", "1e-9"]}
-
-
-def _inference(argv, capsys):
-    import run.inference as inf
-    capsys.readouterr()
-    res, errs = inf.main(inf.parse_args(["prog"] + argv))
-    return res, errs, capsys.readouterr().out
-
-
-def _problem():
-    from lib.dataset import synthetic as syn
-    from run._driver import load_config
-    d = syn.make_poses(N, seed=load_config(cfg_path("pw3d")).seed)
-    return d["db_2d"][:, :, :2], d["camera_param"], d["db_2d"][:, :, 2]
-
-
-def _rows_and_T():
-    """The fused loop of the driver's synthetic pw3d run again: x [H N,17,3], T [H N,3] on the device (same kernels, same bits)."""
-    from lib.dataset import synthetic as syn
-    from run._driver import load_config
-    from zedo_hip.pipeline import Pipeline, ZeDOConfig
-    cfg = load_config(cfg_path("pw3d"))
-    z = cfg.ZeDO
-    uv, K, conf = _problem()
-    pipe = Pipeline(syn.make_weights(seed=cfg.seed), ZeDOConfig(z.IPO_iterations, z.IPO_keylist, z.RotAxes, z.IPO_T, z.IPO_minScaleT, z.IPO_maxScaleT,
-                                                                S, z.sampling_eps, 0.1, 1000, 0.1, 20.0), "cuda")
-    pipe.load(syn.make_clusters(H, seed=cfg.seed), np.concatenate([uv, conf[:, :, None]], -1), K)
-    return pipe.run()
 
 
 @pytest.fixture(scope="module")
@@ -74,14 +46,10 @@ def runs(tmp_path_factory):
 def arrays():
     """The run's own arrays again (same kernels, same bits): rows x, T, the per-(row, joint) distances, the detections."""
     import zedo_hip as zh
-    uv, K, conf = _problem()
-    x, T = _rows_and_T()
+    uv, K, conf = _problem(N)
+    x, T = _rows_and_T(N, H, S)
     _, _, jerr = zh.joint_reproj(x, T, dev(uv), dev(K), return_rows=True)
     return dict(x=x.cpu().numpy(), T=T.cpu().numpy(), jerr=jerr.cpu().numpy(), conf=conf)
-
-
-def _sel(runs, name):
-    return np.load(str(runs[name][1])[:-4] + "_selected.npz")
 
 
 def test_results_file_is_unchanged_and_the_key_set_is_the_documented_one(runs):

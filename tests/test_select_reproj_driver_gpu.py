@@ -4,14 +4,12 @@ root-relative pose, its translation and its error in pixels.  Fused and step-wis
 real ranks on one GPU (gloo rehearsal transport) against the one-rank run.
 The selection does not depend on the arithmetic mode of the dense layers: one session runs it."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from _select_ref import reproj_ref
-from _shared import ROOT, cfg_path, free_port, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
+from _shared import _inference, _problem, cfg_path, run_two_ranks, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -19,20 +17,6 @@ torch = pytest.importorskip("torch")
 N, H, S = 8, 3, 10
 BASE = ["--config", cfg_path("pw3d"), "--synthetic", str(N), "--hypo", str(H), "--oil_iterations", str(S)]
 ARRAYS = ("pose", "hypothesis", "reproj_px", "T")
-
-
-def _inference(argv, capsys):
-    import run.inference as inf
-    capsys.readouterr()
-    res, errs = inf.main(inf.parse_args(["prog"] + argv))
-    return res, errs, capsys.readouterr().out
-
-
-def _problem(seed_cfg="pw3d"):
-    from lib.dataset import synthetic as syn
-    from run._driver import load_config
-    d = syn.make_poses(N, seed=load_config(cfg_path(seed_cfg)).seed)
-    return d["db_2d"][:, :, :2], d["camera_param"], d["db_2d"][:, :, 2]
 
 
 def _check_selected(sel, results, uv, K, conf, n=N, h=H):
@@ -66,7 +50,7 @@ def test_selected_npz_beside_an_unchanged_results_file(one_rank, tmp_path, capsy
     a, b = np.load(d / "results.npy"), np.load(tmp_path / "results.npy")
     assert a.shape == (N, H, 17, 3) and a.tobytes() == b.tobytes()                                  # results.npy bit for bit
     sel = np.load(d / "results_selected.npz")
-    uv, K, conf = _problem()
+    uv, K, conf = _problem(N)
     _check_selected(sel, a, uv, K, conf)
     # the hypothesis kept is the arg-min over ALL rows: the same loop again (same kernels, same bits) for every row's T
     from lib.dataset import synthetic as syn
@@ -141,18 +125,7 @@ def test_two_ranks_on_one_gpu_write_the_one_rank_file(one_rank, tmp_path):
     """Two fresh processes, two members of one gloo process group on device 0, each on its own row shard (12 rows each of 24): rank 0's
     _selected.npz is byte for byte the one-rank run's in all four arrays, results.npy as well."""
     d, _ = one_rank
-    env = dict(os.environ)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "ZEDO_FORCE_DIST", "ZEDO_BENCH_FORCE_DIST"):
-        env.pop(k, None)
-    env.update(ZEDO_SHARE_DEVICE="1", ZEDO_DIST_BACKEND="gloo", ZEDO_NO_BUILD="1", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1",
-               MASTER_PORT=str(free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0",
-               PYTHONPATH=os.path.join(ROOT, "zedo-release_amd") + os.pathsep + env.get("PYTHONPATH", ""))
-    cmd = ["timeout", "-k", "10", "300", sys.executable, "-m", "run.inference"] + BASE + ["--out", str(tmp_path / "results.npy"), "--select", "reproj"]
-    procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), cwd=str(tmp_path), stdout=subprocess.PIPE,
-                              stderr=subprocess.PIPE, text=True) for r in range(2)]
-    done = [p.communicate() + (p.returncode,) for p in procs]
-    for r, (out, err, rc) in enumerate(done):                       # every exit status, before anything else is looked at
-        assert rc == 0, (r, rc, out[-2000:], err[-4000:])
+    run_two_ranks(BASE + ["--out", str(tmp_path / "results.npy"), "--select", "reproj"], tmp_path)
     assert np.load(tmp_path / "results.npy").tobytes() == np.load(d / "results.npy").tobytes()
     one, two = np.load(d / "results_selected.npz"), np.load(tmp_path / "results_selected.npz")
     assert sorted(two.files) == sorted(ARRAYS)

@@ -6,13 +6,11 @@ from a 'wild' npz, and two real ranks on one GPU (gloo rehearsal transport) agai
 closer to ground truth on real video is not measured: the inputs here are synthetic and the weights random.
 The selection does not depend on the arithmetic mode of the dense layers: one session runs it."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from _shared import ROOT, cfg_path, free_port, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
+from _shared import _inference, cfg_path, run_two_ranks, one_arithmetic_mode  # noqa: F401  (one_arithmetic_mode: autouse fixture)
 from _temporal_ref import clips, cost_bound, temporal_ref
 
 pytestmark = pytest.mark.gpu
@@ -22,13 +20,6 @@ N, H, S, L, LAM = 12, 3, 10, 5, 100.0
 BASE = ["--config", cfg_path("pw3d"), "--synthetic", str(N), "--hypo", str(H), "--oil_iterations", str(S)]
 TEMPORAL = ["--select", "temporal", "--seq_len", str(L), "--smooth", "100"]
 ARRAYS = ("pose", "hypothesis", "hypothesis_per_frame", "reproj_px", "reproj_px_all", "path_cost", "T", "seq_start", "smooth")
-
-
-def _inference(argv, capsys):
-    import run.inference as inf
-    capsys.readouterr()
-    res, errs = inf.main(inf.parse_args(["prog"] + argv))
-    return res, errs, capsys.readouterr().out
 
 
 def _check_selected(sel, sel_reproj, results, seq, lam=LAM, n=N, h=H):
@@ -195,18 +186,7 @@ def test_two_ranks_on_one_gpu_write_the_one_rank_file(one_rank, tmp_path):
     """Two fresh processes, two members of one gloo process group on device 0, each on its own row shard (18 rows each of 36): rank 0's
     _selected.npz is byte for byte the one-rank run's in all nine arrays, results.npy as well."""
     d, _ = one_rank
-    env = dict(os.environ)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "ZEDO_FORCE_DIST", "ZEDO_BENCH_FORCE_DIST"):
-        env.pop(k, None)
-    env.update(ZEDO_SHARE_DEVICE="1", ZEDO_DIST_BACKEND="gloo", ZEDO_NO_BUILD="1", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1",
-               MASTER_PORT=str(free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0",
-               PYTHONPATH=os.path.join(ROOT, "zedo-release_amd") + os.pathsep + env.get("PYTHONPATH", ""))
-    cmd = ["timeout", "-k", "10", "300", sys.executable, "-m", "run.inference"] + BASE + ["--out", str(tmp_path / "results.npy")] + TEMPORAL
-    procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), cwd=str(tmp_path), stdout=subprocess.PIPE,
-                              stderr=subprocess.PIPE, text=True) for r in range(2)]
-    done = [p.communicate() + (p.returncode,) for p in procs]
-    for r, (out, err, rc) in enumerate(done):                       # every exit status, before anything else is looked at
-        assert rc == 0, (r, rc, out[-2000:], err[-4000:])
+    run_two_ranks(BASE + ["--out", str(tmp_path / "results.npy")] + TEMPORAL, tmp_path)
     assert np.load(tmp_path / "results.npy").tobytes() == np.load(d / "results.npy").tobytes()
     one, two = np.load(d / "results_selected.npz"), np.load(tmp_path / "results_selected.npz")
     assert sorted(two.files) == sorted(ARRAYS)

@@ -13,6 +13,8 @@ import os
 import numpy as np
 import torch
 
+from run._select import MODES, NONE, SELECT_HELP, SelectInputs, check_select_args, mode_of, prune_refusal  # noqa: F401  (check_select_args: re-exported)
+
 N_JOINTS, JOINT_DIM, HIDDEN_DIM, EMBED_DIM, CONDITION_DIM = 17, 3, 1024, 512, 3
 
 
@@ -29,23 +31,7 @@ def build_parser(description, inference=False):
     p.add_argument("--math", choices=("f32", "f16x3"), default=None,
                    help="arithmetic of the dense layers: f32 = exact fp32 MFMA (default), f16x3 = split-fp16 operands on the fp16 "
                         "matrix pipe at fp32-level accuracy, ~2x faster (same as the ZEDO_MATH environment variable)")
-    p.add_argument("--select", choices=("none", "reproj", "joints", "temporal", "joints-temporal", "joints-fused", "joints-tree", "joints-tree-fused"),
-                   default="none",
-                   help="run.inference only: reproj = also keep, per pose, the hypothesis whose x + T reprojects closest to the 2D "
-                        "detections (confidence-weighted, no ground truth needed) -> <out>_selected.npz; joints = keep, per JOINT, the "
-                        "hypothesis whose joint reprojects closest to its detection and assemble the pose from those joints; temporal = "
-                        "the frames are a video: per clip the hypothesis sequence that minimises reprojection error plus --smooth times "
-                        "the mean joint displacement between consecutive frames (Viterbi); joints-temporal = both: per clip and per JOINT the "
-                        "hypothesis sequence that minimises that joint's reprojection distance plus --smooth times that joint's displacement "
-                        "in the camera frame (one Viterbi chain per joint), the pose assembled from those joints; joints-fused = the soft "
-                        "answer of the same chain model at --temperature: per joint the posterior mean position over the hypotheses, its "
-                        "covariance (the depth ambiguity in metres) and the most probable hypothesis with its probability; joints-tree = "
-                        "joints with the skeleton as a coupling: per pose the assignment of a hypothesis to every joint that minimises the "
-                        "joints' confidence-weighted reprojection distances plus --bone times, for every bone, the difference between the "
-                        "assembled bone's length and the length its two hypotheses give that bone (exact min-sum over the bone tree); "
-                        "joints-tree-fused = the soft answer of the same skeleton model at --temperature, from one image: per joint the "
-                        "posterior mean position over the hypotheses, its covariance, the most probable hypothesis with its probability "
-                        "and every bone's expected mismatch (exact sum-product over the bone tree)")
+    p.add_argument("--select", choices=tuple(MODES), default=NONE.name, help=SELECT_HELP)
     p.add_argument("--smooth", type=float, default=None, metavar="LAMBDA",
                    help="--select temporal: weight of the motion cost in pixels per metre (default 100: a mean joint jump of 1 cm costs as "
                         "much as 1 px of reprojection error; the default is UNTUNED - its effect on accuracy has not been measured); "
@@ -81,47 +67,6 @@ def build_parser(description, inference=False):
         p.add_argument("--data", type=str, default=None, help="npz with db_2d, camera_param[, db_3d] ('wild' dataset)")
         p.add_argument("--out", type=str, default="results.npy")
     return p
-
-
-def check_select_args(args):
-    """--smooth / --seq_len belong to --select temporal, joints-temporal and joints-fused; --smooth defaults to 100 there.  --temperature
-    belongs to --select joints-fused and defaults to 1 there.  --accel belongs to --select joints-temporal and has no default.  --bone
-    belongs to --select joints-tree and defaults to 100 there.  --select joints-tree-fused takes --bone and --temperature with the same
-    defaults and checks."""
-    select = getattr(args, "select", "none") or "none"
-    bone = getattr(args, "bone", None)
-    if select not in ("joints-tree", "joints-tree-fused"):
-        if bone is not None:
-            raise SystemExit("--bone is a switch of --select joints-tree")
-    elif bone is None:
-        args.bone = 100.0
-    elif not (np.isfinite(bone) and bone >= 0):
-        raise SystemExit(f"--bone {bone}: a finite weight >= 0 expected")
-    accel = getattr(args, "accel", None)
-    if accel is not None:
-        if select != "joints-temporal":
-            raise SystemExit("--accel is a switch of --select joints-temporal")
-        if not (np.isfinite(accel) and accel >= 0):
-            raise SystemExit(f"--accel {accel}: a finite weight >= 0 expected")
-    smooth, seq_len = getattr(args, "smooth", None), getattr(args, "seq_len", None)
-    temperature = getattr(args, "temperature", None)
-    if select not in ("joints-fused", "joints-tree-fused"):
-        if temperature is not None:
-            raise SystemExit("--temperature is a switch of --select joints-fused")
-    elif temperature is None:
-        args.temperature = 1.0
-    elif not (np.isfinite(temperature) and temperature > 0):
-        raise SystemExit(f"--temperature {temperature}: a finite temperature > 0 expected")
-    if select not in ("temporal", "joints-temporal", "joints-fused"):
-        if smooth is not None or seq_len is not None:
-            raise SystemExit("--smooth and --seq_len are switches of --select temporal and --select joints-temporal")
-        return
-    if smooth is None:
-        args.smooth = 100.0
-    elif not (np.isfinite(smooth) and smooth >= 0):
-        raise SystemExit(f"--smooth {smooth}: a finite weight >= 0 expected")
-    if seq_len is not None and seq_len < 1:
-        raise SystemExit(f"--seq_len {seq_len}: at least one frame per clip")
 
 
 def load_config(path):
@@ -272,7 +217,7 @@ def pruned_path(out):
 
 
 def selected_path(out):
-    """<out without .npy>_selected.npz: where run.inference --select reproj / joints / temporal / joints-temporal / joints-fused / joints-tree / joints-tree-fused writes the pose it keeps per detection."""
+    """<out without .npy>_selected.npz: where run.inference --select (every choice but none) writes the pose it keeps per detection."""
     return (out[:-4] if out.endswith(".npy") else out) + "_selected.npz"
 
 
@@ -280,19 +225,18 @@ def run(args, inference=False):
     from lib.algorithms.advanced import sde_lib
     from lib.algorithms.advanced.model import ScoreModelFC_Adv
     from lib.algorithms.ema import ExponentialMovingAverage
-    from zedo_hip.pipeline import (Pipeline, ZeDOConfig, barrier, empty_selection, force_dist, gather_row_shards, init_dist,
-                                   local_device_index, parse_prune_plan, prune_row_steps, reduce_min_over_ranks, shard_hypotheses,
-                                   shard_rows, take_rows)
+    from zedo_hip.pipeline import (Pipeline, ZeDOConfig, barrier, force_dist, gather_row_shards, init_dist, local_device_index,
+                                   parse_prune_plan, prune_row_steps, shard_hypotheses, shard_rows)
 
-    select = getattr(args, "select", "none") or "none"
-    if select != "none" and not inference:
+    mode = mode_of(args)                             # the --select table (run/_select.py): everything mode-specific below comes from its entry
+    select = mode.name
+    if mode.fn is not None and not inference:
         raise SystemExit(f"--select {select} is honoured by run.inference only: run.opt_main scores every hypothesis against 3D ground "
                          "truth (best of H), and the ground-truth evaluation of a selected pose is printed by run.inference --eval")
     check_select_args(args)
     prune = getattr(args, "prune", None)
-    if prune is not None and select in ("joints", "temporal", "joints-temporal", "joints-fused", "joints-tree", "joints-tree-fused"):
-        raise SystemExit(f"--prune with --select {select} is not supported yet (a follow-up): the pruned run keeps different hypotheses "
-                         "per pose; use --select reproj or none")
+    if prune is not None and prune_refusal(select):
+        raise SystemExit(prune_refusal(select))
     if prune is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("--prune runs on one rank only: the rows are sharded by (hypothesis, pose), so the hypotheses of one pose live on "
                          "several ranks and no rank can rank them; pose-sharded pruning is not built")
@@ -341,12 +285,8 @@ def run(args, inference=False):
     z = config.ZeDO
     S = args.oil_iterations or z.OIL_iterations
     H, N = len(sample_poses), len(gt_3d)
-    if select == "joints-tree-fused":
-        import zedo_hip
-        cap = zedo_hip.joint_tree_marginal_max_h(N_JOINTS)
-        if H > cap:
-            raise SystemExit(f"--select joints-tree-fused admits at most {cap} hypotheses per pose at {N_JOINTS} joints (the model of a pose lives "
-                             f"in the LDS of one workgroup), --hypo {H} given: use fewer hypotheses, or --select joints-tree")
+    if mode.admits is not None:
+        mode.admits(select, H, N_JOINTS)
     lo, rows = shard_rows(H * N, rank, world)
     why = not_fused_because(config)
     if prune is not None:
@@ -356,7 +296,7 @@ def run(args, inference=False):
             plan = parse_prune_plan(prune, H, S)
         except ValueError as e:
             raise SystemExit(f"--prune: {e}")
-    hyp = None
+    hyp = pipe = None
     if why is None:
         cfg = ZeDOConfig(z.IPO_iterations, z.IPO_keylist, z.RotAxes, z.IPO_T, z.IPO_minScaleT, z.IPO_maxScaleT, S,
                          z.sampling_eps, sde.T, sde.N, sde.beta_0, sde.beta_1)
@@ -374,8 +314,8 @@ def run(args, inference=False):
         if rank == 0:
             print(f"configuration outside the fused pipeline ({why}): stepping the loop of run/opt_main.py:166-222 "
                   f"through the per-step sampling_fn surface, hypotheses split over {world} rank(s)")
-        x = stepwise_loop(config, model, sde, sample_poses, gt_2d, K, S, device, hypotheses=(h_lo, h_cnt), return_T=select != "none")
-        if select != "none":
+        x = stepwise_loop(config, model, sde, sample_poses, gt_2d, K, S, device, hypotheses=(h_lo, h_cnt), return_T=mode.fn is not None)
+        if mode.fn is not None:
             x, T = x
 
     batch_results = None
@@ -389,217 +329,8 @@ def run(args, inference=False):
                 np.savez(pruned_path(args.out), hypothesis=hyp.t().contiguous().cpu().numpy().astype(np.int32),
                          stage_step=np.array([s for s, _ in plan], np.int32), stage_keep=np.array([k for _, k in plan], np.int32))
     selected = None
-    if inference and select == "reproj":
-        # per pose the hypothesis whose x + T reprojects closest to the detections (zedo_min_reproj) on this rank's rows, MIN over the
-        # ranks, the winners taken from the gathered rows: every rank ends with the same four arrays, rank 0 writes them
-        import zedo_hip
-        if rows == 0:
-            best, idx = empty_selection(N, device)
-        elif why is None:
-            best, idx = pipe.select_reproj(x, T, row_offset=lo)
-        else:
-            d2 = torch.tensor(np.ascontiguousarray(gt_2d), dtype=torch.float32, device=device)
-            Kd = torch.tensor(np.ascontiguousarray(K), dtype=torch.float32, device=device)
-            _, best, idx = zedo_hip.min_reproj(x, T.contiguous(), d2[:, :, :2].contiguous(), Kd, d2[:, :, 2].contiguous(), N, lo)
-        best, idx = reduce_min_over_ranks(best, idx)
-        full_T = T if hyp is not None else gather_row_shards(T.contiguous(), H * N, lo=None if why is None else lo)
-        # with --prune idx is a survivor slot: the file names the original hypothesis
-        kept = idx if hyp is None else take_rows(hyp.reshape(-1), idx, H, N)
-        selected = dict(pose=take_rows(full, idx, H, N).cpu().numpy(), hypothesis=kept.cpu().numpy().astype(np.int32),
-                        reproj_px=best.cpu().numpy(), T=take_rows(full_T, idx, H, N).cpu().numpy())
-        if rank == 0:
-            np.savez(selected_path(args.out), **selected)
-    if inference and select == "joints":
-        # per (pose, joint) the hypothesis whose joint reprojects closest to its detection (zedo_joint_reproj) on this rank's rows, beside
-        # the pose-level winner (zedo_min_reproj) whose frame the assembled pose is written in; both MIN over the ranks (element-wise), the
-        # joints gathered from all rows (zedo_joint_compose): every rank ends with the same arrays, rank 0 writes them
-        import zedo_hip
-        if why is None:
-            uvd, Kd, cfd = pipe.uv, pipe.K, pipe.conf
-        else:
-            d2 = torch.tensor(np.ascontiguousarray(gt_2d), dtype=torch.float32, device=device)
-            uvd, Kd, cfd = d2[:, :, :2].contiguous(), torch.tensor(np.ascontiguousarray(K), dtype=torch.float32, device=device), d2[:, :, 2].contiguous()
-        if rows == 0:
-            best, idx = empty_selection(N, device)
-            jbest, jidx = (t.reshape(N, N_JOINTS) for t in empty_selection(N * N_JOINTS, device))
-        elif why is None:
-            best, idx = pipe.select_reproj(x, T, row_offset=lo)
-            jbest, jidx = pipe.aggregate_reproj(x, T, row_offset=lo)
-        else:
-            _, best, idx = zedo_hip.min_reproj(x, T.contiguous(), uvd, Kd, cfd, N, lo)
-            jbest, jidx = zedo_hip.joint_reproj(x, T.contiguous(), uvd, Kd, N, lo)
-        best, idx = reduce_min_over_ranks(best, idx)
-        jbest, jidx = reduce_min_over_ranks(jbest, jidx)
-        full_T = gather_row_shards(T.contiguous(), H * N, lo=None if why is None else lo)
-        pose = zedo_hip.joint_compose(full.contiguous(), full_T, jidx.contiguous(), idx.contiguous(), N)
-        T_sel = take_rows(full_T, idx, H, N).contiguous()
-        _, px, _ = zedo_hip.min_reproj(pose, T_sel, uvd, Kd, cfd, N, 0)       # the assembled poses as a one-hypothesis problem
-        selected = dict(pose=pose.cpu().numpy(), joint_hypothesis=jidx.cpu().numpy().astype(np.int32), joint_reproj_px=jbest.cpu().numpy(),
-                        hypothesis=idx.cpu().numpy().astype(np.int32), T=T_sel.cpu().numpy(), reproj_px=px.cpu().numpy(),
-                        reproj_px_pose_level=best.cpu().numpy())
-        if rank == 0:
-            np.savez(selected_path(args.out), **selected)
-
-    def tree_inputs():
-        # what --select joints-tree and joints-tree-fused share, --select joints step for step: each rank evaluates zedo_min_reproj and
-        # zedo_joint_reproj (the route that writes every row's per-joint distances) on its own rows, both MIN over the ranks; the
-        # distances and T are gathered like the rows, so that every rank holds the full arrays; the bone tree is the dataset's.
-        # -> (uvd, Kd, cfd, pose-level best and idx, what --select joints keeps, full_jerr, full_T, parent)
-        import zedo_hip
-        if why is None:
-            uvd, Kd, cfd = pipe.uv, pipe.K, pipe.conf
-        else:
-            d2 = torch.tensor(np.ascontiguousarray(gt_2d), dtype=torch.float32, device=device)
-            uvd, Kd, cfd = d2[:, :, :2].contiguous(), torch.tensor(np.ascontiguousarray(K), dtype=torch.float32, device=device), d2[:, :, 2].contiguous()
-        if rows == 0:
-            best, idx = empty_selection(N, device)
-            jerr = torch.empty((0, N_JOINTS), dtype=torch.float64, device=device)
-            jbest0, jidx0 = (t.reshape(N, N_JOINTS) for t in empty_selection(N * N_JOINTS, device))
-        else:
-            _, best, idx = zedo_hip.min_reproj(x, T.contiguous(), uvd, Kd, cfd, N, lo)
-            jbest0, jidx0, jerr = zedo_hip.joint_reproj(x, T.contiguous(), uvd, Kd, N, lo, return_rows=True)
-        best, idx = reduce_min_over_ranks(best, idx)
-        jbest0, jidx0 = reduce_min_over_ranks(jbest0, jidx0)                       # what --select joints keeps
-        glo = None if why is None else lo
-        full_jerr = gather_row_shards(jerr, H * N, lo=glo).contiguous()
-        full_T = gather_row_shards(T.contiguous(), H * N, lo=glo).contiguous()
-        skeleton = test_dataset.get_skeleton() if hasattr(test_dataset, "get_skeleton") else zedo_hip.H36M_EDGES
-        return uvd, Kd, cfd, best, idx, jidx0, full_jerr, full_T, zedo_hip.skeleton_parents(skeleton, N_JOINTS)
-
-    if inference and select == "joints-tree":
-        # --select joints with the skeleton as a coupling: on the arrays of tree_inputs() every rank runs the same min-sum over the bone
-        # tree (zedo_joint_tree_select, the confidences as weights) and ends with the same arrays, rank 0 writes them
-        import zedo_hip
-        uvd, Kd, cfd, best, idx, jidx0, full_jerr, full_T, parent = tree_inputs()
-        jidx, tcost, jbone = zedo_hip.joint_tree_select(full_jerr, full.contiguous(), full_T, parent, N, args.bone, cfd)
-        pose = zedo_hip.joint_compose(full.contiguous(), full_T, jidx.contiguous(), idx.contiguous(), N)
-        T_sel = take_rows(full_T, idx, H, N).contiguous()
-        _, px, _ = zedo_hip.min_reproj(pose, T_sel, uvd, Kd, cfd, N, 0)           # the assembled poses as a one-hypothesis problem
-        jpx = full_jerr.reshape(H, N, N_JOINTS).gather(0, jidx.to(torch.int64)[None])[0]
-        selected = dict(pose=pose.cpu().numpy(), joint_hypothesis=jidx.cpu().numpy().astype(np.int32),
-                        joint_hypothesis_per_joint=jidx0.cpu().numpy().astype(np.int32), joint_reproj_px=jpx.cpu().numpy(),
-                        joint_bone_m=jbone.cpu().numpy(), tree_cost=tcost.cpu().numpy(), hypothesis=idx.cpu().numpy().astype(np.int32),
-                        T=T_sel.cpu().numpy(), reproj_px=px.cpu().numpy(), reproj_px_pose_level=best.cpu().numpy(),
-                        bone=np.float64(args.bone))
-        if rank == 0:
-            np.savez(selected_path(args.out), **selected)
-    if inference and select == "joints-tree-fused":
-        # the soft answer of the skeleton model of joints-tree, on the same arrays (tree_inputs()): every rank runs the same sum-product
-        # over the bone tree (zedo_joint_tree_marginal, the confidences as weights) and, for comparison, the min-sum of joints-tree at the
-        # same weight and ends with the same arrays, rank 0 writes them
-        import zedo_hip
-        _, _, cfd, best, idx, _, full_jerr, full_T, parent = tree_inputs()
-        mean, cov, hmax, wmax, logz, ebone = zedo_hip.joint_tree_marginal(full_jerr, full.contiguous(), full_T, parent, N, args.bone,
-                                                                          args.temperature, cfd)
-        jtree, _, _ = zedo_hip.joint_tree_select(full_jerr, full.contiguous(), full_T, parent, N, args.bone, cfd)
-        T_sel = take_rows(full_T, idx, H, N).contiguous()
-        pose = (mean - T_sel.to(torch.float64)[:, None, :]).to(torch.float32)     # in the frame --select joints-tree writes in
-        spread = (cov[:, :, 0] + cov[:, :, 3] + cov[:, :, 5]).sqrt()
-        selected = dict(pose=pose.cpu().numpy(), joint_cov=cov.cpu().numpy(), joint_spread_m=spread.cpu().numpy(),
-                        joint_hypothesis=hmax.cpu().numpy().astype(np.int32), joint_weight=wmax.cpu().numpy(), joint_logz=logz.cpu().numpy(),
-                        joint_bone_m=ebone.cpu().numpy(), joint_hypothesis_tree=jtree.cpu().numpy().astype(np.int32),
-                        hypothesis=idx.cpu().numpy().astype(np.int32), T=T_sel.cpu().numpy(), reproj_px_pose_level=best.cpu().numpy(),
-                        bone=np.float64(args.bone), temperature=np.float64(args.temperature))
-        if rank == 0:
-            np.savez(selected_path(args.out), **selected)
-    if inference and select == "temporal":
-        # the frames are a video: each rank evaluates zedo_min_reproj on its own rows, the per-row errors and T are gathered like the rows,
-        # every rank runs the same Viterbi (zedo_temporal_select) on the full arrays and ends with the same arrays, rank 0 writes them
-        import zedo_hip
-        if args.seq_len is not None:
-            seq = np.array(list(range(0, N, args.seq_len)) + [N], np.int32)
-        else:
-            seq = np.asarray(getattr(test_dataset, "seq_start", [0, N]), np.int32)
-        if rows == 0:
-            err = torch.empty((0,), dtype=torch.float64, device=device)
-        elif why is None:
-            err, _, _ = zedo_hip.min_reproj(x, T, pipe.uv, pipe.K, pipe.conf, N, lo)
-        else:
-            d2 = torch.tensor(np.ascontiguousarray(gt_2d), dtype=torch.float32, device=device)
-            Kd = torch.tensor(np.ascontiguousarray(K), dtype=torch.float32, device=device)
-            err, _, _ = zedo_hip.min_reproj(x, T.contiguous(), d2[:, :, :2].contiguous(), Kd, d2[:, :, 2].contiguous(), N, lo)
-        full_err = gather_row_shards(err, H * N, lo=None if why is None else lo).contiguous()
-        full_T = gather_row_shards(T.contiguous(), H * N, lo=None if why is None else lo)
-        per_frame, idx0 = zedo_hip.pose_min(full_err, N)             # what --select reproj keeps
-        path, cost = zedo_hip.temporal_select(full_err, full.contiguous(), seq, N, args.smooth)
-        selected = dict(pose=take_rows(full, path, H, N).cpu().numpy(), hypothesis=path.cpu().numpy().astype(np.int32),
-                        hypothesis_per_frame=idx0.cpu().numpy().astype(np.int32), reproj_px=take_rows(full_err, path, H, N).cpu().numpy(),
-                        reproj_px_all=full_err.reshape(H, N).t().contiguous().cpu().numpy(), path_cost=cost.cpu().numpy(),
-                        T=take_rows(full_T, path, H, N).cpu().numpy(), seq_start=seq.astype(np.int32), smooth=np.float64(args.smooth))
-        if rank == 0:
-            np.savez(selected_path(args.out), **selected)
-
-    def video_joint_inputs():
-        # what --select joints-temporal and joints-fused share: the clips; each rank evaluates zedo_joint_reproj (the route that writes every
-        # row's per-joint distances) and zedo_min_reproj on its own rows; the distances, the errors and T are gathered like the rows, so that
-        # every rank holds the full arrays.  -> (seq, uvd, Kd, cfd, full_err, full_jerr, full_T, full rows, what --select joints keeps)
-        import zedo_hip
-        if args.seq_len is not None:
-            seq = np.array(list(range(0, N, args.seq_len)) + [N], np.int32)
-        else:
-            seq = np.asarray(getattr(test_dataset, "seq_start", [0, N]), np.int32)
-        if why is None:
-            uvd, Kd, cfd = pipe.uv, pipe.K, pipe.conf
-        else:
-            d2 = torch.tensor(np.ascontiguousarray(gt_2d), dtype=torch.float32, device=device)
-            uvd, Kd, cfd = d2[:, :, :2].contiguous(), torch.tensor(np.ascontiguousarray(K), dtype=torch.float32, device=device), d2[:, :, 2].contiguous()
-        if rows == 0:
-            err = torch.empty((0,), dtype=torch.float64, device=device)
-            jerr = torch.empty((0, N_JOINTS), dtype=torch.float64, device=device)
-            jbest0, jidx0 = (t.reshape(N, N_JOINTS) for t in empty_selection(N * N_JOINTS, device))
-        else:
-            err, _, _ = zedo_hip.min_reproj(x, T.contiguous(), uvd, Kd, cfd, N, lo)
-            jbest0, jidx0, jerr = zedo_hip.joint_reproj(x, T.contiguous(), uvd, Kd, N, lo, return_rows=True)
-        jbest0, jidx0 = reduce_min_over_ranks(jbest0, jidx0)                       # what --select joints keeps
-        glo = None if why is None else lo
-        full_err = gather_row_shards(err, H * N, lo=glo).contiguous()
-        full_jerr = gather_row_shards(jerr, H * N, lo=glo).contiguous()
-        full_T = gather_row_shards(T.contiguous(), H * N, lo=glo).contiguous()
-        return seq, uvd, Kd, cfd, full_err, full_jerr, full_T, full.contiguous(), jidx0
-
-    if inference and select == "joints-temporal":
-        # the frames are a video and the pose is assembled joint by joint: each rank evaluates zedo_joint_reproj (the route that writes every
-        # row's per-joint distances) and zedo_min_reproj on its own rows; the distances, the errors and T are gathered like the rows; every
-        # rank runs the pose-level Viterbi (zedo_temporal_select: the frame the pose is written in is itself consistent along the clip) and
-        # the J joint-wise ones (zedo_joint_temporal_select) on the full arrays and ends with the same arrays, rank 0 writes them
-        import zedo_hip
-        seq, uvd, Kd, cfd, full_err, full_jerr, full_T, full, jidx0 = video_joint_inputs()
-        idx, _ = zedo_hip.temporal_select(full_err, full, seq, N, args.smooth)
-        accel = getattr(args, "accel", None)
-        if accel is None:
-            jpath, jcost = zedo_hip.joint_temporal_select(full_jerr, full, full_T, seq, N, args.smooth)
-        else:                                                                     # the second-order chain (zedo_joint_accel_select)
-            jpath, jcost = zedo_hip.joint_accel_select(full_jerr, full, full_T, seq, N, args.smooth, accel)
-        pose = zedo_hip.joint_compose(full, full_T, jpath.contiguous(), idx.contiguous(), N)
-        T_sel = take_rows(full_T, idx, H, N).contiguous()
-        _, px, _ = zedo_hip.min_reproj(pose, T_sel, uvd, Kd, cfd, N, 0)           # the assembled poses as a one-hypothesis problem
-        jpx = full_jerr.reshape(H, N, N_JOINTS).gather(0, jpath.to(torch.int64)[None])[0]
-        selected = dict(pose=pose.cpu().numpy(), joint_hypothesis=jpath.cpu().numpy().astype(np.int32),
-                        joint_hypothesis_per_frame=jidx0.cpu().numpy().astype(np.int32), joint_reproj_px=jpx.cpu().numpy(),
-                        joint_path_cost=jcost.cpu().numpy(), hypothesis=idx.cpu().numpy().astype(np.int32), T=T_sel.cpu().numpy(),
-                        reproj_px=px.cpu().numpy(), reproj_px_pose_level=take_rows(full_err, idx, H, N).cpu().numpy(),
-                        seq_start=seq.astype(np.int32), smooth=np.float64(args.smooth))
-        if accel is not None:
-            selected["accel"] = np.float64(accel)
-        if rank == 0:
-            np.savez(selected_path(args.out), **selected)
-    if inference and select == "joints-fused":
-        # the soft answer of the chain model of joints-temporal: the same unaries, errors and T gathered the same way; every rank runs the
-        # pose-level Viterbi (the frame the pose is written in), the J forward-backward passes (zedo_joint_marginal) and, for comparison,
-        # the J joint-wise Viterbi chains on the full arrays and ends with the same arrays, rank 0 writes them
-        import zedo_hip
-        seq, uvd, Kd, cfd, full_err, full_jerr, full_T, full, _ = video_joint_inputs()
-        idx, _ = zedo_hip.temporal_select(full_err, full, seq, N, args.smooth)
-        mean, cov, hmax, wmax, logz = zedo_hip.joint_marginal(full_jerr, full, full_T, seq, N, args.smooth, args.temperature)
-        jpath, _ = zedo_hip.joint_temporal_select(full_jerr, full, full_T, seq, N, args.smooth)
-        T_sel = take_rows(full_T, idx, H, N).contiguous()
-        pose = (mean - T_sel.to(torch.float64)[:, None, :]).to(torch.float32)     # in the frame --select joints-temporal writes in
-        spread = (cov[:, :, 0] + cov[:, :, 3] + cov[:, :, 5]).sqrt()
-        selected = dict(pose=pose.cpu().numpy(), joint_cov=cov.cpu().numpy(), joint_spread_m=spread.cpu().numpy(),
-                        joint_hypothesis=hmax.cpu().numpy().astype(np.int32), joint_weight=wmax.cpu().numpy(), joint_logz=logz.cpu().numpy(),
-                        joint_hypothesis_viterbi=jpath.cpu().numpy().astype(np.int32), hypothesis=idx.cpu().numpy().astype(np.int32),
-                        T=T_sel.cpu().numpy(), reproj_px_pose_level=take_rows(full_err, idx, H, N).cpu().numpy(),
-                        seq_start=seq.astype(np.int32), smooth=np.float64(args.smooth), temperature=np.float64(args.temperature))
+    if mode.fn is not None:
+        selected = mode.fn(SelectInputs(args, N, H, lo, rows, x, T, full, hyp, why, pipe, (gt_2d, K), test_dataset, device))
         if rank == 0:
             np.savez(selected_path(args.out), **selected)
     errs = None
@@ -623,10 +354,8 @@ def run(args, inference=False):
                 s1 = test_dataset.eval_multi(("rows", sel_rows), protocol2=False, print_verbose=False, row_offset=0)
                 s2 = test_dataset.eval_multi(("rows", sel_rows), protocol2=True, print_verbose=False, row_offset=0)
             if rank == 0:
-                label = {"joints": "joints-aggregated", "temporal": "temporal-selected", "joints-temporal": "joints-temporal", "joints-fused": "joints-fused", "joints-tree": "joints-tree",
-                         "joints-tree-fused": "joints-tree-fused"}.get(select, "reproj-selected")
-                print(f"{label} MPJPE : {s1}")
-                print(f"{label} PA-MPJPE : {s2}")
+                print(f"{mode.label} MPJPE : {s1}")
+                print(f"{mode.label} PA-MPJPE : {s2}")
             errs = (p1, p2, s1, s2)
     if use_dist:
         import torch.distributed as dist
