@@ -48,7 +48,8 @@ extern "C" {
                               * still 5 (additive): + zedo_prune_rank, zedo_prune_gather;
                               * still 5 (additive): + zedo_joint_temporal_workspace_bytes, zedo_joint_temporal_select;
                               * still 5 (additive): + zedo_joint_marginal_workspace_bytes, zedo_joint_marginal;
-                              * still 5 (additive): + zedo_joint_accel_workspace_bytes, zedo_joint_accel_select */
+                              * still 5 (additive): + zedo_joint_accel_workspace_bytes, zedo_joint_accel_select;
+                              * still 5 (additive): + zedo_joint_accel_marginal_workspace_bytes, zedo_joint_accel_marginal */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -492,6 +493,55 @@ size_t zedo_joint_accel_workspace_bytes(int N, int H, int J);
 int zedo_joint_accel_select(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
                             int H, int N, int J, double lambda_v, double lambda_a, void *d_workspace, size_t workspace_bytes,
                             int *d_path_h, double *d_cost, void *stream);
+
+/* ---- fusing hypotheses along a video under the second-order motion model: exact sum-product over pairs ----------------------
+ * The soft answer of zedo_joint_accel_select, as zedo_joint_marginal is the soft answer of zedo_joint_temporal_select: the same
+ * energy read as a probability at a temperature tau,
+ *   p(path of joint j over a chain) proportional to exp(-(sum u + lambda_v sum m + lambda_a sum a) / tau),
+ * and from it, exactly (forward-backward over PAIRS of hypotheses in the log domain), the posterior marginal of every
+ * hypothesis of every (frame, joint), the posterior mean position, its covariance and the most probable hypothesis.  The
+ * marginals of zedo_joint_marginal spread over more hypotheses the faster a limb moves (its motion term is a zero-velocity
+ * prior); these are blind to a constant velocity at lambda_v = 0.  The defaults of the bindings (lambda_v = lambda_a = 100, tau
+ * = 1) are untuned, and whether the fused pose is closer to ground truth than any other on real video is not measured.
+ * Inputs, X, u, m, a, DEAD, the chains (a maximal run c0 .. c1-1 of live frames of one joint inside a clip) and the exclusion of
+ * a hypothesis with a non-finite unary, for that joint only, are those of zedo_joint_accel_select, word for word; tau > 0 is
+ * the temperature in cost units.  All arithmetic in float64, independent for every joint j.  With l[n,h] = -u[n,j,h] / tau (-inf
+ * when excluded), c_v = lambda_v / tau, c_a = lambda_a / tau, LSE the log of a sum of exponentials:
+ *   c1 - c0 == 1:   w[c0,h] = exp(l[c0,h] - logZ),  logZ = LSE_h l[c0,h]
+ *   n == c0+1:      A2[n][h',h] = l[n-1,h'] + (l[n,h] - c_v m[n,h',h])
+ *   n >= c0+2:      A2[n][h',h] = l[n,h] + (-c_v m[n,h',h] + LSE_h'' (A2[n-1][h'',h'] - c_a a[n,h'',h',h]))
+ *   chain end:      B2[c1-1] = 0  and  logZ = LSE over all pairs (h',h) of A2[c1-1][h',h]
+ *   below it:       M[h+][h] = (l[n+1,h+] - c_v m[n+1,h,h+]) + B2[n+1][h,h+],
+ *                   B2[n][h',h] = LSE_h+ (M[h+][h] - c_a a'[n+1,h',h,h+])
+ *   pair marginal:  pi[n][h',h] = exp((A2[n][h',h] + B2[n][h',h]) - logZ)
+ *   marginal:       w[n,h] = sum_h' pi[n][h',h] for n >= c0+1;  w[c0,h'] = sum_h pi[c0+1][h',h]
+ * Every sum over a hypothesis index runs ascending; logZ of a chain of two frames or more adds exp(A2 - max) over the pairs a
+ * lane owns in ascending q = h' H + h (q = lane, lane + 256, ..), then a butterfly over the 64 lanes of a wave, then the four
+ * waves in ascending order.  Every LSE is evaluated shifted by the TRUE maximum of its terms (two walks over the terms): at a
+ * small tau the largest term contributes exactly 1 and nothing that matters underflows.  An excluded hypothesis has w = 0
+ * exactly.  a is the term of zedo_joint_accel_select, e_c = (X[n,h] - 2 X[n-1,h']) + X[n-2,h''], in the forward pass; the
+ * backward pass forms a' with e_c = (X[n-1,h'] - 2 X[n,h]) + X[n+1,h+]: the same second difference in another association,
+ * one rounding apart; the error bound of tests/_joint_accel_marginal_ref.py covers either.
+ * Outputs and a dead (frame, joint) are those of zedo_joint_marginal, word for word: d_mean [N,J,3]; d_cov [N,J,6] from the
+ * centred differences; d_hmax [N,J] int32, the lowest h with the largest marginal; d_wmax [N,J]; d_logz [N,J], repeated on
+ * every frame of the chain; d_w [N,J,H] optional (NULL: not written); a dead (frame, joint) reports NaN in mean and cov,
+ * hypothesis 0, wmax = 0, logz = -inf and a row of zeros in d_w.
+ * Workspace (8-byte aligned, need not be initialised): A2 as [J,N,H,H] float64 - the frames of one chain are contiguous - and
+ * one int32 flag per (frame, joint), padded to 8 bytes: zedo_joint_accel_marginal_workspace_bytes(N, H, J) = 8 N J H^2 +
+ * pad8(4 N J); 0 for sizes the call refuses.  That is 345 MB at 1 015 frames x 17 joints x 50^2: cut a long recording into
+ * calls of whole clips (the chains of different clips are independent).  B2, M and pi never leave the LDS.
+ * Contract: that of zedo_joint_accel_select - J >= 1, N >= 1, 1 <= n_seq <= N, 1 <= H <= 64, N*J*H <= INT_MAX, finite
+ * lambda_v >= 0 and lambda_a >= 0 - and finite tau > 0; ZEDO_E_BADARG with nothing written for a NULL pointer other than d_T
+ * and d_w, a non-positive size, H > 64, n_seq > N, N*J*H above INT_MAX, a negative or non-finite lambda_v or lambda_a, tau <= 0
+ * or not finite, or a workspace that is not 8-byte aligned; ZEDO_E_WORKSPACE with nothing written if workspace_bytes is too
+ * small; allocates nothing, synchronises nothing, enqueues on `stream` only: legal under stream capture; no atomics, every sum
+ * in a fixed order: bit-identical from run to run, for any alignment of d_x and any workspace content, with and without d_w.
+ * One workgroup per (clip, joint), twice: a single long clip is serial in time on J CUs. */
+size_t zedo_joint_accel_marginal_workspace_bytes(int N, int H, int J);
+int zedo_joint_accel_marginal(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
+                              int H, int N, int J, double lambda_v, double lambda_a, double tau,
+                              void *d_workspace, size_t workspace_bytes,
+                              double *d_mean, double *d_cov, int *d_hmax, double *d_wmax, double *d_logz, double *d_w, void *stream);
 
 /* ---- skeleton-coupled joint-wise aggregation WITHOUT ground truth: exact min-sum over the bone tree ------------------------
  * zedo_joint_reproj picks every joint of a pose on its own, and the chain models above couple a joint to itself along time.

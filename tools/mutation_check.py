@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: thirty-one one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: thirty-two one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -67,6 +67,8 @@ MUTANTS = [
     ("ZEDO_MUT_TREE_NO_HALF", "zedo_joint_tree_select and zedo_joint_tree_marginal: the bone term compares the assembled length with the SUM of the two hypotheses' lengths, the 0.5 is dropped (zedo_chain.h tr_bone: the recurrences and bone[n,.])"),
     # the skeleton-coupled fusion (tests/test_joint_tree_marginal_gpu.py, tests/test_select_joints_tree_fused_driver_gpu.py): leaves every other
     # test green
+    # the second-order joint-wise fusion (tests/test_joint_accel_marginal_gpu.py): leaves every other test green
+    ("ZEDO_MUT_JAM_NO_BACK_ACCEL", "zedo_joint_accel_marginal: the c_a a term is dropped from the backward pass only - B2 is the first-order one, A2 keeps the term (zedo_joint_accel_marginal.hip joint_accel_marginal_backward_kernel)"),
     ("ZEDO_MUT_TREEMARG_NO_DOWN", "zedo_joint_tree_marginal: Dn = 0 on every joint - the downward pass is dropped, a joint hears from its subtree only (zedo_joint_tree_marginal.hip joint_tree_marginal_kernel)"),
 ]
 

@@ -946,6 +946,23 @@ extern "C" int zedo_joint_accel_select(const double *d_junary, const float *d_x,
     return ZEDO_OK;
 }
 
+// posterior marginals of the second-order model: forward-backward over pairs per (clip, joint), A2 in the workspace
+extern "C" size_t zedo_joint_accel_marginal_workspace_bytes(int N, int H, int J) {
+    return chain_dims_ok(N, H, J, JOINT_ACCEL_HMAX) ? joint_accel_marginal_bytes(N, H, J) : 0;
+}
+
+extern "C" int zedo_joint_accel_marginal(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq, int H,
+                                         int N, int J, double lambda_v, double lambda_a, double tau, void *d_workspace,
+                                         size_t workspace_bytes, double *d_mean, double *d_cov, int *d_hmax, double *d_wmax, double *d_logz,
+                                         double *d_w, void *stream) {
+    const int rc = chain_args_ok({d_junary, d_x, d_seq_start, d_mean, d_cov, d_hmax, d_wmax, d_logz}, n_seq, N, H, J, JOINT_ACCEL_HMAX,
+                                 {lambda_v, lambda_a}, tau, d_workspace, workspace_bytes, joint_accel_marginal_bytes);
+    if (rc != ZEDO_OK) return rc;
+    HIPCHK(launch_joint_accel_marginal(d_junary, d_x, d_T, d_seq_start, n_seq, H, N, J, lambda_v / tau, lambda_a / tau, tau, d_workspace,
+                                       d_mean, d_cov, d_hmax, d_wmax, d_logz, d_w, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
 // ---- the skeleton-coupled models: one workgroup per pose over the bone tree, everything in the LDS, no workspace ----
 // true, with the post-order of the bones in *tr, or the call is ZEDO_E_BADARG: null pointers and ranges, J, whether the kernel's tables
 // of H hypotheses (lds_bytes) fit the LDS, the int product, mu (finite, >= 0), tau (finite, > 0; 1 where the model has none) and their

@@ -1,6 +1,6 @@
 // What the label-free selection and fusion kernels share (zedo_temporal.hip, zedo_joint_temporal.hip, zedo_joint_marginal.hip,
-// zedo_joint_accel.hip, zedo_joint_tree.hip, zedo_joint_tree_marginal.hip): the one copy of their lane layout, their reductions and their
-// staging.  The rules every user relies on live here and nowhere else:
+// zedo_joint_accel.hip, zedo_joint_accel_marginal.hip, zedo_joint_tree.hip, zedo_joint_tree_marginal.hip): the one copy of their lane
+// layout, their reductions and their staging.  The rules every user relies on live here and nowhere else:
 //   - a tie goes to the lowest index (strict comparisons, parts and waves combined in ascending order);
 //   - a sum is a butterfly inside each wave, then the waves in ascending order: a fixed order, no atomics;
 //   - a lane past H reads row H-1 and stores nothing;
@@ -129,6 +129,66 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double *sred, int tid
         v[i] = s;
     }
     __syncthreads();
+}
+
+// ---- what a fusion kernel along a video reads off the marginals of one (frame, joint) (zedo_joint_marginal.hip, zedo_joint_accel_marginal.hip) ----
+// The tail of a backward kernel's frame, as statements in the kernel's own scope: a function of the same text changes the register
+// allocation of joint_marginal_backward_kernel, and that kernel's instruction stream is pinned.  A lane holds K hypotheses h = H0 + k HSTEP
+// with their X in XC [K][3]; OWN (an expression in h) says whether the lane owns h, WEIGHT (an expression in k) is its marginal.  Written:
+// d_w (wout, if not null), the lowest h with the largest marginal, the mean sum_h w X and the covariance sum_h w (X - mean)(X - mean)^T
+// from the centred differences - block_arg and block_sum: a fixed order - and log Z of the chain.  Reached by the whole workgroup.  In
+// scope: H, tid, lz, mean, cov, hmax, wmax, logz, wout, ninf and sred (6 CHAIN_W doubles), sredi (CHAIN_W ints) of the LDS, free on entry
+// and again afterwards.  Declares wk, m3, bw, bh, c6.
+#define ZEDO_CHAIN_MOMENTS(K, H0, HSTEP, OWN, WEIGHT, XC, NJ)                                                                          \
+        double wk[K], m3[3] = {0.0, 0.0, 0.0}, bw = ninf;                                                                              \
+        int bh = INT_MAX;                                                                                                              \
+        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                                                                \
+            const int h = (H0) + k * (HSTEP);                                                                                          \
+            const bool own = OWN;                                                                                                      \
+            wk[k] = own ? (WEIGHT) : 0.0;                                                                                              \
+            if (own) {                                                                                                                 \
+                if (wout) wout[(NJ) * H + h] = wk[k];                                                                                  \
+                if (wk[k] > bw) { bw = wk[k]; bh = h; }            /* ascending h, strict: the lowest h of the lane */                 \
+                _Pragma("unroll") for (int cc = 0; cc < 3; ++cc) m3[cc] += wk[k] * XC[k][cc];                                          \
+            }                                                                                                                          \
+        }                                                                                                                              \
+        block_arg<true>(bw, bh, sred, sredi, tid);                                                                                     \
+        __syncthreads();                                                                                                               \
+        block_sum<3>(m3, sred, tid);                                                                                                   \
+        double c6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};                                                                                 \
+        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                                                                \
+            const double d0 = XC[k][0] - m3[0], d1 = XC[k][1] - m3[1], d2 = XC[k][2] - m3[2];                                          \
+            c6[0] += wk[k] * (d0 * d0); c6[1] += wk[k] * (d0 * d1); c6[2] += wk[k] * (d0 * d2);                                        \
+            c6[3] += wk[k] * (d1 * d1); c6[4] += wk[k] * (d1 * d2); c6[5] += wk[k] * (d2 * d2);                                        \
+        }                                                                                                                              \
+        block_sum<6>(c6, sred, tid);                                                                                                   \
+        if (tid < 3) mean[(NJ) * 3 + tid] = m3[tid];                                                                                   \
+        if (tid < 6) cov[(NJ) * 6 + tid] = c6[tid];                                                                                    \
+        if (tid == 0) { hmax[NJ] = bh == INT_MAX ? 0 : bh; wmax[NJ] = bh == INT_MAX ? 0.0 : bw; logz[NJ] = lz; }
+// a dead (frame, joint): NaN, hypothesis 0, weight 0, log Z = -inf, a row of zeros; OWNER: does the lane own its h = H0 + k HSTEP below H.
+// In scope as above, and qnan.
+#define ZEDO_CHAIN_DEAD_OUTPUTS(K, H0, HSTEP, OWNER, NJ)                                                                               \
+            if (tid < 3) mean[(NJ) * 3 + tid] = qnan;                                                                                  \
+            if (tid < 6) cov[(NJ) * 6 + tid] = qnan;                                                                                   \
+            if (tid == 0) { hmax[NJ] = 0; wmax[NJ] = 0.0; logz[NJ] = ninf; }                                                           \
+            if (wout && (OWNER))                                                                                                       \
+                _Pragma("unroll") for (int k = 0; k < K; ++k)                                                                          \
+                    if ((H0) + k * (HSTEP) < H) wout[(NJ) * H + (H0) + k * (HSTEP)] = 0.0;
+
+// ---- the pairs of the second-order chain models (zedo_joint_accel.hip, zedo_joint_accel_marginal.hip) ----
+// The H^2 pairs q = h' H + h of a (frame, joint) are dealt to the CHAIN_T lanes round robin, KA to a lane: f(integral_constant<int, KA>)
+// of the smallest of the seven instantiations - KA = 1 (H <= 16), 2 (H <= 22), 4 (H <= 32), 7 (H <= 42), 10 (H <= 50), 13 (H <= 57) or 16
+// (H <= 64) - with CHAIN_T KA >= H^2.
+template <class F>
+inline void dispatch_pairs(int H, F &&f) {
+    const int HH = H * H;
+    if (HH <= CHAIN_T) f(IntC<1>());
+    else if (HH <= 2 * CHAIN_T) f(IntC<2>());
+    else if (HH <= 4 * CHAIN_T) f(IntC<4>());
+    else if (HH <= 7 * CHAIN_T) f(IntC<7>());
+    else if (HH <= 10 * CHAIN_T) f(IntC<10>());
+    else if (HH <= 13 * CHAIN_T) f(IntC<13>());
+    else f(IntC<16>());
 }
 
 // ---- the bone tree: one workgroup per pose, everything in the LDS ----

@@ -253,6 +253,12 @@ hipError_t launch_joint_marginal(const double *junary, const float *x, const flo
 size_t joint_accel_bytes(int N, int H, int J);
 hipError_t launch_joint_accel_select(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,
                                      int J, double lambda_v, double lambda_a, void *ws, int *path, double *cost, hipStream_t st);
+// posterior marginals of the second-order chain model (zedo_joint_accel_marginal.hip); ws: joint_accel_marginal_bytes(N, H, J), H <= 64;
+// c_v = lambda_v / tau, c_a = lambda_a / tau
+size_t joint_accel_marginal_bytes(int N, int H, int J);
+hipError_t launch_joint_accel_marginal(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,
+                                       int J, double c_v, double c_a, double tau, void *ws, double *mean, double *cov, int *hmax,
+                                       double *wmax, double *logz, double *w, hipStream_t st);
 // skeleton-coupled joint-wise aggregation (zedo_joint_tree.hip): min-sum over the bone tree, one workgroup per pose, everything in the
 // LDS - joint_tree_lds_bytes(H, J) = 34 J H + 16 H + 4096 of the CU's TR_LDS bytes.  The host derives the post-order of the bones
 // (joint_tree_order: false for a parent array that is not a forest) and hands it to the kernel by value.

@@ -287,18 +287,10 @@ hipError_t launch_joint_accel_select(const double *junary, const float *x, const
     const dim3 grid((unsigned)n_seq * (unsigned)J);                // n_seq <= N and N J H <= INT_MAX
     const hipError_t e = launch_joint_temporal_dead(junary, H, N * J, w.dead, st);
     if (e != hipSuccess) return e;
-#define ZEDO_JA_SCAN(KA)                                                                                                               \
-    hipLaunchKernelGGL((joint_accel_scan_kernel<KA>), grid, dim3(CHAIN_T), 0, st, junary, x, T, seq_start, w.dead, H, N, J, lambda_v, lambda_a, \
-                       w.back2, w.endq)
-    const int HH = H * H;
-    if (HH <= CHAIN_T) ZEDO_JA_SCAN(1);
-    else if (HH <= 2 * CHAIN_T) ZEDO_JA_SCAN(2);
-    else if (HH <= 4 * CHAIN_T) ZEDO_JA_SCAN(4);
-    else if (HH <= 7 * CHAIN_T) ZEDO_JA_SCAN(7);
-    else if (HH <= 10 * CHAIN_T) ZEDO_JA_SCAN(10);
-    else if (HH <= 13 * CHAIN_T) ZEDO_JA_SCAN(13);
-    else ZEDO_JA_SCAN(16);
-#undef ZEDO_JA_SCAN
+    dispatch_pairs(H, [&](auto KA) {
+        hipLaunchKernelGGL((joint_accel_scan_kernel<KA()>), grid, dim3(CHAIN_T), 0, st, junary, x, T, seq_start, w.dead, H, N, J, lambda_v,
+                           lambda_a, w.back2, w.endq);
+    });
     hipLaunchKernelGGL(joint_accel_backtrack_kernel, grid, dim3(256), 0, st, seq_start, w.dead, w.endq, w.back2, H, N, J, path);
     hipLaunchKernelGGL(joint_accel_cost_kernel, grid, dim3(256), 0, st, junary, x, T, seq_start, w.dead, path, H, N, J, lambda_v, lambda_a,
                        cost);

@@ -221,13 +221,7 @@ __global__ __launch_bounds__(CHAIN_T) void joint_marginal_backward_kernel(const 
             }
         }
         if (is_dead) {                                             // (workgroup-uniform) NaN, hypothesis 0, weight 0, log Z = -inf, a row of zeros
-            if (tid < 3) mean[nj * 3 + tid] = qnan;
-            if (tid < 6) cov[nj * 6 + tid] = qnan;
-            if (tid == 0) { hmax[nj] = 0; wmax[nj] = 0.0; logz[nj] = ninf; }
-            if (wout && part == 0)
-#pragma unroll
-                for (int k = 0; k < K; ++k)
-                    if (slot + k * SLOTS < H) wout[nj * H + slot + k * SLOTS] = 0.0;
+            ZEDO_CHAIN_DEAD_OUTPUTS(K, slot, SLOTS, part == 0, nj)
             continue;
         }
         if (ends) {                                                // (workgroup-uniform) B = 0: log Z = LSE_h A[n,j,h], shifted by the largest A
@@ -244,34 +238,7 @@ __global__ __launch_bounds__(CHAIN_T) void joint_marginal_backward_kernel(const 
             block_sum<1>(e, sred, tid);
             lz = v + log(e[0]);
         }
-        double wk[K], m3[3] = {0.0, 0.0, 0.0}, bw = ninf;
-        int bh = INT_MAX;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int h = slot + k * SLOTS;
-            const bool own = part == 0 && h < H;
-            wk[k] = own ? exp(ab[k] - lz) : 0.0;
-            if (own) {
-                if (wout) wout[nj * H + h] = wk[k];
-                if (wk[k] > bw) { bw = wk[k]; bh = h; }            // ascending h, strict: the lowest h of the lane
-#pragma unroll
-                for (int cc = 0; cc < 3; ++cc) m3[cc] += wk[k] * xc[k][cc];
-            }
-        }
-        block_arg<true>(bw, bh, sred, sredi, tid);
-        __syncthreads();
-        block_sum<3>(m3, sred, tid);
-        double c6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const double d0 = xc[k][0] - m3[0], d1 = xc[k][1] - m3[1], d2 = xc[k][2] - m3[2];
-            c6[0] += wk[k] * (d0 * d0); c6[1] += wk[k] * (d0 * d1); c6[2] += wk[k] * (d0 * d2);
-            c6[3] += wk[k] * (d1 * d1); c6[4] += wk[k] * (d1 * d2); c6[5] += wk[k] * (d2 * d2);
-        }
-        block_sum<6>(c6, sred, tid);
-        if (tid < 3) mean[nj * 3 + tid] = m3[tid];
-        if (tid < 6) cov[nj * 6 + tid] = c6[tid];
-        if (tid == 0) { hmax[nj] = bh == INT_MAX ? 0 : bh; wmax[nj] = bh == INT_MAX ? 0.0 : bw; logz[nj] = lz; }
+        ZEDO_CHAIN_MOMENTS(K, slot, SLOTS, part == 0 && h < H, exp(ab[k] - lz), xc, nj)
     }
 }
 

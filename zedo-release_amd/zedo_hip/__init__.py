@@ -76,6 +76,8 @@ SIGNATURES = {
     "zedo_joint_temporal_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _sz, _vp, _vp, _vp]),
     "zedo_joint_accel_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_accel_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp]),
+    "zedo_joint_accel_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
+    "zedo_joint_accel_marginal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_joint_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_marginal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_joint_tree_select": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp, _vp]),
@@ -760,6 +762,29 @@ def joint_marginal(junary, x_full, T_full, seq_start, N=None, lam=100.0, tau=1.0
                                         float(lam), float(tau), _p(ws, torch.uint8), nbytes, _p(mean, torch.float64),
                                         _p(cov, torch.float64), _p(hmax, torch.int32), _p(wmax, torch.float64), _p(logz, torch.float64),
                                         _p(w, torch.float64), _stream(dev)))
+    return (mean, cov, hmax, wmax, logz, w) if return_weights else (mean, cov, hmax, wmax, logz)
+
+
+def joint_accel_marginal(junary, x_full, T_full, seq_start, N=None, lam=100.0, accel=100.0, tau=1.0, return_weights=False):
+    """Fusing hypotheses along a video under the second-order motion model (zedo_joint_accel_marginal): the inputs of joint_accel_select
+    and a temperature tau > 0 in cost units -> (mean [N,J,3] f64, cov [N,J,6] f64, hmax [N,J] i32, wmax [N,J] f64, logz [N,J] f64[, w
+    [N,J,H] f64]): per (clip, joint) the posterior marginals w of the hypotheses under p(path) ~ exp(-(unaries + lam * displacements +
+    accel * second differences) / tau), the chain over pairs of hypotheses joint_accel_select optimises (forward-backward over pairs,
+    fp64), and from them what joint_marginal reports: the posterior mean position in the camera frame, its covariance (xx, xy, xz, yy,
+    yz, zz; m^2), the most probable hypothesis, its probability and the chain's log-partition value.  A dead (frame, joint) reports NaN,
+    0, 0 and -inf.  lam = 100, accel = 100 and tau = 1 are untuned; lam = 0 is blind to a constant velocity.  At most 64 hypotheses; the
+    workspace is 8 bytes per (frame, joint, pair) - 345 MB at 1 015 frames x 17 joints x 50 hypotheses: cut a long recording into calls of
+    whole clips.  Whether the fused pose is closer to ground truth than joint_marginal's is not measured."""
+    dev, seq, N, H, J = _chain_inputs("joint_accel_marginal", junary, x_full, T_full, seq_start, N, joint_wise=True)
+    if H > 64:
+        raise ZedoError(f"joint_accel_marginal: at most 64 hypotheses (the pair tables of a joint stay in the LDS), got H = {H}")
+    with torch.cuda.device(dev):
+        nbytes, ws = _workspace(_lib.zedo_joint_accel_marginal_workspace_bytes, dev, N, H, J)
+        mean, cov, hmax, wmax, logz, w = _marginal_outputs(N, J, H, dev, return_weights)
+        _check(_lib.zedo_joint_accel_marginal(_p(junary, torch.float64), _p(x_full), _p(T_full), _p(seq, torch.int32), seq.numel() - 1, H, N,
+                                              J, float(lam), float(accel), float(tau), _p(ws, torch.uint8), nbytes,
+                                              _p(mean, torch.float64), _p(cov, torch.float64), _p(hmax, torch.int32),
+                                              _p(wmax, torch.float64), _p(logz, torch.float64), _p(w, torch.float64), _stream(dev)))
     return (mean, cov, hmax, wmax, logz, w) if return_weights else (mean, cov, hmax, wmax, logz)
 
 

@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import (H36M_EDGES, SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
+from . import (H36M_EDGES, SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_accel_marginal, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
                joint_temporal_select, joint_tree_marginal, joint_tree_select, skeleton_parents, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
@@ -288,6 +288,20 @@ class Pipeline:
         with torch.cuda.device(self.device):
             _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
             out = joint_marginal(jerr, x, T, seq_start, self.N, lam, tau)
+        return out + (jerr,)
+
+    def fuse_joints_accel(self, x, T, seq_start, lam=100.0, accel=100.0, tau=1.0):
+        """fuse_joints_temporal under the second-order motion model: the same inputs and outputs - (mean [N,17,3] f64, cov [N,17,6] f64,
+        hmax [N,17] i32, wmax [N,17] f64, logz [N,17] f64, jerr [H*N,17] f64) - the posterior mean position of every joint in the camera
+        frame, its covariance, the most probable hypothesis and its probability under the chain over pairs of hypotheses
+        select_joints_accel optimises: lam times the displacement plus accel times the second difference X[n] - 2 X[n-1] + X[n-2], which is
+        blind to a constant velocity, at the temperature tau in pixels (zedo_joint_accel_marginal; at most 64 hypotheses; lam, accel and
+        tau untuned)."""
+        if x.shape[0] != self.H * self.N:
+            raise ValueError(f"fuse_joints_accel: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        with torch.cuda.device(self.device):
+            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
+            out = joint_accel_marginal(jerr, x, T, seq_start, self.N, lam, accel, tau)
         return out + (jerr,)
 
     def take(self, rows_full, idx):
