@@ -49,7 +49,8 @@ extern "C" {
                               * still 5 (additive): + zedo_joint_temporal_workspace_bytes, zedo_joint_temporal_select;
                               * still 5 (additive): + zedo_joint_marginal_workspace_bytes, zedo_joint_marginal;
                               * still 5 (additive): + zedo_joint_accel_workspace_bytes, zedo_joint_accel_select;
-                              * still 5 (additive): + zedo_joint_accel_marginal_workspace_bytes, zedo_joint_accel_marginal */
+                              * still 5 (additive): + zedo_joint_accel_marginal_workspace_bytes, zedo_joint_accel_marginal;
+                              * still 5 (additive): + zedo_joint_stream_state_bytes, zedo_joint_stream_reset, zedo_joint_stream_push */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -409,6 +410,56 @@ size_t zedo_joint_temporal_workspace_bytes(int N, int H, int J);
 int zedo_joint_temporal_select(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
                                int H, int N, int J, double lambda, void *d_workspace, size_t workspace_bytes,
                                int *d_path_h, double *d_cost, void *stream);
+
+/* ---- joint-wise selection on a LIVE video: the same chain, fixed-lag, with the state in caller-owned memory ----------------------
+ * zedo_joint_temporal_select needs the whole clip before it answers.  This is its first-order chain as an online call for S
+ * independent streams at once: frames are pushed in chunks of any size, the tables live in d_state between the calls, and the
+ * decision for a frame comes out `lag` frames after the frame went in.  It is the decision of zedo_joint_temporal_select on the
+ * clip cut after frame n + lag; with a lag of at least the clip's length - 1 and a flush at the end the outputs are that call's
+ * bits.  The choice of lag is untuned; whether a fixed-lag path is closer to ground truth than the per-frame choice on real video
+ * is not measured.
+ * A stream's CLIP is the frames pushed since its last reset or flush, t = 0, 1, ..  X, u, m, DEAD, "chain start", D and back are
+ * those of zedo_joint_temporal_select, word for word, on that clip: prefix quantities, which do not depend on how the frames were
+ * cut into calls.  With lag >= 0:
+ *   frame n of a clip is EMITTED by the first push after which the clip holds frame n + lag, or by the push that flushes the
+ *   stream, whichever comes first; all joints of a frame together, in frame order.
+ *   For a live (n,j) let c_j(n) be the last frame of n's chain on the frames the clip holds after that push - the first m >= n
+ *   whose successor is dead or absent - and e = min(n + lag, c_j(n)).  Then
+ *     h_e = the lowest h that minimises D[e,j,.];  h_{m-1} = back[m,j,h_m] for m = e .. n+1;
+ *     path[n,j] = h_n;  cost[n,j] = D[n,j,h_n].
+ *   A dead (n,j) reports hypothesis 0 and cost +inf.  After a flush the stream's next frame is t = 0 of a new clip.
+ * So lag = 0 gives the lowest arg-min of D[n,j,.], and the outputs do not depend on the chunking.
+ * zedo_joint_stream_push: the chunk is N = S*F frames in the layout of zedo_joint_temporal_select - rows (h,n) h-major with
+ * n = s*F + f: d_junary [H*N,J] float64, d_x [H*N,J,3] fp32, d_T [H*N,3] fp32 or NULL - stream s's chunk is a "clip" of F frames
+ * of an offline call on the same tensors.  d_flush [S] int32 ON THE DEVICE (NULL: none): stream s is flushed after its chunk if
+ * d_flush[s] != 0.  F = 0 is legal only with d_flush; d_junary, d_x and d_T are then unused.
+ * Outputs: d_path_h [S, F+lag, J] int32 and d_cost [S, F+lag, J] float64, row r of stream s = the r-th frame this push emits for
+ * it; d_emit [S,2] int64 = the clip-local index of the first emitted frame (of the next one to be emitted if the count is 0) and
+ * the count.  Rows at and after the count are not written.  With t the frames the clip held before the push, the count is
+ *   held = min(lag, t) + F;   count = held if the stream is flushed, else max(0, held - lag);   first = max(0, t - lag)
+ * - computable on the host without reading d_emit.
+ * zedo_joint_stream_reset empties the streams with d_which[s] != 0 (d_which [S] int32 ON THE DEVICE; NULL: all of them); pending
+ * frames are dropped.  The state need not be initialised before its first reset, and must have been reset before its first push.
+ * State (8-byte aligned), with R = lag + max_frames rows per ring and SJ = S*J chains, in this order:
+ *   D float64 [SJ,R,H] | X float64 [SJ,H,3] and D float64 [SJ,H] of the clip's last frame | the clip's frame count int64 [S] |
+ *   back int32 [SJ,R,H] | the dead flags of the ring's frames int32 [SJ,R] | the dead flag of the last frame int32 [SJ]
+ * - zedo_joint_stream_state_bytes = 8 (SJ R H + 4 SJ H + S) + 4 (SJ R H + SJ R + SJ) rounded up to 8; 0 for shapes the calls
+ * refuse.  Frame m of a clip sits in row m % R.  The emitted count is not stored: it is max(0, frame count - lag).  A push writes
+ * the rows of its F <= max_frames frames and then reads at most the lag frames before them: never a row it has overwritten.
+ * Contract: 1 <= H <= 1024, J >= 1, S >= 1, max_frames >= 1, 0 <= F <= max_frames, lag >= 0, (lag + max_frames)*S*J*H <= INT_MAX,
+ * finite lambda >= 0; ZEDO_E_BADARG with nothing written and the state untouched for a NULL pointer other than d_T, d_flush
+ * (F > 0) and d_which, a size out of these ranges, F = 0 without d_flush, a negative or non-finite lambda, or a state that is not
+ * 8-byte aligned; ZEDO_E_WORKSPACE with nothing written and the state untouched if state_bytes is too small; allocates nothing,
+ * synchronises nothing, enqueues on `stream` only: legal under stream capture - a replay advances the state.  No atomics: the
+ * bits do not depend on the run, the chunking, the content of the state before its reset or the alignment of d_x.  Every value
+ * read from the state is clamped before it is an index.  One workgroup per (stream, joint) for the recurrence, one wave per
+ * (emitted frame, stream, joint) for the decision: at most lag dependent reads of back. */
+size_t zedo_joint_stream_state_bytes(int S, int H, int J, int lag, int max_frames);
+int zedo_joint_stream_reset(void *d_state, size_t state_bytes, int S, int H, int J, int lag, int max_frames, const int *d_which,
+                            void *stream);
+int zedo_joint_stream_push(const double *d_junary, const float *d_x, const float *d_T, int S, int F, int H, int J, int lag,
+                           int max_frames, double lambda, const int *d_flush, void *d_state, size_t state_bytes, int *d_path_h,
+                           double *d_cost, long long *d_emit, void *stream);
 
 /* ---- fusing hypotheses along a video WITHOUT ground truth: per-joint posterior mean and spread ------------------------------
  * zedo_joint_temporal_select answers with one hypothesis per (frame, joint) and says nothing of the others.  This is the

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: thirty-two one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: thirty-three one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -57,6 +57,8 @@ MUTANTS = [
     # the joint-wise temporal selection (tests/test_joint_temporal_gpu.py, tests/test_select_joints_temporal_driver_gpu.py): leaves every
     # other test green
     ("ZEDO_MUT_JT_NO_T", "zedo_joint_temporal_select: the motion term is taken on x alone although d_T was given (zedo_joint_temporal.hip joint_temporal_scan_kernel)"),
+    # the joint-wise selection on live streams (tests/test_joint_stream_gpu.py): leaves every other test green
+    ("ZEDO_MUT_JS_HORIZON", "zedo_joint_stream_push: the horizon of frame n is taken as n + lag - 1, one frame short (zedo_joint_stream.hip joint_stream_emit_kernel)"),
     # the joint-wise fusion (tests/test_joint_marginal_gpu.py, tests/test_select_joints_fused_driver_gpu.py): leaves every other test green
     ("ZEDO_MUT_JM_NO_BACKWARD", "zedo_joint_marginal: B = 0 on every frame - the filtering marginals, not the smoothed ones (zedo_joint_marginal.hip joint_marginal_backward_kernel)"),
     # the second-order joint-wise selection (tests/test_joint_accel_gpu.py, tests/test_select_joints_accel_driver_gpu.py): leaves every other

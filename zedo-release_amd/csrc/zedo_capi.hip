@@ -914,6 +914,45 @@ extern "C" int zedo_joint_temporal_select(const double *d_junary, const float *d
     return ZEDO_OK;
 }
 
+// ---- the same chain on live streams: the tables of S streams live in the caller's state, a ring of lag + max_frames frames each ----
+// the shapes the three entry points accept: S J, then (lag + max_frames) S J H, within int
+static bool stream_dims_ok(int S, int H, int J, int lag, int max_frames) {
+    if (S < 1 || H < 1 || J < 1 || H > JOINT_CHAIN_HMAX || lag < 0 || max_frames < 1) return false;
+    const long long sj = (long long)S * J, rows = (long long)lag + max_frames;
+    return sj <= INT_MAX && rows <= INT_MAX && sj * H <= INT_MAX && rows * (sj * H) <= INT_MAX;
+}
+
+// the state pointer (ZEDO_E_BADARG: NULL, misaligned - the tables are float64 - or a shape out of range), then its size (ZEDO_E_WORKSPACE)
+static int stream_state_ok(const void *state, size_t state_bytes, int S, int H, int J, int lag, int max_frames) {
+    if (!state || !stream_dims_ok(S, H, J, lag, max_frames) || (reinterpret_cast<uintptr_t>(state) & 7)) return ZEDO_E_BADARG;
+    return state_bytes < joint_stream_bytes(S, H, J, lag, max_frames) ? ZEDO_E_WORKSPACE : ZEDO_OK;
+}
+
+extern "C" size_t zedo_joint_stream_state_bytes(int S, int H, int J, int lag, int max_frames) {
+    return stream_dims_ok(S, H, J, lag, max_frames) ? joint_stream_bytes(S, H, J, lag, max_frames) : 0;
+}
+
+extern "C" int zedo_joint_stream_reset(void *d_state, size_t state_bytes, int S, int H, int J, int lag, int max_frames, const int *d_which,
+                                       void *stream) {
+    const int rc = stream_state_ok(d_state, state_bytes, S, H, J, lag, max_frames);
+    if (rc != ZEDO_OK) return rc;
+    HIPCHK(launch_joint_stream_reset(d_state, S, H, J, lag, max_frames, d_which, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
+extern "C" int zedo_joint_stream_push(const double *d_junary, const float *d_x, const float *d_T, int S, int F, int H, int J, int lag,
+                                      int max_frames, double lambda, const int *d_flush, void *d_state, size_t state_bytes, int *d_path_h,
+                                      double *d_cost, long long *d_emit, void *stream) {
+    if (!d_path_h || !d_cost || !d_emit || F < 0 || F > max_frames) return ZEDO_E_BADARG;
+    if (F == 0 ? !d_flush : (!d_junary || !d_x)) return ZEDO_E_BADARG;                   // a push of no frames is a flush
+    if (!std::isfinite(lambda) || lambda < 0.0) return ZEDO_E_BADARG;
+    const int rc = stream_state_ok(d_state, state_bytes, S, H, J, lag, max_frames);
+    if (rc != ZEDO_OK) return rc;
+    HIPCHK(launch_joint_stream_push(d_junary, d_x, d_T, S, F, H, J, lag, max_frames, lambda, d_flush, d_state, d_path_h, d_cost, d_emit,
+                                    (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
 // posterior marginals of the same chain model: forward-backward per (clip, joint), A in the workspace
 extern "C" size_t zedo_joint_marginal_workspace_bytes(int N, int H, int J) {
     return chain_dims_ok(N, H, J, JOINT_CHAIN_HMAX) ? joint_marginal_bytes(N, H, J) : 0;

@@ -74,6 +74,9 @@ SIGNATURES = {
     "zedo_temporal_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _sz, _vp, _vp, _vp]),
     "zedo_joint_temporal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_temporal_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _vp, _sz, _vp, _vp, _vp]),
+    "zedo_joint_stream_state_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "zedo_joint_stream_reset": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _vp]),
+    "zedo_joint_stream_push": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "zedo_joint_accel_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_accel_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp]),
     "zedo_joint_accel_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -648,6 +651,87 @@ def joint_temporal_select(junary, x_full, T_full, seq_start, N=None, lam=100.0):
                                                J, float(lam), _p(ws, torch.uint8), nbytes, _p(path, torch.int32), _p(cost, torch.float64),
                                                _stream(dev)))
     return path, cost
+
+
+def joint_stream_state_bytes(S, H, J, lag, max_frames):
+    """The bytes of state zedo_joint_stream_push needs for S streams of H hypotheses and J joints at this lag and at most max_frames
+    frames per push (host arithmetic: no GPU needed); 0 for a shape the calls refuse."""
+    return int(_lib.zedo_joint_stream_state_bytes(int(S), int(H), int(J), int(lag), int(max_frames)))
+
+
+class JointStream:
+    """Joint-wise selection on a live video (zedo_joint_stream_push): the chain of joint_temporal_select for S independent streams, fed
+    in chunks of at most max_frames frames, every frame decided `lag` frames after it went in - the decision of joint_temporal_select on
+    the stream's clip (the frames since its last reset or flush) cut after frame n + lag.  With lag >= the clip's length - 1 and a flush
+    at the end the outputs are joint_temporal_select's bits.  Owns the state on `device` and resets it on creation.  lam as in
+    joint_temporal_select (untuned); the choice of lag is untuned as well, and whether a fixed-lag path is closer to ground truth than
+    the per-frame choice is not measured."""
+
+    def __init__(self, S, H, J, lag, max_frames, lam=100.0, device=None):
+        _need_gpu()
+        self.S, self.H, self.J, self.lag, self.max_frames, self.lam = int(S), int(H), int(J), int(lag), int(max_frames), float(lam)
+        self.device = _norm_device(device)
+        self.state_bytes = joint_stream_state_bytes(S, H, J, lag, max_frames)
+        if self.state_bytes == 0:
+            raise ZedoError(f"JointStream: S = {S}, H = {H}, J = {J}, lag = {lag}, max_frames = {max_frames} is outside the range of "
+                            "zedo_joint_stream_push (1 <= H <= 1024, lag >= 0, sizes >= 1, (lag + max_frames) S J H <= INT_MAX)")
+        with torch.cuda.device(self.device):
+            self.state = torch.empty((self.state_bytes,), dtype=torch.uint8, device=self.device)
+        self.reset()
+
+    def _flags(self, which):
+        """None, or `which` as an int32 [S] tensor on the device (a tensor, or a sequence of S truth values)."""
+        if which is None:
+            return None
+        if isinstance(which, torch.Tensor):
+            w = which.to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            w = torch.tensor([1 if v else 0 for v in which], dtype=torch.int32, device=self.device)
+        if tuple(w.shape) != (self.S,):
+            raise ValueError(f"JointStream: one flag per stream ([{self.S}]) expected, got {tuple(w.shape)}")
+        return w
+
+    def reset(self, which=None):
+        """Empties the streams with which[s] != 0 (None: all); their pending frames are dropped."""
+        w = self._flags(which)
+        with torch.cuda.device(self.device):
+            _check(_lib.zedo_joint_stream_reset(_p(self.state, torch.uint8), self.state_bytes, self.S, self.H, self.J, self.lag,
+                                                self.max_frames, _p(w, torch.int32), _stream(self.device)))
+
+    def push(self, junary, x, T=None, flush=None):
+        """junary [H*S*F,J] f64, x [H*S*F,J,3] f32, T [H*S*F,3] f32 or None: F <= max_frames new frames of every stream, rows (h, n)
+        h-major with n = s F + f - stream s's chunk is a clip of F frames of joint_temporal_select on the same tensors; flush: None, or
+        [S] flags - the streams whose clip ends with this chunk.  -> (first [S] i64, count [S] i64, path [S,F+lag,J] i32, cost
+        [S,F+lag,J] f64): stream s emits the frames first[s] .. first[s] + count[s] - 1 of its clip in the rows 0 .. count[s] - 1 of
+        path[s] and cost[s]; the rows after them are not written.  count[s] = held if flushed, else max(0, held - lag), with held =
+        min(lag, frames the clip held before) + F.  junary = None: a push of no frames (flush required)."""
+        fl = self._flags(flush)
+        S, H, J = self.S, self.H, self.J
+        if junary is None:
+            F = 0
+            if x is not None or T is not None or fl is None:
+                raise ValueError("JointStream.push: a push of no frames takes flush and nothing else")
+            dev = self.device
+        else:
+            dev = _device_of(junary, x, T, self.state)
+            rows = x.shape[0]
+            F = rows // (H * S)
+            if (rows != H * S * F or F < 1 or tuple(x.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J)
+                    or (T is not None and tuple(T.shape) != (rows, 3))):
+                raise ValueError(f"JointStream.push: junary [H*S*F,J], x [H*S*F,J,3], T [H*S*F,3] with H = {H}, S = {S}, J = {J} expected, "
+                                 f"got {tuple(junary.shape)}, {tuple(x.shape)}, {None if T is None else tuple(T.shape)}")
+        with torch.cuda.device(dev):
+            path = torch.empty((S, F + self.lag, J), dtype=torch.int32, device=dev)
+            cost = torch.empty((S, F + self.lag, J), dtype=torch.float64, device=dev)
+            emit = torch.empty((S, 2), dtype=torch.int64, device=dev)
+            _check(_lib.zedo_joint_stream_push(_p(junary, torch.float64), _p(x), _p(T), S, F, H, J, self.lag, self.max_frames, self.lam,
+                                               _p(fl, torch.int32), _p(self.state, torch.uint8), self.state_bytes, _p(path, torch.int32),
+                                               _p(cost, torch.float64), _p(emit, torch.int64), _stream(dev)))
+        return emit[:, 0], emit[:, 1], path, cost
+
+    def flush(self, which=None):
+        """Ends the clips of the streams with which[s] != 0 (None: all) and emits their pending frames: a push of no frames."""
+        return self.push(None, None, None, [1] * self.S if which is None else which)
 
 
 def joint_accel_select(junary, x_full, T_full, seq_start, N=None, lam=100.0, accel=100.0):

@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import (H36M_EDGES, SINGULAR_MSG, Schedule, Weights, ZedoError, ipo_fit, joint_accel_marginal, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
+from . import (H36M_EDGES, SINGULAR_MSG, JointStream, Schedule, Weights, ZedoError, ipo_fit, joint_accel_marginal, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
                joint_temporal_select, joint_tree_marginal, joint_tree_select, skeleton_parents, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
@@ -264,6 +264,29 @@ class Pipeline:
             _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
             path, cost = joint_temporal_select(jerr, x, T, seq_start, self.N, lam)
         return path, cost, jerr
+
+    def open_joint_stream(self, S, lag, max_frames, lam=100.0):
+        """The state of select_joints_temporal's chain for S live streams (JointStream): H and the joint count are those of the
+        pipeline, every frame is decided `lag` frames after it went in, a push holds at most max_frames frames per stream.  lam and the
+        choice of lag are untuned."""
+        if getattr(self, "uv", None) is None:
+            raise ZedoError("open_joint_stream: call load() first (the joint count is the problem's)")
+        return JointStream(S, self.H, self.uv.shape[1], lag, max_frames, lam, self.device)
+
+    def push_joints_temporal(self, js, x, T, flush=None):
+        """select_joints_temporal on live input, on the problem of load() with N = S F poses - F new frames of each of the S streams of
+        js = open_joint_stream(...), pose n = s F + f: x [H*N,17,3] and T [H*N,3], ALL rows; flush: None, or [S] flags - the streams
+        whose clip ends here.  -> (first [S] i64, count [S] i64, joint_path [S,F+lag,17] i32, joint_cost [S,F+lag,17] f64, jerr
+        [H*N,17] f64): the unaries are zedo_joint_reproj's per-(row, joint) distances exactly as select_joints_temporal forms them; stream
+        s emits the frames first[s] .. first[s] + count[s] - 1 of its clip (zedo_joint_stream_push).  The caller keeps x and T of the
+        frames that are still to come out and assembles their poses with compose."""
+        if x.shape[0] != self.H * self.N or self.N % js.S:
+            raise ValueError(f"push_joints_temporal: all {self.H * self.N} rows of a whole number of frames of {js.S} streams expected, "
+                             f"got {x.shape[0]} rows for {self.N} poses")
+        with torch.cuda.device(self.device):
+            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
+            out = js.push(jerr, x, T, flush)
+        return out + (jerr,)
 
     def select_joints_accel(self, x, T, seq_start, lam=100.0, accel=100.0):
         """select_joints_temporal with a second-order motion model: the same inputs and outputs, each joint's path minimises its unaries
