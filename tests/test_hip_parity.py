@@ -7,6 +7,7 @@ reference's own fp32-vs-fp64 drift recorded in the fixtures (SURVEY.md section 7
 import numpy as np
 import pytest
 
+import _procrustes_ref as PR
 from _shared import IPO_CASES, W, dev, pack, zh  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -426,6 +427,10 @@ def test_rotate_init(zh):
 
 
 def test_min_mpjpe_golden(zh, golden):
+    """Against the values recorded from the reference: P2 keeps atol 3e-7, because the reference's own err_p2 is 3.9e-8 from
+    zedo_oracle.hypothesis_errors in float64 (its capture, not the kernel, sets that tolerance).  Beside it the same rows against
+    the float64 oracle at the bound of tests/_procrustes_ref.py, which is where the kernel's accuracy is held."""
+    import zedo_oracle as O
     g = golden("eval_multi")
     preds = g["preds"]                       # [N,H,17,3] (reference layout)
     N, H = preds.shape[:2]
@@ -437,6 +442,10 @@ def test_min_mpjpe_golden(zh, golden):
         np.testing.assert_allclose(e, g[key], atol=tol, rtol=0)
         np.testing.assert_allclose(best.cpu().numpy(), g[key].min(1), atol=tol, rtol=0)
         assert np.array_equal(best_h.cpu().numpy(), g[key].argmin(1))
+        x32, gth = rows.astype(np.float32), np.tile(gt, (H, 1, 1))
+        d = np.abs(err.cpu().numpy() - O.hypothesis_errors(x32[:, None], gth, p2)[:, 0])
+        bound = PR.bounds64(x32, gth)[int(p2)]
+        assert bound.max() < 1e-12 and (d <= bound).all(), (p2, float((d / bound).max()))
     # shard: rows [N+5, 3N+2) only
     lo, hi = N + 5, 3 * N + 2
     err, best, best_h = zh.min_mpjpe(dev(rows[lo:hi]), dev(gt, torch.float64), N, procrustes=False, row_offset=lo)
@@ -452,12 +461,20 @@ def test_min_mpjpe_rank2_alignment_matches_the_reference_value(zh, golden, tag):
     """Planar prediction / planar ground truth (exactly in z = 0, and in a random plane to float32 rounding): the
     SVD of the alignment has a zero singular value whose direction sign is arbitrary in numpy/LAPACK, but the
     ERROR is the same for either sign (tests/test_oracle_golden.py shows why); the kernel's choice must therefore
-    reproduce the reference's error values (tools/gen_golden.py::gen_eval, transforms.py:42-127)."""
+    reproduce the reference's error values (tools/gen_golden.py::gen_eval, transforms.py:42-127).  The 3e-7 is the reference
+    capture's own distance from float64 (see test_min_mpjpe_golden), so it stays; beside it the same rows against the float64
+    oracle at the bound of tests/_procrustes_ref.py, whose 2 t term is the thickness of BOTH sets; where only one set is planar it exceeds 3e-7, which then stays."""
+    import zedo_oracle as O
     g = golden("eval_multi")
     G, P, ref = g[f"deg_{tag}_gt"], g[f"deg_{tag}_pred"], g[f"deg_{tag}_err_p2"]
     err, best, idx = zh.min_mpjpe(dev(P.astype(np.float32)), dev(G - 0.0, torch.float64), len(G), procrustes=True)
     _report(f"procrustes_rank2_{tag}", [dict(max_abs_err_delta=float(np.abs(err.cpu().numpy() - ref).max()))])
     np.testing.assert_allclose(err.cpu().numpy(), ref, atol=3e-7, rtol=0)
+    d = np.abs(err.cpu().numpy() - O.hypothesis_errors(P.astype(np.float32)[:, None], G - 0.0, True)[:, 0])
+    bound = PR.bounds64(P.astype(np.float32), G - 0.0)[1]
+    _report(f"procrustes_rank2_{tag}_oracle", [dict(max_abs=float(d.max()), largest_share_of_bound=float((d / bound).max()), largest_bound=float(bound.max()))])
+    bound = np.minimum(bound, 3e-7)                                  # (one set planar, the other thick: t is the thick set's and says nothing)
+    assert (d <= bound).all(), float((d / bound).max())
 
 
 def test_min_mpjpe_nan_hypothesis_poisons_the_pose_like_numpy(zh, golden):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: thirty-three one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: thirty-five one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -71,6 +71,10 @@ MUTANTS = [
     # test green
     # the second-order joint-wise fusion (tests/test_joint_accel_marginal_gpu.py): leaves every other test green
     ("ZEDO_MUT_JAM_NO_BACK_ACCEL", "zedo_joint_accel_marginal: the c_a a term is dropped from the backward pass only - B2 is the first-order one, A2 keeps the term (zedo_joint_accel_marginal.hip joint_accel_marginal_backward_kernel)"),
+    # the accuracy of the Procrustes alignment (tests/test_procrustes_gpu.py and the oracle-at-the-bound assertions beside the 3e-7 ones):
+    # both move P2 by 1e-8 and less, below every tolerance the selection tests had (profiles/mutation_procrustes.txt)
+    ("ZEDO_MUT_JACOBI_EARLY", "P2: the Jacobi sweeps of polar_from_svd stop at off < 1e-2 instead of 1e-15 (zedo_metric.hip)"),
+    ("ZEDO_MUT_ALIGN_F32", "P2: the 3x3 alignment matrix M is rounded through fp32 before polar_from_svd (zedo_metric.hip row_error)"),
     ("ZEDO_MUT_TREEMARG_NO_DOWN", "zedo_joint_tree_marginal: Dn = 0 on every joint - the downward pass is dropped, a joint hears from its subtree only (zedo_joint_tree_marginal.hip joint_tree_marginal_kernel)"),
 ]
 

@@ -37,7 +37,11 @@ __device__ void polar_from_svd(double M[3][3], double R[3][3], double &strace) {
                     V[i][p] = c * vp - s * vq; V[i][q] = s * vp + c * vq;
                 }
             }
+#ifdef ZEDO_MUT_JACOBI_EARLY  // tools/mutation_check.py only: the sweeps stop at columns orthogonal to 1e-2
+        if (off < 1e-2) break;
+#else
         if (off < 1e-15) break;
+#endif
     }
     double s[3], U[3][3];
     double smax = 0;
@@ -118,6 +122,9 @@ __device__ __forceinline__ double row_error(const P &p, const G &g, int J, int p
     }
     const double An = sqrt(ssA), Bn = sqrt(ssB);
     for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) M[r][c] /= (An * Bn);
+#ifdef ZEDO_MUT_ALIGN_F32     // tools/mutation_check.py only: the alignment matrix passes through fp32
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) M[r][c] = (double)(float)M[r][c];
+#endif
     double R[3][3], st;
     polar_from_svd(M, R, st);
     const double scale = An * st / Bn;   // Z = A_norm * S_trace * (B0/B_norm) R + A_bar
