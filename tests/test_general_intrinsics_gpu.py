@@ -18,6 +18,7 @@ import sys
 import numpy as np
 import pytest
 
+import _reproj_ref as RR
 from _shared import (IPO_MAX, IPO_MIN, IPO_T, KEYS, TWIN_AXES, dev, general_cameras, pack, problem, report_env as _report, ulp32,
                      unpack, zh)  # noqa: F401  (fixture)
 
@@ -218,7 +219,7 @@ def test_reproj_prepare_on_general_intrinsics(zh, J, N):
 
 def test_reproj_grad_on_general_intrinsics_against_the_reference(zh, golden):
     """zedo_reproj_prepare + zedo_reproj_grad against the reference's gradient_field_gen on general K (tests/golden/ipo_general.npz),
-    T given and T solved, with and without confidences: the tolerances of test_gradient_field_gen_golden."""
+    T given and T solved, with and without confidences: the tolerances of test_gradient_field_gen_golden, and the float64 solve beside them."""
     r = golden("ipo_general")
     for tag, conf in (("wild", r["rp_conf_wild"]), ("none", None)):
         cc = torch.empty(16, 17, device="cuda") if conf is not None else None
@@ -228,10 +229,12 @@ def test_reproj_grad_on_general_intrinsics_against_the_reference(zh, golden):
         _report(dict(test="general_k_reproj", conf=tag, g_given_max_abs=float(np.abs(g - r[f"rp_g_given_{tag}"]).max())))
         np.testing.assert_allclose(g, r[f"rp_g_given_{tag}"], atol=3e-6, rtol=0)
         assert np.array_equal(T.cpu().numpy(), r["rp_T_given"].reshape(16, 3))
+        RR.assert_within(T.cpu().numpy(), g, RR.solve(r["rp_x"], geom.cpu().numpy(), T=r["rp_T_given"].reshape(16, 3)), given=True)
         T = torch.zeros(16, 3, device="cuda")
         g = zh.reproj_grad(dev(r["rp_x"]), geom, T, True).cpu().numpy()
         np.testing.assert_allclose(T.cpu().numpy(), r[f"rp_T_solve_{tag}"].reshape(16, 3), atol=2e-5, rtol=0)
         np.testing.assert_allclose(g, r[f"rp_g_solve_{tag}"], atol=5e-6, rtol=0)
+        RR.assert_within(T.cpu().numpy(), g, RR.solve(r["rp_x"], geom.cpu().numpy()))         # float64 at the derived bound (tests/_reproj_ref.py)
 
 
 def test_initial_translation_on_general_intrinsics(zh):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import _procrustes_ref as PR
+import _reproj_ref as RR
 from _shared import IPO_CASES, W, dev, pack, zh  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -67,6 +68,8 @@ def test_pc_step_golden(zh, W, golden):
 
 
 def test_gradient_field_gen_golden(zh, golden):
+    """Against the captures of the reference at its own fp32 accuracy (they are 1.5e-6 to 2.8e-6 from the float64 solve: its fp32
+    inv(A^T A)) and, beside each, the same rows against the float64 solve at the derived bound (tests/_reproj_ref.py)."""
     r = golden("reproj")
     ones = np.ones((16, 17), np.float32)
     for tag, conf in (("wild", r["conf_wild"]), ("ones", ones), ("none", None)):
@@ -78,21 +81,27 @@ def test_gradient_field_gen_golden(zh, golden):
         g = zh.reproj_grad(dev(r["x"]), geom, T, False).cpu().numpy()
         np.testing.assert_allclose(g, r[f"g_given_{tag}"], atol=3e-6, rtol=0)
         assert np.array_equal(T.cpu().numpy(), r["T_given"].reshape(16, 3))
+        RR.assert_within(T.cpu().numpy(), g, RR.solve(r["x"], geom.cpu().numpy(), T=r["T_given"].reshape(16, 3)), given=True)
         T = torch.zeros(16, 3, device="cuda")
         g = zh.reproj_grad(dev(r["x"]), geom, T, True).cpu().numpy()
         np.testing.assert_allclose(T.cpu().numpy(), r[f"T_solve_{tag}"].reshape(16, 3), atol=2e-5, rtol=0)
         np.testing.assert_allclose(g, r[f"g_solve_{tag}"], atol=5e-6, rtol=0)
+        RR.assert_within(T.cpu().numpy(), g, RR.solve(r["x"], geom.cpu().numpy()))
     # sign fix (T_z < 0 -> -T)
     geom = zh.reproj_prepare(dev(r["uv_neg"]), dev(r["K"]), dev(ones))
     T = torch.zeros(16, 3, device="cuda")
     g = zh.reproj_grad(dev(r["x_rel"]), geom, T, True).cpu().numpy()
     np.testing.assert_allclose(T.cpu().numpy(), r["T_neg"].reshape(16, 3), atol=3e-5, rtol=0)
     np.testing.assert_allclose(g, r["g_neg"], atol=5e-6, rtol=0)
+    ref = RR.solve(r["x_rel"], geom.cpu().numpy())
+    assert (ref["T_unfixed"][:, 2] < 0).all()
+    RR.assert_within(T.cpu().numpy(), g, ref)
     geom = zh.reproj_prepare(dev(r["uv"]), dev(r["K"]), dev(ones))
     T = torch.zeros(16, 3, device="cuda")
     g = zh.reproj_grad(dev(r["x_far"]), geom, T, True).cpu().numpy()
     np.testing.assert_allclose(T.cpu().numpy(), r["T_far"].reshape(16, 3), atol=2e-4, rtol=0)
     np.testing.assert_allclose(g, r["g_far"], atol=3e-5, rtol=0)
+    RR.assert_within(T.cpu().numpy(), g, RR.solve(r["x_far"], geom.cpu().numpy()))
 
 
 def _report(name, rows):

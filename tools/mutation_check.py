@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: thirty-five one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: thirty-seven one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -75,6 +75,10 @@ MUTANTS = [
     # both move P2 by 1e-8 and less, below every tolerance the selection tests had (profiles/mutation_procrustes.txt)
     ("ZEDO_MUT_JACOBI_EARLY", "P2: the Jacobi sweeps of polar_from_svd stop at off < 1e-2 instead of 1e-15 (zedo_metric.hip)"),
     ("ZEDO_MUT_ALIGN_F32", "P2: the 3x3 alignment matrix M is rounded through fp32 before polar_from_svd (zedo_metric.hip row_error)"),
+    # the accuracy of the reprojection solve (tests/test_reproj_accuracy_gpu.py, tests/test_reproj_fused_gpu.py and the float64-at-the-bound
+    # assertions beside the captures) and its row shards: both leave every test green that existed before (profiles/mutation_reproj.txt)
+    ("ZEDO_MUT_REPROJ_UNCENTRED", "reproj_row: the numerator of T_z without the centring of b, d_x b_x + d_y b_y - equal in exact arithmetic, in every launch form (zedo_internal.h)"),
+    ("ZEDO_MUT_RGRAD_OFFSET", "zedo_reproj_grad: row_offset is ignored, the pose of row b is b mod N (zedo_geom.hip reproj_grad_kernel)"),
     ("ZEDO_MUT_TREEMARG_NO_DOWN", "zedo_joint_tree_marginal: Dn = 0 on every joint - the downward pass is dropped, a joint hears from its subtree only (zedo_joint_tree_marginal.hip joint_tree_marginal_kernel)"),
 ]
 
@@ -109,9 +113,11 @@ def main():
     os.makedirs(os.path.dirname(dst), exist_ok=True)
     rows, ok = [], True
     try:
-        only = os.environ.get("ZEDO_MUT_ONLY")          # e.g. ZEDO_MUT_ONLY=ZEDO_MUT_IPO_JOINT: one mutant (+ the clean rebuild)
+        # e.g. ZEDO_MUT_ONLY=ZEDO_MUT_IPO_JOINT: one mutant (+ the clean rebuild); several: separated by commas
+        only = [f for f in os.environ.get("ZEDO_MUT_ONLY", "").split(",") if f]
+        assert all(f in dict(MUTANTS) for f in only), only
         for flag, what in MUTANTS:
-            if only and flag != only:
+            if only and flag not in only:
                 continue
             build(flag)
             # mutations of code both modes share are hunted in the exact-fp32 cells (half the suite time); the two mutations of the

@@ -142,7 +142,11 @@ __global__ __launch_bounds__(128) void reproj_grad_kernel(const float *__restric
 #pragma unroll
         for (int c = 0; c < D; ++c) xr[c] = sx[tid * D + c];
         Tr[0] = T[(size_t)b * 3]; Tr[1] = T[(size_t)b * 3 + 1]; Tr[2] = T[(size_t)b * 3 + 2];
+#ifdef ZEDO_MUT_RGRAD_OFFSET     // tools/mutation_check.py only: row_offset is ignored, the pose is counted from the shard's first row
+        const int n = b % N;
+#else
         const int n = (int)((row_offset + b) % N);
+#endif
         reproj_row<J>(xr, geom + (size_t)n * J * GEOM_F, Tr, solve != 0, gr);
         if (solve) { T[(size_t)b * 3] = Tr[0]; T[(size_t)b * 3 + 1] = Tr[1]; T[(size_t)b * 3 + 2] = Tr[2]; }
     }

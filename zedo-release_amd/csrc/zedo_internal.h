@@ -153,7 +153,11 @@ __device__ __forceinline__ void reproj_row(const float *x, const float *__restri
             const f32x4 a = *reinterpret_cast<const f32x4 *>(gp + j * GEOM_F);
             const float bx = x[3 * j] - x[3 * j + 2] * a[0], by = x[3 * j + 1] - x[3 * j + 2] * a[1];
             const float dx = a[0] - mrx, dy = a[1] - mry;
+#ifdef ZEDO_MUT_REPROJ_UNCENTRED   // tools/mutation_check.py only: b is not centred - the same in exact arithmetic (sum W d = 0)
+            num += a[2] * (dx * bx + dy * by);
+#else
             num += a[2] * (dx * (bx - mbx) + dy * (by - mby));
+#endif
             den += a[2] * (dx * dx + dy * dy);
         }
         float tz = num / den;
