@@ -161,6 +161,36 @@ def unpack(st):
     return st[:, 0:4], st[:, 4], st[:, 5:9], st[:, 10:14], st[:, 9], st[:, 14]
 
 
+# The periodic batch of tests/test_launch_shapes_gpu.py and tests/test_launch_shapes_ref.py
+
+LS_P = 67                                                  # odd and prime: within 128 * 67 rows every base row visits every position of a 128-row tile
+LS_TS = np.array([0.1, 0.05, 0.011], np.float32)           # the noise levels of test_both_math_modes_are_fp32_accurate_against_the_fp64_oracle
+LS_EDGE_ROWS = {3: "zero", 11: "x 100", 19: "x 1e4", 29: "x 1e-20", 37: "x 1e-40 (fp32 denormal)", 43: "constant 5.0", 53: "a row ...",
+                59: "... and its negation"}
+
+
+def launch_shape_base():
+    """The base block [67,17,3]: 0.3 N(0,1) rows (numpy Philox, key [67, 17]), eight of them replaced by LS_EDGE_ROWS."""
+    g = np.random.Generator(np.random.Philox(key=[67, 17]))
+    base = (0.3 * g.standard_normal((LS_P, 17, 3))).astype(np.float32)
+    base[3] = 0.0
+    base[11] *= np.float32(100.0)
+    base[19] *= np.float32(1e4)
+    base[29] *= np.float32(1e-20)
+    base[37] = (base[37].astype(np.float64) * 1e-40).astype(np.float32)
+    base[43] = 5.0
+    base[59] = -base[53]
+    assert (np.abs(base[37]) < np.finfo(np.float32).tiny).all() and (base[37] != 0).any()
+    return base
+
+
+def launch_shape_reference64(weights, base):
+    """O.score_model_forward in float64 on the base block at every LS_TS -> [3,67,17,3]."""
+    import zedo_oracle as O
+    w64 = O.cast_weights(weights, np.float64)
+    return np.stack([O.score_model_forward(w64, base.astype(np.float64), np.float64(t) * 999.0, dtype=np.float64) for t in LS_TS])
+
+
 # ---- 4. a BASELINE-size capture ------------------------------------------------------------------------------------------
 
 def sha_of(*arrs):

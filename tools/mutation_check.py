@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: thirty-seven one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: forty one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -79,6 +79,11 @@ MUTANTS = [
     # assertions beside the captures) and its row shards: both leave every test green that existed before (profiles/mutation_reproj.txt)
     ("ZEDO_MUT_REPROJ_UNCENTRED", "reproj_row: the numerator of T_z without the centring of b, d_x b_x + d_y b_y - equal in exact arithmetic, in every launch form (zedo_internal.h)"),
     ("ZEDO_MUT_RGRAD_OFFSET", "zedo_reproj_grad: row_offset is ignored, the pose of row b is b mod N (zedo_geom.hip reproj_grad_kernel)"),
+    # one tile of one launch shape (tests/test_launch_shapes_gpu.py; profiles/mutation_launch_shapes.txt): each touches exactly one tile that is
+    # neither the first nor the last of its launch, and leaves every test green that existed before
+    ("ZEDO_MUT_PAIR_SEAM", "exact-fp32 pair kernels: the first remainder tile behind the 128x128 tiles takes its bias from the next column block (zedo_gemm.hip layer_pair_kernel)"),
+    ("ZEDO_MUT_F16_PAIR_SEAM", "f16x3 pair kernels: the first 64x64 tile behind the big tiles takes its bias from the next column block (zedo_gemm16.hip layer16_pair_kernel)"),
+    ("ZEDO_MUT_POST64_POSE", "post_dense on 64x64 tiles (above 8 192 rows): the fused reprojection tail of the third tile takes the pose of row b + 1 (zedo_gemm.hip layer_tile)"),
     ("ZEDO_MUT_TREEMARG_NO_DOWN", "zedo_joint_tree_marginal: Dn = 0 on every joint - the downward pass is dropped, a joint hears from its subtree only (zedo_joint_tree_marginal.hip joint_tree_marginal_kernel)"),
 ]
 

@@ -348,7 +348,13 @@ __device__ __forceinline__ void layer_tile(const LayerArgs &a, const int m0, con
                     if (tid < SR) {
                         const int sr = tid;
                         const int b = m0 + (sr >> 5) * TM + j * 32 + (sr & 31);
+#ifdef ZEDO_MUT_POST64_POSE   // tools/mutation_check.py only: the third 64x64 tile of a launch (an interior one) takes the pose of row b + 1
+                        ReprojArgs rpm = a.rp;
+                        if (BM == 64 && m0 == 128) rpm.row0 += 1;
+                        if (b < a.rp.B) ZEDO_REPROJ_STAGED_ROW(17, S + sr * BN, sr & 7, b, rpm);
+#else
                         if (b < a.rp.B) ZEDO_REPROJ_STAGED_ROW(17, S + sr * BN, sr & 7, b, a.rp);
+#endif
                     }
                     __syncthreads();
                 }
@@ -410,6 +416,15 @@ template <int EPI, int W8>
 // (a waves-per-SIMD bound >= 2 also makes hipcc keep the accumulators in VGPRs: no v_accvgpr_read/write, -0.6 %)
 __global__ __launch_bounds__(W8 ? 512 : 256, W8 ? 6 : PLAIN_WGS) void layer_pair_kernel(LayerArgs big, LayerArgs small, int nbig) {
     const ClockProbe probe(big.clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0);
+#ifdef ZEDO_MUT_PAIR_SEAM   // tools/mutation_check.py only: the first remainder tile behind the big tiles takes the bias of the next column block
+    if (nbig > 0 && (int)blockIdx.x >= nbig && xcd_tile((int)blockIdx.x - nbig, (int)gridDim.x - nbig) == 0) {
+        LayerArgs seam = small;
+        seam.bias = small.bias + (W8 ? 128 : 64);
+        if constexpr (W8) layer_body<64, 128, 2, 4, EPI, 2, 32, SCHED_SMALL>(seam, (int)blockIdx.x - nbig, (int)gridDim.x - nbig);
+        else layer_body<64, 64, 2, 2, EPI, 2, 32, SCHED_SMALL>(seam, (int)blockIdx.x - nbig, (int)gridDim.x - nbig);
+        return;
+    }
+#endif
     if constexpr (W8) {
         if ((int)blockIdx.x < nbig) layer_body<128, 128, 2, 4, EPI, 2, PAIR_BK, SCHED_BK16>(big, blockIdx.x, nbig);
         else layer_body<64, 128, 2, 4, EPI, 2, 32, SCHED_SMALL>(small, (int)blockIdx.x - nbig, (int)gridDim.x - nbig);

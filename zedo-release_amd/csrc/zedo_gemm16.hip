@@ -436,6 +436,13 @@ template <int EPI, int BIG_N>
 __global__ __launch_bounds__(256, BIG_N == 256 ? 2 : 3) void layer16_pair_kernel(Layer16Args big, Layer16Args small, int nbig) {
     const ClockProbe probe(big.clk != nullptr && blockIdx.x == 0 && threadIdx.x == 0);
     if ((int)blockIdx.x < nbig) layer16_body<BIG_M, BIG_N, 2, 2, EPI, BIG_N == 256 ? BIG_NBUF16 : MID_NBUF16>(big, blockIdx.x, nbig);
+#ifdef ZEDO_MUT_F16_PAIR_SEAM   // tools/mutation_check.py only: the first 64x64 tile behind the big tiles takes the bias of the next column block
+    else if (nbig > 0 && xcd_tile((int)blockIdx.x - nbig, (int)gridDim.x - nbig) == 0) {
+        Layer16Args seam = small;
+        seam.bias = small.bias + 64;
+        layer16_body<64, 64, 2, 2, EPI, 4>(seam, (int)blockIdx.x - nbig, (int)gridDim.x - nbig);
+    }
+#endif
     else layer16_body<64, 64, 2, 2, EPI, 4>(small, (int)blockIdx.x - nbig, (int)gridDim.x - nbig);
     probe.stop(big.clk);
 }
