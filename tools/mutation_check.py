@@ -54,16 +54,20 @@ MUTANTS = [
     ("ZEDO_MUT_PR_P32", "zedo_prune_rank: tiles of 32 poses (256 < H <= 512) count the kept slots below a - 1 for the output position (zedo_prune.hip prune_rank_kernel)"),
     ("ZEDO_MUT_PG_TRIP", "zedo_prune_gather: the grid-stride loop over the rows stops after its first trip (zedo_prune.hip prune_gather_kernel)"),
     ("ZEDO_MUT_PMIN_LANE_H", "lane-per-pose arg-min (N >= 8192): reports h - h0, the hypothesis counted from the shard's first (zedo_metric.hip pose_min_kernel)"),
-    # the joint-wise temporal selection (tests/test_joint_temporal_gpu.py, tests/test_select_joints_temporal_driver_gpu.py): leaves every
-    # other test green
-    ("ZEDO_MUT_JT_NO_T", "zedo_joint_temporal_select: the motion term is taken on x alone although d_T was given (zedo_joint_temporal.hip joint_temporal_scan_kernel)"),
+    # the joint-wise temporal selection (tests/test_joint_temporal_gpu.py, tests/test_select_joints_temporal_driver_gpu.py), since the
+    # streaming scan takes the statement from the same place the live streams (tests/test_joint_stream_gpu.py), and the tests that hold
+    # another call to the first-order one (in tests/test_joint_accel_gpu.py and tests/test_select_joints_accel_driver_gpu.py); leaves
+    # tests/test_joint_accel_marginal_gpu.py green (profiles/chain_shared_scan.txt: run against these six files)
+    ("ZEDO_MUT_JT_NO_T", "zedo_joint_temporal_select and zedo_joint_stream_push: the motion term is taken on x alone although d_T was given (zedo_chain.h ZEDO_CHAIN_STEP_T: joint_temporal_scan_kernel and joint_stream_scan_kernel)"),
     # the joint-wise selection on live streams (tests/test_joint_stream_gpu.py): leaves every other test green
     ("ZEDO_MUT_JS_HORIZON", "zedo_joint_stream_push: the horizon of frame n is taken as n + lag - 1, one frame short (zedo_joint_stream.hip joint_stream_emit_kernel)"),
     # the joint-wise fusion (tests/test_joint_marginal_gpu.py, tests/test_select_joints_fused_driver_gpu.py): leaves every other test green
     ("ZEDO_MUT_JM_NO_BACKWARD", "zedo_joint_marginal: B = 0 on every frame - the filtering marginals, not the smoothed ones (zedo_joint_marginal.hip joint_marginal_backward_kernel)"),
-    # the second-order joint-wise selection (tests/test_joint_accel_gpu.py, tests/test_select_joints_accel_driver_gpu.py): leaves every other
-    # test green
-    ("ZEDO_MUT_JA_FIRST_DIFF", "zedo_joint_accel_select: the second difference is taken as X[n] - X[n-1] + X[n-2], the factor 2 is dropped (zedo_joint_accel.hip joint_accel_scan_kernel and joint_accel_cost_kernel)"),
+    # the second-order joint-wise selection (tests/test_joint_accel_gpu.py, tests/test_select_joints_accel_driver_gpu.py) and, since its
+    # sum-product twin shares the statement, the second-order fusion (tests/test_joint_accel_marginal_gpu.py); leaves the tests of the
+    # first-order chain green (tests/test_joint_temporal_gpu.py, tests/test_joint_stream_gpu.py, tests/test_select_joints_temporal_driver_gpu.py;
+    # profiles/chain_shared_scan.txt: run against these six files)
+    ("ZEDO_MUT_JA_FIRST_DIFF", "zedo_joint_accel_select and zedo_joint_accel_marginal: the second difference is taken as X[n] - X[n-1] + X[n-2], the factor 2 is dropped (zedo_chain.h accel_lead: the scan and cost kernels of the selection, the forward and backward kernels of the fusion)"),
     # the skeleton-coupled aggregation (tests/test_joint_tree_gpu.py, tests/test_select_joints_tree_driver_gpu.py) and, since its sum-product
     # twin shares the statement, the skeleton-coupled fusion's tests: leaves every other test green
     ("ZEDO_MUT_TREE_NO_HALF", "zedo_joint_tree_select and zedo_joint_tree_marginal: the bone term compares the assembled length with the SUM of the two hypotheses' lengths, the 0.5 is dropped (zedo_chain.h tr_bone: the recurrences and bone[n,.])"),

@@ -1,11 +1,12 @@
-// What the label-free selection and fusion kernels share (zedo_temporal.hip, zedo_joint_temporal.hip, zedo_joint_marginal.hip,
-// zedo_joint_accel.hip, zedo_joint_accel_marginal.hip, zedo_joint_tree.hip, zedo_joint_tree_marginal.hip): the one copy of their lane
-// layout, their reductions and their staging.  The rules every user relies on live here and nowhere else:
+// What the label-free selection and fusion kernels share (zedo_temporal.hip, zedo_joint_temporal.hip, zedo_joint_stream.hip,
+// zedo_joint_marginal.hip, zedo_joint_accel.hip, zedo_joint_accel_marginal.hip, zedo_joint_tree.hip, zedo_joint_tree_marginal.hip): the one
+// copy of their lane layout, their reductions and their staging.  The rules every user relies on live here and nowhere else:
 //   - a tie goes to the lowest index (strict comparisons, parts and waves combined in ascending order);
 //   - a sum is a butterfly inside each wave, then the waves in ascending order: a fixed order, no atomics;
 //   - a lane past H reads row H-1 and stores nothing;
 //   - an offset read from seq_start is clamped to 0 .. N before it is an address.
-// The recurrences themselves - what is minimised or summed - stay in their own files.
+// The recurrences themselves - what is minimised or summed - stay in their own files; the one that two files run, the first-order
+// chain's frame step, is here.
 #pragma once
 #include "zedo_internal.h"
 
@@ -131,6 +132,58 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double *sred, int tid
     __syncthreads();
 }
 
+// ---- the first-order chain's frame step (joint_temporal_scan_kernel on a whole clip, joint_stream_scan_kernel on a chunk of it) ----
+// Everything that decides a bit of D or back, as statements in the kernel's own scope: the streaming call promises the offline call's
+// bits, and the same walk as a __forceinline__ function template changes the register assignment of the offline kernel from its first
+// block on.  A kernel keeps what is its own: where a frame's rows live, where "chain start" comes from, what a chain's end leaves behind.
+// In scope: P, K, SLOTS and ln of ChainLanes<P, K>; tid, H, N, J, j, junary, x, Tr, lambda, inf; xn [K][3], un [K] - the frame that is
+// being fetched - and xc [K][3], uc [K] - the frame in hand; dn [K], bn [K]; chain (n continues a chain) and is_dead, workgroup-uniform;
+// sX [CAP][3], sD [CAP] - frame n-1 - and sPv, sPi [CHAIN_T] of the LDS.
+#ifdef ZEDO_MUT_JT_NO_T   // tools/mutation_check.py only: the motion term is taken on x alone although T was given
+#define ZEDO_CHAIN_STEP_T(G) nullptr
+#else
+#define ZEDO_CHAIN_STEP_T(G) (Tr ? Tr + (G) * 3 : nullptr)
+#endif
+// X[FRAME,h,j,.] and u[FRAME,j,h] of this lane's h into xn, un.  load_cam's statements in place, not a call of it: through the function
+// the compiler joins the three loads of x into one and converts it before the branch on T, i.e. waits for the prefetch ahead of barrier
+// A - an offline call without T on one clip of 1 015 frames (J = 17, H = 50) measured 2 875 us against 2 778 us.
+#define ZEDO_CHAIN_STEP_FETCH(FRAME)                                                                                                   \
+        _Pragma("unroll") for (int k = 0; k < K; ++k) {                                                                                \
+            const size_t g = (size_t)min(ln.slot + k * SLOTS, H - 1) * N + (FRAME);                                                    \
+            const float *px = x + (g * J + j) * 3;                                                                                     \
+            const float *pt = ZEDO_CHAIN_STEP_T(g);                                                                                    \
+            _Pragma("unroll") for (int c = 0; c < 3; ++c) xn[k][c] = (double)px[c] + (pt ? (double)pt[c] : 0.0);                       \
+            un[k] = junary[g * J + j];                                                                                                 \
+        }
+// between barriers A and B: min_h' (D[n-1,h'] + lambda |X[n,h] - X[n-1,h']|) over the lane's part q0 .. q1-1 into dn, the lowest h' that
+// attains it into bn; with P > 1 both go to the LDS
+#define ZEDO_CHAIN_STEP_WALK                                                                                                           \
+        if (chain) {                                                                                                                   \
+            _Pragma("unroll") for (int k = 0; k < K; ++k) { dn[k] = inf; bn[k] = 0; }                                                  \
+            _Pragma("unroll 4") for (int hp = ln.q0; hp < ln.q1; ++hp) {                                                               \
+                const double p0 = sX[hp * 3], p1 = sX[hp * 3 + 1], p2 = sX[hp * 3 + 2], pd = sD[hp];                                   \
+                _Pragma("unroll") for (int k = 0; k < K; ++k) {                                                                        \
+                    const double d0 = xc[k][0] - p0, d1 = xc[k][1] - p1, d2 = xc[k][2] - p2;                                           \
+                    const double c = pd + lambda * sqrt(d0 * d0 + d1 * d1 + d2 * d2);                                                  \
+                    if (hp == ln.q0 || c < dn[k]) { dn[k] = c; bn[k] = hp; }   /* strict: the lowest h' that attains the minimum */    \
+                }                                                                                                                      \
+            }                                                                                                                          \
+            if (P > 1) { sPv[tid] = dn[0]; sPi[tid] = bn[0]; }                                                                         \
+        }
+// after barrier B, by part 0: the parts' minima in ascending part order, strict - the tie still goes to the lowest h'
+#define ZEDO_CHAIN_STEP_COMBINE                                                                                                        \
+            if (chain && P > 1) {                                                                                                      \
+                for (int p = 1; p < ln.np; ++p) {                                                                                      \
+                    const double c = sPv[p * SLOTS + ln.slot];                                                                         \
+                    if (c < dn[0]) { dn[0] = c; bn[0] = sPi[p * SLOTS + ln.slot]; }                                                    \
+                }                                                                                                                      \
+            }
+// d = D[n,j,h] of the owner of h = slot + K_ SLOTS: u + the minimum inside a chain, u at a chain's start, +inf where the unary is not
+// finite or (n, j) is dead.  Declares u0 and d.  (A function of the same text changes joint_stream_scan_kernel's code.)
+#define ZEDO_CHAIN_STEP_VALUE(K_)                                                                                                      \
+                    const double u0 = finite64(uc[K_]) ? uc[K_] : inf;                                                                 \
+                    const double d = chain ? u0 + dn[K_] : (is_dead ? inf : u0);
+
 // ---- what a fusion kernel along a video reads off the marginals of one (frame, joint) (zedo_joint_marginal.hip, zedo_joint_accel_marginal.hip) ----
 // The tail of a backward kernel's frame, as statements in the kernel's own scope: a function of the same text changes the register
 // allocation of joint_marginal_backward_kernel, and that kernel's instruction stream is pinned.  A lane holds K hypotheses h = H0 + k HSTEP
@@ -190,6 +243,44 @@ inline void dispatch_pairs(int H, F &&f) {
     else if (HH <= 13 * CHAIN_T) f(IntC<13>());
     else f(IntC<16>());
 }
+// qh1 [KA], qh0 [KA]: h' and h of the KA pairs q = tid, tid + 256, .. of a lane (a pair past H^2 is computed as pair H^2 - 1 and stored
+// nowhere).  One text in the two forms the pinned kernels need: joint_accel_scan_kernel's code changes when this is a function, that of
+// the fusion kernels when it is not.  The statements take tid, H and HH = H^2 from the scope they stand in.
+#define ZEDO_CHAIN_LANE_PAIRS(KA)                                                                                                      \
+    _Pragma("unroll") for (int k = 0; k < KA; ++k) {                                                                                   \
+        const int q = min(tid + k * CHAIN_T, HH - 1);                                                                                  \
+        qh1[k] = q / H;                                                                                                                \
+        qh0[k] = q - qh1[k] * H;                                                                                                       \
+    }
+template <int KA>
+__device__ __forceinline__ void lane_pairs(int tid, int H, int (&qh1)[KA], int (&qh0)[KA]) {
+    const int HH = H * H;
+    ZEDO_CHAIN_LANE_PAIRS(KA)
+}
+// The leading part a - 2 p of the second difference a - 2 p + b; the caller adds b, and chooses which of the three frames a, p and b are
+__device__ __forceinline__ double accel_lead(double a, double p) {
+#ifdef ZEDO_MUT_JA_FIRST_DIFF   // tools/mutation_check.py only: the factor 2 is dropped, a - p + b
+    return a - p;
+#else
+    return a - 2.0 * p;
+#endif
+}
+// What a forward kernel keeps of frames n and n-1 for the lane's pairs, between its barriers A and B: g [KA][3], g_c = X[n,h,c] -
+// 2 X[n-1,h',c], and lm [KA] = W |X[n,h] - X[n-1,h']| (the squares, then their sum ascending in c).  INIT: the kernel's own statements
+// for pair k, if any.  In scope: qh1, qh0, X0 = X[n], X1 = X[n-1] of the LDS.
+#define ZEDO_CHAIN_PAIR_TERMS(KA, W, INIT)                                                                                             \
+            double g[KA][3], lm[KA];                                                                                                   \
+            _Pragma("unroll") for (int k = 0; k < KA; ++k) {                                                                           \
+                const int h1 = qh1[k], h0 = qh0[k];                                                                                    \
+                double d[3];                                                                                                           \
+                _Pragma("unroll") for (int c = 0; c < 3; ++c) {                                                                        \
+                    const double p = X1[h1 * 3 + c];                                                                                   \
+                    d[c] = X0[h0 * 3 + c] - p;                                                                                         \
+                    g[k][c] = accel_lead(X0[h0 * 3 + c], p);                                                                           \
+                }                                                                                                                      \
+                lm[k] = (W) * sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);                                                           \
+                INIT                                                                                                                   \
+            }
 
 // ---- the bone tree: one workgroup per pose, everything in the LDS ----
 // sqrt(d0^2 + d1^2 + d2^2), d = a - b: products, then the sum ascending in c

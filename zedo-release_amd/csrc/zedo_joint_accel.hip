@@ -8,8 +8,9 @@
 //   joint_accel_backtrack_kernel  the backward pass, one workgroup per (clip, joint), runs of back2 staged through the LDS
 //   joint_accel_cost_kernel       the cost of the kept path re-accumulated along it, one workgroup per (clip, joint): the terms of a run of
 //                                 frames in parallel, their sum by one lane in ascending frame order
-// The (clip, joint) of a workgroup, the camera-frame load and the arg-min reduction are zedo_chain.h's.  E is never stored for all
-// frames.  No atomics.
+// The (clip, joint) of a workgroup, the camera-frame load, the arg-min reduction and - shared with zedo_joint_accel_marginal.hip - a
+// lane's pairs, their terms of frames n and n-1 and the factor 2 of the second difference (accel_lead) are zedo_chain.h's.  E is never
+// stored for all frames.  No atomics.
 #include "zedo_chain.h"
 
 namespace zedo {
@@ -42,14 +43,8 @@ __global__ __launch_bounds__(CHAIN_T) void joint_accel_scan_kernel(const double 
     const int j = cj.j, a = cj.a, b = cj.b;
     if (a >= b) return;                                            // (workgroup-uniform)
     const double inf = __builtin_huge_val();
-    // this lane's pairs (a pair past H^2 is computed as pair H^2 - 1 and stored nowhere)
     int qh1[KA], qh0[KA];                                          // h' and h of pair k
-#pragma unroll
-    for (int k = 0; k < KA; ++k) {
-        const int q = min(tid + k * CHAIN_T, HH - 1);
-        qh1[k] = q / H;
-        qh0[k] = q - qh1[k] * H;
-    }
+    ZEDO_CHAIN_LANE_PAIRS(KA)
     // X[n,h,j,.] and u[n,j,h] of hypothesis h = tid (a lane past H reads hypothesis H-1 and stores nothing)
     double xn[3], un;
     auto fetch = [&](int n) {
@@ -79,25 +74,7 @@ __global__ __launch_bounds__(CHAIN_T) void joint_accel_scan_kernel(const double 
         int bn[KA];
         __syncthreads();                                           // A: E[n-1], X[n], X[n-1], X[n-2], u[n], u[n-1] are in the LDS
         if (scan) {
-            double g[KA][3], lm[KA];                               // g_c = X[n,h,c] - 2 X[n-1,h',c];  lambda_v m[n,h',h]
-#pragma unroll
-            for (int k = 0; k < KA; ++k) {
-                const int h1 = qh1[k], h0 = qh0[k];
-                double d[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const double p = X1[h1 * 3 + c];
-                    d[c] = X0[h0 * 3 + c] - p;
-#ifdef ZEDO_MUT_JA_FIRST_DIFF   // tools/mutation_check.py only: the second difference taken as X[n] - X[n-1] + X[n-2]
-                    g[k][c] = X0[h0 * 3 + c] - p;
-#else
-                    g[k][c] = X0[h0 * 3 + c] - 2.0 * p;
-#endif
-                }
-                lm[k] = lambda_v * sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-                en[k] = inf;
-                bn[k] = 0;
-            }
+            ZEDO_CHAIN_PAIR_TERMS(KA, lambda_v, en[k] = inf; bn[k] = 0;)       // g_c = X[n,h,c] - 2 X[n-1,h',c];  lm = lambda_v m
             if (second) {
 #pragma unroll
                 for (int k = 0; k < KA; ++k) en[k] = U1[qh1[k]] + (U0[qh0[k]] + lm[k]);
@@ -243,11 +220,8 @@ __global__ __launch_bounds__(256) void joint_accel_cost_kernel(const double *__r
                         const int p2 = clampi(path[nj - 2 * (size_t)J], 0, H - 1);
                         double X2[3];
                         load_cam(x, Tr, (size_t)p2 * N + n - 2, J, j, X2);
-#ifdef ZEDO_MUT_JA_FIRST_DIFF
-                        const double e0 = (X0[0] - X1[0]) + X2[0], e1 = (X0[1] - X1[1]) + X2[1], e2 = (X0[2] - X1[2]) + X2[2];
-#else
-                        const double e0 = (X0[0] - 2.0 * X1[0]) + X2[0], e1 = (X0[1] - 2.0 * X1[1]) + X2[1], e2 = (X0[2] - 2.0 * X1[2]) + X2[2];
-#endif
+                        const double e0 = accel_lead(X0[0], X1[0]) + X2[0], e1 = accel_lead(X0[1], X1[1]) + X2[1],
+                                     e2 = accel_lead(X0[2], X1[2]) + X2[2];
                         w = w + lambda_a * sqrt(e0 * e0 + e1 * e1 + e2 * e2);
                     }
                     t = t + w;

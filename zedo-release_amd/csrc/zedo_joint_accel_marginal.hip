@@ -27,17 +27,6 @@ namespace zedo {
 
 constexpr int JAM_CAP = 64;
 
-// h' and h of the KA pairs q = tid, tid + 256, .. of a lane (a pair past H^2 is computed as pair H^2 - 1 and stored nowhere)
-template <int KA>
-__device__ __forceinline__ void jam_pairs(int tid, int H, int (&qh1)[KA], int (&qh0)[KA]) {
-#pragma unroll
-    for (int k = 0; k < KA; ++k) {
-        const int q = min(tid + k * CHAIN_T, H * H - 1);
-        qh1[k] = q / H;
-        qh0[k] = q - qh1[k] * H;
-    }
-}
-
 // lse[k] = LSE_i (tab[i H + col[k]] - c_a |g[k] + Xb[i]|), i = 0 .. H-1, for the KA pairs of a lane: all lanes walk i in lockstep, Xb[i]
 // is a broadcast read and tab[i H + col] of neighbouring lanes is the same or the next double.  First walk: the largest term; second:
 // the sum of exp(term - largest), ascending in i (shifted by 0 where no term is above -inf: every exp is 0 and the result -inf).
@@ -114,7 +103,7 @@ __global__ __launch_bounds__(CHAIN_T) void joint_accel_marginal_forward_kernel(c
     if (a >= b) return;                                            // (workgroup-uniform)
     const double ninf = -__builtin_huge_val();
     int qh1[KA], qh0[KA];
-    jam_pairs<KA>(tid, H, qh1, qh0);
+    lane_pairs<KA>(tid, H, qh1, qh0);
     // X[n,h,j,.] and l[n,j,h] of hypothesis h = tid (a lane past H reads hypothesis H-1 and stores nothing)
     double xn[3], ln;
     auto fetch = [&](int n) {
@@ -142,19 +131,7 @@ __global__ __launch_bounds__(CHAIN_T) void joint_accel_marginal_forward_kernel(c
         double an[KA];
         __syncthreads();                                           // A: A2[n-1], X[n], X[n-1], X[n-2], l[n], l[n-1] are in the LDS
         if (scan) {
-            double g[KA][3], lm[KA];                               // g_c = X[n,h,c] - 2 X[n-1,h',c];  c_v m[n,h',h]
-#pragma unroll
-            for (int k = 0; k < KA; ++k) {
-                const int h1 = qh1[k], h0 = qh0[k];
-                double d[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const double p = X1[h1 * 3 + c];
-                    d[c] = X0[h0 * 3 + c] - p;
-                    g[k][c] = X0[h0 * 3 + c] - 2.0 * p;
-                }
-                lm[k] = c_v * sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-            }
+            ZEDO_CHAIN_PAIR_TERMS(KA, c_v, )                       // g_c = X[n,h,c] - 2 X[n-1,h',c];  lm = c_v m[n,h',h]
             if (second) {
 #pragma unroll
                 for (int k = 0; k < KA; ++k) an[k] = L1[qh1[k]] + (L0[qh0[k]] - lm[k]);
@@ -215,7 +192,7 @@ __global__ __launch_bounds__(CHAIN_T) void joint_accel_marginal_backward_kernel(
     const double c_a_back = c_a;
 #endif
     int qh1[KA], qh0[KA];
-    jam_pairs<KA>(tid, H, qh1, qh0);
+    lane_pairs<KA>(tid, H, qh1, qh0);
     const int hx = min(tid, H - 1);                                // a lane past H reads hypothesis H-1 and stores nothing
     double xn[3], ln, an[KA];
     auto fetch = [&](int n) {
@@ -274,7 +251,7 @@ __global__ __launch_bounds__(CHAIN_T) void joint_accel_marginal_backward_kernel(
 #pragma unroll
             for (int k = 0; k < KA; ++k)
 #pragma unroll
-                for (int c = 0; c < 3; ++c) g[k][c] = X1[qh1[k] * 3 + c] - 2.0 * X0[qh0[k] * 3 + c];
+                for (int c = 0; c < 3; ++c) g[k][c] = accel_lead(X1[qh1[k] * 3 + c], X0[qh0[k] * 3 + c]);
             jam_walk<KA>(sM, Xp, H, qh0, g, c_a_back, bn);
         }
         if (!is_dead && ends) {                                    // (workgroup-uniform) log Z of the chain that ends here

@@ -7,9 +7,9 @@
 //   joint_stream_emit_kernel     one wave per (emitted frame, stream, joint): the horizon from the ring's dead flags, the lowest arg-min
 //                                of D there, at most `lag` back pointers, all read from the ring; nothing of it is in the scan's loop
 //   joint_stream_advance_kernel  one lane per stream: d_emit and the clip's frame count (0 after a flush)
-// A sibling of the offline scan, not a shared body: the offline kernel's instruction stream stays as it is.  The ring holds lag +
-// max_frames frames: frame m of a clip sits in row m % R, a push writes the rows of frames t .. t+F-1 and its emission reads frames
-// >= max(0, t - lag) > t + F - 1 - R - rows this push has not overwritten.  No atomics, no scratch.
+// The two scans are two kernels - their arguments differ - that take the statements of a frame's step from one place, zedo_chain.h.
+// The ring holds lag + max_frames frames: frame m of a clip sits in row m % R, a push writes the rows of frames t .. t+F-1 and its
+// emission reads frames >= max(0, t - lag) > t + F - 1 - R - rows this push has not overwritten.  No atomics, no scratch.
 #include "zedo_chain.h"
 
 namespace zedo {
@@ -54,8 +54,9 @@ __global__ __launch_bounds__(256) void joint_stream_dead_kernel(const double *__
 
 // joint_temporal_scan_kernel on the F frames of stream s's chunk (rows n = s F + f of the call), continued from the state: frame t + f
 // of the clip.  "Chain start" is t + f == 0 or the frame before is dead - for f = 0 that flag is the state's lastdead, not the ring's
-// (with lag = 0 and F = max_frames the dead kernel has just reused that row).  The statements of a frame are the offline kernel's, on
-// the same operands: the bits of D and back are its bits.  The arg-min at a chain's end is not taken here: emission does that.
+// (with lag = 0 and F = max_frames the dead kernel has just reused that row).  The statements of a frame are the offline kernel's
+// (zedo_chain.h: the first-order chain's frame step), on the same operands: the bits of D and back are its bits.  The arg-min at a
+// chain's end is not taken here: emission does that.
 template <int P, int K>
 __global__ __launch_bounds__(CHAIN_T) void joint_stream_scan_kernel(const double *__restrict__ junary, const float *__restrict__ x,
                                                                     const float *__restrict__ Tr, int F, int H, int N, int J, int R,
@@ -80,17 +81,7 @@ __global__ __launch_bounds__(CHAIN_T) void joint_stream_scan_kernel(const double
     const int *const dr = dead + sj * R;
     double *const lX = lastX + sj * H * 3, *const lD = lastD + sj * H;
     double xn[K][3], un[K];
-    auto fetch = [&](int n) {                                      // (load_cam's statements in place: see joint_temporal_scan_kernel)
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const size_t g = (size_t)min(ln.slot + k * SLOTS, H - 1) * N + n;
-            const float *px = x + (g * J + j) * 3;
-            const float *pt = Tr ? Tr + g * 3 : nullptr;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) xn[k][c] = (double)px[c] + (pt ? (double)pt[c] : 0.0);
-            un[k] = junary[g * J + j];
-        }
-    };
+    auto fetch = [&](int n) { ZEDO_CHAIN_STEP_FETCH(n) };
     fetch(a);
     int prev_dead = t0 > 0 ? lastdead[sj] : 1;                     // (workgroup-uniform)
     if (t0 > 0 && ln.part == 0) {                                  // X[t-1,.] and D[t-1,.] of the clip: visible after barrier A
@@ -119,35 +110,15 @@ __global__ __launch_bounds__(CHAIN_T) void joint_stream_scan_kernel(const double
         double dn[K];
         int bn[K];
         __syncthreads();                                           // A: X[n-1,.] and D[n-1,.] are in the LDS
-        if (chain) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) { dn[k] = inf; bn[k] = 0; }
-#pragma unroll 4
-            for (int hp = ln.q0; hp < ln.q1; ++hp) {
-                const double p0 = sX[hp * 3], p1 = sX[hp * 3 + 1], p2 = sX[hp * 3 + 2], pd = sD[hp];
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const double d0 = xc[k][0] - p0, d1 = xc[k][1] - p1, d2 = xc[k][2] - p2;
-                    const double c = pd + lambda * sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-                    if (hp == ln.q0 || c < dn[k]) { dn[k] = c; bn[k] = hp; }   // strict: the lowest h' that attains the minimum
-                }
-            }
-            if (P > 1) { sPv[tid] = dn[0]; sPi[tid] = bn[0]; }
-        }
+        ZEDO_CHAIN_STEP_WALK
         __syncthreads();                                           // B: frame n-1 has been read by every lane
         if (ln.part == 0) {
-            if (chain && P > 1) {
-                for (int p = 1; p < ln.np; ++p) {
-                    const double c = sPv[p * SLOTS + ln.slot];
-                    if (c < dn[0]) { dn[0] = c; bn[0] = sPi[p * SLOTS + ln.slot]; }
-                }
-            }
+            ZEDO_CHAIN_STEP_COMBINE
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 const int h = ln.slot + k * SLOTS;
                 if (h < H) {
-                    const double u0 = finite64(uc[k]) ? uc[k] : inf;
-                    const double d = chain ? u0 + dn[k] : (is_dead ? inf : u0);
+                    ZEDO_CHAIN_STEP_VALUE(k)
                     Dr[(size_t)row * H + h] = d;
                     br[(size_t)row * H + h] = chain ? bn[k] : -1;
                     sD[h] = d;

@@ -5,9 +5,10 @@
 //   joint_temporal_scan_kernel       the forward recurrence, one workgroup per (clip, joint); the transition cost of a pair (h', h) is one
 //                                    square root of three terms and is computed where the recurrence consumes it - there is no H x H table
 //   joint_temporal_backtrack_kernel  the backward pass, one workgroup per (clip, joint), runs of the back table staged through the LDS
-// The (clip, joint) of a workgroup, the lane split and the reductions are zedo_chain.h's.  A chain reads 12 bytes of x per (frame,
-// hypothesis), at a stride of N J 3 floats across h; the other joints of the same pose row sit in the same few 128-byte lines, and
-// neighbours in the grid run at the same time, so a line fetched from HBM for one chain serves the others from the L2.  No atomics.
+// The (clip, joint) of a workgroup, the lane split, the reductions and the statements of the scan's frame step - shared with the
+// streaming scan of zedo_joint_stream.hip - are zedo_chain.h's.  A chain reads 12 bytes of x per (frame, hypothesis), at a stride of
+// N J 3 floats across h; the other joints of the same pose row sit in the same few 128-byte lines, and neighbours in the grid run at
+// the same time, so a line fetched from HBM for one chain serves the others from the L2.  No atomics.
 #include "zedo_chain.h"
 
 namespace zedo {
@@ -50,25 +51,8 @@ __global__ __launch_bounds__(CHAIN_T) void joint_temporal_scan_kernel(const doub
     const int j = cj.j, a = cj.a, b = cj.b;
     if (a >= b) return;                                            // (workgroup-uniform)
     const double inf = __builtin_huge_val();
-    // X[n,h,j,.] and u[n,j,h] of this lane's h.  load_cam's statements in place, not a call of it: through the function the compiler
-    // joins the three loads of x into one and converts it before the branch on T, i.e. waits for the prefetch ahead of barrier A - a
-    // call without T on one clip of 1 015 frames (J = 17, H = 50) measured 2 875 us against 2 778 us.
-    double xn[K][3], un[K];
-    auto fetch = [&](int n) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const size_t g = (size_t)min(ln.slot + k * SLOTS, H - 1) * N + n;
-            const float *px = x + (g * J + j) * 3;
-#ifdef ZEDO_MUT_JT_NO_T   // tools/mutation_check.py only: the motion term is taken on x alone although T was given
-            const float *pt = nullptr;
-#else
-            const float *pt = Tr ? Tr + g * 3 : nullptr;
-#endif
-#pragma unroll
-            for (int c = 0; c < 3; ++c) xn[k][c] = (double)px[c] + (pt ? (double)pt[c] : 0.0);
-            un[k] = junary[g * J + j];
-        }
-    };
+    double xn[K][3], un[K];                                        // X[n,h,j,.] and u[n,j,h] of this lane's h
+    auto fetch = [&](int n) { ZEDO_CHAIN_STEP_FETCH(n) };
     fetch(a);
     for (int n = a; n < b; ++n) {
         double xc[K][3], uc[K];
@@ -86,35 +70,15 @@ __global__ __launch_bounds__(CHAIN_T) void joint_temporal_scan_kernel(const doub
         double dn[K];
         int bn[K];
         __syncthreads();                                           // A: X[n-1,.] and D[n-1,.] are in the LDS
-        if (chain) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) { dn[k] = inf; bn[k] = 0; }
-#pragma unroll 4
-            for (int hp = ln.q0; hp < ln.q1; ++hp) {
-                const double p0 = sX[hp * 3], p1 = sX[hp * 3 + 1], p2 = sX[hp * 3 + 2], pd = sD[hp];
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const double d0 = xc[k][0] - p0, d1 = xc[k][1] - p1, d2 = xc[k][2] - p2;
-                    const double c = pd + lambda * sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-                    if (hp == ln.q0 || c < dn[k]) { dn[k] = c; bn[k] = hp; }   // strict: the lowest h' that attains the minimum
-                }
-            }
-            if (P > 1) { sPv[tid] = dn[0]; sPi[tid] = bn[0]; }
-        }
+        ZEDO_CHAIN_STEP_WALK
         __syncthreads();                                           // B: frame n-1 has been read by every lane
         if (ln.part == 0) {
-            if (chain && P > 1) {
-                for (int p = 1; p < ln.np; ++p) {
-                    const double c = sPv[p * SLOTS + ln.slot];
-                    if (c < dn[0]) { dn[0] = c; bn[0] = sPi[p * SLOTS + ln.slot]; }
-                }
-            }
+            ZEDO_CHAIN_STEP_COMBINE
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 const int h = ln.slot + k * SLOTS;
                 if (h < H) {
-                    const double u0 = finite64(uc[k]) ? uc[k] : inf;
-                    const double d = chain ? u0 + dn[k] : (is_dead ? inf : u0);
+                    ZEDO_CHAIN_STEP_VALUE(k)
                     dn[k] = d;
                     D[nj * H + h] = d;
                     back[nj * H + h] = chain ? bn[k] : -1;
