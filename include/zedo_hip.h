@@ -50,7 +50,9 @@ extern "C" {
                               * still 5 (additive): + zedo_joint_marginal_workspace_bytes, zedo_joint_marginal;
                               * still 5 (additive): + zedo_joint_accel_workspace_bytes, zedo_joint_accel_select;
                               * still 5 (additive): + zedo_joint_accel_marginal_workspace_bytes, zedo_joint_accel_marginal;
-                              * still 5 (additive): + zedo_joint_stream_state_bytes, zedo_joint_stream_reset, zedo_joint_stream_push */
+                              * still 5 (additive): + zedo_joint_stream_state_bytes, zedo_joint_stream_reset, zedo_joint_stream_push;
+                              * still 5 (additive): + zedo_joint_stream_marginal_state_bytes, zedo_joint_stream_marginal_reset,
+                              *                       zedo_joint_stream_marginal_push */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -460,6 +462,58 @@ int zedo_joint_stream_reset(void *d_state, size_t state_bytes, int S, int H, int
 int zedo_joint_stream_push(const double *d_junary, const float *d_x, const float *d_T, int S, int F, int H, int J, int lag,
                            int max_frames, double lambda, const int *d_flush, void *d_state, size_t state_bytes, int *d_path_h,
                            double *d_cost, long long *d_emit, void *stream);
+
+/* ---- joint-wise fusion on a LIVE video WITHOUT ground truth: fixed-lag streaming sum-product ----------------------------------
+ * zedo_joint_stream_push is a hard decision: one hypothesis per joint, no spread.  zedo_joint_marginal (below) gives the soft
+ * answer of the same chain - posterior mean, covariance, most probable hypothesis - but needs the whole clip.  This call gives
+ * that soft answer on live streams, every frame `lag` frames after it went in: fixed-lag smoothing.  Whether a few frames of lag
+ * buy most of the whole-clip answer on real video is not measured; lag, lambda and tau are untuned.
+ * A stream's CLIP, X, u, l, m, DEAD, "chain start", A, B, logZ and w are those of zedo_joint_marginal and
+ * zedo_joint_stream_push, word for word.  A is a prefix quantity of the clip: it does not depend on how the frames were cut
+ * into pushes.  With lag >= 0:
+ *   frame n of a clip is EMITTED by the first push after which the clip holds frame n + lag, or by the push that flushes the
+ *   stream, whichever comes first - the rule, the count and the `first` of zedo_joint_stream_push.
+ *   For a live (n,j) let c_j(n) be the last frame of n's chain on the frames the clip holds after that push and
+ *   e = min(n + lag, c_j(n)).  Then B[e,j,.] = 0 and logZ = LSE_h A[e,j,h]; B[m,j,.] for m = e-1 .. n by the backward recurrence
+ *   of zedo_joint_marginal; w[n,j,h] = exp(A[n,j,h] + B[n,j,h] - logZ).
+ *   mean, cov (from the centred differences), hmax (the lowest h with the largest w), wmax and logz follow from w exactly as
+ *   zedo_joint_marginal forms them; a dead (n,j) reports that call's dead outputs.
+ * In words: the outputs for frame n are those of zedo_joint_marginal on the stream's clip cut after frame n + lag.  lag = 0 gives
+ * the filtering marginals, the softmax of A[n,j,.]; the outputs do not depend on the chunking; with lag >= the clip's length - 1
+ * and a flush they are the offline call's, bit for bit.
+ * zedo_joint_stream_marginal_push: the chunk (d_junary, d_x, d_T; rows (h,n) h-major, n = s*F + f), d_flush, F = 0 and d_emit
+ * [S,2] are those of zedo_joint_stream_push.  Outputs: d_mean [S,F+lag,J,3], d_cov [S,F+lag,J,6], d_hmax (int32), d_wmax and
+ * d_logz [S,F+lag,J], and the optional d_w [S,F+lag,J,H] (NULL: not written); row r of stream s = the r-th frame this push emits
+ * for it.  Rows at and after the count are not written.
+ * zedo_joint_stream_marginal_reset is zedo_joint_stream_reset on this state.
+ * State (8-byte aligned), with R = lag + max_frames rows per ring and SJ = S*J chains, in this order:
+ *   A float64 [SJ,R,H] | X float64 [SJ,R,H,3] | l float64 [SJ,R,H] | the clip's frame count int64 [S] |
+ *   the dead flags of the ring's frames int32 [SJ,R] | the dead flag of the clip's last frame int32 [SJ]
+ * - zedo_joint_stream_marginal_state_bytes = 8 (5 SJ R H + S) + 4 (SJ R + SJ) rounded up to 8; 0 for shapes the calls refuse.
+ * Frame m of a clip sits in row m % R.  The forward step's "previous frame" is the ring's own row (t - 1) % R, read before any
+ * row of the push is written; only the dead flag of the last frame has a slot of its own (with lag = 0 and F = max_frames the
+ * chunk's flags have reused that row by then).  A push writes the rows of its F frames and then reads at most the lag frames
+ * before them: never a row it has overwritten.
+ * Contract: that of zedo_joint_stream_push - 1 <= H <= 1024, J >= 1, S >= 1, max_frames >= 1, 0 <= F <= max_frames, lag >= 0,
+ * (lag + max_frames)*S*J*H <= INT_MAX, finite lambda >= 0 - and finite tau > 0; ZEDO_E_BADARG with nothing written and the
+ * state untouched for a NULL pointer other than d_T, d_w, d_flush (F > 0) and d_which, a size out of these ranges, F = 0
+ * without d_flush, a negative or non-finite lambda, tau <= 0 or not finite, or a state that is not 8-byte aligned;
+ * ZEDO_E_WORKSPACE with nothing written and the state untouched if state_bytes is too small; allocates nothing, synchronises
+ * nothing, enqueues on `stream` only: legal under stream capture - a replay advances the state.  No atomics: the bits do not
+ * depend on the run, the chunking, the content of the state before its reset, the alignment of d_x or whether d_w is given.
+ * Every value read from the state is clamped before it is an index.  lambda and tau are taken to be the same in every push
+ * between a frame going in and coming out; otherwise the outputs are unspecified, never an address.
+ * One workgroup per (stream, joint) for the forward recurrence; one workgroup per (stream, output row, joint) for the backward
+ * walk, where frames of one (stream, joint) that share a horizon - a chain that ends inside the window: a flush or a dead
+ * (frame, joint) - are served by ONE walk.  A whole clip pushed with lag = L - 1 and flushed costs one backward pass, as
+ * offline; a steady-state push costs F walks of lag frames per (stream, joint), which is inherent in fixed-lag smoothing. */
+size_t zedo_joint_stream_marginal_state_bytes(int S, int H, int J, int lag, int max_frames);
+int zedo_joint_stream_marginal_reset(void *d_state, size_t state_bytes, int S, int H, int J, int lag, int max_frames,
+                                     const int *d_which, void *stream);
+int zedo_joint_stream_marginal_push(const double *d_junary, const float *d_x, const float *d_T, int S, int F, int H, int J,
+                                    int lag, int max_frames, double lambda, double tau, const int *d_flush, void *d_state,
+                                    size_t state_bytes, double *d_mean, double *d_cov, int *d_hmax, double *d_wmax,
+                                    double *d_logz, double *d_w, long long *d_emit, void *stream);
 
 /* ---- fusing hypotheses along a video WITHOUT ground truth: per-joint posterior mean and spread ------------------------------
  * zedo_joint_temporal_select answers with one hypothesis per (frame, joint) and says nothing of the others.  This is the

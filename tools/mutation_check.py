@@ -61,6 +61,11 @@ MUTANTS = [
     ("ZEDO_MUT_JT_NO_T", "zedo_joint_temporal_select and zedo_joint_stream_push: the motion term is taken on x alone although d_T was given (zedo_chain.h ZEDO_CHAIN_STEP_T: joint_temporal_scan_kernel and joint_stream_scan_kernel)"),
     # the joint-wise selection on live streams (tests/test_joint_stream_gpu.py): leaves every other test green
     ("ZEDO_MUT_JS_HORIZON", "zedo_joint_stream_push: the horizon of frame n is taken as n + lag - 1, one frame short (zedo_joint_stream.hip joint_stream_emit_kernel)"),
+    # the joint-wise fusion on live streams (tests/test_joint_stream_marginal_gpu.py; profiles/mutation_joint_stream_marginal.txt): leaves
+    # every other test green, and of that file the lag-0 comparisons, the cells whose clips end before the shortened horizon matters, the
+    # clip of one frame and the refusals; the tests that compare the call with itself go red - every one of them also holds it to the
+    # offline call or to the reference
+    ("ZEDO_MUT_JSM_HORIZON", "zedo_joint_stream_marginal_push: the horizon of frame n is taken as n + lag - 1, one frame short (zedo_joint_stream_marginal.hip joint_stream_marginal_emit_kernel)"),
     # the joint-wise fusion (tests/test_joint_marginal_gpu.py, tests/test_select_joints_fused_driver_gpu.py): leaves every other test green
     ("ZEDO_MUT_JM_NO_BACKWARD", "zedo_joint_marginal: B = 0 on every frame - the filtering marginals, not the smoothed ones (zedo_joint_marginal.hip joint_marginal_backward_kernel)"),
     # the second-order joint-wise selection (tests/test_joint_accel_gpu.py, tests/test_select_joints_accel_driver_gpu.py) and, since its

@@ -927,6 +927,11 @@ static int stream_state_ok(const void *state, size_t state_bytes, int S, int H, 
     if (!state || !stream_dims_ok(S, H, J, lag, max_frames) || (reinterpret_cast<uintptr_t>(state) & 7)) return ZEDO_E_BADARG;
     return state_bytes < joint_stream_bytes(S, H, J, lag, max_frames) ? ZEDO_E_WORKSPACE : ZEDO_OK;
 }
+// the same for the state of the fusion on live streams
+static int stream_marginal_state_ok(const void *state, size_t state_bytes, int S, int H, int J, int lag, int max_frames) {
+    if (!state || !stream_dims_ok(S, H, J, lag, max_frames) || (reinterpret_cast<uintptr_t>(state) & 7)) return ZEDO_E_BADARG;
+    return state_bytes < joint_stream_marginal_bytes(S, H, J, lag, max_frames) ? ZEDO_E_WORKSPACE : ZEDO_OK;
+}
 
 extern "C" size_t zedo_joint_stream_state_bytes(int S, int H, int J, int lag, int max_frames) {
     return stream_dims_ok(S, H, J, lag, max_frames) ? joint_stream_bytes(S, H, J, lag, max_frames) : 0;
@@ -950,6 +955,33 @@ extern "C" int zedo_joint_stream_push(const double *d_junary, const float *d_x, 
     if (rc != ZEDO_OK) return rc;
     HIPCHK(launch_joint_stream_push(d_junary, d_x, d_T, S, F, H, J, lag, max_frames, lambda, d_flush, d_state, d_path_h, d_cost, d_emit,
                                     (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
+// the fusion on live streams: A, X and l of lag + max_frames frames per (stream, joint) in the caller's state
+extern "C" size_t zedo_joint_stream_marginal_state_bytes(int S, int H, int J, int lag, int max_frames) {
+    return stream_dims_ok(S, H, J, lag, max_frames) ? joint_stream_marginal_bytes(S, H, J, lag, max_frames) : 0;
+}
+
+extern "C" int zedo_joint_stream_marginal_reset(void *d_state, size_t state_bytes, int S, int H, int J, int lag, int max_frames,
+                                                const int *d_which, void *stream) {
+    const int rc = stream_marginal_state_ok(d_state, state_bytes, S, H, J, lag, max_frames);
+    if (rc != ZEDO_OK) return rc;
+    HIPCHK(launch_joint_stream_marginal_reset(d_state, S, H, J, lag, max_frames, d_which, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
+extern "C" int zedo_joint_stream_marginal_push(const double *d_junary, const float *d_x, const float *d_T, int S, int F, int H, int J,
+                                               int lag, int max_frames, double lambda, double tau, const int *d_flush, void *d_state,
+                                               size_t state_bytes, double *d_mean, double *d_cov, int *d_hmax, double *d_wmax,
+                                               double *d_logz, double *d_w, long long *d_emit, void *stream) {
+    if (!d_mean || !d_cov || !d_hmax || !d_wmax || !d_logz || !d_emit || F < 0 || F > max_frames) return ZEDO_E_BADARG;
+    if (F == 0 ? !d_flush : (!d_junary || !d_x)) return ZEDO_E_BADARG;                   // a push of no frames is a flush
+    if (!std::isfinite(lambda) || lambda < 0.0 || !std::isfinite(tau) || !(tau > 0.0)) return ZEDO_E_BADARG;
+    const int rc = stream_marginal_state_ok(d_state, state_bytes, S, H, J, lag, max_frames);
+    if (rc != ZEDO_OK) return rc;
+    HIPCHK(launch_joint_stream_marginal_push(d_junary, d_x, d_T, S, F, H, J, lag, max_frames, lambda / tau, tau, d_flush, d_state, d_mean,
+                                             d_cov, d_hmax, d_wmax, d_logz, d_w, d_emit, (hipStream_t)stream));
     return ZEDO_OK;
 }
 

@@ -1,12 +1,12 @@
 // What the label-free selection and fusion kernels share (zedo_temporal.hip, zedo_joint_temporal.hip, zedo_joint_stream.hip,
-// zedo_joint_marginal.hip, zedo_joint_accel.hip, zedo_joint_accel_marginal.hip, zedo_joint_tree.hip, zedo_joint_tree_marginal.hip): the one
+// zedo_joint_stream_marginal.hip, zedo_joint_marginal.hip, zedo_joint_accel.hip, zedo_joint_accel_marginal.hip, zedo_joint_tree.hip, zedo_joint_tree_marginal.hip): the one
 // copy of their lane layout, their reductions and their staging.  The rules every user relies on live here and nowhere else:
 //   - a tie goes to the lowest index (strict comparisons, parts and waves combined in ascending order);
 //   - a sum is a butterfly inside each wave, then the waves in ascending order: a fixed order, no atomics;
 //   - a lane past H reads row H-1 and stores nothing;
 //   - an offset read from seq_start is clamped to 0 .. N before it is an address.
-// The recurrences themselves - what is minimised or summed - stay in their own files; the one that two files run, the first-order
-// chain's frame step, is here.
+// The recurrences themselves - what is minimised or summed - stay in their own files; the two that two files run, the first-order
+// chain's frame step and its sum-product twin, are here.
 #pragma once
 #include "zedo_internal.h"
 
@@ -183,6 +183,87 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double *sred, int tid
 #define ZEDO_CHAIN_STEP_VALUE(K_)                                                                                                      \
                     const double u0 = finite64(uc[K_]) ? uc[K_] : inf;                                                                 \
                     const double d = chain ? u0 + dn[K_] : (is_dead ? inf : u0);
+
+// ---- the live streams of the first-order chain (zedo_joint_stream.hip, zedo_joint_stream_marginal.hip) ----
+// The frame count as the kernels take it: a state that was never reset may hold anything, and a row t % R is an address
+__device__ __forceinline__ long long clip_frames(long long t) { return t < 0 ? 0 : (t > (1ll << 62) ? (1ll << 62) : t); }
+// What a push emits for stream s, from the clip's frame count before it: frames e0 .. e0 + cnt - 1; t1: the clip's frames after it
+struct StreamEmit { long long t1, e0, cnt; };
+__device__ __forceinline__ StreamEmit stream_emit(long long t0, int F, int lag, bool flush) {
+    t0 = clip_frames(t0);
+    const long long t1 = t0 + F, e0 = t0 > lag ? t0 - lag : 0, e1 = flush ? t1 : (t1 > lag ? t1 - lag : 0);
+    return {t1, e0, e1 - e0};
+}
+// The kernels of zedo_joint_stream.hip that do not know what a stream's tables hold - the frame count [S], the dead flags [SJ,R] - and
+// serve both streaming calls: reset (t = 0 where which is null or set), the dead flags of a chunk into the ring, and the advance
+// (d_emit and the frame count, 0 after a flush).
+__global__ __launch_bounds__(256) void joint_stream_reset_kernel(const int *__restrict__ which, int S, long long *__restrict__ t);
+__global__ __launch_bounds__(256) void joint_stream_dead_kernel(const double *__restrict__ junary, const long long *__restrict__ t, int S, int F, int H, int J,
+                                         int R, int *__restrict__ dead);
+__global__ __launch_bounds__(256) void joint_stream_advance_kernel(const int *__restrict__ flush, int S, int F, int lag, long long *__restrict__ t,
+                                            long long *__restrict__ emit);
+
+// ---- the first-order chain's sum-product step (zedo_joint_marginal.hip on a whole clip, zedo_joint_stream_marginal.hip on a chunk of
+// it and on the lag window): a Viterbi step with (min, +) replaced by (log-sum-exp, +) ----
+// One lane's share of LSE_h' (sV[h'] - c |xc[k] - sX[h']|) over h' = q0 .. q1-1, for each of its K hypotheses: mx = the largest term
+// (-inf if the share has none above -inf), sm = sum exp(term - mx) ascending in h' (shifted by 0 where mx is -inf: every exp is 0).
+template <int K>
+__device__ __forceinline__ void jm_walk(const double *sX, const double *sV, int q0, int q1, const double (&xc)[K][3], double c,
+                                        double (&mx)[K], double (&sm)[K]) {
+    const double ninf = -__builtin_huge_val();
+#pragma unroll
+    for (int k = 0; k < K; ++k) mx[k] = ninf;
+#pragma unroll 4
+    for (int hp = q0; hp < q1; ++hp) {
+        const double p0 = sX[hp * 3], p1 = sX[hp * 3 + 1], p2 = sX[hp * 3 + 2], pv = sV[hp];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const double d0 = xc[k][0] - p0, d1 = xc[k][1] - p1, d2 = xc[k][2] - p2;
+            const double t = pv - c * sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+            if (t > mx[k]) mx[k] = t;
+        }
+    }
+    double sh[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) { sh[k] = mx[k] > ninf ? mx[k] : 0.0; sm[k] = 0.0; }
+#pragma unroll 2
+    for (int hp = q0; hp < q1; ++hp) {
+        const double p0 = sX[hp * 3], p1 = sX[hp * 3 + 1], p2 = sX[hp * 3 + 2], pv = sV[hp];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const double d0 = xc[k][0] - p0, d1 = xc[k][1] - p1, d2 = xc[k][2] - p2;
+            const double t = pv - c * sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+            sm[k] += exp(t - sh[k]);
+        }
+    }
+}
+
+// Part 0's end of a log-sum-exp: (mx, sm) of its own share and, with P > 1, those of the other parts from the LDS, in ascending part order.
+template <int P>
+__device__ __forceinline__ double jm_combine(double mx, double sm, const double *sPm, const double *sPs, int slots, int slot, int np) {
+    const double ninf = -__builtin_huge_val();
+    if (P > 1) {
+        double M = mx;
+        for (int p = 1; p < np; ++p) {
+            const double v = sPm[p * slots + slot];
+            if (v > M) M = v;
+        }
+        double S = mx == M ? sm : (mx > ninf ? sm * exp(mx - M) : 0.0);
+        for (int p = 1; p < np; ++p) {
+            const double v = sPm[p * slots + slot], q = sPs[p * slots + slot];
+            S += v == M ? q : (v > ninf ? q * exp(v - M) : 0.0);
+        }
+        mx = M;
+        sm = S;
+    }
+    return mx + log(sm);
+}
+// l = l[n,j,h] and v = A[n,j,h] of the owner of h = slot + K_ SLOTS, after barrier B: l = -u / tau (-inf where the unary is not finite);
+// v = l + the log-sum-exp inside a chain, l at a chain's start, -inf where (n, j) is dead.  Declares l and v.  In scope: P, SLOTS, slot
+// and ln of ChainLanes<P, K>; uc [K], mx [K], sm [K]; tau, ninf; chain and is_dead, workgroup-uniform; sPm, sPs [CHAIN_T] of the LDS.
+#define ZEDO_CHAIN_FORWARD_VALUE(K_)                                                                                                   \
+                    const double l = finite64(uc[K_]) ? -uc[K_] / tau : ninf;                                                          \
+                    const double v = is_dead ? ninf : (chain ? l + jm_combine<P>(mx[K_], sm[K_], sPm, sPs, SLOTS, slot, ln.np) : l);
 
 // ---- what a fusion kernel along a video reads off the marginals of one (frame, joint) (zedo_joint_marginal.hip, zedo_joint_accel_marginal.hip) ----
 // The tail of a backward kernel's frame, as statements in the kernel's own scope: a function of the same text changes the register

@@ -254,6 +254,14 @@ hipError_t launch_joint_stream_reset(void *state, int S, int H, int J, int lag, 
 hipError_t launch_joint_stream_push(const double *junary, const float *x, const float *T, int S, int F, int H, int J, int lag,
                                     int max_frames, double lambda, const int *flush, void *state, int *path, double *cost,
                                     long long *emit, hipStream_t st);
+// the fusion of the same chain model on live streams (zedo_joint_stream_marginal.hip); state: joint_stream_marginal_bytes(S, H, J, lag,
+// max_frames), H <= 1024, F <= max_frames; c = lambda / tau
+size_t joint_stream_marginal_bytes(int S, int H, int J, int lag, int max_frames);
+hipError_t launch_joint_stream_marginal_reset(void *state, int S, int H, int J, int lag, int max_frames, const int *which, hipStream_t st);
+hipError_t launch_joint_stream_marginal_push(const double *junary, const float *x, const float *T, int S, int F, int H, int J, int lag,
+                                             int max_frames, double c, double tau, const int *flush, void *state, double *mean,
+                                             double *cov, int *hmax, double *wmax, double *logz, double *w, long long *emit,
+                                             hipStream_t st);
 // posterior marginals of the same chain model (zedo_joint_marginal.hip); ws: joint_marginal_bytes(N, H, J), H <= 1024; c = lambda / tau
 size_t joint_marginal_bytes(int N, int H, int J);
 hipError_t launch_joint_marginal(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N, int J,

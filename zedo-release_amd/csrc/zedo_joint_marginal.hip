@@ -17,60 +17,6 @@
 
 namespace zedo {
 
-// One lane's share of LSE_h' (sV[h'] - c |xc[k] - sX[h']|) over h' = q0 .. q1-1, for each of its K hypotheses: mx = the largest term
-// (-inf if the share has none above -inf), sm = sum exp(term - mx) ascending in h' (shifted by 0 where mx is -inf: every exp is 0).
-template <int K>
-__device__ __forceinline__ void jm_walk(const double *sX, const double *sV, int q0, int q1, const double (&xc)[K][3], double c,
-                                        double (&mx)[K], double (&sm)[K]) {
-    const double ninf = -__builtin_huge_val();
-#pragma unroll
-    for (int k = 0; k < K; ++k) mx[k] = ninf;
-#pragma unroll 4
-    for (int hp = q0; hp < q1; ++hp) {
-        const double p0 = sX[hp * 3], p1 = sX[hp * 3 + 1], p2 = sX[hp * 3 + 2], pv = sV[hp];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const double d0 = xc[k][0] - p0, d1 = xc[k][1] - p1, d2 = xc[k][2] - p2;
-            const double t = pv - c * sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-            if (t > mx[k]) mx[k] = t;
-        }
-    }
-    double sh[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) { sh[k] = mx[k] > ninf ? mx[k] : 0.0; sm[k] = 0.0; }
-#pragma unroll 2
-    for (int hp = q0; hp < q1; ++hp) {
-        const double p0 = sX[hp * 3], p1 = sX[hp * 3 + 1], p2 = sX[hp * 3 + 2], pv = sV[hp];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const double d0 = xc[k][0] - p0, d1 = xc[k][1] - p1, d2 = xc[k][2] - p2;
-            const double t = pv - c * sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-            sm[k] += exp(t - sh[k]);
-        }
-    }
-}
-
-// Part 0's end of a log-sum-exp: (mx, sm) of its own share and, with P > 1, those of the other parts from the LDS, in ascending part order.
-template <int P>
-__device__ __forceinline__ double jm_combine(double mx, double sm, const double *sPm, const double *sPs, int slots, int slot, int np) {
-    const double ninf = -__builtin_huge_val();
-    if (P > 1) {
-        double M = mx;
-        for (int p = 1; p < np; ++p) {
-            const double v = sPm[p * slots + slot];
-            if (v > M) M = v;
-        }
-        double S = mx == M ? sm : (mx > ninf ? sm * exp(mx - M) : 0.0);
-        for (int p = 1; p < np; ++p) {
-            const double v = sPm[p * slots + slot], q = sPs[p * slots + slot];
-            S += v == M ? q : (v > ninf ? q * exp(v - M) : 0.0);
-        }
-        mx = M;
-        sm = S;
-    }
-    return mx + log(sm);
-}
-
 // The forward recurrence of one (clip, joint) on ChainLanes<P, K>: the lane (part, slot) owns h = slot + k SLOTS of frame n and walks its
 // part of the h' of frame n-1, which sits in the LDS.  (A lane past H reads hypothesis H-1 and stores nothing.)
 //   l[n,j,h] = -u[n,j,h] / tau, -inf where the unary is not finite
@@ -127,8 +73,7 @@ __global__ __launch_bounds__(CHAIN_T) void joint_marginal_forward_kernel(const d
             for (int k = 0; k < K; ++k) {
                 const int h = slot + k * SLOTS;
                 if (h < H) {
-                    const double l = finite64(uc[k]) ? -uc[k] / tau : ninf;
-                    const double v = is_dead ? ninf : (chain ? l + jm_combine<P>(mx[k], sm[k], sPm, sPs, SLOTS, slot, ln.np) : l);
+                    ZEDO_CHAIN_FORWARD_VALUE(k)
                     A[nj * H + h] = v;
                     sV[h] = v;
                     sX[h * 3] = xc[k][0]; sX[h * 3 + 1] = xc[k][1]; sX[h * 3 + 2] = xc[k][2];

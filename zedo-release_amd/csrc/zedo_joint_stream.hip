@@ -33,9 +33,8 @@ size_t joint_stream_bytes(int S, int H, int J, int lag, int max_frames) {
     return JointStreamState(nullptr, S, H, J, (size_t)lag + max_frames).bytes;
 }
 
-// The frame count as the kernels take it: a state that was never reset may hold anything, and a row t % R is an address
-__device__ __forceinline__ long long clip_frames(long long t) { return t < 0 ? 0 : (t > (1ll << 62) ? (1ll << 62) : t); }
-
+// (clip_frames, stream_emit: zedo_chain.h - the fusion on live streams, zedo_joint_stream_marginal.hip, takes them and the reset, dead
+// and advance kernels below as they are)
 __global__ __launch_bounds__(256) void joint_stream_reset_kernel(const int *__restrict__ which, int S, long long *__restrict__ t) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s < S && (!which || which[s] != 0)) t[s] = 0;
@@ -134,14 +133,6 @@ __global__ __launch_bounds__(CHAIN_T) void joint_stream_scan_kernel(const double
         prev_dead = is_dead ? 1 : 0;
         row = row + 1 == R ? 0 : row + 1;
     }
-}
-
-// What a push emits for stream s, from the clip's frame count before it: frames e0 .. e0 + cnt - 1; t1: the clip's frames after it
-struct StreamEmit { long long t1, e0, cnt; };
-__device__ __forceinline__ StreamEmit stream_emit(long long t0, int F, int lag, bool flush) {
-    t0 = clip_frames(t0);
-    const long long t1 = t0 + F, e0 = t0 > lag ? t0 - lag : 0, e1 = flush ? t1 : (t1 > lag ? t1 - lag : 0);
-    return {t1, e0, e1 - e0};
 }
 
 // One wave per (stream, output row r, joint): frame n = e0 + r of the clip, if the push emits it.  The horizon e = min(n + lag, the last

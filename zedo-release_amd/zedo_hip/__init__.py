@@ -81,6 +81,10 @@ SIGNATURES = {
     "zedo_joint_accel_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp]),
     "zedo_joint_accel_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_accel_marginal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "zedo_joint_stream_marginal_state_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "zedo_joint_stream_marginal_reset": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _vp]),
+    "zedo_joint_stream_marginal_push": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _vp]),
     "zedo_joint_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_marginal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_joint_tree_select": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp, _vp]),
@@ -667,14 +671,16 @@ class JointStream:
     joint_temporal_select (untuned); the choice of lag is untuned as well, and whether a fixed-lag path is closer to ground truth than
     the per-frame choice is not measured."""
 
+    _WHAT, _CALL = "JointStream", "zedo_joint_stream"              # the entry points: _CALL + "_state_bytes", "_reset", "_push"
+
     def __init__(self, S, H, J, lag, max_frames, lam=100.0, device=None):
         _need_gpu()
         self.S, self.H, self.J, self.lag, self.max_frames, self.lam = int(S), int(H), int(J), int(lag), int(max_frames), float(lam)
         self.device = _norm_device(device)
-        self.state_bytes = joint_stream_state_bytes(S, H, J, lag, max_frames)
+        self.state_bytes = int(getattr(_lib, self._CALL + "_state_bytes")(int(S), int(H), int(J), int(lag), int(max_frames)))
         if self.state_bytes == 0:
-            raise ZedoError(f"JointStream: S = {S}, H = {H}, J = {J}, lag = {lag}, max_frames = {max_frames} is outside the range of "
-                            "zedo_joint_stream_push (1 <= H <= 1024, lag >= 0, sizes >= 1, (lag + max_frames) S J H <= INT_MAX)")
+            raise ZedoError(f"{self._WHAT}: S = {S}, H = {H}, J = {J}, lag = {lag}, max_frames = {max_frames} is outside the range of "
+                            f"{self._CALL}_push (1 <= H <= 1024, lag >= 0, sizes >= 1, (lag + max_frames) S J H <= INT_MAX)")
         with torch.cuda.device(self.device):
             self.state = torch.empty((self.state_bytes,), dtype=torch.uint8, device=self.device)
         self.reset()
@@ -688,15 +694,31 @@ class JointStream:
         else:
             w = torch.tensor([1 if v else 0 for v in which], dtype=torch.int32, device=self.device)
         if tuple(w.shape) != (self.S,):
-            raise ValueError(f"JointStream: one flag per stream ([{self.S}]) expected, got {tuple(w.shape)}")
+            raise ValueError(f"{self._WHAT}: one flag per stream ([{self.S}]) expected, got {tuple(w.shape)}")
         return w
 
     def reset(self, which=None):
         """Empties the streams with which[s] != 0 (None: all); their pending frames are dropped."""
         w = self._flags(which)
         with torch.cuda.device(self.device):
-            _check(_lib.zedo_joint_stream_reset(_p(self.state, torch.uint8), self.state_bytes, self.S, self.H, self.J, self.lag,
-                                                self.max_frames, _p(w, torch.int32), _stream(self.device)))
+            _check(getattr(_lib, self._CALL + "_reset")(_p(self.state, torch.uint8), self.state_bytes, self.S, self.H, self.J, self.lag,
+                                                        self.max_frames, _p(w, torch.int32), _stream(self.device)))
+
+    def _chunk(self, junary, x, T, flush):
+        """-> (the flush flags on the device or None, F, the device) of a push; ValueError for shapes that are not a chunk."""
+        fl = self._flags(flush)
+        S, H, J = self.S, self.H, self.J
+        if junary is None:
+            if x is not None or T is not None or fl is None:
+                raise ValueError(f"{self._WHAT}.push: a push of no frames takes flush and nothing else")
+            return fl, 0, self.device
+        rows = x.shape[0]
+        F = rows // (H * S)
+        if (rows != H * S * F or F < 1 or tuple(x.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J)
+                or (T is not None and tuple(T.shape) != (rows, 3))):
+            raise ValueError(f"{self._WHAT}.push: junary [H*S*F,J], x [H*S*F,J,3], T [H*S*F,3] with H = {H}, S = {S}, J = {J} expected, "
+                             f"got {tuple(junary.shape)}, {tuple(x.shape)}, {None if T is None else tuple(T.shape)}")
+        return fl, F, _device_of(junary, x, T, self.state)
 
     def push(self, junary, x, T=None, flush=None):
         """junary [H*S*F,J] f64, x [H*S*F,J,3] f32, T [H*S*F,3] f32 or None: F <= max_frames new frames of every stream, rows (h, n)
@@ -705,33 +727,68 @@ class JointStream:
         [S,F+lag,J] f64): stream s emits the frames first[s] .. first[s] + count[s] - 1 of its clip in the rows 0 .. count[s] - 1 of
         path[s] and cost[s]; the rows after them are not written.  count[s] = held if flushed, else max(0, held - lag), with held =
         min(lag, frames the clip held before) + F.  junary = None: a push of no frames (flush required)."""
-        fl = self._flags(flush)
+        fl, F, dev = self._chunk(junary, x, T, flush)
         S, H, J = self.S, self.H, self.J
-        if junary is None:
-            F = 0
-            if x is not None or T is not None or fl is None:
-                raise ValueError("JointStream.push: a push of no frames takes flush and nothing else")
-            dev = self.device
-        else:
-            dev = _device_of(junary, x, T, self.state)
-            rows = x.shape[0]
-            F = rows // (H * S)
-            if (rows != H * S * F or F < 1 or tuple(x.shape) != (rows, J, 3) or tuple(junary.shape) != (rows, J)
-                    or (T is not None and tuple(T.shape) != (rows, 3))):
-                raise ValueError(f"JointStream.push: junary [H*S*F,J], x [H*S*F,J,3], T [H*S*F,3] with H = {H}, S = {S}, J = {J} expected, "
-                                 f"got {tuple(junary.shape)}, {tuple(x.shape)}, {None if T is None else tuple(T.shape)}")
         with torch.cuda.device(dev):
-            path = torch.empty((S, F + self.lag, J), dtype=torch.int32, device=dev)
-            cost = torch.empty((S, F + self.lag, J), dtype=torch.float64, device=dev)
+            rows = F + self.lag                                      # lag = 0 and no frames: a row nobody writes keeps the pointers non-NULL
+            path = torch.empty((S, max(rows, 1), J), dtype=torch.int32, device=dev)
+            cost = torch.empty((S, max(rows, 1), J), dtype=torch.float64, device=dev)
             emit = torch.empty((S, 2), dtype=torch.int64, device=dev)
             _check(_lib.zedo_joint_stream_push(_p(junary, torch.float64), _p(x), _p(T), S, F, H, J, self.lag, self.max_frames, self.lam,
                                                _p(fl, torch.int32), _p(self.state, torch.uint8), self.state_bytes, _p(path, torch.int32),
                                                _p(cost, torch.float64), _p(emit, torch.int64), _stream(dev)))
-        return emit[:, 0], emit[:, 1], path, cost
+        return emit[:, 0], emit[:, 1], path[:, :rows], cost[:, :rows]
 
     def flush(self, which=None):
         """Ends the clips of the streams with which[s] != 0 (None: all) and emits their pending frames: a push of no frames."""
         return self.push(None, None, None, [1] * self.S if which is None else which)
+
+
+def joint_stream_marginal_state_bytes(S, H, J, lag, max_frames):
+    """The bytes of state zedo_joint_stream_marginal_push needs for S streams of H hypotheses and J joints at this lag and at most
+    max_frames frames per push (host arithmetic: no GPU needed); 0 for a shape the calls refuse."""
+    return int(_lib.zedo_joint_stream_marginal_state_bytes(int(S), int(H), int(J), int(lag), int(max_frames)))
+
+
+class JointMarginalStream(JointStream):
+    """Joint-wise fusion on a live video (zedo_joint_stream_marginal_push): the chain model of joint_marginal for S independent streams,
+    fed in chunks of at most max_frames frames, every frame's marginals formed `lag` frames after it went in - the outputs of
+    joint_marginal on the stream's clip (the frames since its last reset or flush) cut after frame n + lag: fixed-lag smoothing.  lag = 0
+    gives the filtering marginals; with lag >= the clip's length - 1 and a flush at the end the outputs are joint_marginal's bits.  Owns
+    the state on `device` and resets it on creation.  lam and tau as in joint_marginal, the same in every push; lam = 100 and tau = 1
+    are untuned, the choice of lag is untuned as well, and whether the fused pose is closer to ground truth than a selected one is not
+    measured.  A steady-state push costs F backward walks of lag frames per (stream, joint)."""
+    _WHAT, _CALL = "JointMarginalStream", "zedo_joint_stream_marginal"
+
+    def __init__(self, S, H, J, lag, max_frames, lam=100.0, tau=1.0, device=None):
+        self.tau = float(tau)
+        super().__init__(S, H, J, lag, max_frames, lam, device)
+
+    def push(self, junary, x, T=None, flush=None, return_weights=False):
+        """The chunk and flush of JointStream.push -> (first [S] i64, count [S] i64, mean [S,F+lag,J,3] f64, cov [S,F+lag,J,6] f64, hmax
+        [S,F+lag,J] i32, wmax [S,F+lag,J] f64, logz [S,F+lag,J] f64[, w [S,F+lag,J,H] f64]): stream s emits the frames first[s] ..
+        first[s] + count[s] - 1 of its clip in the rows 0 .. count[s] - 1; the rows after them are not written.  The outputs of a row
+        are joint_marginal's: posterior mean position in the camera frame, covariance (xx, xy, xz, yy, yz, zz; m^2), the most probable
+        hypothesis, its probability, log Z of the chain cut at the frame's horizon; a dead (frame, joint) reports NaN, 0, 0 and -inf.
+        junary = None: a push of no frames (flush required)."""
+        fl, F, dev = self._chunk(junary, x, T, flush)
+        S, H, J = self.S, self.H, self.J
+        with torch.cuda.device(dev):
+            rows = F + self.lag                                      # lag = 0 and no frames: a row nobody writes keeps the pointers non-NULL
+            mean, cov, hmax, wmax, logz, w = (None if t is None else t.view(S, max(rows, 1), *t.shape[1:])
+                                              for t in _marginal_outputs(S * max(rows, 1), J, H, dev, return_weights))
+            emit = torch.empty((S, 2), dtype=torch.int64, device=dev)
+            _check(_lib.zedo_joint_stream_marginal_push(_p(junary, torch.float64), _p(x), _p(T), S, F, H, J, self.lag, self.max_frames,
+                                                        self.lam, self.tau, _p(fl, torch.int32), _p(self.state, torch.uint8),
+                                                        self.state_bytes, _p(mean, torch.float64), _p(cov, torch.float64),
+                                                        _p(hmax, torch.int32), _p(wmax, torch.float64), _p(logz, torch.float64),
+                                                        _p(w, torch.float64), _p(emit, torch.int64), _stream(dev)))
+        out = (emit[:, 0], emit[:, 1]) + tuple(t[:, :rows] for t in (mean, cov, hmax, wmax, logz))
+        return out + (w[:, :rows],) if return_weights else out
+
+    def flush(self, which=None, return_weights=False):
+        """Ends the clips of the streams with which[s] != 0 (None: all) and emits their pending frames: a push of no frames."""
+        return self.push(None, None, None, [1] * self.S if which is None else which, return_weights)
 
 
 def joint_accel_select(junary, x_full, T_full, seq_start, N=None, lam=100.0, accel=100.0):

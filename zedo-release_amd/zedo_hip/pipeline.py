@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import (H36M_EDGES, SINGULAR_MSG, JointStream, Schedule, Weights, ZedoError, ipo_fit, joint_accel_marginal, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
+from . import (H36M_EDGES, SINGULAR_MSG, JointMarginalStream, JointStream, Schedule, Weights, ZedoError, ipo_fit, joint_accel_marginal, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
                joint_temporal_select, joint_tree_marginal, joint_tree_select, skeleton_parents, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
@@ -311,6 +311,29 @@ class Pipeline:
         with torch.cuda.device(self.device):
             _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
             out = joint_marginal(jerr, x, T, seq_start, self.N, lam, tau)
+        return out + (jerr,)
+
+    def open_joint_fuse_stream(self, S, lag, max_frames, lam=100.0, tau=1.0):
+        """The state of fuse_joints_temporal's chain model for S live streams (JointMarginalStream): H and the joint count are those of
+        the pipeline, every frame's marginals are formed `lag` frames after it went in, a push holds at most max_frames frames per
+        stream.  lam, tau and the choice of lag are untuned."""
+        if getattr(self, "uv", None) is None:
+            raise ZedoError("open_joint_fuse_stream: call load() first (the joint count is the problem's)")
+        return JointMarginalStream(S, self.H, self.uv.shape[1], lag, max_frames, lam, tau, self.device)
+
+    def push_fuse_joints_temporal(self, js, x, T, flush=None):
+        """fuse_joints_temporal on live input, on the problem of load() with N = S F poses - F new frames of each of the S streams of
+        js = open_joint_fuse_stream(...), pose n = s F + f: x [H*N,17,3] and T [H*N,3], ALL rows; flush: None, or [S] flags - the streams
+        whose clip ends here.  -> (first [S] i64, count [S] i64, mean [S,F+lag,17,3] f64, cov [S,F+lag,17,6] f64, hmax [S,F+lag,17] i32,
+        wmax [S,F+lag,17] f64, logz [S,F+lag,17] f64, jerr [H*N,17] f64): the unaries are zedo_joint_reproj's per-(row, joint) distances
+        exactly as push_joints_temporal forms them; stream s emits the frames first[s] .. first[s] + count[s] - 1 of its clip, each as
+        fuse_joints_temporal reports it on the clip cut `lag` frames later (zedo_joint_stream_marginal_push)."""
+        if x.shape[0] != self.H * self.N or self.N % js.S:
+            raise ValueError(f"push_fuse_joints_temporal: all {self.H * self.N} rows of a whole number of frames of {js.S} streams "
+                             f"expected, got {x.shape[0]} rows for {self.N} poses")
+        with torch.cuda.device(self.device):
+            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
+            out = js.push(jerr, x, T, flush)
         return out + (jerr,)
 
     def fuse_joints_accel(self, x, T, seq_start, lam=100.0, accel=100.0, tau=1.0):
