@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: forty one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: forty-three one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -93,6 +93,11 @@ MUTANTS = [
     ("ZEDO_MUT_PAIR_SEAM", "exact-fp32 pair kernels: the first remainder tile behind the 128x128 tiles takes its bias from the next column block (zedo_gemm.hip layer_pair_kernel)"),
     ("ZEDO_MUT_F16_PAIR_SEAM", "f16x3 pair kernels: the first 64x64 tile behind the big tiles takes its bias from the next column block (zedo_gemm16.hip layer16_pair_kernel)"),
     ("ZEDO_MUT_POST64_POSE", "post_dense on 64x64 tiles (above 8 192 rows): the fused reprojection tail of the third tile takes the pose of row b + 1 (zedo_gemm.hip layer_tile)"),
+    # the time-bias table of a schedule (tests/test_schedule_gpu.py; profiles/mutation_schedule.txt): the first is reached only by schedules
+    # of more than 1 024 timestamps and leaves every test green that existed before; the second stays inside that file's float64 criterion
+    # (0.68 of it at label 2000) and is caught by tests/test_pc_native_gpu.py::test_chained_steps_against_the_float64_reference
+    ("ZEDO_MUT_BIAS_TILE", "schedule tables above 1 024 rows: in the three cost-model shapes of launch_small ONE EPI_BIAS tile, the second row tile of the second column block, takes its bias from the next column block (zedo_gemm.hip layer_tile)"),
+    ("ZEDO_MUT_POSEMB_FAST", "posemb_kernel: __sinf / __cosf, the hardware fast forms without range reduction, in place of sinf / cosf (zedo_geom.hip)"),
     ("ZEDO_MUT_TREEMARG_NO_DOWN", "zedo_joint_tree_marginal: Dn = 0 on every joint - the downward pass is dropped, a joint hears from its subtree only (zedo_joint_tree_marginal.hip joint_tree_marginal_kernel)"),
 ]
 

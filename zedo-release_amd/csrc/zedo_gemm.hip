@@ -194,6 +194,11 @@ __device__ __forceinline__ void layer_tile(const LayerArgs &a, const int m0, con
     // epilogue parameters -> LDS once (LDS reads are free next to MFMAs, VMEM loads are not)
     if (EPI != EPI_PARTIAL && tid < BN / 4) {
         *reinterpret_cast<f32x4 *>(Ps + tid * 4) = *reinterpret_cast<const f32x4 *>(a.bias + n0 + tid * 4);
+#ifdef ZEDO_MUT_BIAS_TILE   // tools/mutation_check.py only: in the three cost-model shapes of launch_small (x128 tiles on a 2-deep ring) ONE
+        // EPI_BIAS tile, the second row tile of the second column block, takes its bias from the next column block
+        if (EPI == EPI_BIAS && NBUF == 2 && BK == 32 && BN == 128 && m0 == BM && n0 == BN && a.N >= 3 * BN)
+            *reinterpret_cast<f32x4 *>(Ps + tid * 4) = *reinterpret_cast<const f32x4 *>(a.bias + n0 + BN + tid * 4);
+#endif
         if constexpr (EPI == EPI_GN_SILU || EPI == EPI_GN_SILU_RES) {
             *reinterpret_cast<f32x4 *>(Ps + BN + tid * 4) = *reinterpret_cast<const f32x4 *>(a.gamma + n0 + tid * 4);
             *reinterpret_cast<f32x4 *>(Ps + 2 * BN + tid * 4) = *reinterpret_cast<const f32x4 *>(a.beta + n0 + tid * 4);

@@ -283,6 +283,9 @@ __global__ void posemb_kernel(const float *__restrict__ t, int S, int Sp, float 
         const float freq = expf((float)k * emb);
         const float arg = (t[s] * label_scale) * freq;
         o = c < half ? sinf(arg) : cosf(arg);
+#ifdef ZEDO_MUT_POSEMB_FAST   // tools/mutation_check.py only: the hardware fast forms, no range reduction
+        o = c < half ? __sinf(arg) : __cosf(arg);
+#endif
     }
     pe[i] = o;
 }
