@@ -246,6 +246,9 @@ int zedo_ipo_fit(const float *d_x0, const float *d_uv, const float *d_K, const i
  * i.e. torch.optim.Adam's per-parameter state (opt_main.py:183).  it_begin = iterations already applied to
  * d_state; with it_begin == 0 the input content is ignored and the fit starts from RotOpt's initial values
  * (simple_zeroshot_opt.py:11-16).  Runs iterations [it_begin, it_begin + iters) and writes the state back.
+ * A fit split into resumed calls returns the bits of the unsplit fit, in R, T, q, scale and all 15 state columns, in either
+ * kernel and across iteration 2048, where Adam's bias corrections leave their constant table (tests/test_ipo_state_gpu.py).
+ * Rows of d_state behind row B - 1 are not touched; iters == 0 with it_begin > 0 returns R, T of the state as it is.
  */
 int zedo_ipo_fit_resume(const float *d_x0, const float *d_uv, const float *d_K, const int *h_keylist, int k,
                         int axes_mask, float ipo_T, float min_scale, float max_scale, int iters, double normaliser,

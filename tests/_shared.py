@@ -5,6 +5,7 @@ Imported by the tests, by the child scripts they embed and by tools/ the way tes
 
 Nothing of lib.*, run.*, zedo_hip or zedo_oracle is imported at module level: tools/gen_golden.py runs with the reference's `lib`
 first on sys.path, the tests with the mirror's, and each function binds the one its caller has."""
+import functools
 import hashlib
 import json
 import os
@@ -159,6 +160,89 @@ def pack(q, sc, mq, vq, ms, vs):
 
 def unpack(st):
     return st[:, 0:4], st[:, 4], st[:, 5:9], st[:, 10:14], st[:, 9], st[:, 14]
+
+
+# The oracle as the source of optimiser states for zedo_ipo_fit_resume (tests/test_general_intrinsics_gpu.py, tests/test_ipo_state_gpu.py,
+# tests/test_ipo_state_ref.py, the single-iteration tests of tests/test_hip_parity.py and tests/test_joint_counts_gpu.py)
+
+def initial_state(N):
+    z4, z1 = np.zeros((N, 4)), np.zeros(N)
+    q0 = z4.copy()
+    q0[:, 0] = 1
+    return pack(q0, np.ones(N), z4, z4, z1, z1)
+
+
+def state_of(t):
+    """A trace entry of O.ipo_fit -> the packed state."""
+    return pack(t[0], t[1], t[3], t[4], t[5], t[6])
+
+
+def oracle_args(J, kl, N, general=True):
+    import zedo_oracle as O
+    cl, uvn, Kn = problem(J, N, 1, general)
+    c64, K64 = uvn.astype(np.float64), Kn.astype(np.float64)
+    x64 = np.broadcast_to(cl[0][None], (N, J, 3)).astype(np.float64)
+    return x64[:, kl], O.ipo_init_T(c64, K64, IPO_T, dtype=np.float64), K64, c64[:, kl]
+
+
+def oracle_resume(args, axes, norm, state, it0, iters=1, dtype=np.float64, minT=IPO_MIN, maxT=IPO_MAX):
+    """``iters`` oracle iterations in ``dtype`` from the packed ``state`` declared to be the one after it0 iterations (state and
+    problem are rounded to dtype first: with float32, what the kernel is handed) -> (the packed state after them in float64,
+    R, T [B,3], |residual| [iters,B,k,2] of the forwards that produced the gradients)."""
+    import zedo_oracle as O
+    tr = []
+    a = [np.asarray(x, dtype) for x in args]
+    R, T = O.ipo_fit(*a, axes, minT, maxT, iters, normaliser=norm, dtype=dtype, trace=tr, init=unpack(np.asarray(state).astype(dtype)), it0=it0)[:2]
+    end = state_of(tr[-1]) if tr else np.asarray(state).astype(dtype)
+    return end.astype(np.float64), R, T.reshape(-1, 3), np.stack([t[7] for t in tr]) if tr else np.zeros((0,) + a[3].shape)
+
+
+class MomentRule:
+    """The project's rule for a block of Adam moments after one call from a float64 state handed over in fp32:
+        |x - x64| <= 2 max |x32 - x64| + ulp32(max |x64|)
+    x32 being the fp32 ORACLE's result from the same fp32 state, all three maxima over the clear pose-iterations added.  The factor 2
+    is the margin between two fp32 evaluations of one formula (the kernels sum the key joints in a pairing tree, the oracle in einsum
+    order); nothing in it is fitted to a kernel."""
+
+    def __init__(self):
+        self.delta, self.delta32, self.largest = 0.0, 0.0, 0.0
+
+    def add(self, got, o32, want):
+        if want.size:
+            self.delta = max(self.delta, float(np.abs(got - want).max()))
+            self.delta32 = max(self.delta32, float(np.abs(o32 - want).max()))
+            self.largest = max(self.largest, float(np.abs(want).max()))
+
+    @property
+    def bound(self):
+        return 2.0 * self.delta32 + float(ulp32(np.float64(self.largest)))
+
+    @property
+    def ratio(self):
+        return self.delta / self.bound if self.bound > 0 else float(self.delta > 0)
+
+    def holds(self):
+        return self.delta <= self.bound
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_run(J, kl, N, axes, general=True, iters=50):
+    """The float64 oracle's first ``iters`` iterations: states[i] = packed state after i iterations (float64), clear[i] = the poses
+    whose residuals in iteration i + 1 are all >= 1e-3 px (a key joint at the root contributes no gradient and is not counted), and
+    m32[i] [N,10] = both moment rows (state[:, 5:15]) after ONE fp32 oracle iteration from states[i] rounded to fp32 - what the
+    kernel is handed."""
+    import zedo_oracle as O
+    kl = list(kl)
+    cl = problem(J, N, 1, general)[0]
+    args = oracle_args(J, kl, N, general)
+    norm = N * len(kl) * 2
+    tr = []
+    O.ipo_fit(*args, axes, IPO_MIN, IPO_MAX, iters, normaliser=norm, dtype=np.float64, trace=tr)
+    states = [initial_state(N)] + [state_of(t) for t in tr]
+    moving = np.abs(cl[0][kl]).max(-1) > 0
+    clear = [t[7][:, moving, :].reshape(N, -1).min(1) >= 1e-3 for t in tr]
+    m32 = [oracle_resume(args, axes, norm, states[it], it, 1, np.float32)[0][:, 5:15] for it in range(iters)]
+    return states, clear, m32
 
 
 # The periodic batch of tests/test_launch_shapes_gpu.py and tests/test_launch_shapes_ref.py

@@ -8,8 +8,7 @@ Here K has skew, a homogeneous row other than (0, 0, 1) and K22 != 1 (lib.datase
 camera_param [N,3,3] reaches these kernels unchanged), the detections are re-projected through it, and every axis subset runs.  Adam's
 bias corrections are also run across the end of the constant table (iteration 2048).  The arbiter is the numpy oracle in float64,
 which tests/test_general_intrinsics_oracle.py pins to captures of the reference on such input; the bounds are the ones the suite
-applies to pinhole input, except the bound on the first moments, which is computed from the fp32 oracle (see the test)."""
-import functools
+applies to pinhole input, except the bound on the two moment rows, which is computed from the fp32 oracle (see the test)."""
 import json
 import os
 import subprocess
@@ -19,8 +18,8 @@ import numpy as np
 import pytest
 
 import _reproj_ref as RR
-from _shared import (IPO_MAX, IPO_MIN, IPO_T, KEYS, TWIN_AXES, dev, general_cameras, pack, problem, report_env as _report, ulp32,
-                     unpack, zh)  # noqa: F401  (fixture)
+from _shared import (IPO_MAX, IPO_MIN, IPO_T, KEYS, TWIN_AXES, MomentRule, dev, general_cameras, oracle_args, oracle_resume, oracle_run,
+                     problem, report_env as _report, ulp32, zh)  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -28,50 +27,6 @@ torch = pytest.importorskip("torch")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 AXES = ["", "x", "y", "z", "xy", "xz", "yz", "xyz"]
 SLOT = {"x": 1, "y": 2, "z": 3}
-
-
-def initial_state(N):
-    z4, z1 = np.zeros((N, 4)), np.zeros(N)
-    q0 = z4.copy()
-    q0[:, 0] = 1
-    return pack(q0, np.ones(N), z4, z4, z1, z1)
-
-
-def state_of(t):
-    return pack(t[0], t[1], t[3], t[4], t[5], t[6])
-
-
-def oracle_args(J, kl, N, general=True):
-    import zedo_oracle as O
-    cl, uvn, Kn = problem(J, N, 1, general)
-    c64, K64 = uvn.astype(np.float64), Kn.astype(np.float64)
-    x64 = np.broadcast_to(cl[0][None], (N, J, 3)).astype(np.float64)
-    return x64[:, kl], O.ipo_init_T(c64, K64, IPO_T, dtype=np.float64), K64, c64[:, kl]
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_run(J, kl, N, axes, general=True, iters=50):
-    """The float64 oracle's first ``iters`` iterations: states[i] = packed state after i iterations (float64), clear[i] = the poses
-    whose residuals in iteration i + 1 are all >= 1e-3 px (a key joint at the root contributes no gradient and is not counted), and
-    m32[i] = the first moments after ONE fp32 oracle iteration from states[i] rounded to fp32 - what the kernel is handed."""
-    import zedo_oracle as O
-    kl = list(kl)
-    cl = problem(J, N, 1, general)[0]
-    args = oracle_args(J, kl, N, general)
-    norm = N * len(kl) * 2
-    tr = []
-    O.ipo_fit(*args, axes, IPO_MIN, IPO_MAX, iters, normaliser=norm, dtype=np.float64, trace=tr)
-    states = [initial_state(N)] + [state_of(t) for t in tr]
-    moving = np.abs(cl[0][kl]).max(-1) > 0
-    clear = [t[7][:, moving, :].reshape(N, -1).min(1) >= 1e-3 for t in tr]
-    a32 = [np.asarray(a, np.float32) for a in args]
-    m32 = []
-    for it in range(iters):
-        t32 = []
-        O.ipo_fit(*a32, axes, IPO_MIN, IPO_MAX, 1, normaliser=norm, dtype=np.float32, trace=t32,
-                  init=unpack(states[it].astype(np.float32)), it0=it)
-        m32.append(state_of(t32[0])[:, 5:10].astype(np.float64))
-    return states, clear, m32
 
 
 # ---- a / b. single iterations from the float64 state: parameters, first moments, absent axes ---------------------------------
@@ -95,6 +50,8 @@ def test_ipo_single_iterations_on_general_intrinsics(zh, J, kl, N, axes, general
     the kernel sums the key joints in a pairing tree, the oracle in einsum order (the project's usual margin between two fp32
     evaluations of one formula).
 
+    Second moments (state[:, 10:15] = 0.999 v_old + 0.001 g g): the same rule with v in the place of m (_shared.MomentRule).
+
     Axes absent from the mask: parameter and both moments bit for bit what went in, and the returned q an exact 0."""
     states, clear, m32 = oracle_run(J, tuple(kl), N, axes, general)
     cl, uvn, Kn = problem(J, N, 1, general)
@@ -102,7 +59,7 @@ def test_ipo_single_iterations_on_general_intrinsics(zh, J, kl, N, axes, general
     norm = N * len(kl) * 2
     absent = [SLOT[a] for a in "xyz" if a not in axes]
     present = [0] + [SLOT[a] for a in axes] + [4]
-    worst, n_amb, dm_gpu, dm_32, m_max = 0.0, 0, 0.0, 0.0, 0.0
+    worst, n_amb, rule_m, rule_v = 0.0, 0, MomentRule(), MomentRule()
     for it in range(50):
         s_in = states[it].astype(np.float32)
         st = dev(s_in)
@@ -120,17 +77,16 @@ def test_ipo_single_iterations_on_general_intrinsics(zh, J, kl, N, axes, general
             d = float(np.abs(out - states[it + 1])[c][:, :5].max())
             worst = max(worst, d)
             assert d <= 1e-6, (it, d)
-            m64 = states[it + 1][c][:, 5:10]
-            dm_gpu = max(dm_gpu, float(np.abs(out[c][:, 5:10] - m64).max()))
-            dm_32 = max(dm_32, float(np.abs(m32[it][c] - m64).max()))
-            m_max = max(m_max, float(np.abs(m64).max()))
-    bound = 2.0 * dm_32 + float(ulp32(np.float64(m_max)))
+            rule_m.add(out[c][:, 5:10], m32[it][c][:, 0:5], states[it + 1][c][:, 5:10])
+            rule_v.add(out[c][:, 10:15], m32[it][c][:, 5:10], states[it + 1][c][:, 10:15])
     _report(dict(test="general_k_ipo", J=J, k=len(kl), N=N, axes=axes, K="general" if general else "pinhole",
-                 ambiguous_pose_iterations=n_amb, max_param_delta=worst, max_moment_delta=dm_gpu, fp32_oracle_moment_delta=dm_32,
-                 moment_bound=bound, moment_ratio=dm_gpu / bound))
+                 ambiguous_pose_iterations=n_amb, max_param_delta=worst, max_moment_delta=rule_m.delta, fp32_oracle_moment_delta=rule_m.delta32,
+                 moment_bound=rule_m.bound, moment_ratio=rule_m.ratio, max_v_delta=rule_v.delta, fp32_oracle_v_delta=rule_v.delta32,
+                 v_bound=rule_v.bound, v_ratio=rule_v.ratio))
     assert n_amb <= 0.05 * 50 * N, n_amb
     assert worst > 0
-    assert dm_gpu <= bound, (dm_gpu, bound)
+    assert rule_m.holds(), (rule_m.delta, rule_m.bound)
+    assert rule_v.holds() and rule_v.largest > 0, (rule_v.delta, rule_v.bound)
     assert (np.abs(states[50][:, present]).min(0) > 0).all() and (states[50][:, absent] == 0).all()
 
 
@@ -142,9 +98,9 @@ def test_adam_bias_corrections_across_the_end_of_the_table(zh):
     ((17, [0, 1, 4]), N = 8, "xyz", general K) is DECLARED to be the state after it0 iterations: one iteration from it with
     it_begin = it0 on either side of the seam and far beyond it, and four iterations in one call from 2046 (the seam is crossed
     inside the kernel's loop), against O.ipo_fit(init=, it0=) in float64.  Bound: 1e-6 on the parameters of poses whose residuals are
-    all >= 1e-3 px (in all four iterations for the second part).  (Running thousands of iterations to get there would end in a
-    converged L1 fit that sits on its sign changes.)"""
-    import zedo_oracle as O
+    all >= 1e-3 px (in all four iterations for the second part); the second moments of the same poses by the rule of
+    test_ipo_single_iterations_on_general_intrinsics, the fp32 oracle running the same call from the same fp32 state.  (Running
+    thousands of iterations to get there would end in a converged L1 fit that sits on its sign changes.)"""
     J, kl, N, axes = 17, [0, 1, 4], 8, "xyz"
     states = oracle_run(J, tuple(kl), N, axes)[0]
     cl, uvn, Kn = problem(J, N)
@@ -155,30 +111,40 @@ def test_adam_bias_corrections_across_the_end_of_the_table(zh):
     s20 = states[20]
 
     def run(it0, iters):
-        tr = []
-        O.ipo_fit(*args, axes, IPO_MIN, IPO_MAX, iters, normaliser=norm, dtype=np.float64, trace=tr, init=unpack(s20), it0=it0)
-        clear = np.all([t[7][:, moving, :].reshape(N, -1).min(1) >= 1e-3 for t in tr], axis=0)
+        want, _, _, res = oracle_resume(args, axes, norm, s20, it0, iters)
+        clear = (res[:, :, moving, :].reshape(iters, N, -1).min(2) >= 1e-3).all(0)
         st = dev(s20.astype(np.float32))
         zh.ipo_fit(x0, uv, K, kl, axes, IPO_T, IPO_MIN, IPO_MAX, iters, norm, N, state=st, it_begin=it0)
-        return st.cpu().numpy().astype(np.float64), state_of(tr[-1]), clear
+        return st.cpu().numpy().astype(np.float64), want, clear, oracle_resume(args, axes, norm, s20, it0, iters, np.float32)[0]
+
+    def second_moments(got, want, clear, o32):
+        rule = MomentRule()
+        rule.add(got[clear][:, 10:15], o32[clear][:, 10:15], want[clear][:, 10:15])
+        return rule
 
     n_amb, ends = 0, {}
     for it0 in (2046, 2047, 2048, 2049, 4095):
-        got, want, clear = run(it0, 1)
+        got, want, clear, o32 = run(it0, 1)
         n_amb += int((~clear).sum())
         d = float(np.abs(got - want)[clear][:, :5].max())
         dm = float(np.abs(got - want)[clear][:, 5:10].max())
-        _report(dict(test="general_k_adam_table", it_begin=it0, iters=1, clear_poses=int(clear.sum()), max_param_delta=d, max_moment_delta=dm))
+        rv = second_moments(got, want, clear, o32)
+        _report(dict(test="general_k_adam_table", it_begin=it0, iters=1, clear_poses=int(clear.sum()), max_param_delta=d, max_moment_delta=dm,
+                     max_v_delta=rv.delta, v_bound=rv.bound, v_ratio=rv.ratio))
         assert d <= 1e-6, (it0, d)
+        assert rv.holds() and rv.largest > 0, (it0, rv.delta, rv.bound)
         ends[it0] = want
     assert n_amb <= 0.05 * 5 * N, n_amb
     # neighbouring iterations differ by far more than the bound (2.6e-5 on either side of the seam): an it_begin that is off by one,
     # in the table index or in the host's beta^it_begin, cannot pass
     assert min(np.abs(ends[a] - ends[a + 1])[:, :5].max() for a in (2046, 2047, 2048)) > 1e-5
-    got, want, clear = run(2046, 4)
+    got, want, clear, o32 = run(2046, 4)
     d = float(np.abs(got - want)[clear][:, :5].max())
-    _report(dict(test="general_k_adam_table", it_begin=2046, iters=4, clear_poses=int(clear.sum()), max_param_delta=d))
+    rv = second_moments(got, want, clear, o32)
+    _report(dict(test="general_k_adam_table", it_begin=2046, iters=4, clear_poses=int(clear.sum()), max_param_delta=d, max_v_delta=rv.delta,
+                 v_bound=rv.bound, v_ratio=rv.ratio))
     assert clear.sum() >= N // 2 and d <= 1e-6, (int(clear.sum()), d)
+    assert rv.holds() and rv.largest > 0, (rv.delta, rv.bound)
 
 
 # ---- d. rays, T0, singular systems ------------------------------------------------------------------------------------------------

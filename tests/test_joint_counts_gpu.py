@@ -16,8 +16,8 @@ import numpy as np
 import pytest
 
 import _procrustes_ref as PR
-from _shared import (IPO_KEYS, IPO_MAX, IPO_MIN, IPO_T, cameras, cfg_path, dev, make_ipo_problem, pack, report_env as _report, ulp32,
-                     zh)  # noqa: F401  (fixture)
+from _shared import (IPO_KEYS, IPO_MAX, IPO_MIN, IPO_T, MomentRule, cameras, cfg_path, dev, initial_state, make_ipo_problem, oracle_resume,
+                     report_env as _report, state_of, ulp32, zh)  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -460,7 +460,8 @@ def test_ipo_single_iterations_from_the_oracle_state(zh, J, kl, N, axes):
     """The method of test_ipo_single_iterations_from_reference_state with the float64 oracle as the state source (the oracle's
     float64 run is pinned to the reference's to 1e-8 at 17 joints, key lists of 1 .. 17 joints): each of the first 50 Adam
     iterations on its own through zedo_ipo_fit_resume from the oracle's float64 state, |delta parameter| <= 1e-6 on poses whose
-    residuals are all sign-unambiguous (|e| >= 1e-3 px; a key joint at the root contributes no gradient and is not counted).
+    residuals are all sign-unambiguous (|e| >= 1e-3 px; a key joint at the root contributes no gradient and is not counted); the
+    second moments of the same pose-iterations by the rule of test_ipo_single_iterations_from_reference_state (_shared.MomentRule).
     uv is [N, J, 2] and x0 [1, J, 3] with J up to 33: key indices reach past 16, the strides are J."""
     import zedo_oracle as O
     cl, uvn, Kn = make_ipo_problem(J, N)
@@ -468,15 +469,13 @@ def test_ipo_single_iterations_from_the_oracle_state(zh, J, kl, N, axes):
     norm = N * len(kl) * 2
     c64, K64 = uvn.astype(np.float64), Kn.astype(np.float64)
     x64 = np.broadcast_to(cl[0][None], (N, J, 3)).astype(np.float64)
+    args = (x64[:, kl], O.ipo_init_T(c64, K64, IPO_T, dtype=np.float64), K64, c64[:, kl])
     tr = []
-    O.ipo_fit(x64[:, kl], O.ipo_init_T(c64, K64, IPO_T, dtype=np.float64), K64, c64[:, kl], axes, IPO_MIN, IPO_MAX, 50,
-              normaliser=norm, dtype=np.float64, trace=tr)
+    O.ipo_fit(*args, axes, IPO_MIN, IPO_MAX, 50, normaliser=norm, dtype=np.float64, trace=tr)
 
-    z4, z1 = np.zeros((N, 4)), np.zeros(N)
-    q0 = z4.copy(); q0[:, 0] = 1
-    states = [pack(q0, np.ones(N), z4, z4, z1, z1)] + [pack(t[0], t[1], t[3], t[4], t[5], t[6]) for t in tr]
+    states = [initial_state(N)] + [state_of(t) for t in tr]
     moving = np.abs(cl[0][kl]).max(-1) > 0
-    worst, n_amb = 0.0, 0
+    worst, n_amb, rule_v = 0.0, 0, MomentRule()
     for it in range(50):
         st = dev(states[it].astype(np.float32))
         zh.ipo_fit(x0, uv, K, kl, axes, IPO_T, IPO_MIN, IPO_MAX, 1, norm, N, state=st, it_begin=it)
@@ -487,9 +486,13 @@ def test_ipo_single_iterations_from_the_oracle_state(zh, J, kl, N, axes):
             d = float(np.abs(out - states[it + 1])[clear, :5].max())
             worst = max(worst, d)
             assert d <= 1e-6, (it, d)
-    _report(dict(test="joint_counts_ipo", J=J, k=len(kl), N=N, axes=axes, ambiguous_pose_iterations=n_amb, max_param_delta=worst))
+            o32 = oracle_resume(args, axes, norm, states[it], it, 1, np.float32)[0]
+            rule_v.add(out[clear, 10:], o32[clear, 10:], states[it + 1][clear, 10:])
+    _report(dict(test="joint_counts_ipo", J=J, k=len(kl), N=N, axes=axes, ambiguous_pose_iterations=n_amb, max_param_delta=worst,
+                 max_v_delta=rule_v.delta, fp32_oracle_v_delta=rule_v.delta32, v_bound=rule_v.bound, v_ratio=rule_v.ratio))
     assert n_amb <= 0.05 * 50 * N, n_amb
     assert worst > 0 or N * 50 == n_amb
+    assert rule_v.holds() and (rule_v.largest > 0 or N * 50 == n_amb), (rule_v.delta, rule_v.bound)
 
 
 def test_ipo_shard_equals_the_unsharded_rows(zh):

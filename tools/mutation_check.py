@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: forty-three one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: fifty-two one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -8,6 +8,7 @@ library is rebuilt and re-tested at the end (row "none": must be all green), so 
 """
 import os
 import re
+import shutil
 import subprocess
 import sys
 import time
@@ -98,11 +99,21 @@ MUTANTS = [
     # (0.68 of it at label 2000) and is caught by tests/test_pc_native_gpu.py::test_chained_steps_against_the_float64_reference
     ("ZEDO_MUT_BIAS_TILE", "schedule tables above 1 024 rows: in the three cost-model shapes of launch_small ONE EPI_BIAS tile, the second row tile of the second column block, takes its bias from the next column block (zedo_gemm.hip layer_tile)"),
     ("ZEDO_MUT_POSEMB_FAST", "posemb_kernel: __sinf / __cosf, the hardware fast forms without range reduction, in place of sinf / cosf (zedo_geom.hip)"),
+    # the resumable IPO state (tests/test_ipo_state_gpu.py and the second-moment assertions of the single-iteration tests;
+    # profiles/mutation_ipo_state.txt: run against the six files that launch the IPO kernels).  None of them changes an address.
+    ("ZEDO_MUT_IPO_CLAMP_LO", "IPO: the clamp backward tests scale <= max only, the lower bound is forgotten, in both kernels - three cells of the earlier single-iteration tests reach it from trajectory states, none at the boundary or in the lane-per-row kernel (zedo_geom.hip)"),
+    ("ZEDO_MUT_IPO_STORE_V", "zedo_ipo_fit_resume: the scale's exp_avg is stored into the slot of its exp_avg_sq, state[14] (zedo_geom.hip ipo_store)"),
+    ("ZEDO_MUT_IPO_ROW_LOAD_V", "zedo_ipo_fit_resume: the lane-per-row kernel resumes with exp_avg_sq = 0, the half-wave kernel does not (zedo_geom.hip ipo_row_kernel)"),
     ("ZEDO_MUT_TREEMARG_NO_DOWN", "zedo_joint_tree_marginal: Dn = 0 on every joint - the downward pass is dropped, a joint hears from its subtree only (zedo_joint_tree_marginal.hip joint_tree_marginal_kernel)"),
 ]
 
 
 def build(flag):
+    # ZEDO_MUT_LIBS=<dir>: libraries built beforehand (<dir>/<flag>.so, <dir>/none.so for the product) are copied into place instead
+    # of compiling here - hipcc cross-compiles gfx950 on a host without a GPU
+    if os.environ.get("ZEDO_MUT_LIBS"):
+        shutil.copyfile(os.path.join(os.environ["ZEDO_MUT_LIBS"], (flag or "none") + ".so"), os.path.join(ROOT, "zedo-release_amd", "zedo_hip", "libzedo_hip.so"))
+        return
     for f in os.listdir(CSRC):
         if f.endswith(".hip"):
             os.utime(os.path.join(CSRC, f))
@@ -113,7 +124,9 @@ def build(flag):
 def run_suite(modes=None):
     """modes: None = both arithmetic modes of the suite (tests/conftest.py), "f32" / "f16x3" = that one only (ZEDO_TEST_MATH)."""
     t0 = time.time()
-    cmd = [sys.executable, "-m", "pytest", "tests", "-m", "gpu", "-q", "--no-header", "-rf", "-p", "no:cacheprovider"]
+    # ZEDO_MUT_TESTS: the test files to run instead of the whole suite, separated by blanks (a mutant of one kernel family against
+    # the files that launch it)
+    cmd = [sys.executable, "-m", "pytest"] + (os.environ.get("ZEDO_MUT_TESTS", "").split() or ["tests"]) + ["-m", "gpu", "-q", "--no-header", "-rf", "-p", "no:cacheprovider"]
     if os.environ.get("ZEDO_MUT_DESELECT"):          # e.g. the three-minute end-to-end ensembles: "not lie_inside and not pooled"
         cmd += ["-k", os.environ["ZEDO_MUT_DESELECT"]]
     env = dict(os.environ)
@@ -152,8 +165,10 @@ def main():
             print(f"{flag}: {len(failed)} red / {passed} green in {dt:.0f} s", flush=True)
     finally:
         build(None)
-    failed, passed, dt, out = run_suite()
-    rows.append(("none", "the product library (rebuilt without any mutation)", failed, passed, dt))
+    # the clean library in the cells the mutants ran in
+    clean_modes = "f32" if only and not any(f.startswith("ZEDO_MUT_F16_") for f in only) else None
+    failed, passed, dt, out = run_suite(clean_modes)
+    rows.append(("none", "the product library (rebuilt without any mutation)" + (" [f32 cells]" if clean_modes else " [both modes]"), failed, passed, dt))
     ok &= len(failed) == 0
     with open(dst, "w") as f:
         f.write("mutation | what | red tests | green | suite seconds\n")

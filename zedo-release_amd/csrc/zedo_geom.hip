@@ -456,7 +456,11 @@ __device__ __forceinline__ void ipo_store(const AdamP &qr, const AdamP &qi, cons
     if (stp) {
         stp[0] = qr.p; stp[1] = qi.p; stp[2] = qj.p; stp[3] = qk.p; stp[4] = sc.p;
         stp[5] = qr.m; stp[6] = qi.m; stp[7] = qj.m; stp[8] = qk.m; stp[9] = sc.m;
+#ifdef ZEDO_MUT_IPO_STORE_V   // tools/mutation_check.py only: the scale's first moment lands in the slot of its second
+        stp[10] = qr.v; stp[11] = qi.v; stp[12] = qj.v; stp[13] = qk.v; stp[14] = sc.m;
+#else
         stp[10] = qr.v; stp[11] = qi.v; stp[12] = qj.v; stp[13] = qk.v; stp[14] = sc.v;
+#endif
     }
 }
 
@@ -525,7 +529,11 @@ __global__ __launch_bounds__(64) void ipo_kernel(const float *__restrict__ x0, c
         for (int e = 0; e < 10; ++e) S[e] = half_sum(jact ? t[e] : 0.f);   // lanes without a joint: exact +0
         float gr, gi, gj, gk;
         ipo_quat_grads(S, r, i, j, kk, o.ts, gr, gi, gj, gk);
+#ifdef ZEDO_MUT_IPO_CLAMP_LO  // tools/mutation_check.py only: the clamp backward forgets the lower bound (both kernels)
+        const float gs = (sc.p <= max_s) ? S[0] : 0.f;
+#else
         const float gs = (sc.p >= min_s && sc.p <= max_s) ? S[0] : 0.f;   // clamp backward
+#endif
         float step_size, bc2s;
         ipo_adam_terms(it_begin + it, b1p, b2p, step_size, bc2s);
         // The five Adam updates are the same statements on different data: lane c of the half-wave (c = 0..4 <-> rot_vect,
@@ -641,6 +649,9 @@ __global__ __launch_bounds__(IPO_ROW_TB) void ipo_row_kernel(const float *__rest
     if (stp && it_begin > 0) {
         qr = AdamP{stp[0], stp[5], stp[10]}; qi = AdamP{stp[1], stp[6], stp[11]}; qj = AdamP{stp[2], stp[7], stp[12]};
         qk = AdamP{stp[3], stp[8], stp[13]}; sc = AdamP{stp[4], stp[9], stp[14]};
+#ifdef ZEDO_MUT_IPO_ROW_LOAD_V  // tools/mutation_check.py only: the lane-per-row kernel resumes with exp_avg_sq = 0 (the half-wave kernel does not)
+        qr.v = qi.v = qj.v = qk.v = sc.v = 0.f;
+#endif
     }
     double b1p = b1p0, b2p = b2p0;
     for (int it = 0; it < iters; ++it) {
@@ -653,7 +664,11 @@ __global__ __launch_bounds__(IPO_ROW_TB) void ipo_row_kernel(const float *__rest
         for (int e = 0; e < 10; ++e) S[e] = d0[e] + d1[e];
         float gr, gi, gj, gk;
         ipo_quat_grads(S, r, i, j, kk, o.ts, gr, gi, gj, gk);
+#ifdef ZEDO_MUT_IPO_CLAMP_LO  // tools/mutation_check.py only: the clamp backward forgets the lower bound (both kernels)
+        const float gs = (sc.p <= max_s) ? S[0] : 0.f;
+#else
         const float gs = (sc.p >= min_s && sc.p <= max_s) ? S[0] : 0.f;   // clamp backward
+#endif
         float step_size, bc2s;
         ipo_adam_terms(it_begin + it, b1p, b2p, step_size, bc2s);
         qr.step(gr, step_size, bc2s);
