@@ -184,3 +184,47 @@ def spread_of(x, T, N):
     """-> (spread [N,J]: per (frame, joint) the largest coordinate range of X over the hypotheses, xmax: the largest |X|)."""
     X = camera_frame(x, T, N)
     return (X.max(axis=0) - X.min(axis=0)).max(axis=-1), float(np.abs(X).max())
+
+
+def chain_reference(r):
+    """The reference arrays of hold_marginals out of what joint_marginal_ref returns (or the streaming reference, which words its dict
+    alike): log w = A + B - logZ."""
+    with np.errstate(invalid="ignore"):                              # a dead (frame, joint): -inf - -inf, which nothing looks at
+        log_w = r["A"] + r["B"] - r["logz"][:, :, None]
+    return dict(log_w_ref=log_w, logz_ref=r["logz"], mean_ref=r["mean"], cov_ref=r["cov"], hmax_ref=r["hmax"], w_ref=r["w"], dead=r["dead"])
+
+
+def hold_marginals(out, *, log_w_ref, logz_ref, mean_ref, cov_ref, hmax_ref, w_ref, dead, beta, x, T, N, left_out_cap=None):
+    """The one place the marginal outputs of a fusion call are held to a reference: out = (mean, cov, hmax, wmax, logz, w) as numpy
+    arrays [N,J,..] against the reference's arrays, given beta, the bound on a log-marginal (marg_bound of the caller's model).  Asserts:
+    a dead (frame, joint) is NaN / hypothesis 0 / weight 0 / logz -inf with w == 0; w > 0 wherever the reference's is above 1e-300;
+    |log w - log_w_ref| there, |sum_h w - 1| and |logz - ref| on the live ones are at most beta; the mean and the covariance are within
+    mean_bound / cov_bound of it; hmax and wmax are the arg-max of w as written; hmax is the reference's wherever the reference's
+    runner-up is clear of 2 beta in the logarithm - and, with left_out_cap, at most that share of the live (frame, joint) is not.
+    -> what was observed (the callers print it; a failing assertion shows it)."""
+    mean, cov, hmax, wmax, logz, w = out
+    H, live = w.shape[2], ~dead
+    top = lambda a: float(a.max()) if a.size else 0.0
+    assert np.array_equal(np.isnan(mean[:, :, 0]), dead) and (w[dead] == 0.0).all()
+    assert (hmax[dead] == 0).all() and (wmax[dead] == 0.0).all() and np.isneginf(logz[dead]).all()
+    big = w_ref > 1e-300
+    assert (w[big] > 0).all()
+    spread, xmax = spread_of(x, T, N)
+    mb, cb = mean_bound(beta, xmax), np.broadcast_to(cov_bound(beta, spread, xmax)[:, :, None], cov.shape)
+    e_cov = np.abs(cov - cov_ref)
+    clear = live.copy()
+    if H > 1:
+        top2 = np.sort(w_ref, axis=2)[:, :, -2:]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            clear = live & (np.log(top2[:, :, 1]) - np.log(top2[:, :, 0]) > 2 * beta)
+    seen = dict(e_lw=top(np.abs(np.log(w[big].astype(np.longdouble)) - log_w_ref[big])), e_sum=top(np.abs(w.sum(2)[live] - 1.0)),
+                e_lz=top(np.abs(logz[live] - logz_ref[live])), beta=beta, e_mean=top(np.abs(mean - mean_ref)[live]), mean_bound=mb,
+                e_cov=top(e_cov[live]), cov_bound=float(cb[live].min()) if live.any() else 0.0,
+                hmax_differs=int((hmax != hmax_ref).sum()), not_clear=int(live.sum() - clear.sum()),
+                left_out=1.0 - float(clear[live].mean()) if live.any() else 0.0)
+    assert seen["e_lw"] <= beta and seen["e_sum"] <= beta and seen["e_lz"] <= beta, seen
+    assert seen["e_mean"] <= mb and (e_cov[live] <= cb[live]).all(), seen
+    assert np.array_equal(hmax[live], np.argmax(w, axis=2)[live]) and np.array_equal(wmax[live], w.max(axis=2)[live])
+    assert left_out_cap is None or seen["left_out"] <= left_out_cap, seen
+    assert np.array_equal(hmax[clear], hmax_ref[clear]), seen
+    return seen

@@ -3,13 +3,13 @@ A is the forward table of _joint_marginal_ref.joint_marginal_ref on the whole cl
 frames were cut into pushes; per live (n, j) the horizon e = min(n + lag, the last frame of n's chain on the clip) is found as
 _joint_stream_ref.fixed_lag finds it, B is walked from B[e] = 0 down to n with lse_ascending, logZ = LSE_h A[e,j,h], and w, the mean,
 the covariance (centred, asc_sum), hmax, wmax and logz follow as the offline reference words them.  Also the comparison the GPU tests
-hold the kernels to (a copy of hold_to of tests/test_joint_marginal_gpu.py: the same derived bounds, with L the clip's length) and the
+hold the kernels to (_joint_marginal_ref.hold_marginals: the same derived bounds, with L the clip's length, and EVERY arg-max) and the
 check of the inputs that lets every arg-max be compared.  Pinned on its own by tests/test_joint_stream_marginal_ref.py."""
 import functools
 
 import numpy as np
 
-from _joint_marginal_ref import asc_sum, cov_bound, joint_marginal_ref, lse_ascending, marg_bound, mean_bound, spread_of
+from _joint_marginal_ref import asc_sum, chain_reference, hold_marginals, joint_marginal_ref, lse_ascending, marg_bound
 from _joint_marginal_ref import reference as offline_reference
 from _joint_temporal_ref import camera_frame, case
 from _temporal_ref import clips
@@ -89,37 +89,13 @@ def reference(J, N, H, L, lam, tau, lag, with_T=True):
 def hold_to(out, r, x, T, N, L, tag):
     """Every output (mean, cov, hmax, wmax, logz, w as numpy arrays [N, ..]) against the reference r within the derived bounds of
     _joint_marginal_ref, L the clip's length; prints observed against bound.  -> the largest log-marginal error."""
-    mean, cov, hmax, wmax, logz, w = out
-    H = w.shape[2]
-    beta = marg_bound(min(L, N), H, r["G"])
-    live = ~r["dead"]
-    assert np.array_equal(np.isnan(mean[:, :, 0]), r["dead"]) and (w[r["dead"]] == 0.0).all()
-    big = r["w"] > 1e-300
-    with np.errstate(invalid="ignore"):                              # a dead (frame, joint): -inf - -inf, not among `big`
-        lw_ref = (r["A"] + r["B"] - r["logz"][:, :, None])[big]
-    assert (w[big] > 0).all()
-    e_lw = float(np.abs(np.log(w[big].astype(np.longdouble)) - lw_ref).max())
-    e_sum = float(np.abs(w.sum(2)[live] - 1.0).max())
-    e_lz = float(np.abs(logz[live] - r["logz"][live]).max())
-    spread, xmax = spread_of(x, T, N)
-    mb, cb = mean_bound(beta, xmax), cov_bound(beta, spread, xmax)[:, :, None]
-    e_mean = float(np.abs(mean - r["mean"])[live].max())
-    e_cov = np.abs(cov - r["cov"])
-    print(f"joint-stream-marginal {tag}: G = {r['G']:.3g}; max |log w - ref| = {e_lw:.3e}, |sum w - 1| = {e_sum:.3e}, |logz - ref| = "
-          f"{e_lz:.3e} (bound {beta:.3e}); |mean - ref| = {e_mean:.3e} m (bound {mb:.3e}); |cov - ref| = {e_cov[live].max():.3e} m^2 "
-          f"(smallest bound {cb[live].min():.3e}); hmax differs on {int((hmax != r['hmax']).sum())} of {hmax.size}")
-    assert e_lw <= beta and e_sum <= beta and e_lz <= beta
-    assert e_mean <= mb and (e_cov[live] <= np.broadcast_to(cb, cov.shape)[live]).all()
-    # the arg-max: the lowest h with the largest of the marginals as written, and the reference's - check_inputs: EVERY one is clear
-    assert np.array_equal(hmax[live], np.argmax(w, axis=2)[live]) and np.array_equal(wmax[live], w.max(axis=2)[live])
-    assert (hmax[r["dead"]] == 0).all() and (wmax[r["dead"]] == 0.0).all() and np.isneginf(logz[r["dead"]]).all()
-    if H > 1:
-        top2 = np.sort(r["w"], axis=2)[:, :, -2:]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            clear = live & (np.log(top2[:, :, 1]) - np.log(top2[:, :, 0]) > 2 * beta)
-        assert clear[live].all()
-    assert np.array_equal(hmax[live], r["hmax"][live])
-    return e_lw
+    s = hold_marginals(out, beta=marg_bound(min(L, N), out[5].shape[2], r["G"]), x=x, T=T, N=N, **chain_reference(r))
+    print(f"joint-stream-marginal {tag}: G = {r['G']:.3g}; max |log w - ref| = {s['e_lw']:.3e}, |sum w - 1| = {s['e_sum']:.3e}, |logz - ref| = "
+          f"{s['e_lz']:.3e} (bound {s['beta']:.3e}); |mean - ref| = {s['e_mean']:.3e} m (bound {s['mean_bound']:.3e}); |cov - ref| = "
+          f"{s['e_cov']:.3e} m^2 (smallest bound {s['cov_bound']:.3e}); hmax differs on {s['hmax_differs']} of {out[2].size}")
+    # the reference's arg-max - check_inputs: EVERY one is clear of the bound
+    assert s["not_clear"] == 0 and np.array_equal(out[2][~r["dead"]], r["hmax"][~r["dead"]])
+    return s["e_lw"]
 
 
 def smallest_log_gap(w, dead):

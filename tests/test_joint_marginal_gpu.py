@@ -9,13 +9,12 @@ positive semi-definite; a dead (frame, joint) and excluded entries; bit identity
 the alignment of d_x and d_w NULL or not; the refusals of the raw ABI.
 Whether the fused pose is closer to ground truth than a selected one is not measured here or anywhere: these tests hold the arithmetic.
 The fusion does not depend on the arithmetic mode of the dense layers: one session runs it."""
-import ctypes
-
 import numpy as np
 import pytest
 
-from _joint_marginal_ref import (IDS, MARGINAL_CASES, cov_bound, joint_marginal_ref, marg_bound, mean_bound, reference, softmax_bound,
-                                 softmax_ref, spread_of)
+from _invariance import all_same, clamped_offsets, cur_stream, dirty, launch_invariant, ptr as P, refusal_sweep, same, sentinels
+from _joint_marginal_ref import (IDS, MARGINAL_CASES, chain_reference, cov_bound, hold_marginals, joint_marginal_ref, marg_bound, reference,
+                                 softmax_bound, softmax_ref, spread_of)
 from _joint_ref import case as reproj_case
 from _joint_temporal_ref import camera_frame, case, dead_joint_case
 from _shared import dev, one_arithmetic_mode, problem, zh  # noqa: F401  (fixtures; one_arithmetic_mode is autouse)
@@ -25,18 +24,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 LAM, TAU = 100.0, 1.0
-
-
-def bits(t):
-    return t.view(torch.int64) if t.dtype == torch.float64 else t
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
-
-
-def all_same(out, ref):
-    return len(out) == len(ref) and all(same(a, b) for a, b in zip(out, ref))
+SHAPES = lambda N, J, H: (((N, J, 3), torch.float64), ((N, J, 6), torch.float64), ((N, J), torch.int32), ((N, J), torch.float64),
+                          ((N, J), torch.float64), ((N, J, H), torch.float64))
 
 
 def run(zh, x, T, u, seq, lam=LAM, tau=TAU, weights=True):
@@ -46,44 +35,18 @@ def run(zh, x, T, u, seq, lam=LAM, tau=TAU, weights=True):
 
 def hold_to(out, r, x, T, N, L, tag):
     """Every output against the reference r within the derived bounds; prints observed against bound.  -> the largest log-marginal error."""
-    mean, cov, hmax, wmax, logz, w = out
-    H = w.shape[2]
-    beta = marg_bound(min(L, N), H, r["G"])
-    live = ~r["dead"]
-    assert np.array_equal(np.isnan(mean[:, :, 0]), r["dead"]) and (w[r["dead"]] == 0.0).all()
-    big = r["w"] > 1e-300
-    with np.errstate(invalid="ignore"):                              # a dead (frame, joint): -inf - -inf, not among `big`
-        lw_ref = (r["A"] + r["B"] - r["logz"][:, :, None])[big]
-    assert (w[big] > 0).all()
-    e_lw = float(np.abs(np.log(w[big].astype(np.longdouble)) - lw_ref).max())
-    e_sum = float(np.abs(w.sum(2)[live] - 1.0).max())
-    e_lz = float(np.abs(logz[live] - r["logz"][live]).max())
-    spread, xmax = spread_of(x, T, N)
-    mb, cb = mean_bound(beta, xmax), cov_bound(beta, spread, xmax)[:, :, None]
-    e_mean = float(np.abs(mean - r["mean"])[live].max())
-    e_cov = np.abs(cov - r["cov"])
-    print(f"joint-marginal {tag}: G = {r['G']:.3g}; max |log w - ref| = {e_lw:.3e}, |sum w - 1| = {e_sum:.3e}, |logz - ref| = {e_lz:.3e} "
-          f"(bound {beta:.3e}); |mean - ref| = {e_mean:.3e} m (bound {mb:.3e}); |cov - ref| = {e_cov[live].max():.3e} m^2 (smallest bound "
-          f"{cb[live].min():.3e}); hmax differs on {int((hmax != r['hmax']).sum())} of {hmax.size}")
-    assert e_lw <= beta and e_sum <= beta and e_lz <= beta
-    assert e_mean <= mb and (e_cov[live] <= np.broadcast_to(cb, cov.shape)[live]).all()
-    # the arg-max: the lowest h with the largest of the marginals as written, and the reference's wherever its runner-up is clear of the bound
-    assert np.array_equal(hmax[live], np.argmax(w, axis=2)[live]) and np.array_equal(wmax[live], w.max(axis=2)[live])
-    assert (hmax[r["dead"]] == 0).all() and (wmax[r["dead"]] == 0.0).all() and np.isneginf(logz[r["dead"]]).all()
-    if H > 1:
-        top2 = np.sort(r["w"], axis=2)[:, :, -2:]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            clear = live & (np.log(top2[:, :, 1]) - np.log(top2[:, :, 0]) > 2 * beta)
-        assert np.array_equal(hmax[clear], r["hmax"][clear])
-    return e_lw
+    s = hold_marginals(out, beta=marg_bound(min(L, N), out[5].shape[2], r["G"]), x=x, T=T, N=N, **chain_reference(r))
+    print(f"joint-marginal {tag}: G = {r['G']:.3g}; max |log w - ref| = {s['e_lw']:.3e}, |sum w - 1| = {s['e_sum']:.3e}, |logz - ref| = "
+          f"{s['e_lz']:.3e} (bound {s['beta']:.3e}); |mean - ref| = {s['e_mean']:.3e} m (bound {s['mean_bound']:.3e}); |cov - ref| = "
+          f"{s['e_cov']:.3e} m^2 (smallest bound {s['cov_bound']:.3e}); hmax differs on {s['hmax_differs']} of {out[2].size}")
+    return s["e_lw"]
 
 
 @pytest.mark.parametrize("J,N,H,L", MARGINAL_CASES, ids=IDS)
 def test_marginals_mean_and_covariance_match_the_float64_reference(zh, J, N, H, L):
     x, T, u = case(J, N, H)
     out = zh.joint_marginal(dev(u, torch.float64), dev(x), dev(T), clips(N, L), lam=LAM, tau=TAU, return_weights=True)
-    for t, shape, dt in zip(out, ((N, J, 3), (N, J, 6), (N, J), (N, J), (N, J), (N, J, H)),
-                            (torch.float64, torch.float64, torch.int32, torch.float64, torch.float64, torch.float64)):
+    for t, (shape, dt) in zip(out, SHAPES(N, J, H)):
         assert tuple(t.shape) == shape and t.dtype == dt
     hold_to([t.cpu().numpy() for t in out], reference(J, N, H, L, LAM, TAU), x, T, N, L, f"J={J} N={N} H={H} L={L}")
 
@@ -195,42 +158,24 @@ def test_the_bits_do_not_depend_on_the_workspace_the_stream_the_alignment_or_d_w
     ref = zh.joint_marginal(ud, xd, Td, seq, lam=LAM, tau=TAU, return_weights=True)
     assert all_same(zh.joint_marginal(ud, xd, Td, seq, lam=LAM, tau=TAU), ref[:5])                 # d_w NULL (through the binding)
     # raw ABI: a dirty workspace, with and without d_w
-    P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
     nbytes = zh._lib.zedo_joint_marginal_workspace_bytes(N, H, J)
     sd = torch.tensor(seq, dtype=torch.int32, device="cuda")
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    for with_w in (True, False):
-        ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device="cuda")
-        assert bool(torch.isnan(ws[:nbytes // 8 * 8].view(torch.float64)).all())
-        o = [torch.full(s, -7, dtype=d, device="cuda") for s, d in (((N, J, 3), torch.float64), ((N, J, 6), torch.float64), ((N, J), torch.int32),
-                                                                     ((N, J), torch.float64), ((N, J), torch.float64), ((N, J, H), torch.float64))]
-        assert zh._lib.zedo_joint_marginal(P(ud), P(xd), P(Td), P(sd), len(seq) - 1, H, N, J, LAM, TAU, P(ws), nbytes, P(o[0]), P(o[1]), P(o[2]),
-                                           P(o[3]), P(o[4]), P(o[5]) if with_w else None, st) == 0
-        torch.cuda.synchronize()
-        assert all_same(o[:5], ref[:5]) and (same(o[5], ref[5]) if with_w else bool((o[5] == -7).all()))
-    # a side stream, seq_start as a device tensor (warms the allocator for the capture)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        o = zh.joint_marginal(ud, xd, Td, sd, lam=LAM, tau=TAU, return_weights=True)
+
+    def raw(ws, o, st, with_w=True):
+        return zh._lib.zedo_joint_marginal(P(ud), P(xd), P(Td), P(sd), len(seq) - 1, H, N, J, LAM, TAU, P(ws), nbytes, P(o[0]), P(o[1]), P(o[2]),
+                                           P(o[3]), P(o[4]), P(o[5]) if with_w else None, st)
+
+    o = sentinels(SHAPES(N, J, H))
+    assert raw(dirty(nbytes, 0xFF), o, cur_stream(), with_w=False) == 0
     torch.cuda.synchronize()
-    assert all_same(o, ref)
-    # captured (a single branch) and replayed: the call allocates nothing and synchronises nothing of its own
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        out = zh.joint_marginal(ud, xd, Td, sd, N=N, lam=LAM, tau=TAU, return_weights=True)
-    for _ in range(2):
-        for t in out:
-            t.zero_()
-        g.replay()
-        torch.cuda.synchronize()
-        assert all_same(out, ref)
-    # d_x 12 bytes past a 16-byte boundary
-    buf = torch.empty(H * N * J * 3 + 3, dtype=torch.float32, device="cuda")
-    xb = buf[3:].view(H * N, J, 3)
-    xb.copy_(xd)
-    assert xd.data_ptr() % 16 == 0 and xb.data_ptr() % 16 == 12 and xb.is_contiguous()
-    assert all_same(zh.joint_marginal(ud, xb, Td, seq, lam=LAM, tau=TAU, return_weights=True), ref)
+    assert all_same(o[:5], ref[:5]) and bool((o[5] == -7).all())
+
+    def via_binding(x=xd, seq_on_device=False):
+        # under capture N is given: reading it off the device tensor would synchronise
+        return zh.joint_marginal(ud, x, Td, sd if seq_on_device else seq, N=N if torch.cuda.is_current_stream_capturing() else None, lam=LAM,
+                                 tau=TAU, return_weights=True)
+
+    launch_invariant(ref, via_binding, xd, raw, SHAPES(N, J, H), nbytes)
 
 
 def test_clip_offsets_that_break_the_rules_are_clamped(zh):
@@ -238,9 +183,7 @@ def test_clip_offsets_that_break_the_rules_are_clamped(zh):
     J, N, H = 5, 12, 3
     x, T, u = case(J, N, H)
     xd, Td, ud = dev(x), dev(T), dev(u, torch.float64)
-    ref = zh.joint_marginal(ud, xd, Td, [0, N], return_weights=True)
-    for seq in ([0, N + 1000], [-5, N]):
-        assert all_same(zh.joint_marginal(ud, xd, Td, seq, N=N, return_weights=True), ref), seq
+    clamped_offsets(lambda seq: zh.joint_marginal(ud, xd, Td, seq, N=N, return_weights=True), N)
 
 
 def test_refusals_at_the_raw_abi(zh):
@@ -248,7 +191,6 @@ def test_refusals_at_the_raw_abi(zh):
     lambda, tau of 0, negative, NaN and inf, and a misaligned workspace: ZEDO_E_BADARG; a workspace one byte short: ZEDO_E_WORKSPACE;
     nothing written either way.  The same call with valid arguments is accepted, with and without d_T."""
     lib = zh._lib
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
     J, N, H, L = 5, 12, 3, 4
     x, T, u = case(J, N, H)
     xd, Td, ud = dev(x), dev(T), dev(u, torch.float64)
@@ -260,29 +202,17 @@ def test_refusals_at_the_raw_abi(zh):
     assert lib.zedo_joint_marginal_workspace_bytes(1, 1024, 1) > 0
     for n, h, j in ((0, H, J), (N, 0, J), (N, H, 0), (-1, H, J), (N, 1025, J), (2 ** 16, 2 ** 10, 2 ** 5), (2 ** 30, 1, 2)):
         assert lib.zedo_joint_marginal_workspace_bytes(n, h, j) == 0, (n, h, j)
-    ws = torch.full((need + 8,), 0x5A, dtype=torch.uint8, device="cuda")
-    outs = [torch.full(s, -7, dtype=d, device="cuda") for s, d in (((N, J, 3), torch.float64), ((N, J, 6), torch.float64), ((N, J), torch.int32),
-                                                                    ((N, J), torch.float64), ((N, J), torch.float64), ((N, J, H), torch.float64))]
+    ws = dirty(need + 8, 0x5A)
+    outs = sentinels(SHAPES(N, J, H))
     ptrs = [P(ud), P(xd), P(Td), P(sd), P(ws)] + [P(t) for t in outs]
 
     def call(p=ptrs, n_seq=len(seq) - 1, h=H, n=N, j=J, lam=LAM, tau=TAU, nbytes=need):
         return lib.zedo_joint_marginal(p[0], p[1], p[2], p[3], n_seq, h, n, j, lam, tau, p[4], nbytes, p[5], p[6], p[7], p[8], p[9], p[10], None)
 
-    for k in (0, 1, 3, 4, 5, 6, 7, 8, 9):
-        assert call([None if i == k else p for i, p in enumerate(ptrs)]) == -1, k
-    assert call(n_seq=0) == -1 and call(n_seq=N + 1) == -1 and call(h=0) == -1 and call(n=0) == -1 and call(j=0) == -1
-    assert call(h=-1) == -1 and call(n=-3) == -1 and call(j=-1) == -1
-    assert call(h=1025, nbytes=2 ** 40) == -1
-    assert call(h=2 ** 10, n=2 ** 16, j=2 ** 5, nbytes=2 ** 40) == -1 and call(h=1, n=2 ** 30, j=2, nbytes=2 ** 40) == -1
-    assert call(lam=-1.0) == -1 and call(lam=float("nan")) == -1 and call(lam=float("inf")) == -1
-    for tau in (0.0, -0.0, -1.0, float("nan"), float("inf"), float("-inf")):
-        assert call(tau=tau) == -1, tau
-    assert call([ctypes.c_void_p(ws.data_ptr() + 4) if i == 4 else p for i, p in enumerate(ptrs)]) == -1
-    assert call(nbytes=need - 1) == -3 and call(nbytes=0) == -3
-    torch.cuda.synchronize()
-    assert all(bool((t == -7).all()) for t in outs) and bool((ws == 0x5A).all())
-    assert call() == 0                                               # the control
-    torch.cuda.synchronize()
+    sizes = [dict(n_seq=0), dict(n_seq=N + 1), dict(h=0), dict(n=0), dict(j=0), dict(h=-1), dict(n=-3), dict(j=-1), dict(h=1025, nbytes=2 ** 40),
+             dict(h=2 ** 10, n=2 ** 16, j=2 ** 5, nbytes=2 ** 40), dict(h=1, n=2 ** 30, j=2, nbytes=2 ** 40)]
+    refusal_sweep(call, ptrs, (0, 1, 3, 4, 5, 6, 7, 8, 9), sizes=sizes, weights=("lam",), taus=("tau",), workspace_slot=4, need=need,
+                  untouched=[(t, -7) for t in outs] + [(ws, 0x5A)])
     r = reference(J, N, H, L, LAM, TAU)
     assert np.array_equal(outs[2].cpu().numpy(), r["hmax"]) and bool((ws[need:] == 0x5A).all())
     assert np.abs(outs[5].cpu().numpy() - r["w"]).max() < 1e-9

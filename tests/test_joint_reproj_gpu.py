@@ -6,14 +6,13 @@ zedo_pose_min with it), on shards, ties, NaN, joints behind the camera, at the r
 
 Distance bound 1e-9 px, the bound and derivation of tests/test_select_reproj_gpu.py: pixel coordinates are below 2^14, where an fp64 ulp is
 1.8e-12; a joint's chain has fewer than 20 roundings, and a single joint's chain is shorter than the row's weighted mean: about 4e-11.
-bits(t): the int64 view of a float64 tensor; "bitwise" is torch.equal on bits.
+"bitwise" is torch.equal on _invariance.bits, the integer view of a floating tensor.
 Whether the assembled pose is closer to ground truth than the pose-level selection is not measured here or anywhere: these tests hold the
 arithmetic, not the criterion's accuracy.  The selection does not depend on the arithmetic mode of the dense layers: one session runs it."""
-import ctypes
-
 import numpy as np
 import pytest
 
+from _invariance import misaligned, ptr as P, replays_to, same, sentinels
 from _joint_ref import CASES, IDS, case, check_inputs, compose_ref, joint_reproj_ref, joint_select_ref
 from _shared import dev, one_arithmetic_mode, problem, zh  # noqa: F401  (fixtures; one_arithmetic_mode is autouse)
 
@@ -21,14 +20,6 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 TOL = 1e-9
-
-
-def bits(t):
-    return t.view(torch.int64) if t.dtype == torch.float64 else t
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
 
 
 def run(zh, x, T, uv, K, off=0, rows=True):
@@ -73,10 +64,7 @@ def test_the_routes_agree(zh, J, N, H):
     assert same(wb, best) and same(wi, idx)
     pb, pi = zh.pose_min(jerr.reshape(-1), N * J, 0)
     assert same(pb.reshape(N, J), best) and same(pi.reshape(N, J), idx)
-    buf = torch.empty(B * J * 3 + 51, dtype=torch.float32, device="cuda")
-    xb = buf[51:].view(B, J, 3)
-    xb.copy_(xd)
-    assert xd.data_ptr() % 16 == 0 and xb.data_ptr() % 16 == 12 and xb.is_contiguous()
+    xb = misaligned(xd, floats=51)
     ub, ui, uj = zh.joint_reproj(xb, Td, uvd, Kd, return_rows=True)
     assert same(ub, best) and same(ui, idx) and same(uj, jerr)
     ub, ui = zh.joint_reproj(xb, Td, uvd, Kd)
@@ -246,7 +234,6 @@ def test_compose(zh):
     assert np.array_equal(rel.cpu().numpy()[own].view(np.int32), x.reshape(H, N, J, 3)[rh, np.arange(N)][own].view(np.int32))
     # raw ABI: indices outside 0 .. H-1
     lib = zh._lib
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
     bad = idx.clone()
     bad[3, 4], bad[5, 0] = -1, H
     out = torch.full((N, J, 3), -7.0, device="cuda")
@@ -281,16 +268,13 @@ def test_refusals_at_the_raw_abi(zh):
     """Each required NULL, B = 0, N = 0, J = 0 and row_offset = -1: ZEDO_E_BADARG, nothing written; B*J above INT_MAX as well (refused before
     any pointer is used); a NULL d_jerr is accepted."""
     lib = zh._lib
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
     J, N, H = 17, 3, 4
     B = N * H
     x = torch.full((B, J, 3), 0.25, device="cuda")
     T = torch.tensor([[0.0, 0.0, 5.0]], device="cuda").repeat(B, 1).contiguous()
     uv = torch.full((N, J, 2), 500.0, device="cuda")
     K = torch.tensor([[1100.0, 0, 500], [0, 1100, 500], [0, 0, 1]], device="cuda").repeat(N, 1, 1).contiguous()
-    jerr = torch.full((B, J), -7.0, dtype=torch.float64, device="cuda")
-    best = torch.full((N, J), -7.0, dtype=torch.float64, device="cuda")
-    bh = torch.full((N, J), -7, dtype=torch.int32, device="cuda")
+    jerr, best, bh = sentinels((((B, J), torch.float64), ((N, J), torch.float64), ((N, J), torch.int32)))
     ptrs = [P(x), P(T), P(uv), P(K), P(jerr), P(best), P(bh)]
     call = lambda p, b=B, n=N, j=J, off=0: lib.zedo_joint_reproj(p[0], p[1], p[2], p[3], b, n, j, off, p[4], p[5], p[6], None)
     for k in (0, 1, 2, 3, 5, 6):
@@ -320,16 +304,7 @@ def test_the_call_is_capturable(zh, rows):
     with torch.cuda.stream(s):
         zh.joint_reproj(x, T, uv, K, return_rows=rows)            # warm the allocator on the capture stream
     torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        out = zh.joint_reproj(x, T, uv, K, return_rows=rows)
-    for _ in range(2):
-        for t in out:
-            t.zero_()
-        g.replay()
-        torch.cuda.synchronize()
-        for to, te in zip(out, eager):
-            assert same(to, te)
+    replays_to(eager, lambda: zh.joint_reproj(x, T, uv, K, return_rows=rows), s)
 
 
 def test_pipeline_aggregate_reproj_and_compose(zh, weights0):

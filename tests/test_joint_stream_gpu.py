@@ -17,6 +17,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from _invariance import cur_stream, dirty, misaligned, ptr as P, same, sentinels
 from _joint_ref import case as reproj_case
 from _joint_stream_ref import LAGS, check_inputs, chunkings, emitted, fixed_lag
 from _joint_temporal_ref import ALL_CASES, IDS, LAMBDAS, case, dead_joint_case, joint_temporal_ref, reference
@@ -27,18 +28,6 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 SENT_P, SENT_C = -7, -7.0
-
-
-def bits(t):
-    return t.view(torch.int64) if t.dtype == torch.float64 else t
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
-
-
-def P(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def gather(xd, Td, ud, N, frames):
@@ -58,17 +47,14 @@ class Streams:
         self.lib, self.S, self.H, self.J, self.lag, self.mf, self.lam = zh._lib, S, H, J, lag, max_frames, lam
         self.nbytes = self.lib.zedo_joint_stream_state_bytes(S, H, J, lag, max_frames)
         assert self.nbytes > 0
-        self.state = torch.full((self.nbytes,), fill, dtype=torch.uint8, device="cuda")
+        self.state = dirty(self.nbytes, fill)
         self.t = [0] * S
         self.out = [[] for _ in range(S)]
         self.reset()
 
-    def st(self):
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def reset(self, which=None):
         w = None if which is None else torch.tensor(which, dtype=torch.int32, device="cuda")
-        assert self.lib.zedo_joint_stream_reset(P(self.state), self.nbytes, self.S, self.H, self.J, self.lag, self.mf, P(w), self.st()) == 0
+        assert self.lib.zedo_joint_stream_reset(P(self.state), self.nbytes, self.S, self.H, self.J, self.lag, self.mf, P(w), cur_stream()) == 0
         for s in range(self.S):
             if which is None or which[s]:
                 self.t[s] = 0
@@ -76,11 +62,10 @@ class Streams:
     def push(self, u, x, T, F, flush=None):
         S, J, lag = self.S, self.J, self.lag
         fl = None if flush is None else torch.tensor(flush, dtype=torch.int32, device="cuda")
-        path = torch.full((S, F + lag, J), SENT_P, dtype=torch.int32, device="cuda")
-        cost = torch.full((S, F + lag, J), SENT_C, dtype=torch.float64, device="cuda")
+        path, cost = sentinels((((S, F + lag, J), torch.int32), ((S, F + lag, J), torch.float64)), SENT_P)
         emit = torch.full((S, 2), -1, dtype=torch.int64, device="cuda")
         rc = self.lib.zedo_joint_stream_push(P(u), P(x), P(T), S, F, self.H, J, lag, self.mf, self.lam, P(fl), P(self.state), self.nbytes,
-                                             P(path), P(cost), P(emit), self.st())
+                                             P(path), P(cost), P(emit), cur_stream())
         assert rc == 0, rc
         want = [emitted(self.t[s], F, lag, bool(flush and flush[s])) for s in range(S)]
         assert emit.cpu().tolist() == [list(w) for w in want], (emit.cpu().tolist(), want)
@@ -272,11 +257,7 @@ def test_the_bits_do_not_depend_on_the_state_the_stream_or_the_alignment(zh):
         # d_x 12 bytes past a 16-byte boundary, pushed whole
         st = Streams(zh, 2, H, J, lag, L, lam)
         uu, xx, TT = gather(xd, Td, ud, N, [list(range(0, L)), list(range(L, 2 * L))])
-        buf = torch.empty(xx.numel() + 3, dtype=torch.float32, device="cuda")
-        xb = buf[3:].view(xx.shape)
-        xb.copy_(xx)
-        assert xx.data_ptr() % 16 == 0 and xb.data_ptr() % 16 == 12 and xb.is_contiguous()
-        st.push(uu, xb, TT, L)                                        # no flush: L - lag frames come out
+        st.push(uu, misaligned(xx), TT, L)                                        # no flush: L - lag frames come out
         st.push(None, None, None, 0, [1, 1])                          # F = 0: the pending min(lag, L) frames
         for k in range(2):
             fr, p, c = st.collected(k)
@@ -285,15 +266,14 @@ def test_the_bits_do_not_depend_on_the_state_the_stream_or_the_alignment(zh):
     lag = L - 1
     st = Streams(zh, 2, H, J, lag, 1, lam)
     su, sx, sT = (t.clone() for t in gather(xd, Td, ud, N, [[0], [L]]))
-    op = torch.full((2, 1 + lag, J), SENT_P, dtype=torch.int32, device="cuda")
-    oc = torch.full((2, 1 + lag, J), SENT_C, dtype=torch.float64, device="cuda")
+    op, oc = sentinels((((2, 1 + lag, J), torch.int32), ((2, 1 + lag, J), torch.float64)), SENT_P)
     oe = torch.full((2, 2), -1, dtype=torch.int64, device="cuda")
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=side):
         rc = st.lib.zedo_joint_stream_push(P(su), P(sx), P(sT), 2, 1, H, J, lag, 1, lam, None, P(st.state), st.nbytes, P(op), P(oc), P(oe),
-                                           st.st())
+                                           cur_stream())
     assert rc == 0
     got_p, got_c = [[], []], [[], []]
     for f in range(L):
@@ -361,7 +341,7 @@ def test_refusals_at_the_raw_abi(zh):
     S, F = 3, 4
     uu, xx, TT = gather(xd, Td, ud, N, [list(range(a, a + F)) for a in (0, 4, 8)])
     need = lib.zedo_joint_stream_state_bytes(S, H, J, lag, mf)
-    state = torch.full((need + 8,), 0x5A, dtype=torch.uint8, device="cuda")
+    state = dirty(need + 8, 0x5A)
     assert lib.zedo_joint_stream_reset(P(state), need, S, H, J, lag, mf, None, None) == 0
     u2, x2, T2 = gather(xd, Td, ud, N, [[a, a + 1] for a in (0, 4, 8)])
     tmp = (torch.empty((S, 2 + lag, J), dtype=torch.int32, device="cuda"), torch.empty((S, 2 + lag, J), dtype=torch.float64, device="cuda"),
@@ -370,8 +350,7 @@ def test_refusals_at_the_raw_abi(zh):
                                       None) == 0
     torch.cuda.synchronize()
     before = state.clone()                                           # a state in use: two frames per stream
-    path = torch.full((S, F + lag, J), SENT_P, dtype=torch.int32, device="cuda")
-    cost = torch.full((S, F + lag, J), SENT_C, dtype=torch.float64, device="cuda")
+    path, cost = sentinels((((S, F + lag, J), torch.int32), ((S, F + lag, J), torch.float64)), SENT_P)
     emit = torch.full((S, 2), -1, dtype=torch.int64, device="cuda")
     fl = torch.ones(S, dtype=torch.int32, device="cuda")
     ptrs = dict(u=P(uu), x=P(xx), T=P(TT), fl=P(fl), st=P(state), p=P(path), c=P(cost), e=P(emit))

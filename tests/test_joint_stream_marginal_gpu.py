@@ -17,6 +17,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from _invariance import all_same, cur_stream, dirty, misaligned, ptr as P, same, sentinels
 from _joint_marginal_ref import IDS, MARGINAL_CASES, joint_marginal_ref, marg_bound, softmax_bound, softmax_ref
 from _joint_ref import case as reproj_case
 from _joint_stream_marginal_ref import FINITE_CASES, LAGS, fixed_lag_marginal, hold_to, reference
@@ -33,22 +34,6 @@ SENT = -7
 NAMES = ("mean", "cov", "hmax", "wmax", "logz", "w")
 
 
-def bits(t):
-    return t.view(torch.int64) if t.dtype == torch.float64 else t
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
-
-
-def all_same(out, ref):
-    return len(out) == len(ref) and all(same(a, b) for a, b in zip(out, ref))
-
-
-def P(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 def gather(xd, Td, ud, N, frames):
     """frames [S][F]: the frame of the case every stream pushes -> the chunk's (u, x, T), rows (h, n) h-major with n = s F + f."""
     H = xd.shape[0] // N
@@ -59,9 +44,8 @@ def gather(xd, Td, ud, N, frames):
 
 def outputs(S, rows, J, H):
     """The six outputs [S, rows, ..] pre-filled with the sentinel."""
-    f64 = lambda *shape: torch.full(shape, float(SENT), dtype=torch.float64, device="cuda")
-    return [f64(S, rows, J, 3), f64(S, rows, J, 6), torch.full((S, rows, J), SENT, dtype=torch.int32, device="cuda"), f64(S, rows, J),
-            f64(S, rows, J), f64(S, rows, J, H)]
+    f64 = lambda *tail: ((S, rows, J) + tail, torch.float64)
+    return sentinels((f64(3), f64(6), ((S, rows, J), torch.int32), f64(), f64(), f64(H)), SENT)
 
 
 class Streams:
@@ -75,18 +59,15 @@ class Streams:
         self.with_w = with_w
         self.nbytes = self.lib.zedo_joint_stream_marginal_state_bytes(S, H, J, lag, max_frames)
         assert self.nbytes > 0
-        self.state = torch.full((self.nbytes,), fill, dtype=torch.uint8, device="cuda")
+        self.state = dirty(self.nbytes, fill)
         self.t = [0] * S
         self.out = [[] for _ in range(S)]
         self.reset()
 
-    def st(self):
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def reset(self, which=None):
         w = None if which is None else torch.tensor(which, dtype=torch.int32, device="cuda")
         assert self.lib.zedo_joint_stream_marginal_reset(P(self.state), self.nbytes, self.S, self.H, self.J, self.lag, self.mf, P(w),
-                                                         self.st()) == 0
+                                                         cur_stream()) == 0
         for s in range(self.S):
             if which is None or which[s]:
                 self.t[s] = 0
@@ -98,7 +79,7 @@ class Streams:
         emit = torch.full((S, 2), -1, dtype=torch.int64, device="cuda")
         rc = self.lib.zedo_joint_stream_marginal_push(P(u), P(x), P(T), S, F, self.H, J, lag, self.mf, self.lam, self.tau, P(fl), P(self.state),
                                                       self.nbytes, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(o[5]) if self.with_w else None,
-                                                      P(emit), self.st())
+                                                      P(emit), cur_stream())
         assert rc == 0, rc
         want = [emitted(self.t[s], F, lag, bool(flush and flush[s])) for s in range(S)]
         assert emit.cpu().tolist() == [list(w) for w in want], (emit.cpu().tolist(), want)
@@ -347,11 +328,7 @@ def test_the_bits_do_not_depend_on_the_state_the_stream_the_alignment_or_d_w(zh)
         # d_x 12 bytes past a 16-byte boundary, pushed whole
         st = Streams(zh, 2, H, J, lag, L)
         uu, xx, TT = gather(xd, Td, ud, N, [list(range(0, L)), list(range(L, 2 * L))])
-        buf = torch.empty(xx.numel() + 3, dtype=torch.float32, device="cuda")
-        xb = buf[3:].view(xx.shape)
-        xb.copy_(xx)
-        assert xx.data_ptr() % 16 == 0 and xb.data_ptr() % 16 == 12 and xb.is_contiguous()
-        st.push(uu, xb, TT, L)                                        # no flush: L - lag frames come out
+        st.push(uu, misaligned(xx), TT, L)                                        # no flush: L - lag frames come out
         st.push(None, None, None, 0, [1, 1])                          # F = 0: the pending min(lag, L) frames
         for k in range(2):
             fr, o = st.collected(k)
@@ -367,7 +344,7 @@ def test_the_bits_do_not_depend_on_the_state_the_stream_the_alignment_or_d_w(zh)
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g, stream=side):
         rc = st.lib.zedo_joint_stream_marginal_push(P(su), P(sx), P(sT), 2, 1, H, J, lag, 1, LAM, TAU, None, P(st.state), st.nbytes, P(o[0]),
-                                                    P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(o[5]), P(oe), st.st())
+                                                    P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(o[5]), P(oe), cur_stream())
     assert rc == 0
     got = [[[] for _ in range(6)] for _ in range(2)]
     for f in range(L):
@@ -457,7 +434,7 @@ def test_refusals_at_the_raw_abi(zh):
     S, F = 3, 4
     uu, xx, TT = gather(xd, Td, ud, N, [list(range(a, a + F)) for a in (0, 4, 8)])
     need = lib.zedo_joint_stream_marginal_state_bytes(S, H, J, lag, mf)
-    state = torch.full((need + 8,), 0x5A, dtype=torch.uint8, device="cuda")
+    state = dirty(need + 8, 0x5A)
     assert lib.zedo_joint_stream_marginal_reset(P(state), need, S, H, J, lag, mf, None, None) == 0
     u2, x2, T2 = gather(xd, Td, ud, N, [[a, a + 1] for a in (0, 4, 8)])
     tmp = outputs(S, 2 + lag, J, H) + [torch.empty((S, 2), dtype=torch.int64, device="cuda")]

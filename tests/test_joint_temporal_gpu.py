@@ -6,14 +6,13 @@ _temporal_ref.cost_bound(1, L, .) = 20 L 2^-53 relative (asserted; the differenc
 on the reference alone that no minimum the recurrence takes has a runner-up closer than 1e-6.  Without T the call is held, bit for bit, to J calls of zedo_temporal_select on one-joint
 slices.  Bit identity across a dirty workspace, a side stream, stream capture, the alignment of d_x and seq_start on the device; unaries
 from zedo_joint_reproj; the limits (lambda = 0, clips of one frame); excluded entries and a dead (frame, joint); the refusals of the raw
-ABI.  bits(t): the int64 view of a float64 tensor.
+ABI.
 Whether joint-wise temporal paths are closer to ground truth than the per-frame joint-wise arg-min is not measured here or anywhere:
 these tests hold the arithmetic.  The selection does not depend on the arithmetic mode of the dense layers: one session runs it."""
-import ctypes
-
 import numpy as np
 import pytest
 
+from _invariance import clamped_offsets, dirty, launch_invariant, ptr as P, refusal_sweep, same, sentinels
 from _joint_ref import case as reproj_case
 from _joint_ref import joint_reproj_ref
 from _joint_temporal_ref import (ALL_CASES, IDS, LAMBDAS, case, check_inputs, dead_joint_case, joint_temporal_ref, per_frame_argmin,
@@ -24,13 +23,7 @@ from _temporal_ref import clips, cost_bound
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-
-def bits(t):
-    return t.view(torch.int64) if t.dtype == torch.float64 else t
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
+OUT_SPECS = lambda N, J: (((N, J), torch.int32), ((N, J), torch.float64))
 
 
 def run(zh, x, T, u, seq, lam):
@@ -80,42 +73,17 @@ def test_the_bits_do_not_depend_on_the_workspace_the_stream_or_the_alignment(zh,
     lam = 100.0
     path, cost = zh.joint_temporal_select(ud, xd, Td, seq, lam=lam)
     assert np.array_equal(path.cpu().numpy(), reference(J, N, H, L, lam)["path"])
-    # raw ABI: a dirty workspace
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
     nbytes = zh._lib.zedo_joint_temporal_workspace_bytes(N, H, J)
-    ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device="cuda")
-    assert bool(torch.isnan(ws[:nbytes // 8 * 8].view(torch.float64)).all())
     sd = torch.tensor(seq, dtype=torch.int32, device="cuda")
-    p = torch.full((N, J), -7, dtype=torch.int32, device="cuda")
-    k = torch.full((N, J), -7.0, dtype=torch.float64, device="cuda")
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    assert zh._lib.zedo_joint_temporal_select(P(ud), P(xd), P(Td), P(sd), len(seq) - 1, H, N, J, lam, P(ws), nbytes, P(p), P(k), st) == 0
-    torch.cuda.synchronize()
-    assert same(p, path) and same(k, cost)
-    # a side stream, seq_start as a device tensor (warms the allocator for the capture)
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        p, k = zh.joint_temporal_select(ud, xd, Td, sd, lam=lam)
-    torch.cuda.synchronize()
-    assert same(p, path) and same(k, cost)
-    # captured (a single branch) and replayed: the call allocates nothing and synchronises nothing of its own
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        out = zh.joint_temporal_select(ud, xd, Td, sd, N=N, lam=lam)
-    for _ in range(2):
-        for t in out:
-            t.zero_()
-        g.replay()
-        torch.cuda.synchronize()
-        assert same(out[0], path) and same(out[1], cost)
-    # d_x 12 bytes past a 16-byte boundary
-    buf = torch.empty(H * N * J * 3 + 3, dtype=torch.float32, device="cuda")
-    xb = buf[3:].view(H * N, J, 3)
-    xb.copy_(xd)
-    assert xd.data_ptr() % 16 == 0 and xb.data_ptr() % 16 == 12 and xb.is_contiguous()
-    p, k = zh.joint_temporal_select(ud, xb, Td, seq, lam=lam)
-    assert same(p, path) and same(k, cost)
+
+    def raw(ws, o, st):
+        return zh._lib.zedo_joint_temporal_select(P(ud), P(xd), P(Td), P(sd), len(seq) - 1, H, N, J, lam, P(ws), nbytes, P(o[0]), P(o[1]), st)
+
+    def via_binding(x=xd, seq_on_device=False):
+        # under capture N is given: reading it off the device tensor would synchronise
+        return zh.joint_temporal_select(ud, x, Td, sd if seq_on_device else seq, N=N if torch.cuda.is_current_stream_capturing() else None, lam=lam)
+
+    launch_invariant((path, cost), via_binding, xd, raw, OUT_SPECS(N, J), nbytes)
 
 
 def test_unaries_from_joint_reproj(zh):
@@ -198,10 +166,7 @@ def test_clip_offsets_that_break_the_rules_are_clamped(zh):
     J, N, H = 5, 12, 3
     x, T, u = case(J, N, H)
     xd, Td, ud = dev(x), dev(T), dev(u, torch.float64)
-    path, cost = zh.joint_temporal_select(ud, xd, Td, [0, N], lam=100.0)
-    for seq in ([0, N + 1000], [-5, N]):
-        p, k = zh.joint_temporal_select(ud, xd, Td, seq, N=N, lam=100.0)
-        assert same(p, path) and same(k, cost), seq
+    clamped_offsets(lambda seq: zh.joint_temporal_select(ud, xd, Td, seq, N=N, lam=100.0), N)
 
 
 def test_refusals_at_the_raw_abi(zh):
@@ -209,7 +174,6 @@ def test_refusals_at_the_raw_abi(zh):
     and a misaligned workspace: ZEDO_E_BADARG; a workspace one byte short: ZEDO_E_WORKSPACE; nothing written either way.  The same call
     with valid arguments is accepted, with and without d_T."""
     lib = zh._lib
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
     J, N, H, L = 5, 12, 3, 4
     x, T, u = case(J, N, H)
     xd, Td, ud = dev(x), dev(T), dev(u, torch.float64)
@@ -221,27 +185,17 @@ def test_refusals_at_the_raw_abi(zh):
     assert lib.zedo_joint_temporal_workspace_bytes(1, 1024, 1) > 0
     for n, h, j in ((0, H, J), (N, 0, J), (N, H, 0), (-1, H, J), (N, 1025, J), (2 ** 16, 2 ** 10, 2 ** 5), (2 ** 30, 1, 2)):
         assert lib.zedo_joint_temporal_workspace_bytes(n, h, j) == 0, (n, h, j)
-    ws = torch.full((need + 8,), 0x5A, dtype=torch.uint8, device="cuda")
-    path = torch.full((N, J), -7, dtype=torch.int32, device="cuda")
-    cost = torch.full((N, J), -7.0, dtype=torch.float64, device="cuda")
+    ws = dirty(need + 8, 0x5A)
+    path, cost = sentinels(OUT_SPECS(N, J))
     ptrs = [P(ud), P(xd), P(Td), P(sd), P(ws), P(path), P(cost)]
 
     def call(p=ptrs, n_seq=len(seq) - 1, h=H, n=N, j=J, lam=100.0, nbytes=need):
         return lib.zedo_joint_temporal_select(p[0], p[1], p[2], p[3], n_seq, h, n, j, lam, p[4], nbytes, p[5], p[6], None)
 
-    for k in (0, 1, 3, 4, 5, 6):
-        assert call([None if i == k else p for i, p in enumerate(ptrs)]) == -1, k
-    assert call(n_seq=0) == -1 and call(n_seq=N + 1) == -1 and call(h=0) == -1 and call(n=0) == -1 and call(j=0) == -1
-    assert call(h=-1) == -1 and call(n=-3) == -1 and call(j=-1) == -1
-    assert call(h=1025, nbytes=2 ** 40) == -1
-    assert call(h=2 ** 10, n=2 ** 16, j=2 ** 5, nbytes=2 ** 40) == -1 and call(h=1, n=2 ** 30, j=2, nbytes=2 ** 40) == -1
-    assert call(lam=-1.0) == -1 and call(lam=float("nan")) == -1 and call(lam=float("inf")) == -1
-    assert call([ctypes.c_void_p(ws.data_ptr() + 4) if i == 4 else p for i, p in enumerate(ptrs)]) == -1
-    assert call(nbytes=need - 1) == -3 and call(nbytes=0) == -3
-    torch.cuda.synchronize()
-    assert bool((path == -7).all()) and bool((cost == -7.0).all()) and bool((ws == 0x5A).all())
-    assert call() == 0                                               # the control
-    torch.cuda.synchronize()
+    sizes = [dict(n_seq=0), dict(n_seq=N + 1), dict(h=0), dict(n=0), dict(j=0), dict(h=-1), dict(n=-3), dict(j=-1), dict(h=1025, nbytes=2 ** 40),
+             dict(h=2 ** 10, n=2 ** 16, j=2 ** 5, nbytes=2 ** 40), dict(h=1, n=2 ** 30, j=2, nbytes=2 ** 40)]
+    refusal_sweep(call, ptrs, (0, 1, 3, 4, 5, 6), sizes=sizes, weights=("lam",), workspace_slot=4, need=need,
+                  untouched=((path, -7), (cost, -7.0), (ws, 0x5A)))
     assert np.array_equal(path.cpu().numpy(), reference(J, N, H, L, 100.0)["path"]) and bool((ws[need:] == 0x5A).all())
     assert call([None if i == 2 else p for i, p in enumerate(ptrs)]) == 0          # d_T may be NULL
     torch.cuda.synchronize()

@@ -14,6 +14,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from _invariance import all_same, launch_invariant, ptr as P, refusal_sweep, same, sentinels
 import _joint_tree_ref as R
 from _joint_ref import case as reproj_case
 from _joint_tree_ref import case
@@ -21,14 +22,6 @@ from _shared import dev, one_arithmetic_mode, problem, zh  # noqa: F401  (fixtur
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-
-def bits(t):
-    return t.view(torch.int64) if t.dtype == torch.float64 else t
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
 
 
 def held(out, r, J, mu, what):
@@ -128,28 +121,8 @@ def test_the_bits_do_not_depend_on_the_run_the_stream_or_the_alignment(zh, J, N,
     parent, mu = R.default_tree(J), 100.0
     ref = zh.joint_tree_select(ud, xd, Td, parent, N, mu)
     assert np.array_equal(ref[0].cpu().numpy(), R.reference(J, N, H, mu)["joint_h"])
-    again = zh.joint_tree_select(ud, xd, Td, parent, N, mu)
-    assert all(same(a, b) for a, b in zip(again, ref))
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        out = zh.joint_tree_select(ud, xd, Td, parent, N, mu)     # (warms the allocator for the capture)
-    torch.cuda.synchronize()
-    assert all(same(a, b) for a, b in zip(out, ref))
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        out = zh.joint_tree_select(ud, xd, Td, parent, N, mu)
-    for _ in range(2):
-        for t in out:
-            t.zero_()
-        g.replay()
-        torch.cuda.synchronize()
-        assert all(same(a, b) for a, b in zip(out, ref))
-    buf = torch.empty(H * N * J * 3 + 3, dtype=torch.float32, device="cuda")
-    xb = buf[3:].view(H * N, J, 3)
-    xb.copy_(xd)
-    assert xd.data_ptr() % 16 == 0 and xb.data_ptr() % 16 == 12 and xb.is_contiguous()
-    assert all(same(a, b) for a, b in zip(zh.joint_tree_select(ud, xb, Td, parent, N, mu), ref))
+    assert all_same(zh.joint_tree_select(ud, xd, Td, parent, N, mu), ref)                        # two runs
+    launch_invariant(ref, lambda x=xd, seq_on_device=False: zh.joint_tree_select(ud, x, Td, parent, N, mu), xd)
 
 
 def test_refusals_at_the_raw_abi(zh):
@@ -157,36 +130,25 @@ def test_refusals_at_the_raw_abi(zh):
     is no forest, a negative / NaN / infinite mu: ZEDO_E_BADARG and the sentinel-filled outputs untouched.  The same call with valid
     arguments is accepted, with and without d_T and d_weight."""
     lib = zh._lib
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
     J, N, H = 5, 12, 3
     x, T, u = case(J, N, H)
     xd, Td, ud, wd = dev(x), dev(T), dev(u, torch.float64), dev(R.confidences(N, J))
     par = lambda v: np.ascontiguousarray(np.asarray(v, np.int32))
     good = par(R.heap_tree(J))
-    joint_h = torch.full((N, J), -7, dtype=torch.int32, device="cuda")
-    cost = torch.full((N,), -7.0, dtype=torch.float64, device="cuda")
-    bone = torch.full((N, J), -7.0, dtype=torch.float64, device="cuda")
+    joint_h, cost, bone = sentinels((((N, J), torch.int32), ((N,), torch.float64), ((N, J), torch.float64)))
     ptrs = [P(ud), P(xd), P(Td), P(wd), None, P(joint_h), P(cost), P(bone)]
 
     def call(p=ptrs, parent=good, h=H, n=N, j=J, mu=100.0):
         pp = None if parent is None else parent.ctypes.data_as(ctypes.c_void_p)
         return lib.zedo_joint_tree_select(p[0], p[1], p[2], p[3], pp, h, n, j, mu, p[5], p[6], p[7], None)
 
-    for k in (0, 1, 5, 6, 7):
-        assert call([None if i == k else p for i, p in enumerate(ptrs)]) == -1, k
-    assert call(parent=None) == -1
-    assert call(h=0) == -1 and call(n=0) == -1 and call(j=0) == -1 and call(h=-1) == -1 and call(n=-3) == -1 and call(j=-1) == -1
     big = par([-1] + list(range(64)))
-    for jj, hh in R.TOO_LARGE:                                        # sizes above the caps (the pointers are never followed)
-        assert call(parent=big, h=hh, n=1, j=jj) == -1, (jj, hh)
-    assert call(parent=big, h=2 ** 10, n=2 ** 20, j=4) == -1          # H N J above INT_MAX
-    for bad in ([0, 0, 0, 1, 1], [-1, 0, 0, 1, 5], [-1, 0, 0, 1, -2], [1, 0, -1, 2, 2], [-1, 0, 0, 4, 3], [1, 2, 3, 4, 0]):
-        assert call(parent=par(bad)) == -1, bad                       # self, out of range (twice), two cycles beside a root, no root
-    assert call(mu=-1.0) == -1 and call(mu=float("nan")) == -1 and call(mu=float("inf")) == -1
-    torch.cuda.synchronize()
-    assert bool((joint_h == -7).all()) and bool((cost == -7.0).all()) and bool((bone == -7.0).all())
-    assert call() == 0                                                # the control
-    torch.cuda.synchronize()
+    sizes = [dict(parent=None), dict(h=0), dict(n=0), dict(j=0), dict(h=-1), dict(n=-3), dict(j=-1)]
+    sizes += [dict(parent=big, h=hh, n=1, j=jj) for jj, hh in R.TOO_LARGE]                # sizes above the caps (the pointers are never followed)
+    sizes += [dict(parent=big, h=2 ** 10, n=2 ** 20, j=4)]                                 # H N J above INT_MAX
+    # a parent array that is no forest: self, out of range (twice), two cycles beside a root, no root
+    sizes += [dict(parent=par(bad)) for bad in ([0, 0, 0, 1, 1], [-1, 0, 0, 1, 5], [-1, 0, 0, 1, -2], [1, 0, -1, 2, 2], [-1, 0, 0, 4, 3], [1, 2, 3, 4, 0])]
+    refusal_sweep(call, ptrs, (0, 1, 5, 6, 7), sizes=sizes, weights=("mu",), untouched=((joint_h, -7), (cost, -7.0), (bone, -7.0)))
     w = R.confidences(N, J)
     assert np.array_equal(joint_h.cpu().numpy(), R.joint_tree_ref(u, x, T, list(good), 100.0, N, w)["joint_h"])
     assert call([None if i in (2, 3) else p for i, p in enumerate(ptrs)]) == 0           # d_T and d_weight may be NULL
@@ -217,9 +179,9 @@ def test_pipeline_aggregate_tree(zh, weights0):
     for mu in (100.0, 0.0):
         want = zh.joint_tree_select(jerr, xd, Td, R.H36M_PARENTS, N, mu, pipe.conf)
         got = pipe.aggregate_tree(xd, Td, mu=mu)
-        assert all(same(a, b) for a, b in zip(got[:3], want)) and same(got[3], jerr)
+        assert all_same(got[:3], want) and same(got[3], jerr)
     got = pipe.aggregate_tree(xd, Td, mu=30.0, parent=R.reversed_chain(17))
-    assert all(same(a, b) for a, b in zip(got[:3], zh.joint_tree_select(jerr, xd, Td, R.reversed_chain(17), N, 30.0, pipe.conf)))
+    assert all_same(got[:3], zh.joint_tree_select(jerr, xd, Td, R.reversed_chain(17), N, 30.0, pipe.conf))
     assert same(pipe.compose(xd, Td, want[0]), zh.joint_compose(xd, Td, want[0]))
     with pytest.raises(ValueError):
         pipe.aggregate_tree(xd[:N], Td[:N])

@@ -16,6 +16,8 @@ import ctypes
 import numpy as np
 import pytest
 
+from _invariance import all_same, cur_stream, launch_invariant, ptr as P, refusal_sweep, same, sentinels
+from _joint_marginal_ref import hold_marginals
 import _joint_tree_marginal_ref as M
 import _joint_tree_ref as R
 from _joint_ref import case as reproj_case
@@ -27,18 +29,7 @@ torch = pytest.importorskip("torch")
 
 MU, TAU = 100.0, 1.0
 SHAPES = (((3,), torch.float64), ((6,), torch.float64), ((), torch.int32), ((), torch.float64), ((), torch.float64), ((), torch.float64))
-
-
-def bits(t):
-    return t.view(torch.int64) if t.dtype == torch.float64 else t
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
-
-
-def all_same(out, ref):
-    return len(out) == len(ref) and all(same(a, b) for a, b in zip(out, ref))
+OUT_SPECS = lambda N, J, H: [((N, J) + tail, dt) for tail, dt in SHAPES + (((H,), torch.float64),)]
 
 
 def run(zh, x, T, u, parent, N, mu=MU, tau=TAU, weight=None):
@@ -50,33 +41,19 @@ def run(zh, x, T, u, parent, N, mu=MU, tau=TAU, weight=None):
 def hold_to(out, r, x, T, N, tag):
     """Every output against the reference r within the derived bounds; prints observed against bound."""
     mean, cov, hmax, wmax, logz, bone, w = out
-    J, H = w.shape[1], w.shape[2]
-    beta = M.marg_bound(J, H, r["G"])
-    live, dead = r["live"], ~r["live"]
-    assert np.array_equal(np.isnan(mean[:, :, 0]), dead) and np.array_equal(np.isnan(cov).any(2), dead) and (w[dead] == 0.0).all()
-    assert (hmax[dead] == 0).all() and (wmax[dead] == 0.0).all() and np.isneginf(logz[dead]).all() and (bone[dead] == 0.0).all()
-    assert (w[np.isneginf(r["lw"])] == 0.0).all()                    # excluded entries are exactly 0
-    big = r["w"] > 1e-300
-    assert (w[big] > 0).all()
-    e_lw = float(np.abs(np.log(w[big].astype(np.longdouble)) - r["lw"][big]).max()) if big.any() else 0.0
-    e_sum = float(np.abs(w.sum(2)[live] - 1.0).max()) if live.any() else 0.0
-    e_lz = float(np.abs(logz[live] - r["logz"][live]).max()) if live.any() else 0.0
-    spread, xmax = M.spread_of(x, T, N)
-    mb, cb = M.mean_bound(beta, xmax), M.cov_bound(beta, spread, xmax)[:, :, None]
+    dead = ~r["live"]
+    beta = M.marg_bound(w.shape[1], w.shape[2], r["G"])
+    s = hold_marginals((mean, cov, hmax, wmax, logz, w), log_w_ref=r["lw"], logz_ref=r["logz"], mean_ref=r["mean"], cov_ref=r["cov"],
+                       hmax_ref=r["hmax"], w_ref=r["w"], dead=dead, beta=beta, x=x, T=T, N=N, left_out_cap=0.01)
+    # what only the tree has: the covariance of a dead joint, the bone output, and excluded entries that are exactly 0
+    assert np.array_equal(np.isnan(cov).any(2), dead) and (bone[dead] == 0.0).all() and (w[np.isneginf(r["lw"])] == 0.0).all()
     bb = M.bone_bound(beta, r["bmax"], r["lmax"])
-    e_mean = float(np.abs(mean - r["mean"])[live].max()) if live.any() else 0.0
-    e_cov = np.abs(cov - r["cov"])
     e_bone = float(np.abs(bone - r["bone"]).max())
-    clear = M.clear_argmax(r, beta)
-    print(f"joint-tree-marginal {tag}: G = {r['G']:.3g}; max |log w - ref| = {e_lw:.3e}, |sum w - 1| = {e_sum:.3e}, |logz - ref| = {e_lz:.3e} "
-          f"(bound {beta:.3e}); |mean - ref| = {e_mean:.3e} m (bound {mb:.3e}); |cov - ref| = {e_cov[live].max() if live.any() else 0.0:.3e} m^2 "
-          f"(smallest bound {cb[live].min() if live.any() else 0.0:.3e}); |bone - ref| = {e_bone:.3e} m (bound {bb:.3e}); hmax differs on "
-          f"{int((hmax != r['hmax']).sum())} of {hmax.size}, {int(live.sum() - clear.sum())} left out")
-    assert e_lw <= beta and e_sum <= beta and e_lz <= beta
-    assert e_mean <= mb and (e_cov[live] <= np.broadcast_to(cb, cov.shape)[live]).all() and e_bone <= bb
-    # the arg-max: the lowest h with the largest of the marginals as written, and the reference's wherever its runner-up is clear of the bound
-    assert np.array_equal(hmax[live], np.argmax(w, axis=2)[live]) and np.array_equal(wmax[live], w.max(axis=2)[live])
-    assert clear.sum() >= 0.99 * live.sum() and np.array_equal(hmax[clear], r["hmax"][clear])
+    print(f"joint-tree-marginal {tag}: G = {r['G']:.3g}; max |log w - ref| = {s['e_lw']:.3e}, |sum w - 1| = {s['e_sum']:.3e}, |logz - ref| = "
+          f"{s['e_lz']:.3e} (bound {beta:.3e}); |mean - ref| = {s['e_mean']:.3e} m (bound {s['mean_bound']:.3e}); |cov - ref| = {s['e_cov']:.3e} m^2 "
+          f"(smallest bound {s['cov_bound']:.3e}); |bone - ref| = {e_bone:.3e} m (bound {bb:.3e}); hmax differs on {s['hmax_differs']} of "
+          f"{hmax.size}, {s['not_clear']} left out")
+    assert e_bone <= bb
 
 
 @pytest.mark.parametrize("J,N,H", M.CASES, ids=M.IDS)
@@ -204,35 +181,14 @@ def test_the_bits_do_not_depend_on_the_run_d_w_the_stream_or_the_alignment(zh, J
     ref = zh.joint_tree_marginal(ud, xd, Td, parent, N, MU, TAU, wd, return_weights=True)
     assert all_same(zh.joint_tree_marginal(ud, xd, Td, parent, N, MU, TAU, wd, return_weights=True), ref)
     assert all_same(zh.joint_tree_marginal(ud, xd, Td, parent, N, MU, TAU, wd), ref[:6])           # d_w NULL (through the binding)
-    P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
     par = np.ascontiguousarray(np.asarray(parent, np.int32))
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    for with_w in (True, False):
-        o = [torch.full((N, J) + tail, -7, dtype=d, device="cuda") for tail, d in SHAPES + (((H,), torch.float64),)]
+    for with_w in (True, False):                                     # d_w pre-filled at the raw ABI, and NULL
+        o = sentinels(OUT_SPECS(N, J, H))
         assert zh._lib.zedo_joint_tree_marginal(P(ud), P(xd), P(Td), P(wd), par.ctypes.data_as(ctypes.c_void_p), H, N, J, MU, TAU, P(o[0]), P(o[1]),
-                                                P(o[2]), P(o[3]), P(o[4]), P(o[5]), P(o[6]) if with_w else None, st) == 0
+                                                P(o[2]), P(o[3]), P(o[4]), P(o[5]), P(o[6]) if with_w else None, cur_stream()) == 0
         torch.cuda.synchronize()
         assert all_same(o[:6], ref[:6]) and (same(o[6], ref[6]) if with_w else bool((o[6] == -7).all()))
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        out = zh.joint_tree_marginal(ud, xd, Td, parent, N, MU, TAU, wd, return_weights=True)       # (warms the allocator for the capture)
-    torch.cuda.synchronize()
-    assert all_same(out, ref)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        out = zh.joint_tree_marginal(ud, xd, Td, parent, N, MU, TAU, wd, return_weights=True)
-    for _ in range(2):
-        for t in out:
-            t.zero_()
-        g.replay()
-        torch.cuda.synchronize()
-        assert all_same(out, ref)
-    buf = torch.empty(H * N * J * 3 + 3, dtype=torch.float32, device="cuda")
-    xb = buf[3:].view(H * N, J, 3)
-    xb.copy_(xd)
-    assert xd.data_ptr() % 16 == 0 and xb.data_ptr() % 16 == 12 and xb.is_contiguous()
-    assert all_same(zh.joint_tree_marginal(ud, xb, Td, parent, N, MU, TAU, wd, return_weights=True), ref)
+    launch_invariant(ref, lambda x=xd, seq_on_device=False: zh.joint_tree_marginal(ud, x, Td, parent, N, MU, TAU, wd, return_weights=True), xd)
 
 
 def test_refusals_at_the_raw_abi(zh):
@@ -240,38 +196,26 @@ def test_refusals_at_the_raw_abi(zh):
     INT_MAX, a parent array that is no forest, tau of 0, negative, NaN and inf, a negative / NaN / infinite mu: ZEDO_E_BADARG and the
     pattern-filled outputs untouched.  The same call with valid arguments is accepted, with and without d_T, d_weight and d_w."""
     lib = zh._lib
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
     J, N, H = 5, 12, 3
     x, T, u = case(J, N, H)
     xd, Td, ud, wd = dev(x), dev(T), dev(u, torch.float64), dev(M.confidences(N, J))
     par = lambda v: np.ascontiguousarray(np.asarray(v, np.int32))
     good = par(R.heap_tree(J))
-    outs = [torch.full((N, J) + tail, -7, dtype=d, device="cuda") for tail, d in SHAPES + (((H,), torch.float64),)]
+    outs = sentinels(OUT_SPECS(N, J, H))
     ptrs = [P(ud), P(xd), P(Td), P(wd)] + [P(t) for t in outs]
 
     def call(p=ptrs, parent=good, h=H, n=N, j=J, mu=MU, tau=TAU):
         pp = None if parent is None else parent.ctypes.data_as(ctypes.c_void_p)
         return lib.zedo_joint_tree_marginal(p[0], p[1], p[2], p[3], pp, h, n, j, mu, tau, p[4], p[5], p[6], p[7], p[8], p[9], p[10], None)
 
-    for k in (0, 1, 4, 5, 6, 7, 8, 9):
-        assert call([None if i == k else p for i, p in enumerate(ptrs)]) == -1, k
-    assert call(parent=None) == -1
-    assert call(h=0) == -1 and call(n=0) == -1 and call(j=0) == -1 and call(h=-1) == -1 and call(n=-3) == -1 and call(j=-1) == -1
     big = par([-1] + list(range(64)))
-    for jj in (1, 17, 64):                                            # sizes above the caps (the pointers are never followed)
-        assert call(parent=big, h=zh.joint_tree_marginal_max_h(jj) + 1, n=1, j=jj) == -1, jj
-    assert call(parent=big, h=2, n=1, j=65) == -1
-    assert call(parent=big, h=2 ** 10, n=2 ** 20, j=2) == -1          # H N J above INT_MAX
-    for bad in ([0, 0, 0, 1, 1], [-1, 0, 0, 1, 5], [-1, 0, 0, 1, -2], [1, 0, -1, 2, 2], [-1, 0, 0, 4, 3], [1, 2, 3, 4, 0]):
-        assert call(parent=par(bad)) == -1, bad                       # self, out of range (twice), two cycles beside a root, no root
-    for tau in (0.0, -0.0, -1.0, float("nan"), float("inf"), float("-inf")):
-        assert call(tau=tau) == -1, tau
-    assert call(mu=-1.0) == -1 and call(mu=float("nan")) == -1 and call(mu=float("inf")) == -1
-    assert call(mu=1e300, tau=1e-300) == -1                           # mu / tau is not finite
-    torch.cuda.synchronize()
-    assert all(bool((t == -7).all()) for t in outs)
-    assert call() == 0                                                # the control
-    torch.cuda.synchronize()
+    sizes = [dict(parent=None), dict(h=0), dict(n=0), dict(j=0), dict(h=-1), dict(n=-3), dict(j=-1)]
+    sizes += [dict(parent=big, h=zh.joint_tree_marginal_max_h(jj) + 1, n=1, j=jj) for jj in (1, 17, 64)]     # sizes above the caps (the pointers are never followed)
+    sizes += [dict(parent=big, h=2, n=1, j=65), dict(parent=big, h=2 ** 10, n=2 ** 20, j=2)]                # ... and H N J above INT_MAX
+    # a parent array that is no forest: self, out of range (twice), two cycles beside a root, no root
+    sizes += [dict(parent=par(bad)) for bad in ([0, 0, 0, 1, 1], [-1, 0, 0, 1, 5], [-1, 0, 0, 1, -2], [1, 0, -1, 2, 2], [-1, 0, 0, 4, 3], [1, 2, 3, 4, 0])]
+    sizes += [dict(mu=1e300, tau=1e-300)]                            # mu / tau is not finite
+    refusal_sweep(call, ptrs, (0, 1, 4, 5, 6, 7, 8, 9), sizes=sizes, weights=("mu",), taus=("tau",), untouched=[(t, -7) for t in outs])
     r = M.joint_tree_marginal_ref(u, x, T, list(good), MU, TAU, N, M.confidences(N, J))
     assert np.array_equal(outs[2].cpu().numpy(), r["hmax"]) and np.abs(outs[6].cpu().numpy() - r["w"]).max() < 1e-9
     for t in outs:

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import _procrustes_ref as PR
+from _invariance import misaligned
 from _shared import dev, one_arithmetic_mode, report_env as _report, zh  # noqa: F401  (fixtures; one_arithmetic_mode is autouse)
 
 pytestmark = pytest.mark.gpu
@@ -27,11 +28,7 @@ def hp():
 
 def unaligned(a):
     """a [B,J,3] fp32 on the device behind a pointer 4 bytes off 16-byte alignment: the generic kernel's dispatch condition."""
-    buf = torch.empty(a.size + 1, dtype=torch.float32, device="cuda")
-    x = buf[1:].view(a.shape)
-    x.copy_(dev(a))
-    assert x.data_ptr() % 16 == 4 and x.is_contiguous()
-    return x
+    return misaligned(dev(a), floats=1)
 
 
 def operands(hp, kernel):

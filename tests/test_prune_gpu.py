@@ -6,27 +6,15 @@ trips along a row of the gather and a second trip of its grid over the rows; cha
 capture of both calls replayed on new input.
 Whether pruning by reprojection error costs accuracy is not measured here or anywhere: these tests hold the arithmetic.  The pruning
 does not depend on the arithmetic mode of the dense layers: one session runs it."""
-import ctypes
-
 import numpy as np
 import pytest
 
+from _invariance import BADARG, all_same, bits, cur_stream, ptr as P, same, sentinels
 from _prune_ref import GATHER_J, RANK_CASES, case, gather_ref, keep_ref, rank_ks
 from _shared import dev, one_arithmetic_mode, zh  # noqa: F401  (fixtures; one_arithmetic_mode is autouse)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
-
-BADARG = -1
-P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def bits(t):
-    return t.view({torch.float64: torch.int64, torch.float32: torch.int32}.get(t.dtype, t.dtype))
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
 
 
 def rows(H, N, J, seed=0):
@@ -117,8 +105,7 @@ def test_an_entry_outside_the_slots_is_never_an_address(zh, J):
         bT = torch.full((K * N * 3 + 2 * G,), -7.0, dtype=torch.float32, device="cuda")
         bh = torch.full((K * N + 2 * G,), -7, dtype=torch.int32, device="cuda")
         xo, To, ho = bx[G:-G], bT[G:-G], bh[G:-G]
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        assert zh._lib.zedo_prune_gather(P(kd), H, K, N, J, P(xd), P(Td), P(hd), P(xo), P(To), P(ho), st) == 0
+        assert zh._lib.zedo_prune_gather(P(kd), H, K, N, J, P(xd), P(Td), P(hd), P(xo), P(To), P(ho), cur_stream()) == 0
         torch.cuda.synchronize()
         for b in (bx, bT, bh):
             assert bool((b[:G] == -7).all()) and bool((b[-G:] == -7).all())
@@ -145,11 +132,8 @@ def test_the_gather_walks_the_rows_behind_the_grids_first_trip(zh):
     # row 0 of the table: slot n % 2, row 1: the other one (not the ascending table of prune_rank: the gather takes any table)
     first = (torch.arange(N, device="cuda") % 2).to(torch.int32)
     keep = torch.stack([first, 1 - first]).contiguous()
-    xo = torch.full((rows, J, 3), -7.0, device="cuda")
-    To = torch.full((rows, 3), -7.0, device="cuda")
-    ho = torch.full((K, N), -7, dtype=torch.int32, device="cuda")
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    assert zh._lib.zedo_prune_gather(P(keep), H, K, N, J, P(xd), P(Td), P(hd), P(xo), P(To), P(ho), st) == 0
+    xo, To, ho = sentinels((((rows, J, 3), torch.float32), ((rows, 3), torch.float32), ((K, N), torch.int32)))
+    assert zh._lib.zedo_prune_gather(P(keep), H, K, N, J, P(xd), P(Td), P(hd), P(xo), P(To), P(ho), cur_stream()) == 0
     torch.cuda.synchronize()
     g = (keep.long() * N + torch.arange(N, device="cuda")[None, :]).reshape(-1)
     tail = slice(first_trip, rows)
@@ -183,9 +167,7 @@ def test_refusals_leave_the_outputs_untouched(zh):
     x, T = (dev(a) for a in rows(H, N, J))
     hyp = torch.zeros((H, N), dtype=torch.int32, device="cuda")
     kd = dev(keep_ref(case(H, N), N, K), torch.int32)
-    xo = torch.full((K * N, J, 3), -7.0, device="cuda")
-    To = torch.full((K * N, 3), -7.0, device="cuda")
-    ho = torch.full((K, N), -7, dtype=torch.int32, device="cuda")
+    xo, To, ho = sentinels((((K * N, J, 3), torch.float32), ((K * N, 3), torch.float32), ((K, N), torch.int32)))
     ok = dict(keep=kd, H=H, K=K, N=N, J=J, x=x, T=T, hyp=hyp, xo=xo, To=To, ho=ho)
 
     def gather(**kw):
@@ -236,5 +218,5 @@ def test_one_capture_of_both_calls_replays_on_new_input(zh):
         k_e = zh.prune_rank(dev(e2, torch.float64), N, K)
         o_e = zh.prune_gather(k_e, dev(x2), dev(T2))
         assert same(keep, k_e) and np.array_equal(k_e.cpu().numpy(), keep_ref(e2, N, K))
-        assert all(same(a, b) for a, b in zip(out, o_e))
+        assert all_same(out, o_e)
         assert not np.array_equal(keep_ref(e2, N, K), keep_ref(case(H, N), N, K))                  # the input did change the table

@@ -6,14 +6,14 @@ at the raw ABI's refusals and under stream capture.
 
 Row-error bound 1e-9 px: pixel coordinates are below 2^14, where an fp64 ulp is 1.8e-12; a joint's chain has fewer than 20 roundings and
 the weighted mean does not amplify: about 4e-11, so 1e-9 leaves a 25x margin.
-bits(t): the int64 view of a float64 tensor; "bitwise" is torch.equal on bits.
+"bitwise" is torch.equal on _invariance.bits, the integer view of a floating tensor.
 The selection does not depend on the arithmetic mode of the dense layers: one session runs it."""
-import ctypes
 import functools
 
 import numpy as np
 import pytest
 
+from _invariance import bits, misaligned, ptr as P, replays_to, sentinels
 from _select_ref import reproj_ref, select_ref
 from _shared import dev, one_arithmetic_mode, problem, zh  # noqa: F401  (fixtures; one_arithmetic_mode is autouse)
 
@@ -28,10 +28,6 @@ BOUNDARY_CASES = [(17, 7, 30), (17, 63, 3), (33, 5, 4), (64, 3, 3), (17, 8219, 2
 CASES = CASES + BOUNDARY_CASES
 IDS = [f"J{J}-N{N}-H{H}" for J, N, H in CASES]
 TOL = 1e-9
-
-
-def bits(t):
-    return t.view(torch.int64) if t.dtype == torch.float64 else t
 
 
 @functools.lru_cache(maxsize=None)
@@ -105,10 +101,7 @@ def test_every_path_returns_the_same_bits(zh, J, N, H):
     x, T, uv, K, conf = case(J, N, H)
     B = H * N
     xd, Td, uvd, Kd, cd = dev(x), dev(T), dev(uv), dev(K), dev(conf)
-    buf = torch.empty((B + 1) * J * 3, dtype=torch.float32, device="cuda")
-    xb = buf[J * 3:].view(B, J, 3)
-    xb.copy_(xd)
-    assert xd.data_ptr() % 16 == 0 and xb.data_ptr() % 16 == 12 and xb.is_contiguous()
+    xb = misaligned(xd, floats=J * 3)                               # one row in: 204 or 60 bytes, 12 past a 16-byte boundary
     for c in (None, cd):
         a, b = zh.min_reproj(xd, Td, uvd, Kd, c), zh.min_reproj(xb, Td, uvd, Kd, c)
         for ta, tb in zip(a, b):
@@ -222,7 +215,6 @@ def test_refusals_at_the_raw_abi(zh):
     """A NULL d_err (and every other required pointer), B = 0, N = 0, J = 0 and row_offset = -1: ZEDO_E_BADARG, nothing written; a NULL
     d_conf is accepted."""
     lib = zh._lib
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
     J, N, H = 17, 3, 4
     B = N * H
     x = torch.full((B, J, 3), 0.25, device="cuda")
@@ -230,9 +222,7 @@ def test_refusals_at_the_raw_abi(zh):
     uv = torch.full((N, J, 2), 500.0, device="cuda")
     K = torch.tensor([[1100.0, 0, 500], [0, 1100, 500], [0, 0, 1]], device="cuda").repeat(N, 1, 1).contiguous()
     conf = torch.full((N, J), 0.5, device="cuda")
-    err = torch.full((B,), -7.0, dtype=torch.float64, device="cuda")
-    best = torch.full((N,), -7.0, dtype=torch.float64, device="cuda")
-    bh = torch.full((N,), -7, dtype=torch.int32, device="cuda")
+    err, best, bh = sentinels((((B,), torch.float64), ((N,), torch.float64), ((N,), torch.int32)))
     ptrs = [P(x), P(T), P(uv), P(K), P(conf), P(err), P(best), P(bh)]
     call = lambda p, b=B, n=N, j=J, off=0: lib.zedo_min_reproj(p[0], p[1], p[2], p[3], p[4], b, n, j, off, p[5], p[6], p[7], None)
     for k in (5, 0, 1, 2, 3, 6, 7):
@@ -257,16 +247,7 @@ def test_the_call_is_capturable(zh):
     with torch.cuda.stream(s):
         zh.min_reproj(x, T, uv, K, conf)                          # warm the allocator on the capture stream
     torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        out = zh.min_reproj(x, T, uv, K, conf)
-    for _ in range(2):
-        for t in out:
-            t.zero_()
-        g.replay()
-        torch.cuda.synchronize()
-        for to, te in zip(out, eager):
-            assert torch.equal(bits(to), bits(te))
+    replays_to(eager, lambda: zh.min_reproj(x, T, uv, K, conf), s)
 
 
 def test_pipeline_select_reproj_and_take(zh, weights0):

@@ -3,34 +3,19 @@
 zedo_min_mpjpe(procrustes = 0) writes and slot 1 what procrustes = 1 writes, BIT FOR BIT, through each of the three row-error
 kernels (generic, row-major staged, pose-major), both arg-min kernels, every joint count, shards, NaN and ties.
 
-bits(t): the int64 view of a float64 tensor; "equal" is torch.equal on bits (NaN payloads included).
+"equal" is torch.equal on _invariance.bits (NaN payloads included).
 The selection does not depend on the arithmetic mode of the dense layers: one session runs it."""
-import ctypes
-
 import numpy as np
 import pytest
 
+from _invariance import bits, misaligned, ptr as P, refusal_sweep, replays_to, sentinels
 from _shared import dev, one_arithmetic_mode, zh  # noqa: F401  (fixtures; one_arithmetic_mode is autouse)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 
-def bits(t):
-    return t.view(torch.int64) if t.dtype == torch.float64 else t
-
-
 NAMES = ("err", "best", "best_h")
-
-
-def unaligned(x):
-    """The same rows 4 bytes off a 16-byte boundary: the launch takes the generic one-lane-per-row kernel."""
-    B, J = x.shape[0], x.shape[1]
-    buf = torch.empty(B * J * 3 + 1, dtype=torch.float32, device="cuda")
-    xb = buf[1:].view(B, J, 3)
-    xb.copy_(x)
-    assert x.data_ptr() % 16 == 0 and xb.data_ptr() % 16 == 4 and xb.is_contiguous()
-    return xb
 
 
 def pair(zh, x, gt, N, off=0):
@@ -114,7 +99,7 @@ def test_both_generic_kernel_is_bitwise_the_aligned_run_and_the_two_calls(zh, N,
     """The same inputs with the row pointer 4 bytes off a 16-byte boundary (row_error_kernel): equal to the aligned run of the one
     call and to the two calls on the unaligned pointer."""
     x, gt, B = _row_major_case(N, H, off, cut, 166)
-    xb = unaligned(x)
+    xb = misaligned(x, floats=1)                                 # 4 bytes off a 16-byte boundary: the generic one-lane-per-row kernel
     both_b = zh.min_mpjpe_both(xb, gt, N, row_offset=off)
     assert_same(both_b, zh.min_mpjpe_both(x, gt, N, row_offset=off), "generic vs staged")
     assert_is_the_pair(both_b, pair(zh, xb, gt, N, off), "generic")
@@ -143,7 +128,7 @@ def test_both_pose_major_kernel_is_bitwise_the_two_calls(zh, pose_major_gt, shar
     xa = dev(x)
     both = zh.min_mpjpe_both(xa, gt, N, row_offset=off)
     assert_is_the_pair(both, pair(zh, xa, gt, N, off), shard)
-    assert_same(both, zh.min_mpjpe_both(unaligned(xa), gt, N, row_offset=off), shard + ": pose-major vs generic")
+    assert_same(both, zh.min_mpjpe_both(misaligned(xa, floats=1), gt, N, row_offset=off), shard + ": pose-major vs generic")
     assert int(torch.isnan(both[0][0]).sum()) == 2 and int(torch.isnan(both[0][1]).sum()) == 2
     held = torch.zeros(N, dtype=torch.bool, device="cuda")
     if shard == "partial":
@@ -229,22 +214,14 @@ def test_both_halves_feed_pose_min(zh):
 def test_both_refusals_at_the_raw_abi(zh):
     """A NULL pointer for each of the five pointers in turn, B = 0, N = 0, J = 0 and row_offset = -1: ZEDO_E_BADARG, nothing written."""
     lib = zh._lib
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
     B, N, J = 12, 4, 17
     x = torch.full((B, J, 3), 0.25, device="cuda")
     gt = torch.zeros((N, J, 3), dtype=torch.float64, device="cuda")
-    err = torch.full((2, B), -7.0, dtype=torch.float64, device="cuda")
-    best = torch.full((2, N), -7.0, dtype=torch.float64, device="cuda")
-    bh = torch.full((2, N), -7, dtype=torch.int32, device="cuda")
+    err, best, bh = sentinels((((2, B), torch.float64), ((2, N), torch.float64), ((2, N), torch.int32)))
     ptrs = [P(x), P(gt), P(err), P(best), P(bh)]
-    call = lambda p, b=B, n=N, j=J, off=0: lib.zedo_min_mpjpe_both(p[0], p[1], b, n, j, off, p[2], p[3], p[4], None)
-    for k in range(5):
-        assert call([None if i == k else p for i, p in enumerate(ptrs)]) == -1, k
-    assert call(ptrs, b=0) == -1 and call(ptrs, n=0) == -1 and call(ptrs, j=0) == -1 and call(ptrs, off=-1) == -1
-    torch.cuda.synchronize()
-    assert bool((err == -7.0).all()) and bool((best == -7.0).all()) and bool((bh == -7).all())
-    assert call(ptrs) == 0                                                       # the control: the same call is accepted
-    torch.cuda.synchronize()
+    call = lambda p=ptrs, b=B, n=N, j=J, off=0: lib.zedo_min_mpjpe_both(p[0], p[1], b, n, j, off, p[2], p[3], p[4], None)
+    refusal_sweep(call, ptrs, range(5), sizes=[dict(b=0), dict(n=0), dict(j=0), dict(off=-1)],
+                  untouched=((err, -7.0), (best, -7.0), (bh, -7)))              # ... and the control: the same call is accepted
     assert bool((err != -7.0).all()) and bool((best != -7.0).all()) and bool((bh >= 0).all())
 
 
@@ -287,12 +264,4 @@ def test_both_is_capturable(zh):
     with torch.cuda.stream(s):
         zh.min_mpjpe_both(x, gt, 23, row_offset=17)             # warm the allocator on the capture stream
     torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        out = zh.min_mpjpe_both(x, gt, 23, row_offset=17)
-    for _ in range(2):
-        for t in out:
-            t.zero_()
-        g.replay()
-        torch.cuda.synchronize()
-        assert_same(out, eager, "replay")
+    replays_to(eager, lambda: zh.min_mpjpe_both(x, gt, 23, row_offset=17), s)

@@ -5,14 +5,12 @@ reference of tests/_temporal_ref.py (pinned on its own in tests/test_temporal_re
 minimum the recurrence takes has a runner-up closer than 1e-6: an exact comparison of paths cannot hide behind a near tie.
 Bit identity across chunk sizes, a dirty workspace, stream capture, a side stream and the alignment of d_x; unaries from
 zedo_min_reproj; the limits (lambda = 0, clips of one frame); excluded rows and dead frames; the refusals of the raw ABI.
-bits(t): the int64 view of a float64 tensor.
 Whether the temporal path is closer to ground truth than the per-frame arg-min is not measured here or anywhere: these tests hold the
 arithmetic, not the criterion's accuracy.  The selection does not depend on the arithmetic mode of the dense layers: one session runs it."""
-import ctypes
-
 import numpy as np
 import pytest
 
+from _invariance import clamped_offsets, dirty, launch_invariant, misaligned, ptr as P, refusal_sweep, same, sentinels
 from _joint_ref import case as reproj_case
 from _select_ref import reproj_ref, select_ref
 from _shared import dev, one_arithmetic_mode, problem, zh  # noqa: F401  (fixtures; one_arithmetic_mode is autouse)
@@ -22,13 +20,7 @@ from _temporal_ref import (ALL_CASES, IDS, LAMBDAS, case, check_inputs, clips, c
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-
-def bits(t):
-    return t.view(torch.int64) if t.dtype == torch.float64 else t
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(bits(a), bits(b))
+OUT_SPECS = lambda N: (((N,), torch.int32), ((N,), torch.float64))
 
 
 def run(zh, x, u, seq, lam, chunk=0):
@@ -72,35 +64,18 @@ def test_the_bits_do_not_depend_on_the_chunk_the_workspace_or_the_stream(zh, J, 
         assert zh._lib.zedo_temporal_workspace_bytes(N, H, c) < zh._lib.zedo_temporal_workspace_bytes(N, H, 0)
         p, k = zh.temporal_select(ud, xd, seq, lam=lam, chunk_frames=c)
         assert same(p, path) and same(k, cost), c
-    # raw ABI: a dirty workspace, sized for chunks of 3 frames
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
-    nbytes = zh._lib.zedo_temporal_workspace_bytes(N, H, 3)
-    ws = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device="cuda")
-    assert bool(torch.isnan(ws[:nbytes // 8 * 8].view(torch.float64)).all())
+    nbytes = zh._lib.zedo_temporal_workspace_bytes(N, H, 3)         # the raw call: a workspace sized for chunks of 3 frames
     sd = torch.tensor(seq, dtype=torch.int32, device="cuda")
-    p = torch.full((N,), -7, dtype=torch.int32, device="cuda")
-    k = torch.full((N,), -7.0, dtype=torch.float64, device="cuda")
-    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    assert zh._lib.zedo_temporal_select(P(ud), P(xd), P(sd), len(seq) - 1, H, N, J, lam, P(ws), nbytes, P(p), P(k), st) == 0
-    torch.cuda.synchronize()
-    assert same(p, path) and same(k, cost)
-    # a side stream
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        p, k = zh.temporal_select(ud, xd, sd, lam=lam, chunk_frames=7)    # (also: seq_start as a device tensor; warms the allocator for the capture)
-    torch.cuda.synchronize()
-    assert same(p, path) and same(k, cost)
-    # captured (a single branch) and replayed: the call allocates nothing and synchronises nothing of its own
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        out = zh.temporal_select(ud, xd, sd, N=N, lam=lam, chunk_frames=7)
-    for _ in range(2):
-        for t in out:
-            t.zero_()
-        g.replay()
-        torch.cuda.synchronize()
-        assert same(out[0], path) and same(out[1], cost)
+
+    def raw(ws, o, st):
+        return zh._lib.zedo_temporal_select(P(ud), P(xd), P(sd), len(seq) - 1, H, N, J, lam, P(ws), nbytes, P(o[0]), P(o[1]), st)
+
+    def via_binding(x=xd, seq_on_device=False):
+        # under capture N is given: reading it off the device tensor would synchronise
+        return zh.temporal_select(ud, x, sd if seq_on_device else seq, N=N if torch.cuda.is_current_stream_capturing() else None, lam=lam,
+                                  chunk_frames=7)
+
+    launch_invariant((path, cost), via_binding, xd, raw, OUT_SPECS(N), nbytes)
 
 
 def test_an_unaligned_pose_tensor_gives_the_same_bits(zh):
@@ -108,10 +83,7 @@ def test_an_unaligned_pose_tensor_gives_the_same_bits(zh):
     x, u = case(J, N, H)
     xd, ud = dev(x), dev(u, torch.float64)
     path, cost = zh.temporal_select(ud, xd, clips(N, L), lam=100.0)
-    buf = torch.empty(H * N * J * 3 + 51, dtype=torch.float32, device="cuda")
-    xb = buf[51:].view(H * N, J, 3)
-    xb.copy_(xd)
-    assert xd.data_ptr() % 16 == 0 and xb.data_ptr() % 16 == 12 and xb.is_contiguous()
+    xb = misaligned(xd, floats=51)
     p, k = zh.temporal_select(ud, xb, clips(N, L), lam=100.0)
     assert same(p, path) and same(k, cost)
 
@@ -190,10 +162,7 @@ def test_clip_offsets_that_break_the_rules_are_clamped(zh):
     J, N, H = 17, 70, 50
     x, u = case(J, N, H)
     xd, ud = dev(x), dev(u, torch.float64)
-    path, cost = zh.temporal_select(ud, xd, [0, N], lam=100.0)
-    for seq in ([0, N + 1000], [-5, N]):
-        p, k = zh.temporal_select(ud, xd, seq, N=N, lam=100.0)
-        assert same(p, path) and same(k, cost), seq
+    clamped_offsets(lambda seq: zh.temporal_select(ud, xd, seq, N=N, lam=100.0), N)
 
 
 def test_refusals_at_the_raw_abi(zh):
@@ -201,7 +170,6 @@ def test_refusals_at_the_raw_abi(zh):
     INT_MAX: ZEDO_E_BADARG; a workspace one byte short of one frame of transitions: ZEDO_E_WORKSPACE; nothing written either way.  The
     same call with valid arguments is accepted."""
     lib = zh._lib
-    P = lambda t: ctypes.c_void_p(t.data_ptr())
     J, N, H, L = 5, 12, 3, 4
     x, u = case(J, N, H)
     xd, ud = dev(x), dev(u, torch.float64)
@@ -213,25 +181,16 @@ def test_refusals_at_the_raw_abi(zh):
     assert lib.zedo_temporal_workspace_bytes(N, H, 0) == lib.zedo_temporal_workspace_bytes(N, H, N) == lib.zedo_temporal_workspace_bytes(N, H, N + 9)
     assert lib.zedo_temporal_workspace_bytes(70880, 50, 0) - lib.zedo_temporal_workspace_bytes(70880, 50, 1) + 50 * 50 * 8 <= 256 << 20
     assert lib.zedo_temporal_workspace_bytes(0, H, 0) == 0 and lib.zedo_temporal_workspace_bytes(N, 2 ** 16, 0) == 0
-    ws = torch.full((one + 8,), 0x5A, dtype=torch.uint8, device="cuda")
-    path = torch.full((N,), -7, dtype=torch.int32, device="cuda")
-    cost = torch.full((N,), -7.0, dtype=torch.float64, device="cuda")
+    ws = dirty(one + 8, 0x5A)
+    path, cost = sentinels(OUT_SPECS(N))
     ptrs = [P(ud), P(xd), P(sd), P(ws), P(path), P(cost)]
 
     def call(p=ptrs, n_seq=len(seq) - 1, h=H, n=N, j=J, lam=100.0, nbytes=one):
         return lib.zedo_temporal_select(p[0], p[1], p[2], n_seq, h, n, j, lam, p[3], nbytes, p[4], p[5], None)
 
-    for k in range(6):
-        assert call([None if i == k else p for i, p in enumerate(ptrs)]) == -1, k
-    assert call(n_seq=0) == -1 and call(n_seq=N + 1) == -1 and call(h=0) == -1 and call(n=0) == -1 and call(j=0) == -1
-    assert call(lam=-1.0) == -1 and call(lam=float("nan")) == -1 and call(lam=float("inf")) == -1
-    assert call(h=2 ** 16, n=2 ** 16) == -1 and call(h=46341, n=1, n_seq=1) == -1
-    assert call([ctypes.c_void_p(ws.data_ptr() + 4) if i == 3 else p for i, p in enumerate(ptrs)]) == -1
-    assert call(nbytes=one - 1) == -3 and call(nbytes=0) == -3
-    torch.cuda.synchronize()
-    assert bool((path == -7).all()) and bool((cost == -7.0).all()) and bool((ws == 0x5A).all())
-    assert call() == 0                                               # the control
-    torch.cuda.synchronize()
+    sizes = [dict(n_seq=0), dict(n_seq=N + 1), dict(h=0), dict(n=0), dict(j=0), dict(h=2 ** 16, n=2 ** 16), dict(h=46341, n=1, n_seq=1)]
+    refusal_sweep(call, ptrs, range(6), sizes=sizes, weights=("lam",), workspace_slot=3, need=one,
+                  untouched=((path, -7), (cost, -7.0), (ws, 0x5A)))
     r = reference(J, N, H, L, 100.0)
     assert np.array_equal(path.cpu().numpy(), r["path"]) and bool((ws[one:] == 0x5A).all())
     with pytest.raises(ValueError):

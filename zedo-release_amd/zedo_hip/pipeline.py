@@ -199,6 +199,18 @@ class Pipeline:
         with torch.cuda.device(self.device):
             return joint_reproj(x, T, self.uv, self.K, self.N, row_offset)
 
+    def _joint_unaries(self, name, x, T, streams=None):
+        """What the joint-wise methods below start with: x holds all H*N rows (streams: of a whole number of frames of that many live
+        streams) - the ValueError speaks for the method `name` - and jerr [H*N,17] f64, zedo_joint_reproj's per-(row, joint) distances
+        on the problem of load(), formed on the pipeline's device."""
+        if x.shape[0] != self.H * self.N or (streams is not None and self.N % streams):
+            if streams is None:
+                raise ValueError(f"{name}: all {self.H * self.N} rows expected, got {x.shape[0]}")
+            raise ValueError(f"{name}: all {self.H * self.N} rows of a whole number of frames of {streams} streams expected, "
+                             f"got {x.shape[0]} rows for {self.N} poses")
+        with torch.cuda.device(self.device):
+            return joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)[2]
+
     def aggregate_tree(self, x, T, mu=100.0, parent=None):
         """aggregate_reproj with the skeleton as a coupling, on the problem of load(): x [H*N,17,3] and T [H*N,3], ALL rows (a pose's every
         hypothesis takes part) -> (joint_h [N,17] i32, cost [N] f64, bone [N,17] f64, jerr [H*N,17] f64): the unaries are
@@ -206,14 +218,11 @@ class Pipeline:
         mu (pixels per metre, default untuned) times every bone's mismatch between its assembled length and the length its two hypotheses
         give it (zedo_joint_tree_select, exact min-sum over the tree).  parent [17]: the bone tree, default H36M's.
         compose(x, T, joint_h, ref) assembles the pose."""
-        if x.shape[0] != self.H * self.N:
-            raise ValueError(f"aggregate_tree: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        jerr = self._joint_unaries("aggregate_tree", x, T)
         if parent is None:
             parent = skeleton_parents(H36M_EDGES, self.uv.shape[1])
         with torch.cuda.device(self.device):
-            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
-            joint_h, cost, bone = joint_tree_select(jerr, x, T, parent, self.N, mu, self.conf)
-        return joint_h, cost, bone, jerr
+            return joint_tree_select(jerr, x, T, parent, self.N, mu, self.conf) + (jerr,)
 
     def fuse_tree(self, x, T, mu=100.0, tau=1.0, parent=None):
         """The soft answer of aggregate_tree, on the problem of load(): x [H*N,17,3] and T [H*N,3], ALL rows -> (mean [N,17,3] f64, cov
@@ -222,14 +231,11 @@ class Pipeline:
         the exact posterior marginals of the same energy at the temperature tau (pixels), read as a fused position, its covariance, the
         most probable hypothesis, its probability, the component's log-partition value and every bone's expected mismatch
         (zedo_joint_tree_marginal, sum-product over the tree).  mu and tau: defaults untuned.  parent [17]: the bone tree, default H36M's."""
-        if x.shape[0] != self.H * self.N:
-            raise ValueError(f"fuse_tree: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        jerr = self._joint_unaries("fuse_tree", x, T)
         if parent is None:
             parent = skeleton_parents(H36M_EDGES, self.uv.shape[1])
         with torch.cuda.device(self.device):
-            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
-            out = joint_tree_marginal(jerr, x, T, parent, self.N, mu, tau, self.conf)
-        return out + (jerr,)
+            return joint_tree_marginal(jerr, x, T, parent, self.N, mu, tau, self.conf) + (jerr,)
 
     def compose(self, x_full, T_full, joint_idx, ref_idx=None):
         """The pose assembled from the joints aggregate_reproj selected: x_full [H*N,17,3], T_full [H*N,3] (all global rows), joint_idx
@@ -258,12 +264,9 @@ class Pipeline:
         are zedo_joint_reproj's per-(row, joint) distances (pixels), each joint's path minimises them plus lam (pixels per metre, default
         untuned) times that joint's displacement in the camera frame between consecutive choices (zedo_joint_temporal_select).
         compose(x, T, joint_path, ref) assembles the pose."""
-        if x.shape[0] != self.H * self.N:
-            raise ValueError(f"select_joints_temporal: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        jerr = self._joint_unaries("select_joints_temporal", x, T)
         with torch.cuda.device(self.device):
-            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
-            path, cost = joint_temporal_select(jerr, x, T, seq_start, self.N, lam)
-        return path, cost, jerr
+            return joint_temporal_select(jerr, x, T, seq_start, self.N, lam) + (jerr,)
 
     def open_joint_stream(self, S, lag, max_frames, lam=100.0):
         """The state of select_joints_temporal's chain for S live streams (JointStream): H and the joint count are those of the
@@ -280,25 +283,18 @@ class Pipeline:
         [H*N,17] f64): the unaries are zedo_joint_reproj's per-(row, joint) distances exactly as select_joints_temporal forms them; stream
         s emits the frames first[s] .. first[s] + count[s] - 1 of its clip (zedo_joint_stream_push).  The caller keeps x and T of the
         frames that are still to come out and assembles their poses with compose."""
-        if x.shape[0] != self.H * self.N or self.N % js.S:
-            raise ValueError(f"push_joints_temporal: all {self.H * self.N} rows of a whole number of frames of {js.S} streams expected, "
-                             f"got {x.shape[0]} rows for {self.N} poses")
+        jerr = self._joint_unaries("push_joints_temporal", x, T, js.S)
         with torch.cuda.device(self.device):
-            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
-            out = js.push(jerr, x, T, flush)
-        return out + (jerr,)
+            return js.push(jerr, x, T, flush) + (jerr,)
 
     def select_joints_accel(self, x, T, seq_start, lam=100.0, accel=100.0):
         """select_joints_temporal with a second-order motion model: the same inputs and outputs, each joint's path minimises its unaries
         plus lam times its displacement plus accel (pixels per metre, default untuned) times its second difference X[n] - 2 X[n-1] +
         X[n-2] in the camera frame, which is blind to a constant velocity (zedo_joint_accel_select; at most 64 hypotheses).  joint_cost
         is the cost of the kept path re-accumulated along it."""
-        if x.shape[0] != self.H * self.N:
-            raise ValueError(f"select_joints_accel: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        jerr = self._joint_unaries("select_joints_accel", x, T)
         with torch.cuda.device(self.device):
-            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
-            path, cost = joint_accel_select(jerr, x, T, seq_start, self.N, lam, accel)
-        return path, cost, jerr
+            return joint_accel_select(jerr, x, T, seq_start, self.N, lam, accel) + (jerr,)
 
     def fuse_joints_temporal(self, x, T, seq_start, lam=100.0, tau=1.0):
         """Joint-wise fusion along a video without ground truth on the problem of load(): x [H*N,17,3] and T [H*N,3], ALL rows, seq_start =
@@ -306,12 +302,9 @@ class Pipeline:
         jerr [H*N,17] f64): the unaries are zedo_joint_reproj's per-(row, joint) distances (pixels); the posterior mean position of every
         joint in the camera frame, its covariance, the most probable hypothesis and its probability under the chain model
         select_joints_temporal optimises, at the temperature tau in pixels (zedo_joint_marginal; lam and tau untuned)."""
-        if x.shape[0] != self.H * self.N:
-            raise ValueError(f"fuse_joints_temporal: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        jerr = self._joint_unaries("fuse_joints_temporal", x, T)
         with torch.cuda.device(self.device):
-            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
-            out = joint_marginal(jerr, x, T, seq_start, self.N, lam, tau)
-        return out + (jerr,)
+            return joint_marginal(jerr, x, T, seq_start, self.N, lam, tau) + (jerr,)
 
     def open_joint_fuse_stream(self, S, lag, max_frames, lam=100.0, tau=1.0):
         """The state of fuse_joints_temporal's chain model for S live streams (JointMarginalStream): H and the joint count are those of
@@ -328,13 +321,9 @@ class Pipeline:
         wmax [S,F+lag,17] f64, logz [S,F+lag,17] f64, jerr [H*N,17] f64): the unaries are zedo_joint_reproj's per-(row, joint) distances
         exactly as push_joints_temporal forms them; stream s emits the frames first[s] .. first[s] + count[s] - 1 of its clip, each as
         fuse_joints_temporal reports it on the clip cut `lag` frames later (zedo_joint_stream_marginal_push)."""
-        if x.shape[0] != self.H * self.N or self.N % js.S:
-            raise ValueError(f"push_fuse_joints_temporal: all {self.H * self.N} rows of a whole number of frames of {js.S} streams "
-                             f"expected, got {x.shape[0]} rows for {self.N} poses")
+        jerr = self._joint_unaries("push_fuse_joints_temporal", x, T, js.S)
         with torch.cuda.device(self.device):
-            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
-            out = js.push(jerr, x, T, flush)
-        return out + (jerr,)
+            return js.push(jerr, x, T, flush) + (jerr,)
 
     def fuse_joints_accel(self, x, T, seq_start, lam=100.0, accel=100.0, tau=1.0):
         """fuse_joints_temporal under the second-order motion model: the same inputs and outputs - (mean [N,17,3] f64, cov [N,17,6] f64,
@@ -343,12 +332,9 @@ class Pipeline:
         select_joints_accel optimises: lam times the displacement plus accel times the second difference X[n] - 2 X[n-1] + X[n-2], which is
         blind to a constant velocity, at the temperature tau in pixels (zedo_joint_accel_marginal; at most 64 hypotheses; lam, accel and
         tau untuned)."""
-        if x.shape[0] != self.H * self.N:
-            raise ValueError(f"fuse_joints_accel: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        jerr = self._joint_unaries("fuse_joints_accel", x, T)
         with torch.cuda.device(self.device):
-            _, _, jerr = joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)
-            out = joint_accel_marginal(jerr, x, T, seq_start, self.N, lam, accel, tau)
-        return out + (jerr,)
+            return joint_accel_marginal(jerr, x, T, seq_start, self.N, lam, accel, tau) + (jerr,)
 
     def take(self, rows_full, idx):
         """The winning row of every pose: rows_full [H*N, ...] (all global rows, h-major), idx [N] -> rows_full.view(H, N, ...)[idx, arange(N)].
