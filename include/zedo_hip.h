@@ -52,7 +52,9 @@ extern "C" {
                               * still 5 (additive): + zedo_joint_accel_marginal_workspace_bytes, zedo_joint_accel_marginal;
                               * still 5 (additive): + zedo_joint_stream_state_bytes, zedo_joint_stream_reset, zedo_joint_stream_push;
                               * still 5 (additive): + zedo_joint_stream_marginal_state_bytes, zedo_joint_stream_marginal_reset,
-                              *                       zedo_joint_stream_marginal_push */
+                              *                       zedo_joint_stream_marginal_push;
+                              * still 5 (additive): + zedo_joint_accel_stream_state_bytes, zedo_joint_accel_stream_reset,
+                              *                       zedo_joint_accel_stream_push */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -601,6 +603,60 @@ size_t zedo_joint_accel_workspace_bytes(int N, int H, int J);
 int zedo_joint_accel_select(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
                             int H, int N, int J, double lambda_v, double lambda_a, void *d_workspace, size_t workspace_bytes,
                             int *d_path_h, double *d_cost, void *stream);
+
+/* ---- the second-order model on a LIVE video: fixed-lag streaming Viterbi over pairs -----------------------------------------
+ * zedo_joint_stream_push serves live input with the first-order chain, whose motion term gets cheaper the faster a limb moves;
+ * zedo_joint_accel_select fixes that but needs the whole clip.  This is zedo_joint_accel_select's chain over pairs as an online
+ * call for S independent streams: frames are pushed in chunks of any size, the tables live in d_state between the calls, and the
+ * decision for a frame comes out `lag` frames after the frame went in.  lambda_v, lambda_a and the lag are UNTUNED; accuracy on
+ * real video is UNMEASURED.
+ * The chunk (d_junary, d_x, d_T; rows (h,n) h-major, n = s*F + f), d_flush, d_which, d_emit [S,2], the emitted count and the
+ * `first` emitted frame, F = 0 being legal only with d_flush, rows at and after the count not being written, a dead (n,j)
+ * reporting hypothesis 0 and cost +inf, and the frame after a flush being t = 0 of a new clip are those of
+ * zedo_joint_stream_push, word for word.  X, u, m, a, DEAD, "chain", E, back2 and the tie rules are those of
+ * zedo_joint_accel_select on the stream's clip, word for word: prefix quantities, which do not depend on the chunking.
+ *   For a live (n,j) let c_j(n) be the last frame of n's chain on the frames the clip holds after the push that emits n, c0 the
+ *   chain's first frame, and e = min(n + lag, c_j(n)).  Then
+ *     e == c0 (a chain of one frame so far):  path[n,j] = the lowest h that minimises u[e,j,.];  cost[n,j] = that minimum
+ *     otherwise:  (h',h) = the pair with the smallest E[e], ties to the lowest h' H + h;  p_e = h, p_{e-1} = h';
+ *                 p_{m-2} = back2[m][p_{m-1}, p_m] for m = e .. n+2;  path[n,j] = p_n;  cost[n,j] = min E[e]
+ * d_cost is the cost of the best path on the clip cut after e, a path that passes through path[n,j].  It is deliberately NOT
+ * the re-accumulated cost of zedo_joint_accel_select: fixed-lag decisions of consecutive frames need not lie on one path, so
+ * there is no path to re-accumulate along.
+ * So the decision for frame n is the path of zedo_joint_accel_select on the clip cut after frame n + lag; lag = 0 gives the h of
+ * the arg-min pair of E[n]; the outputs do not depend on the chunking; with lag >= the clip's length - 1 and a flush the paths
+ * are the offline call's bits.
+ * Outputs: d_path_h [S, F+lag, J] int32, d_cost [S, F+lag, J] float64, d_emit [S,2] int64, as zedo_joint_stream_push.
+ * zedo_joint_accel_stream_reset is zedo_joint_stream_reset on this state.
+ * State (8-byte aligned, need not be initialised before its first reset, must have been reset before its first push), with
+ * R = lag + max_frames rows per ring, SJ = S*J chains and HH = H*H, in this order:
+ *   one 16-byte record per frame of the ring [SJ,R]: min E (a chain's first frame: min u) float64, the arg-min pair h' H + h (a
+ *   chain's first frame: h) int32, the frame's kind (0 dead, 1 first of a chain, 2 inside one) int32 | one block of HH + 7 H + 1
+ *   float64 per chain [SJ]: E [HH], X [H,3] of the clip's last frame, X [H,3] of the one before, u [H] of the last frame, and the
+ *   dead flags of those two frames as two int32 | the clip's frame count int64 [S] | the dead flags of the ring's frames int32
+ *   [SJ,R] | back2, one byte per pair, uint8 [SJ,R,HH]
+ * - zedo_joint_accel_stream_state_bytes = 8 (SJ R + SJ HH + 7 SJ H + S) + 4 (3 SJ R + 2 SJ) + SJ R HH rounded up to 8; 0 for
+ * shapes the calls refuse.  That is 27 MB at S = 16, J = 17, H = 50, lag = 30, max_frames = 1.  E is not kept for the ring's
+ * frames (8 HH bytes per frame).  Frame m of a clip sits in row m % R.  A push writes the rows of its F <= max_frames frames and
+ * then reads at most the lag frames before them: never a row it has overwritten.  The flags of the two frames before a chunk
+ * have slots of their own (with lag = 0 and F = max_frames the chunk has reused their rows).
+ * Contract: 1 <= H <= 64 (the pair table stays in the LDS), J >= 1, S >= 1, max_frames >= 1, 0 <= F <= max_frames, lag >= 0,
+ * (lag + max_frames)*S*J*H*H <= INT_MAX, finite lambda_v >= 0 and lambda_a >= 0; ZEDO_E_BADARG with nothing written and the
+ * state untouched for a NULL pointer other than d_T, d_flush (F > 0) and d_which, a size out of these ranges, H > 64, F = 0
+ * without d_flush, a negative or non-finite lambda_v or lambda_a, or a state that is not 8-byte aligned; ZEDO_E_WORKSPACE with
+ * nothing written and the state untouched if state_bytes is too small; allocates nothing, synchronises nothing, enqueues on
+ * `stream` only: legal under stream capture - a replay advances the state.  No atomics, no scratch: the bits do not depend on
+ * the run, the chunking, the content of the state before its reset or the alignment of d_x.  Every value read from the state is
+ * clamped before it is an index.  lambda_v and lambda_a are taken to be the same in every push between a frame going in and
+ * coming out.  One workgroup per (stream, joint) for the recurrence - the H^3 walk of zedo_joint_accel_select plus one block
+ * reduction per live frame; one wave per (emitted frame, stream, joint) for the decision: at most max(0, lag - 1) dependent
+ * reads of back2. */
+size_t zedo_joint_accel_stream_state_bytes(int S, int H, int J, int lag, int max_frames);
+int zedo_joint_accel_stream_reset(void *d_state, size_t state_bytes, int S, int H, int J, int lag, int max_frames,
+                                  const int *d_which, void *stream);
+int zedo_joint_accel_stream_push(const double *d_junary, const float *d_x, const float *d_T, int S, int F, int H, int J,
+                                 int lag, int max_frames, double lambda_v, double lambda_a, const int *d_flush, void *d_state,
+                                 size_t state_bytes, int *d_path_h, double *d_cost, long long *d_emit, void *stream);
 
 /* ---- fusing hypotheses along a video under the second-order motion model: exact sum-product over pairs ----------------------
  * The soft answer of zedo_joint_accel_select, as zedo_joint_marginal is the soft answer of zedo_joint_temporal_select: the same

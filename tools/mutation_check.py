@@ -74,6 +74,9 @@ MUTANTS = [
     # first-order chain green (tests/test_joint_temporal_gpu.py, tests/test_joint_stream_gpu.py, tests/test_select_joints_temporal_driver_gpu.py;
     # profiles/chain_shared_scan.txt: run against these six files)
     ("ZEDO_MUT_JA_FIRST_DIFF", "zedo_joint_accel_select and zedo_joint_accel_marginal: the second difference is taken as X[n] - X[n-1] + X[n-2], the factor 2 is dropped (zedo_chain.h accel_lead: the scan and cost kernels of the selection, the forward and backward kernels of the fusion)"),
+    # the second-order selection on live streams (tests/test_joint_accel_stream_gpu.py; profiles/mutation_joint_accel_stream.txt): leaves
+    # every other test green, and of that file the lag-0 comparisons, the clips that end before the shortened horizon matters and the refusals
+    ("ZEDO_MUT_JAS_HORIZON", "zedo_joint_accel_stream_push: the horizon of frame n is taken as n + lag - 1, one frame short (zedo_joint_accel_stream.hip joint_accel_stream_emit_kernel)"),
     # the skeleton-coupled aggregation (tests/test_joint_tree_gpu.py, tests/test_select_joints_tree_driver_gpu.py) and, since its sum-product
     # twin shares the statement, the skeleton-coupled fusion's tests: leaves every other test green
     ("ZEDO_MUT_TREE_NO_HALF", "zedo_joint_tree_select and zedo_joint_tree_marginal: the bone term compares the assembled length with the SUM of the two hypotheses' lengths, the 0.5 is dropped (zedo_chain.h tr_bone: the recurrences and bone[n,.])"),

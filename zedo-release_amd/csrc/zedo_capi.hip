@@ -1017,6 +1017,42 @@ extern "C" int zedo_joint_accel_select(const double *d_junary, const float *d_x,
     return ZEDO_OK;
 }
 
+// the second-order model on live streams: back2 and the arg-min pair of lag + max_frames frames per (stream, joint) in the caller's state
+// the shapes the three entry points accept: those of the first-order streams at H <= 64, and (lag + max_frames) S J H^2 within int
+static bool accel_stream_dims_ok(int S, int H, int J, int lag, int max_frames) {
+    if (!stream_dims_ok(S, H, J, lag, max_frames) || H > JOINT_ACCEL_HMAX) return false;
+    return ((long long)lag + max_frames) * ((long long)S * J * H) * H <= INT_MAX;
+}
+static int accel_stream_state_ok(const void *state, size_t state_bytes, int S, int H, int J, int lag, int max_frames) {
+    if (!state || !accel_stream_dims_ok(S, H, J, lag, max_frames) || (reinterpret_cast<uintptr_t>(state) & 7)) return ZEDO_E_BADARG;
+    return state_bytes < joint_accel_stream_bytes(S, H, J, lag, max_frames) ? ZEDO_E_WORKSPACE : ZEDO_OK;
+}
+
+extern "C" size_t zedo_joint_accel_stream_state_bytes(int S, int H, int J, int lag, int max_frames) {
+    return accel_stream_dims_ok(S, H, J, lag, max_frames) ? joint_accel_stream_bytes(S, H, J, lag, max_frames) : 0;
+}
+
+extern "C" int zedo_joint_accel_stream_reset(void *d_state, size_t state_bytes, int S, int H, int J, int lag, int max_frames,
+                                             const int *d_which, void *stream) {
+    const int rc = accel_stream_state_ok(d_state, state_bytes, S, H, J, lag, max_frames);
+    if (rc != ZEDO_OK) return rc;
+    HIPCHK(launch_joint_accel_stream_reset(d_state, S, H, J, lag, max_frames, d_which, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
+extern "C" int zedo_joint_accel_stream_push(const double *d_junary, const float *d_x, const float *d_T, int S, int F, int H, int J, int lag,
+                                            int max_frames, double lambda_v, double lambda_a, const int *d_flush, void *d_state,
+                                            size_t state_bytes, int *d_path_h, double *d_cost, long long *d_emit, void *stream) {
+    if (!d_path_h || !d_cost || !d_emit || F < 0 || F > max_frames) return ZEDO_E_BADARG;
+    if (F == 0 ? !d_flush : (!d_junary || !d_x)) return ZEDO_E_BADARG;                   // a push of no frames is a flush
+    if (!std::isfinite(lambda_v) || lambda_v < 0.0 || !std::isfinite(lambda_a) || lambda_a < 0.0) return ZEDO_E_BADARG;
+    const int rc = accel_stream_state_ok(d_state, state_bytes, S, H, J, lag, max_frames);
+    if (rc != ZEDO_OK) return rc;
+    HIPCHK(launch_joint_accel_stream_push(d_junary, d_x, d_T, S, F, H, J, lag, max_frames, lambda_v, lambda_a, d_flush, d_state, d_path_h,
+                                          d_cost, d_emit, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
 // posterior marginals of the second-order model: forward-backward over pairs per (clip, joint), A2 in the workspace
 extern "C" size_t zedo_joint_accel_marginal_workspace_bytes(int N, int H, int J) {
     return chain_dims_ok(N, H, J, JOINT_ACCEL_HMAX) ? joint_accel_marginal_bytes(N, H, J) : 0;

@@ -1,12 +1,12 @@
 // What the label-free selection and fusion kernels share (zedo_temporal.hip, zedo_joint_temporal.hip, zedo_joint_stream.hip,
-// zedo_joint_stream_marginal.hip, zedo_joint_marginal.hip, zedo_joint_accel.hip, zedo_joint_accel_marginal.hip, zedo_joint_tree.hip, zedo_joint_tree_marginal.hip): the one
+// zedo_joint_stream_marginal.hip, zedo_joint_marginal.hip, zedo_joint_accel.hip, zedo_joint_accel_stream.hip, zedo_joint_accel_marginal.hip, zedo_joint_tree.hip, zedo_joint_tree_marginal.hip): the one
 // copy of their lane layout, their reductions and their staging.  The rules every user relies on live here and nowhere else:
 //   - a tie goes to the lowest index (strict comparisons, parts and waves combined in ascending order);
 //   - a sum is a butterfly inside each wave, then the waves in ascending order: a fixed order, no atomics;
 //   - a lane past H reads row H-1 and stores nothing;
 //   - an offset read from seq_start is clamped to 0 .. N before it is an address.
-// The recurrences themselves - what is minimised or summed - stay in their own files; the two that two files run, the first-order
-// chain's frame step and its sum-product twin, are here.
+// The recurrences themselves - what is minimised or summed - stay in their own files; the three that two files run, the first-order
+// chain's frame step, its sum-product twin and the second-order chain's frame step, are here.
 #pragma once
 #include "zedo_internal.h"
 
@@ -362,6 +362,42 @@ __device__ __forceinline__ double accel_lead(double a, double p) {
                 lm[k] = (W) * sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);                                                           \
                 INIT                                                                                                                   \
             }
+// ---- the second-order chain's frame step (joint_accel_scan_kernel on a whole clip, joint_accel_stream_scan_kernel on a chunk of it) ----
+// Everything that decides a bit of E or back2, between a kernel's barriers A and B, as statements in the kernel's own scope - the
+// streaming call promises the offline call's bits: the second-frame rule, the H^3 walk with its strict comparison, the final additions.
+// Leaves E[n] of the lane's pairs in en [KA] and the lowest h'' in bn [KA] (not at a second frame).  A kernel keeps what is its own:
+// where back2 lives, where "start" and "second" come from, what a frame's arg-min is for.  In scope: H, inf, lambda_v, lambda_a; qh1,
+// qh0 [KA]; scan (n continues a chain) and second, workgroup-uniform; of the LDS: sE = E[n-1] h''-major, X0, X1, X2 = X of frames n, n-1,
+// n-2, U0, U1 = u of frames n, n-1.
+#define ZEDO_CHAIN_PAIR_STEP(KA)                                                                                                       \
+        if (scan) {                                                                                                                    \
+            ZEDO_CHAIN_PAIR_TERMS(KA, lambda_v, en[k] = inf; bn[k] = 0;)      /* g_c = X[n,h,c] - 2 X[n-1,h',c];  lm = lambda_v m */    \
+            if (second) {                                                                                                              \
+                _Pragma("unroll") for (int k = 0; k < KA; ++k) en[k] = U1[qh1[k]] + (U0[qh0[k]] + lm[k]);                              \
+            } else {                                                                                                                   \
+                for (int h2 = 0; h2 < H; ++h2) {                                                                                       \
+                    const double p0 = X2[h2 * 3], p1 = X2[h2 * 3 + 1], p2 = X2[h2 * 3 + 2];   /* broadcast */                          \
+                    const double *row = sE + h2 * H;                                                                                   \
+                    _Pragma("unroll") for (int k = 0; k < KA; ++k) {                                                                   \
+                        const double e0 = g[k][0] + p0, e1 = g[k][1] + p1, e2 = g[k][2] + p2;                                          \
+                        const double c = row[qh1[k]] + lambda_a * sqrt(e0 * e0 + e1 * e1 + e2 * e2);                                   \
+                        if (h2 == 0 || c < en[k]) { en[k] = c; bn[k] = h2; }  /* strict: the lowest h'' that attains the minimum */    \
+                    }                                                                                                                  \
+                }                                                                                                                      \
+                _Pragma("unroll") for (int k = 0; k < KA; ++k) en[k] = U0[qh0[k]] + (lm[k] + en[k]);                                   \
+            }                                                                                                                          \
+        }
+// The horizon of frame n on a live stream, by one wave: the last frame of n's chain among n .. hi - the first m whose successor's flag in
+// the ring dr [R] is set, or hi.  64 flags per step, by ballot; wave-uniform.
+__device__ __forceinline__ long long stream_horizon(const int *__restrict__ dr, long long n, long long hi, int R, int lane) {
+    for (long long m0 = n + 1; m0 <= hi; m0 += 64) {
+        const long long m = m0 + lane;
+        const int d = m <= hi ? dr[(int)(m % R)] : 0;
+        const unsigned long long mask = __ballot(d != 0);
+        if (mask) return m0 + (__ffsll((long long)mask) - 1) - 1;
+    }
+    return hi;
+}
 
 // ---- the bone tree: one workgroup per pose, everything in the LDS ----
 // sqrt(d0^2 + d1^2 + d2^2), d = a - b: products, then the sum ascending in c

@@ -271,6 +271,13 @@ hipError_t launch_joint_marginal(const double *junary, const float *x, const flo
 size_t joint_accel_bytes(int N, int H, int J);
 hipError_t launch_joint_accel_select(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,
                                      int J, double lambda_v, double lambda_a, void *ws, int *path, double *cost, hipStream_t st);
+// the same second-order chain on live streams (zedo_joint_accel_stream.hip); state: joint_accel_stream_bytes(S, H, J, lag, max_frames),
+// H <= 64, F <= max_frames
+size_t joint_accel_stream_bytes(int S, int H, int J, int lag, int max_frames);
+hipError_t launch_joint_accel_stream_reset(void *state, int S, int H, int J, int lag, int max_frames, const int *which, hipStream_t st);
+hipError_t launch_joint_accel_stream_push(const double *junary, const float *x, const float *T, int S, int F, int H, int J, int lag,
+                                          int max_frames, double lambda_v, double lambda_a, const int *flush, void *state, int *path,
+                                          double *cost, long long *emit, hipStream_t st);
 // posterior marginals of the second-order chain model (zedo_joint_accel_marginal.hip); ws: joint_accel_marginal_bytes(N, H, J), H <= 64;
 // c_v = lambda_v / tau, c_a = lambda_a / tau
 size_t joint_accel_marginal_bytes(int N, int H, int J);

@@ -73,26 +73,7 @@ __global__ __launch_bounds__(CHAIN_T) void joint_accel_scan_kernel(const double 
         double en[KA];
         int bn[KA];
         __syncthreads();                                           // A: E[n-1], X[n], X[n-1], X[n-2], u[n], u[n-1] are in the LDS
-        if (scan) {
-            ZEDO_CHAIN_PAIR_TERMS(KA, lambda_v, en[k] = inf; bn[k] = 0;)       // g_c = X[n,h,c] - 2 X[n-1,h',c];  lm = lambda_v m
-            if (second) {
-#pragma unroll
-                for (int k = 0; k < KA; ++k) en[k] = U1[qh1[k]] + (U0[qh0[k]] + lm[k]);
-            } else {
-                for (int h2 = 0; h2 < H; ++h2) {
-                    const double p0 = X2[h2 * 3], p1 = X2[h2 * 3 + 1], p2 = X2[h2 * 3 + 2];   // broadcast
-                    const double *row = sE + h2 * H;
-#pragma unroll
-                    for (int k = 0; k < KA; ++k) {
-                        const double e0 = g[k][0] + p0, e1 = g[k][1] + p1, e2 = g[k][2] + p2;
-                        const double c = row[qh1[k]] + lambda_a * sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-                        if (h2 == 0 || c < en[k]) { en[k] = c; bn[k] = h2; }      // strict: the lowest h'' that attains the minimum
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < KA; ++k) en[k] = U0[qh0[k]] + (lm[k] + en[k]);
-            }
-        }
+        ZEDO_CHAIN_PAIR_STEP(KA)                                   // the frame's step (zedo_chain.h): E[n] into en, the lowest h'' into bn
         double v = inf;                                            // a chain of one frame: the candidates are u[n,.]
         int vq = INT_MAX;
         if (ends && start && tid < H) { v = U0[tid]; vq = tid; }

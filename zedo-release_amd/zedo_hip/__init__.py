@@ -79,6 +79,9 @@ SIGNATURES = {
     "zedo_joint_stream_push": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "zedo_joint_accel_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_accel_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp]),
+    "zedo_joint_accel_stream_state_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "zedo_joint_accel_stream_reset": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _vp]),
+    "zedo_joint_accel_stream_push": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "zedo_joint_accel_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_accel_marginal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_joint_stream_marginal_state_bytes": (_sz, [_i, _i, _i, _i, _i]),
@@ -672,6 +675,7 @@ class JointStream:
     the per-frame choice is not measured."""
 
     _WHAT, _CALL = "JointStream", "zedo_joint_stream"              # the entry points: _CALL + "_state_bytes", "_reset", "_push"
+    _RANGE = "1 <= H <= 1024, lag >= 0, sizes >= 1, (lag + max_frames) S J H <= INT_MAX"
 
     def __init__(self, S, H, J, lag, max_frames, lam=100.0, device=None):
         _need_gpu()
@@ -680,7 +684,7 @@ class JointStream:
         self.state_bytes = int(getattr(_lib, self._CALL + "_state_bytes")(int(S), int(H), int(J), int(lag), int(max_frames)))
         if self.state_bytes == 0:
             raise ZedoError(f"{self._WHAT}: S = {S}, H = {H}, J = {J}, lag = {lag}, max_frames = {max_frames} is outside the range of "
-                            f"{self._CALL}_push (1 <= H <= 1024, lag >= 0, sizes >= 1, (lag + max_frames) S J H <= INT_MAX)")
+                            f"{self._CALL}_push ({self._RANGE})")
         with torch.cuda.device(self.device):
             self.state = torch.empty((self.state_bytes,), dtype=torch.uint8, device=self.device)
         self.reset()
@@ -808,6 +812,44 @@ def joint_accel_select(junary, x_full, T_full, seq_start, N=None, lam=100.0, acc
                                             J, float(lam), float(accel), _p(ws, torch.uint8), nbytes, _p(path, torch.int32),
                                             _p(cost, torch.float64), _stream(dev)))
     return path, cost
+
+
+def joint_accel_stream_state_bytes(S, H, J, lag, max_frames):
+    """The bytes of state zedo_joint_accel_stream_push needs for S streams of H hypotheses and J joints at this lag and at most
+    max_frames frames per push (host arithmetic: no GPU needed); 0 for a shape the calls refuse."""
+    return int(_lib.zedo_joint_accel_stream_state_bytes(int(S), int(H), int(J), int(lag), int(max_frames)))
+
+
+class JointAccelStream(JointStream):
+    """Joint-wise selection on a live video under the second-order motion model (zedo_joint_accel_stream_push): the chain over pairs of
+    joint_accel_select for S independent streams, fed in chunks of at most max_frames frames, every frame decided `lag` frames after it
+    went in - the path of joint_accel_select on the stream's clip (the frames since its last reset or flush) cut after frame n + lag.
+    lag = 0 gives the h of the arg-min pair of E[n]; with lag >= the clip's length - 1 and a flush at the end the paths are
+    joint_accel_select's bits.  cost is the cost of the best path on the clip cut at the frame's horizon - not joint_accel_select's
+    re-accumulated cost: fixed-lag decisions of consecutive frames need not lie on one path.  At most 64 hypotheses.  Owns the state on
+    `device` and resets it on creation.  lam, accel and lag are untuned; accuracy on real video is unmeasured."""
+    _WHAT, _CALL = "JointAccelStream", "zedo_joint_accel_stream"
+    _RANGE = "1 <= H <= 64, lag >= 0, sizes >= 1, (lag + max_frames) S J H^2 <= INT_MAX"
+
+    def __init__(self, S, H, J, lag, max_frames, lam=100.0, accel=100.0, device=None):
+        self.accel = float(accel)
+        super().__init__(S, H, J, lag, max_frames, lam, device)
+
+    def push(self, junary, x, T=None, flush=None):
+        """The chunk and flush of JointStream.push -> (first [S] i64, count [S] i64, path [S,F+lag,J] i32, cost [S,F+lag,J] f64), rows
+        as there.  junary = None: a push of no frames (flush required)."""
+        fl, F, dev = self._chunk(junary, x, T, flush)
+        S, H, J = self.S, self.H, self.J
+        with torch.cuda.device(dev):
+            rows = F + self.lag                                      # lag = 0 and no frames: a row nobody writes keeps the pointers non-NULL
+            path = torch.empty((S, max(rows, 1), J), dtype=torch.int32, device=dev)
+            cost = torch.empty((S, max(rows, 1), J), dtype=torch.float64, device=dev)
+            emit = torch.empty((S, 2), dtype=torch.int64, device=dev)
+            _check(_lib.zedo_joint_accel_stream_push(_p(junary, torch.float64), _p(x), _p(T), S, F, H, J, self.lag, self.max_frames,
+                                                     self.lam, self.accel, _p(fl, torch.int32), _p(self.state, torch.uint8),
+                                                     self.state_bytes, _p(path, torch.int32), _p(cost, torch.float64),
+                                                     _p(emit, torch.int64), _stream(dev)))
+        return emit[:, 0], emit[:, 1], path[:, :rows], cost[:, :rows]
 
 
 # the 16 bones every ported dataset's get_skeleton() returns (H36M's 17 joints)

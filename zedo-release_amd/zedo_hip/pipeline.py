@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import (H36M_EDGES, SINGULAR_MSG, JointMarginalStream, JointStream, Schedule, Weights, ZedoError, ipo_fit, joint_accel_marginal, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
+from . import (H36M_EDGES, SINGULAR_MSG, JointAccelStream, JointMarginalStream, JointStream, Schedule, Weights, ZedoError, ipo_fit, joint_accel_marginal, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
                joint_temporal_select, joint_tree_marginal, joint_tree_select, skeleton_parents, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
@@ -295,6 +295,25 @@ class Pipeline:
         jerr = self._joint_unaries("select_joints_accel", x, T)
         with torch.cuda.device(self.device):
             return joint_accel_select(jerr, x, T, seq_start, self.N, lam, accel) + (jerr,)
+
+    def open_joint_accel_stream(self, S, lag, max_frames, lam=100.0, accel=100.0):
+        """The state of select_joints_accel's chain over pairs for S live streams (JointAccelStream): H (at most 64) and the joint count
+        are those of the pipeline, every frame is decided `lag` frames after it went in, a push holds at most max_frames frames per
+        stream.  lam, accel and the choice of lag are untuned."""
+        if getattr(self, "uv", None) is None:
+            raise ZedoError("open_joint_accel_stream: call load() first (the joint count is the problem's)")
+        return JointAccelStream(S, self.H, self.uv.shape[1], lag, max_frames, lam, accel, self.device)
+
+    def push_joints_accel(self, js, x, T, flush=None):
+        """select_joints_accel on live input, on the problem of load() with N = S F poses - F new frames of each of the S streams of
+        js = open_joint_accel_stream(...), pose n = s F + f: x [H*N,17,3] and T [H*N,3], ALL rows; flush: None, or [S] flags - the
+        streams whose clip ends here.  -> (first [S] i64, count [S] i64, joint_path [S,F+lag,17] i32, joint_cost [S,F+lag,17] f64, jerr
+        [H*N,17] f64): the unaries are zedo_joint_reproj's per-(row, joint) distances exactly as push_joints_temporal forms them; stream
+        s emits the frames first[s] .. first[s] + count[s] - 1 of its clip, each as select_joints_accel decides it on the clip cut `lag`
+        frames later (zedo_joint_accel_stream_push); joint_cost is the cost of the best path on that cut clip."""
+        jerr = self._joint_unaries("push_joints_accel", x, T, js.S)
+        with torch.cuda.device(self.device):
+            return js.push(jerr, x, T, flush) + (jerr,)
 
     def fuse_joints_temporal(self, x, T, seq_start, lam=100.0, tau=1.0):
         """Joint-wise fusion along a video without ground truth on the problem of load(): x [H*N,17,3] and T [H*N,3], ALL rows, seq_start =
