@@ -5,6 +5,7 @@ Imported by the tests, by the child scripts they embed and by tools/ the way tes
 
 Nothing of lib.*, run.*, zedo_hip or zedo_oracle is imported at module level: tools/gen_golden.py runs with the reference's `lib`
 first on sys.path, the tests with the mirror's, and each function binds the one its caller has."""
+import ctypes
 import functools
 import hashlib
 import json
@@ -19,6 +20,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+LIB = os.path.join(ROOT, "zedo-release_amd", "zedo_hip", "libzedo_hip.so")
 
 
 # ---- 1. noise and scores -------------------------------------------------------------------------------------------------
@@ -338,6 +340,21 @@ class Capture:
 
 def dev(a, dtype=torch.float32):
     return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
+
+
+def host_lib():
+    """libzedo_hip.so as a ctypes.CDLL, for the CPU tests of its exports and its host arithmetic; built first if it is missing.  torch
+    is imported above: it must precede the dlopen of libzedo_hip.so, since torch bundles its own HIP runtime."""
+    if not os.path.exists(LIB):
+        import __graft_entry__
+        __graft_entry__.build()
+    return ctypes.CDLL(LIB)
+
+
+def host_fn(name, restype, argtypes):
+    fn = getattr(host_lib(), name)
+    fn.restype, fn.argtypes = restype, argtypes
+    return fn
 
 
 def cfg_path(name):

@@ -5,10 +5,9 @@ import os
 import re
 
 import pytest
-import torch  # noqa: F401  (must precede dlopen of libzedo_hip.so: torch bundles its own HIP runtime)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "zedo-release_amd", "zedo_hip", "libzedo_hip.so")
+from _shared import ROOT, host_lib  # (imports torch first: it must precede the dlopen of libzedo_hip.so, torch bundles its own HIP runtime)
+
 HDR = os.path.join(ROOT, "include", "zedo_hip.h")
 
 
@@ -20,10 +19,7 @@ def declared_functions():
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(LIB):
-        import __graft_entry__
-        __graft_entry__.build()
-    return ctypes.CDLL(LIB)
+    return host_lib()
 
 
 def test_header_declares_the_expected_surface():

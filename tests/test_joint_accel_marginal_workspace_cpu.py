@@ -3,13 +3,11 @@ is host arithmetic).  With nj = N J and pad8 rounding up to 8 bytes:
     zedo_joint_accel_marginal_workspace_bytes = 8 nj H^2 + pad8(4 nj)       A2 f64 [J,N,H,H] | dead i32
 and 0 for a shape outside the entry point's range (H above 64, a non-positive size, N J or N J H past INT_MAX)."""
 import ctypes
-import os
 
 import pytest
-import torch  # noqa: F401  (must precede dlopen of libzedo_hip.so: torch bundles its own HIP runtime)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "zedo-release_amd", "zedo_hip", "libzedo_hip.so")
+from _shared import host_fn  # (imports torch first: it must precede the dlopen of libzedo_hip.so, torch bundles its own HIP runtime)
+
 INT_MAX = 2 ** 31 - 1
 CAP = 64
 
@@ -19,13 +17,7 @@ SHAPES = [(1, 1, 1), (3, 7, 5), (70, 50, 17), (2, 3, 64), (2, 3, 65), (1015, 50,
 
 @pytest.fixture(scope="module")
 def fn():
-    if not os.path.exists(LIB):
-        import __graft_entry__
-        __graft_entry__.build()
-    f = ctypes.CDLL(LIB).zedo_joint_accel_marginal_workspace_bytes
-    f.restype = ctypes.c_size_t
-    f.argtypes = [ctypes.c_int] * 3
-    return f
+    return host_fn("zedo_joint_accel_marginal_workspace_bytes", ctypes.c_size_t, [ctypes.c_int] * 3)
 
 
 def formula(N, H, J):

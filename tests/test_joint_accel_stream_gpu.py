@@ -17,102 +17,22 @@ arithmetic.  The selection does not depend on the arithmetic mode of the dense l
 import numpy as np
 import pytest
 
-from _invariance import cur_stream, dirty, launch_invariant, ptr as P, refusal_sweep, same, sentinels
+from _invariance import all_same, launch_invariant, misaligned, ptr as P, refusal_sweep, same
 from _joint_accel_ref import cost_bound
-from _joint_accel_stream_ref import (BIG, BIG_WEIGHTS, GPU_CASES, LAGS, WEIGHTS, case, chunkings, clips, dead_joint_case, emitted,
-                                     fixed_lag, forward, tables)
+from _joint_accel_stream_ref import (BIG, BIG_WEIGHTS, GPU_CASES, LAGS, WEIGHTS, case, chunkings, clips, dead_joint_case, fixed_lag,
+                                     forward, tables)
 from _joint_ref import case as reproj_case
 from _shared import dev, one_arithmetic_mode, problem, zh  # noqa: F401  (fixtures; one_arithmetic_mode is autouse)
+from _stream_harness import (Streams, StreamCall, each_alone, frames_of, gather, groups, raw_push, replay_frame_by_frame, reset_refusals,
+                             run_clips, sizes, state_in_use, whole_push)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-SENT_P, SENT_C = -7, -7.0
+CALL = StreamCall("zedo_joint_accel_stream", ("lam_v", "lam_a"), lambda S, rows, J, H: (((S, rows, J), torch.int32), ((S, rows, J), torch.float64)),
+                  index=0, max_h=64)
 CELLS = [(c, w) for c in GPU_CASES for w in WEIGHTS] + [(BIG, BIG_WEIGHTS)]
 CELL_IDS = [f"J{c[0]}-N{c[1]}-H{c[2]}-L{c[3]}-v{w[0]:g}-a{w[1]:g}" for c, w in CELLS]
-
-
-def gather(xd, Td, ud, N, frames):
-    """frames [S][F]: the frame of the case every stream pushes -> the chunk's (u, x, T), rows (h, n) h-major with n = s F + f."""
-    H = xd.shape[0] // N
-    fr = torch.tensor(frames, dtype=torch.int64, device="cuda")
-    rows = (torch.arange(H, device="cuda")[:, None, None] * N + fr[None]).reshape(-1)
-    return ud[rows].contiguous(), xd[rows].contiguous(), None if Td is None else Td[rows].contiguous()
-
-
-class Streams:
-    """S streams at the raw ABI: the state pre-filled with `fill` bytes and then reset; every push checks its return code, and - after
-    one synchronisation - d_emit against the header's formula and the rows past the count against the sentinel.  out[s]: the (clip-local
-    frame, path row [J], cost row [J]) this stream has emitted, in order, on the device."""
-
-    def __init__(self, zh, S, H, J, lag, max_frames, lam_v, lam_a, fill=0xFF):
-        self.lib, self.S, self.H, self.J, self.lag, self.mf, self.w = zh._lib, S, H, J, lag, max_frames, (lam_v, lam_a)
-        self.nbytes = self.lib.zedo_joint_accel_stream_state_bytes(S, H, J, lag, max_frames)
-        assert self.nbytes > 0
-        self.state = dirty(self.nbytes, fill)
-        self.t = [0] * S
-        self.out = [[] for _ in range(S)]
-        self.reset()
-
-    def reset(self, which=None):
-        w = None if which is None else torch.tensor(which, dtype=torch.int32, device="cuda")
-        assert self.lib.zedo_joint_accel_stream_reset(P(self.state), self.nbytes, self.S, self.H, self.J, self.lag, self.mf, P(w),
-                                                      cur_stream()) == 0
-        for s in range(self.S):
-            if which is None or which[s]:
-                self.t[s] = 0
-
-    def push(self, u, x, T, F, flush=None):
-        S, J, lag = self.S, self.J, self.lag
-        fl = None if flush is None else torch.tensor(flush, dtype=torch.int32, device="cuda")
-        path, cost = sentinels((((S, F + lag, J), torch.int32), ((S, F + lag, J), torch.float64)), SENT_P)
-        emit = torch.full((S, 2), -1, dtype=torch.int64, device="cuda")
-        rc = self.lib.zedo_joint_accel_stream_push(P(u), P(x), P(T), S, F, self.H, J, lag, self.mf, self.w[0], self.w[1], P(fl),
-                                                   P(self.state), self.nbytes, P(path), P(cost), P(emit), cur_stream())
-        assert rc == 0, rc
-        want = [emitted(self.t[s], F, lag, bool(flush and flush[s])) for s in range(S)]
-        assert emit.cpu().tolist() == [list(w) for w in want], (emit.cpu().tolist(), want)
-        for s, (first, count) in enumerate(want):
-            assert bool((path[s, count:] == SENT_P).all()) and bool((cost[s, count:] == SENT_C).all())
-            assert bool((path[s, :count] >= 0).all()) and bool((path[s, :count] < self.H).all())
-            self.out[s].append((first, path[s, :count], cost[s, :count]))
-            self.t[s] = 0 if flush and flush[s] else self.t[s] + F
-        return path, cost, emit
-
-    def collected(self, s):
-        """(frames [n], path [n,J], cost [n,J]) of everything stream s has emitted."""
-        o = self.out[s]
-        return ([f + r for f, p, _ in o for r in range(p.shape[0])], torch.cat([p for _, p, _ in o]), torch.cat([c for _, _, c in o]))
-
-
-def run_clips(zh, xd, Td, ud, N, starts, L, lag, cut, w, **kw):
-    """The clips [a, a + L) for a in starts as len(starts) streams, pushed in chunks of cut[i] frames with a flush at the end ->
-    (path [S,L,J] i32, cost [S,L,J] f64) on the device."""
-    S, H, J = len(starts), xd.shape[0] // N, xd.shape[1]
-    st = Streams(zh, S, H, J, lag, max(cut), w[0], w[1], **kw)
-    f0 = 0
-    for i, F in enumerate(cut):
-        u, x, T = gather(xd, Td, ud, N, [[a + f0 + f for f in range(F)] for a in starts])
-        st.push(u, x, T, F, [1] * S if i == len(cut) - 1 else None)
-        f0 += F
-    outs = [st.collected(s) for s in range(S)]
-    assert all(o[0] == list(range(L)) for o in outs)                 # every frame once, in order
-    return torch.stack([o[1] for o in outs]), torch.stack([o[2] for o in outs])
-
-
-def groups(N, L):
-    """The clips of clips(N, L) as groups of equal length: [(starts, length)] - the equal ones as streams of one call, a shorter last one
-    on its own."""
-    seq = clips(N, L)
-    full = [a for a, b in zip(seq[:-1], seq[1:]) if b - a == L]
-    out = [(full, L)] if full else []
-    if seq[-1] - seq[-2] != L:
-        out.append(([seq[-2]], seq[-1] - seq[-2]))
-    return out
-
-
-def frames_of(starts, Lc):
-    return np.array([[a + f for f in range(Lc)] for a in starts])
 
 
 @pytest.mark.parametrize("cell", CELLS, ids=CELL_IDS)
@@ -132,7 +52,7 @@ def test_a_lag_that_covers_the_clip_gives_the_paths_of_the_offline_call(zh, cell
             end = np.repeat(cn[rows][:, -1:], Lc, axis=1)            # (no dead frame in these cases: a clip is one chain per joint)
             assert np.isfinite(end).all()
             for name, cut in chunkings(Lc).items():
-                p, c = run_clips(zh, xd, Td, ud, N, starts, Lc, L - 1, cut, w)
+                p, c = run_clips(zh, CALL, xd, Td, ud, N, starts, Lc, L - 1, cut, w)
                 assert same(p, path[torch.as_tensor(rows, device="cuda")]), (with_T, name, Lc)
                 c = c.cpu().numpy()
                 assert (np.abs(c - end) <= cost_bound(Lc, c) + cost_bound(Lc, end)).all(), (with_T, name, Lc)
@@ -153,7 +73,7 @@ def test_a_finite_lag_is_the_reference(zh, cell):
             for name, cut in chunkings(Lc).items():
                 if Lc > 40 and name == "single":
                     continue
-                p, c = run_clips(zh, xd, Td, ud, N, starts, Lc, lag, cut, w)
+                p, c = run_clips(zh, CALL, xd, Td, ud, N, starts, Lc, lag, cut, w)
                 if first is None:
                     first = (p, c)
                     err, bound = np.abs(c.cpu().numpy() - rc[rows]), cost_bound(L, rc[rows])
@@ -175,7 +95,7 @@ def test_the_ring_wraps(zh):
         tab = tables(J, N, H, L, *w)
         for lag, cut in ((3, [1] * L), (0, [4] * 32 + [2]), (1, [4] * 32 + [2])):
             rp, rc = fixed_lag(tab, [0, L], lag)
-            p, c = run_clips(zh, xd, Td, ud, N, [0], L, lag, cut, w)
+            p, c = run_clips(zh, CALL, xd, Td, ud, N, [0], L, lag, cut, w)
             assert np.array_equal(p[0].cpu().numpy(), rp), (w, lag)
             assert (np.abs(c[0].cpu().numpy() - rc) <= cost_bound(L, rc)).all(), (w, lag)
 
@@ -191,8 +111,8 @@ def test_excluded_entries_and_a_dead_frame_joint_inside_the_lag_window(zh, lag):
     for w in WEIGHTS:
         rp, rc = fixed_lag(forward(u, x, T, [0, 9], *w), [0, 9], lag)
         for name, cut in chunkings(9).items():
-            p, c = run_clips(zh, xd, Td, ud, 9, [0], 9, lag, cut, w)
-            p0, c0 = run_clips(zh, xd, Td, cd, 9, [0], 9, lag, cut, w)
+            p, c = run_clips(zh, CALL, xd, Td, ud, 9, [0], 9, lag, cut, w)
+            p0, c0 = run_clips(zh, CALL, xd, Td, cd, 9, [0], 9, lag, cut, w)
             assert same(p[0][:, others], p0[0][:, others]) and same(c[0][:, others], c0[0][:, others])
             pn, cn = p[0].cpu().numpy(), c[0].cpu().numpy()
             assert np.array_equal(pn, rp) and pn[4, j] == 0 and np.isposinf(cn[4, j])
@@ -211,27 +131,10 @@ def test_streams_are_independent_and_chains_of_one_and_two_frames(zh, lag):
     frames = [[0, 1, 2, 3, 4, 5, 6, 7], [3, 4, 5, 2, 3, 4, 5, 6], [8, 7, 0, 1, 2, 3, 4, 5]]
     flush_at = [{5, 7}, {2, 7}, {7}]
     reset_after = [set(), set(), {1}]
-
-    def run(members):
-        st = Streams(zh, len(members), H, J, lag, 1, *w)
-        per_push = []
-        for i in range(8):
-            uu, xx, TT = gather(xd, Td, ud, N, [[frames[s][i]] for s in members])
-            fl = [1 if i in flush_at[s] else 0 for s in members]
-            per_push.append(st.push(uu, xx, TT, 1, fl if any(fl) else None))
-            rs = [1 if i in reset_after[s] else 0 for s in members]
-            if any(rs):
-                st.reset(rs)
-        return st, per_push
-
-    all3, pushes3 = run([0, 1, 2])
-    for s in range(3):
-        _, pushes1 = run([s])
-        for (p3, c3, e3), (p1, c1, e1) in zip(pushes3, pushes1):
-            assert same(p3[s:s + 1], p1) and same(c3[s:s + 1], c1) and same(e3[s:s + 1], e1)
+    all3 = each_alone(zh, CALL, xd, Td, ud, N, frames, flush_at, reset_after, lag, w)
     carried = [[[0, 1, 2, 3, 4, 5], [6, 7]], [[3, 4, 5], [2, 3, 4, 5, 6]], [[0, 1, 2, 3, 4, 5]]]
     for s in range(3):
-        fr, p, c = all3.collected(s)
+        fr, (p, c) = all3.collected(s)
         assert fr == [f for cl in carried[s] for f in range(len(cl))]
         at = 0
         for cl in carried[s]:
@@ -252,71 +155,28 @@ def test_the_bits_do_not_depend_on_the_state_the_stream_or_the_alignment(zh):
     (J, N, H, L), w = BIG, BIG_WEIGHTS
     x, T, u = case(J, N, H)
     xd, Td, ud = dev(x), dev(T), dev(u, torch.float64)
-    lib = zh._lib
     for lag in (3, L - 1):
-        want = run_clips(zh, xd, Td, ud, N, [0, L], L, lag, chunkings(L)["growing"], w)
-        got = run_clips(zh, xd, Td, ud, N, [0, L], L, lag, [L], w, fill=0x00)
-        assert same(got[0], want[0]) and same(got[1], want[1])
+        want = run_clips(zh, CALL, xd, Td, ud, N, [0, L], L, lag, chunkings(L)["growing"], w)
+        assert all_same(run_clips(zh, CALL, xd, Td, ud, N, [0, L], L, lag, [L], w, fill=0x00), want)
         for k, a in enumerate((0, L)):
-            got = run_clips(zh, xd, Td, ud, N, [a], L, lag, [L], w)
-            assert same(got[0][0], want[0][k]) and same(got[1][0], want[1][k])
+            got = run_clips(zh, CALL, xd, Td, ud, N, [a], L, lag, [L], w)
+            assert all_same([t[0] for t in got], [t[k] for t in want])
         uu, xx, TT = gather(xd, Td, ud, N, [list(range(0, L)), list(range(L, 2 * L))])
-        nbytes = lib.zedo_joint_accel_stream_state_bytes(2, H, J, lag, L)
-        fl = torch.ones(2, dtype=torch.int32, device="cuda")
-
-        def whole(x=None, seq_on_device=False):
-            """reset + the two clips pushed whole + flush, on a fresh 0xFF state, nothing synchronised: the emitted rows"""
-            x = xx if x is None else x
-            state = dirty(nbytes, 0xFF)
-            path, cost = sentinels((((2, L + lag, J), torch.int32), ((2, L + lag, J), torch.float64)), SENT_P)
-            emit = torch.full((2, 2), -1, dtype=torch.int64, device="cuda")
-            assert lib.zedo_joint_accel_stream_reset(P(state), nbytes, 2, H, J, lag, L, None, cur_stream()) == 0
-            assert lib.zedo_joint_accel_stream_push(P(uu), P(x), P(TT), 2, L, H, J, lag, L, w[0], w[1], P(fl), P(state), nbytes, P(path),
-                                                    P(cost), P(emit), cur_stream()) == 0
-            return path[:, :L], cost[:, :L], emit
-
+        whole = whole_push(zh, CALL, (uu, xx, TT), 2, L, H, J, lag, w)
         ref = whole()
         torch.cuda.synchronize()
-        assert same(ref[0], want[0]) and same(ref[1], want[1]) and ref[2].tolist() == [[0, L]] * 2
+        assert all_same(ref[:-1], want) and ref[-1].tolist() == [[0, L]] * 2
         launch_invariant(ref, whole, xx)
-        # without a flush L - lag frames come out; F = 0: the pending min(lag, L) frames
-        st = Streams(zh, 2, H, J, lag, L, *w)
-        st.push(uu, xx, TT, L)
+        # d_x at the offset again, without a flush: L - lag frames come out; F = 0: the pending min(lag, L) frames
+        st = Streams(zh, CALL, 2, H, J, lag, L, w)
+        st.push(uu, misaligned(xx), TT, L)
         st.push(None, None, None, 0, [1, 1])
         for k in range(2):
-            fr, p, c = st.collected(k)
-            assert fr == list(range(L)) and same(p, want[0][k]) and same(c, want[1][k])
+            fr, o = st.collected(k)
+            assert fr == list(range(L)) and all_same(o, [t[k] for t in want])
     # captured: one frame per replay on static tensors, lag = 3
-    lag = 3
-    want = run_clips(zh, xd, Td, ud, N, [0, L], L, lag, [L], w)
-    st = Streams(zh, 2, H, J, lag, 1, *w)
-    su, sx, sT = (t.clone() for t in gather(xd, Td, ud, N, [[0], [L]]))
-    op, oc = sentinels((((2, 1 + lag, J), torch.int32), ((2, 1 + lag, J), torch.float64)), SENT_P)
-    oe = torch.full((2, 2), -1, dtype=torch.int64, device="cuda")
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        rc = lib.zedo_joint_accel_stream_push(P(su), P(sx), P(sT), 2, 1, H, J, lag, 1, w[0], w[1], None, P(st.state), st.nbytes, P(op), P(oc),
-                                              P(oe), cur_stream())
-    assert rc == 0
-    got_p, got_c = [[], []], [[], []]
-    for f in range(L):
-        for dst, src in zip((su, sx, sT), gather(xd, Td, ud, N, [[f], [L + f]])):
-            dst.copy_(src)
-        g.replay()
-        torch.cuda.synchronize()
-        assert oe.cpu().tolist() == [list(emitted(f, 1, lag, False))] * 2
-        for k in range(2):
-            n = int(oe[k, 1])
-            got_p[k] += [op[k, r].clone() for r in range(n)]
-            got_c[k] += [oc[k, r].clone() for r in range(n)]
-    st.t = [L, L]
-    fp, fc, _ = st.push(None, None, None, 0, [1, 1])
-    for k in range(2):
-        p = torch.stack(got_p[k] + [fp[k, r] for r in range(lag)])
-        c = torch.stack(got_c[k] + [fc[k, r] for r in range(lag)])
-        assert same(p, want[0][k]) and same(c, want[1][k])
+    want = run_clips(zh, CALL, xd, Td, ud, N, [0, L], L, 3, [L], w)
+    assert all_same(replay_frame_by_frame(zh, CALL, xd, Td, ud, N, [0, L], L, 3, w), want)
 
 
 @pytest.mark.parametrize("J,N,H,L", [(5, 12, 3, 4), (3, 130, 7, 130), (3, 40, 64, 9)], ids=lambda v: str(v))
@@ -335,7 +195,7 @@ def test_the_degenerate_weights(zh, J, N, H, L):
             assert hard[1].tolist() == mine[1].tolist() == [Lc] * S and same(hard[2][:, :Lc], mine[2][:, :Lc])
         for w in WEIGHTS:
             tab = tables(J, N, H, L, *w)
-            p, _ = run_clips(zh, xd, Td, ud, N, starts, Lc, 0, chunkings(Lc)["growing"], w)
+            p, _ = run_clips(zh, CALL, xd, Td, ud, N, starts, Lc, 0, chunkings(Lc)["growing"], w)
             rows = frames_of(starts, Lc)
             assert np.array_equal(p.cpu().numpy(), np.where(tab["start"], tab["argq"], tab["argq"] % H)[rows])
 
@@ -347,7 +207,7 @@ def test_the_binding_owns_the_state(zh):
     x, T, u = case(J, N, H)
     xd, Td, ud = dev(x), dev(T), dev(u, torch.float64)
     starts = [0, 4, 8]
-    want = run_clips(zh, xd, Td, ud, N, starts, L, lag, [3, 1], w)
+    want = run_clips(zh, CALL, xd, Td, ud, N, starts, L, lag, [3, 1], w)
     js = zh.JointAccelStream(3, H, J, lag, 3, lam=w[0], accel=w[1])
     assert js.state_bytes == zh.joint_accel_stream_state_bytes(3, H, J, lag, 3) == js.state.numel()
     js.push(*gather(xd, Td, ud, N, [[a] for a in starts]))           # to be dropped
@@ -363,8 +223,12 @@ def test_the_binding_owns_the_state(zh):
     for k in (0, 2):
         assert same(torch.cat([p1[k, :1], p2[k, :3]]), want[0][k]) and same(torch.cat([c1[k, :1], c2[k, :3]]), want[1][k])
     assert same(torch.cat([p1[1, :1], p2[1, :1], p3[1, :2]]), want[0][1]) and same(torch.cat([c1[1, :1], c2[1, :1], c3[1, :2]]), want[1][1])
+    f4, n4, _, _ = js.flush()
+    assert n4.tolist() == [0, 0, 0] and f4.tolist() == [0, 0, 0]
     with pytest.raises(ValueError):
         js.push(chunk[0][:-1], chunk[1], chunk[2])
+    with pytest.raises(ValueError):
+        js.push(chunk[0], chunk[1], chunk[2], flush=[1, 0])
     with pytest.raises(ValueError):
         js.push(None, None, None)
     with pytest.raises(zh.ZedoError):
@@ -377,51 +241,31 @@ def test_the_binding_owns_the_state(zh):
 def test_refusals_at_the_raw_abi(zh):
     """refusal_sweep: a NULL pointer other than d_T / d_flush / d_which, every size out of range - H = 65 included - F > max_frames,
     F = 0 without d_flush, a negative lag, the index bound, a weight < 0, NaN or inf, a misaligned state: ZEDO_E_BADARG; a state one byte
-    short: ZEDO_E_WORKSPACE; outputs and the bytes of a state in use unchanged either way.  The same call as it stands is accepted."""
+    short or of no bytes: ZEDO_E_WORKSPACE; outputs and the bytes of a state in use unchanged either way, by the refusals of the reset as
+    well.  The same call as it stands is accepted."""
     lib = zh._lib
-    J, N, H, lag, mf = 5, 12, 3, 2, 4
+    J, N, H, lag, mf, w = 5, 12, 3, 2, 4, (30.0, 100.0)
     x, T, u = case(J, N, H)
     xd, Td, ud = dev(x), dev(T), dev(u, torch.float64)
-    S, F = 3, 4
-    uu, xx, TT = gather(xd, Td, ud, N, [list(range(a, a + F)) for a in (0, 4, 8)])
-    need = lib.zedo_joint_accel_stream_state_bytes(S, H, J, lag, mf)
-    state = dirty(need + 8, 0x5A)
-    assert lib.zedo_joint_accel_stream_reset(P(state), need, S, H, J, lag, mf, None, None) == 0
-    u2, x2, T2 = gather(xd, Td, ud, N, [[a, a + 1] for a in (0, 4, 8)])
-    tmp = sentinels((((S, 2 + lag, J), torch.int32), ((S, 2 + lag, J), torch.float64), ((S, 2), torch.int64)))
-    assert lib.zedo_joint_accel_stream_push(P(u2), P(x2), P(T2), S, 2, H, J, lag, mf, 30.0, 100.0, None, P(state), need, P(tmp[0]), P(tmp[1]),
-                                            P(tmp[2]), None) == 0
-    torch.cuda.synchronize()
-    before = state.clone()                                           # a state in use: two frames per stream
-    path, cost = sentinels((((S, F + lag, J), torch.int32), ((S, F + lag, J), torch.float64)), SENT_P)
-    emit = torch.full((S, 2), -1, dtype=torch.int64, device="cuda")
+    S, F, starts = 3, 4, (0, 4, 8)
+    uu, xx, TT = gather(xd, Td, ud, N, [list(range(a, a + F)) for a in starts])
+    use = state_in_use(zh, CALL, xd, Td, ud, N, starts, lag, mf, w)  # two frames per stream
+    state, need = use.state, use.need
+    out, emit = CALL.blank(S, F + lag, J, H), torch.full((S, 2), -1, dtype=torch.int64, device="cuda")
     fl = torch.ones(S, dtype=torch.int32, device="cuda")
-    ptrs = [P(uu), P(xx), P(TT), P(fl), P(state), P(path), P(cost), P(emit)]
-
-    def call(p=ptrs, f=F, h=H, j=J, s=S, lg=lag, m=mf, lam_v=30.0, lam_a=100.0, nbytes=need, no_flush=False):
-        return lib.zedo_joint_accel_stream_push(p[0], p[1], p[2], s, f, h, j, lg, m, lam_v, lam_a, None if no_flush else p[3], p[4], nbytes,
-                                                p[5], p[6], p[7], None)
-
-    big = 2 ** 40
-    sizes = [dict(h=65, nbytes=big), dict(h=1024, nbytes=big), dict(h=0), dict(h=-1), dict(j=0), dict(s=0), dict(m=0), dict(f=mf + 1),
-             dict(f=-1), dict(f=0, no_flush=True), dict(lg=-1), dict(lg=2 ** 31 - 1, nbytes=big),
-             dict(h=64, s=2 ** 10, j=2 ** 5, lg=8, m=8, nbytes=big)]
-    refusal_sweep(call, ptrs, (0, 1, 4, 5, 6, 7), sizes=sizes, weights=("lam_v", "lam_a"), workspace_slot=4, need=need,
-                  untouched=((path, SENT_P), (cost, SENT_C), (emit, -1), (state, before)))
+    ptrs = [P(uu), P(xx), P(TT), P(fl), P(state)] + [P(t) for t in out] + [P(emit)]
+    call = raw_push(lib, CALL, ptrs, S, F, H, J, lag, mf, w, need)
+    reset_refusals(lib, CALL, use, S, H, J, lag, mf)
+    more = [dict(h=1024, nbytes=2 ** 40), dict(h=64, s=2 ** 10, j=2 ** 5, lg=8, m=8, nbytes=2 ** 40)]
+    refusal_sweep(call, ptrs, CALL.required(), sizes=sizes(CALL, mf) + more, weights=CALL.weights, workspace_slot=4, need=need,
+                  untouched=[(t, CALL.sentinel) for t in out] + [(emit, -1), (state, use.before)])
     # the control of the sweep pushed four frames onto the two and flushed: six come out
-    assert emit.tolist() == [[0, 6]] * S and bool((state[need:] == 0x5A).all()) and not torch.equal(state, before)
-    for bad in (dict(h=65), dict(lg=-1), dict(m=0)):
-        kw = dict(zip(("h", "lg", "m"), (H, lag, mf)))
-        kw.update(bad)
-        assert lib.zedo_joint_accel_stream_reset(P(state), big, S, kw["h"], J, kw["lg"], kw["m"], None, None) == -1
-    assert lib.zedo_joint_accel_stream_reset(None, need, S, H, J, lag, mf, None, None) == -1
-    assert lib.zedo_joint_accel_stream_reset(P(state[4:]), need, S, H, J, lag, mf, None, None) == -1
-    assert lib.zedo_joint_accel_stream_reset(P(state), need - 1, S, H, J, lag, mf, None, None) == -3
+    assert emit.tolist() == [[0, 6]] * S and bool((state[need:] == 0x5A).all()) and not torch.equal(state, use.before)
     # without T and without flush; then a flush of no frames
-    assert call([P(u2), P(x2), None] + ptrs[3:], f=2, no_flush=True) == 0
+    assert call([P(t) for t in use.chunk2[:2]] + [None] + ptrs[3:], f=2, no_flush=True) == 0
     assert call([None, None, None] + ptrs[3:], f=0) == 0
     torch.cuda.synchronize()
-    assert emit.tolist() == [[0, 2]] * S
+    assert emit.tolist() == [[0, 2]] * S and bool((state[need:] == 0x5A).all())
 
 
 def test_pipeline_push_joints_accel(zh, weights0):

@@ -5,25 +5,17 @@ max_frames, SJ = S J and HH = H^2:
         t i64 [S] | dead i32 [SJ,R] | back2 u8 [SJ,R,HH]
 and 0 for a shape the calls refuse (no GPU call: the function is host arithmetic)."""
 import ctypes
-import os
 
 import pytest
-import torch  # noqa: F401  (must precede dlopen of libzedo_hip.so: torch bundles its own HIP runtime)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "zedo-release_amd", "zedo_hip", "libzedo_hip.so")
+from _shared import host_fn  # (imports torch first: it must precede the dlopen of libzedo_hip.so, torch bundles its own HIP runtime)
+
 INT_MAX = 2 ** 31 - 1
 
 
 @pytest.fixture(scope="module")
 def state_bytes():
-    if not os.path.exists(LIB):
-        import __graft_entry__
-        __graft_entry__.build()
-    fn = ctypes.CDLL(LIB).zedo_joint_accel_stream_state_bytes
-    fn.restype = ctypes.c_size_t
-    fn.argtypes = [ctypes.c_int] * 5
-    return fn
+    return host_fn("zedo_joint_accel_stream_state_bytes", ctypes.c_size_t, [ctypes.c_int] * 5)
 
 
 def pad(v, k):

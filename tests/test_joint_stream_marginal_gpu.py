@@ -12,129 +12,34 @@ Every push of the comparisons goes through Streams: the raw ABI on a state pre-f
 with a sentinel; d_emit is held to the header's formula after every push and the rows past the count to the sentinel.
 Whether the fused pose is closer to ground truth than a selected one is not measured here or anywhere: these tests hold the arithmetic.
 The fusion does not depend on the arithmetic mode of the dense layers: one session runs it."""
-import ctypes
-
 import numpy as np
 import pytest
 
-from _invariance import all_same, cur_stream, dirty, misaligned, ptr as P, same, sentinels
+from _invariance import all_same, launch_invariant, misaligned, ptr as P, refusal_sweep, same
 from _joint_marginal_ref import IDS, MARGINAL_CASES, joint_marginal_ref, marg_bound, softmax_bound, softmax_ref
 from _joint_ref import case as reproj_case
 from _joint_stream_marginal_ref import FINITE_CASES, LAGS, fixed_lag_marginal, hold_to, reference
-from _joint_stream_ref import chunkings, emitted
+from _joint_stream_ref import chunkings
 from _joint_temporal_ref import case, dead_joint_case
 from _shared import dev, one_arithmetic_mode, problem, zh  # noqa: F401  (fixtures; one_arithmetic_mode is autouse)
+from _stream_harness import (Streams, StreamCall, by_frame, each_alone, frames_of, gather, groups, raw_push, replay_frame_by_frame,
+                             reset_refusals, run_clips, sizes, state_in_use, whole_push)
 from _temporal_ref import clips
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 LAM, TAU = 100.0, 1.0
-SENT = -7
+LT = (LAM, TAU)
 NAMES = ("mean", "cov", "hmax", "wmax", "logz", "w")
 
 
-def gather(xd, Td, ud, N, frames):
-    """frames [S][F]: the frame of the case every stream pushes -> the chunk's (u, x, T), rows (h, n) h-major with n = s F + f."""
-    H = xd.shape[0] // N
-    fr = torch.tensor(frames, dtype=torch.int64, device="cuda")
-    rows = (torch.arange(H, device="cuda")[:, None, None] * N + fr[None]).reshape(-1)
-    return ud[rows].contiguous(), xd[rows].contiguous(), None if Td is None else Td[rows].contiguous()
-
-
 def outputs(S, rows, J, H):
-    """The six outputs [S, rows, ..] pre-filled with the sentinel."""
     f64 = lambda *tail: ((S, rows, J) + tail, torch.float64)
-    return sentinels((f64(3), f64(6), ((S, rows, J), torch.int32), f64(), f64(), f64(H)), SENT)
+    return f64(3), f64(6), ((S, rows, J), torch.int32), f64(), f64(), f64(H)
 
 
-class Streams:
-    """S streams at the raw ABI: the state pre-filled with `fill` bytes and then reset; every push checks its return code, and - after
-    one synchronisation - d_emit against the header's formula and the rows past the count against the sentinel.  out[s]: the (clip-local
-    frame, [the six output rows]) this stream has emitted, in order, on the device.  with_w = False passes d_w = NULL: its rows stay
-    at the sentinel."""
-
-    def __init__(self, zh, S, H, J, lag, max_frames, lam=LAM, tau=TAU, fill=0xFF, with_w=True):
-        self.lib, self.S, self.H, self.J, self.lag, self.mf, self.lam, self.tau = zh._lib, S, H, J, lag, max_frames, lam, tau
-        self.with_w = with_w
-        self.nbytes = self.lib.zedo_joint_stream_marginal_state_bytes(S, H, J, lag, max_frames)
-        assert self.nbytes > 0
-        self.state = dirty(self.nbytes, fill)
-        self.t = [0] * S
-        self.out = [[] for _ in range(S)]
-        self.reset()
-
-    def reset(self, which=None):
-        w = None if which is None else torch.tensor(which, dtype=torch.int32, device="cuda")
-        assert self.lib.zedo_joint_stream_marginal_reset(P(self.state), self.nbytes, self.S, self.H, self.J, self.lag, self.mf, P(w),
-                                                         cur_stream()) == 0
-        for s in range(self.S):
-            if which is None or which[s]:
-                self.t[s] = 0
-
-    def push(self, u, x, T, F, flush=None):
-        S, J, lag = self.S, self.J, self.lag
-        fl = None if flush is None else torch.tensor(flush, dtype=torch.int32, device="cuda")
-        o = outputs(S, F + lag, J, self.H)
-        emit = torch.full((S, 2), -1, dtype=torch.int64, device="cuda")
-        rc = self.lib.zedo_joint_stream_marginal_push(P(u), P(x), P(T), S, F, self.H, J, lag, self.mf, self.lam, self.tau, P(fl), P(self.state),
-                                                      self.nbytes, P(o[0]), P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(o[5]) if self.with_w else None,
-                                                      P(emit), cur_stream())
-        assert rc == 0, rc
-        want = [emitted(self.t[s], F, lag, bool(flush and flush[s])) for s in range(S)]
-        assert emit.cpu().tolist() == [list(w) for w in want], (emit.cpu().tolist(), want)
-        for s, (first, count) in enumerate(want):
-            assert all(bool((t[s, count:] == SENT).all()) for t in o)
-            assert bool((o[2][s, :count] >= 0).all()) and bool((o[2][s, :count] < self.H).all())
-            if not self.with_w:
-                assert bool((o[5] == SENT).all())
-            self.out[s] += [(first + r, [t[s, r] for t in o]) for r in range(count)]
-            self.t[s] = 0 if flush and flush[s] else self.t[s] + F
-        return o, emit
-
-    def collected(self, s):
-        """(frames [n], the six outputs [n, ..]) of everything stream s has emitted."""
-        o = self.out[s]
-        return [f for f, _ in o], [torch.stack([rows[k] for _, rows in o]) for k in range(6)]
-
-
-def run_clips(zh, xd, Td, ud, N, starts, L, lag, cut, lam=LAM, tau=TAU, **kw):
-    """The clips [a, a + L) for a in starts as len(starts) streams, pushed in chunks of cut[i] frames with a flush at the end -> the six
-    outputs [S, L, ..] on the device."""
-    S, H, J = len(starts), xd.shape[0] // N, xd.shape[1]
-    st = Streams(zh, S, H, J, lag, max(cut), lam, tau, **kw)
-    f0 = 0
-    for i, F in enumerate(cut):
-        u, x, T = gather(xd, Td, ud, N, [[a + f0 + f for f in range(F)] for a in starts])
-        st.push(u, x, T, F, [1] * S if i == len(cut) - 1 else None)
-        f0 += F
-    outs = [st.collected(s) for s in range(S)]
-    assert all(o[0] == list(range(L)) for o in outs)                 # every frame once, in order
-    return [torch.stack([o[1][k] for o in outs]) for k in range(6)]
-
-
-def groups(N, L):
-    """The clips of clips(N, L) as groups of equal length: [(starts, length)] - the equal ones as streams of one call, a shorter last one
-    on its own."""
-    seq = clips(N, L)
-    full = [a for a, b in zip(seq[:-1], seq[1:]) if b - a == L]
-    out = [(full, L)] if full else []
-    if seq[-1] - seq[-2] != L:
-        out.append(([seq[-2]], seq[-1] - seq[-2]))
-    return out
-
-
-def by_frame(zh, xd, Td, ud, N, L, lag, name, lam=LAM, tau=TAU, **kw):
-    """All clips of clips(N, L) streamed under the chunking `name` -> the six outputs [N, ..] on the device, in the case's frame order."""
-    out = None
-    for starts, Lc in groups(N, L):
-        o = run_clips(zh, xd, Td, ud, N, starts, Lc, lag, chunkings(Lc)[name], lam, tau, **kw)
-        if out is None:
-            out = [torch.empty((N,) + tuple(t.shape[2:]), dtype=t.dtype, device="cuda") for t in o]
-        rows = torch.tensor([[a + f for f in range(Lc)] for a in starts], device="cuda")
-        for dst, src in zip(out, o):
-            dst[rows] = src
-    return out
+CALL = StreamCall("zedo_joint_stream_marginal", ("lam", "tau"), outputs, index=2, max_h=1024, optional=dict(with_w=5))
 
 
 @pytest.mark.parametrize("J,N,H,L", MARGINAL_CASES, ids=IDS)
@@ -147,7 +52,7 @@ def test_a_lag_that_covers_the_clip_gives_the_bits_of_the_offline_call(zh, J, N,
         Td = dev(T) if with_T else None
         ref = zh.joint_marginal(ud, xd, Td, clips(N, L), lam=LAM, tau=TAU, return_weights=True)
         for name in ("whole", "single", "growing"):
-            out = by_frame(zh, xd, Td, ud, N, L, L - 1, name)
+            out = by_frame(zh, CALL, xd, Td, ud, N, L, L - 1, name, LT)
             for k, a, b in zip(NAMES, out, ref):
                 assert same(a, b), (with_T, name, k)
 
@@ -162,11 +67,11 @@ def test_a_finite_lag_is_the_reference_and_the_offline_call_on_the_truncated_cli
     three frames of the first clip the row equals the GPU offline call on the clip cut after min(n + lag, last), bit for bit."""
     x, T, u = case(J, N, H)
     xd, Td, ud = dev(x), dev(T), dev(u, torch.float64)
-    first = by_frame(zh, xd, Td, ud, N, L, lag, "whole", lam, tau)
+    first = by_frame(zh, CALL, xd, Td, ud, N, L, lag, "whole", (lam, tau))
     hold_to([t.cpu().numpy() for t in first], reference(J, N, H, L, lam, tau, lag), x, T, N, L,
             f"J={J} N={N} H={H} L={L} lag={lag} lambda={lam:g} tau={tau:g}")
     for name in ("single", "growing"):
-        assert all_same(by_frame(zh, xd, Td, ud, N, L, lag, name, lam, tau), first), name
+        assert all_same(by_frame(zh, CALL, xd, Td, ud, N, L, lag, name, (lam, tau)), first), name
     seq = clips(N, L)
     a, Lc = seq[0], seq[1] - seq[0]
     for n in sorted({0, Lc // 2, max(0, Lc - 1 - lag)}):
@@ -186,13 +91,13 @@ def test_lag_zero_is_a_softmax_of_A_and_lambda_zero_a_softmax_of_the_unaries(zh,
     xd, Td, ud = dev(x), dev(T), dev(u, torch.float64)
     starts, Lc = groups(N, L)[0]
     S = len(starts)
-    st = Streams(zh, S, H, J, 0, Lc)
+    st = Streams(zh, CALL, S, H, J, 0, Lc, LT)
     uu, xx, TT = gather(xd, Td, ud, N, [[a + f for f in range(Lc)] for a in starts])
     o, _ = st.push(uu, xx, TT, Lc)
     torch.cuda.synchronize()
     A = st.state[:S * J * Lc * H * 8].view(torch.float64).view(S, J, Lc, H).permute(0, 2, 1, 3).cpu().numpy()      # [S, Lc, J, H]
     r = reference(J, N, H, L, LAM, TAU, 0)
-    rows = np.array([[a + f for f in range(Lc)] for a in starts])
+    rows = frames_of(starts, Lc)
     beta = marg_bound(Lc, H, r["G"])
     e_A = float(np.abs(A - r["A"][rows]).max())
     w, logz = o[5].cpu().numpy(), o[4].cpu().numpy()
@@ -202,7 +107,7 @@ def test_lag_zero_is_a_softmax_of_A_and_lambda_zero_a_softmax_of_the_unaries(zh,
     sm = softmax_ref(u, N, TAU)
     sb = softmax_bound(L, H, joint_marginal_ref(u, x, T, clips(N, L), 0.0, TAU)["G"], np.log(sm))
     for lag in (0, 3):
-        w0 = by_frame(zh, xd, Td, ud, N, L, lag, "growing", 0.0, TAU)[5].cpu().numpy()
+        w0 = by_frame(zh, CALL, xd, Td, ud, N, L, lag, "growing", (0.0, TAU))[5].cpu().numpy()
         e = float(np.abs(np.log(w0.astype(np.longdouble)) - np.log(sm)).max())
         print(f"lambda 0, lag {lag}, J={J} N={N} H={H}: max |log w - log softmax| = {e:.3e} (bound {sb:.3e})")
         assert e <= sb
@@ -218,7 +123,7 @@ def test_a_cold_stream_is_the_hard_stream(zh, J, N, H, L):
     for lag in LAGS:
         for starts, Lc in groups(N, L):
             cut = chunkings(Lc)["growing"]
-            o = run_clips(zh, xd, Td, ud, N, starts, Lc, lag, cut, LAM, 1e-9)
+            o = run_clips(zh, CALL, xd, Td, ud, N, starts, Lc, lag, cut, (LAM, 1e-9))
             js = zh.JointStream(len(starts), H, J, lag, max(cut), lam=LAM)
             path, f0 = [], 0
             for i, F in enumerate(cut):
@@ -240,25 +145,7 @@ def test_streams_are_independent(zh):
     frames = [[0, 1, 2, 3, 4, 5, 6, 7], [4, 5, 6, 7, 8, 9, 10, 11], [8, 9, 0, 1, 2, 3, 4, 5]]
     flush_at = [{7}, {3, 7}, {7}]
     reset_after = [set(), set(), {1}]
-
-    def run(members):
-        st = Streams(zh, len(members), H, J, lag, 1)
-        per_push = []
-        for i in range(8):
-            uu, xx, TT = gather(xd, Td, ud, N, [[frames[s][i]] for s in members])
-            fl = [1 if i in flush_at[s] else 0 for s in members]
-            o, e = st.push(uu, xx, TT, 1, fl if any(fl) else None)
-            per_push.append(o + [e])
-            rs = [1 if i in reset_after[s] else 0 for s in members]
-            if any(rs):
-                st.reset(rs)
-        return st, per_push
-
-    all3, pushes3 = run([0, 1, 2])
-    for s in range(3):
-        _, pushes1 = run([s])
-        for o3, o1 in zip(pushes3, pushes1):
-            assert all(same(a[s:s + 1], b) for a, b in zip(o3, o1))
+    all3 = each_alone(zh, CALL, xd, Td, ud, N, frames, flush_at, reset_after, lag, LT)
     carried = [[list(range(0, 8))], [list(range(4, 8)), list(range(8, 12))], [list(range(0, 6))]]
     for s in range(3):
         fr, o = all3.collected(s)
@@ -282,8 +169,8 @@ def test_excluded_entries_and_a_dead_frame_joint_inside_the_lag_window(zh, lag):
     r = fixed_lag_marginal(u, x, T, [0, 9], LAM, TAU, lag)
     first = None
     for name, cut in chunkings(9).items():
-        o = [t[0] for t in run_clips(zh, xd, Td, ud, 9, [0], 9, lag, cut)]
-        o0 = [t[0] for t in run_clips(zh, xd, Td, cd, 9, [0], 9, lag, cut)]
+        o = [t[0] for t in run_clips(zh, CALL, xd, Td, ud, 9, [0], 9, lag, cut, LT)]
+        o0 = [t[0] for t in run_clips(zh, CALL, xd, Td, cd, 9, [0], 9, lag, cut, LT)]
         assert all(same(a[:, others], b[:, others]) for a, b in zip(o, o0))
         if first is None:
             first = o
@@ -305,62 +192,36 @@ def test_excluded_entries_and_a_dead_frame_joint_inside_the_lag_window(zh, lag):
 
 
 def test_the_bits_do_not_depend_on_the_state_the_stream_the_alignment_or_d_w(zh):
-    """A state pre-filled with 0x00 instead of 0xFF; a side stream; d_w NULL; d_x at a 12-byte offset; a flush with F = 0; and one F = 1
-    push captured into a graph on a single branch and replayed L times with the inputs copied into its static tensors - a replay
-    advances the state - whose concatenated emission, with that of a final flush of no frames, is the offline call."""
+    """A state pre-filled with 0x00 instead of 0xFF; d_w NULL; a side stream, the call captured and replayed twice and d_x at a 12-byte
+    offset (launch_invariant, on reset + push + flush as one call); a flush with F = 0; and one F = 1 push captured into a graph on a
+    single branch and replayed L times with the inputs copied into its static tensors - a replay advances the state - whose concatenated
+    emission, with that of a final flush of no frames, is the offline call."""
     J, N, H, L = 17, 70, 50, 35
     x, T, u = case(J, N, H)
     xd, Td, ud = dev(x), dev(T), dev(u, torch.float64)
     ref = [t.view(2, L, *t.shape[1:]) for t in zh.joint_marginal(ud, xd, Td, clips(N, L), lam=LAM, tau=TAU, return_weights=True)]
     for lag in (3, L - 1):
         cut = chunkings(L)["growing"]
-        want = run_clips(zh, xd, Td, ud, N, [0, L], L, lag, cut)
+        want = run_clips(zh, CALL, xd, Td, ud, N, [0, L], L, lag, cut, LT)
         if lag == L - 1:
             assert all_same(want, ref)
-        assert all_same(run_clips(zh, xd, Td, ud, N, [0, L], L, lag, cut, fill=0x00), want)
-        assert all_same(run_clips(zh, xd, Td, ud, N, [0, L], L, lag, cut, with_w=False)[:5], want[:5])
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            got = run_clips(zh, xd, Td, ud, N, [0, L], L, lag, cut)
-        torch.cuda.synchronize()
-        assert all_same(got, want)
-        # d_x 12 bytes past a 16-byte boundary, pushed whole
-        st = Streams(zh, 2, H, J, lag, L)
+        assert all_same(run_clips(zh, CALL, xd, Td, ud, N, [0, L], L, lag, cut, LT, fill=0x00), want)
+        assert all_same(run_clips(zh, CALL, xd, Td, ud, N, [0, L], L, lag, cut, LT, with_w=False)[:5], want[:5])
         uu, xx, TT = gather(xd, Td, ud, N, [list(range(0, L)), list(range(L, 2 * L))])
-        st.push(uu, misaligned(xx), TT, L)                                        # no flush: L - lag frames come out
-        st.push(None, None, None, 0, [1, 1])                          # F = 0: the pending min(lag, L) frames
+        whole = whole_push(zh, CALL, (uu, xx, TT), 2, L, H, J, lag, LT)
+        one = whole()
+        torch.cuda.synchronize()
+        assert all_same(one[:-1], want) and one[-1].tolist() == [[0, L]] * 2
+        launch_invariant(one, whole, xx)
+        # d_x at the offset again, without a flush: L - lag frames come out; F = 0: the pending min(lag, L) frames
+        st = Streams(zh, CALL, 2, H, J, lag, L, LT)
+        st.push(uu, misaligned(xx), TT, L)
+        st.push(None, None, None, 0, [1, 1])
         for k in range(2):
             fr, o = st.collected(k)
             assert fr == list(range(L)) and all_same(o, [t[k] for t in want])
     # captured: one frame per replay on static tensors, lag = L - 1
-    lag = L - 1
-    st = Streams(zh, 2, H, J, lag, 1)
-    su, sx, sT = (t.clone() for t in gather(xd, Td, ud, N, [[0], [L]]))
-    o = outputs(2, 1 + lag, J, H)
-    oe = torch.full((2, 2), -1, dtype=torch.int64, device="cuda")
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        rc = st.lib.zedo_joint_stream_marginal_push(P(su), P(sx), P(sT), 2, 1, H, J, lag, 1, LAM, TAU, None, P(st.state), st.nbytes, P(o[0]),
-                                                    P(o[1]), P(o[2]), P(o[3]), P(o[4]), P(o[5]), P(oe), cur_stream())
-    assert rc == 0
-    got = [[[] for _ in range(6)] for _ in range(2)]
-    for f in range(L):
-        for dst, src in zip((su, sx, sT), gather(xd, Td, ud, N, [[f], [L + f]])):
-            dst.copy_(src)
-        g.replay()
-        torch.cuda.synchronize()
-        assert oe.cpu().tolist() == [list(emitted(f, 1, lag, False))] * 2
-        for k in range(2):
-            for i in range(6):
-                got[k][i] += [o[i][k, r].clone() for r in range(int(oe[k, 1]))]
-    st.t = [L, L]
-    fo, _ = st.push(None, None, None, 0, [1, 1])
-    for k in range(2):
-        full = [torch.stack(got[k][i] + [fo[i][k, r] for r in range(lag)]) for i in range(6)]
-        assert all_same(full, [t[k] for t in ref])
+    assert all_same(replay_frame_by_frame(zh, CALL, xd, Td, ud, N, [0, L], L, L - 1, LT), ref)
 
 
 def test_the_binding_owns_the_state(zh):
@@ -370,7 +231,7 @@ def test_the_binding_owns_the_state(zh):
     x, T, u = case(J, N, H)
     xd, Td, ud = dev(x), dev(T), dev(u, torch.float64)
     starts = [0, 4, 8]
-    want = run_clips(zh, xd, Td, ud, N, starts, L, lag, [3, 1], lam, tau)
+    want = run_clips(zh, CALL, xd, Td, ud, N, starts, L, lag, [3, 1], (lam, tau))
     js = zh.JointMarginalStream(3, H, J, lag, 3, lam=lam, tau=tau)
     assert js.state_bytes == zh.joint_stream_marginal_state_bytes(3, H, J, lag, 3) == js.state.numel()
     js.push(*gather(xd, Td, ud, N, [[a] for a in starts]))           # to be dropped
@@ -424,60 +285,32 @@ def test_the_binding_ends_a_clip_without_frames_at_lag_zero(zh):
 
 
 def test_refusals_at_the_raw_abi(zh):
-    """A NULL pointer other than d_T / d_w / d_flush / d_which, H = 1025, F > max_frames, F = 0 without d_flush, a negative lag, lambda < 0
-    or NaN, tau of 0, negative, NaN and inf, a misaligned state: ZEDO_E_BADARG; a state one byte short: ZEDO_E_WORKSPACE; outputs and the
-    state's bytes unchanged either way.  The same call with valid arguments is accepted."""
+    """refusal_sweep: a NULL pointer other than d_T / d_w / d_flush / d_which, every size out of range - H = 1025 included - F >
+    max_frames, F = 0 without d_flush, a negative lag, lambda < 0, NaN or inf, tau of 0, negative, NaN and inf, a misaligned state:
+    ZEDO_E_BADARG; a state one byte short or of no bytes: ZEDO_E_WORKSPACE; outputs and the bytes of a state in use unchanged either way,
+    by the refusals of the reset as well.  The same call as it stands is accepted."""
     lib = zh._lib
     J, N, H, lag, mf = 5, 12, 3, 2, 4
     x, T, u = case(J, N, H)
     xd, Td, ud = dev(x), dev(T), dev(u, torch.float64)
-    S, F = 3, 4
-    uu, xx, TT = gather(xd, Td, ud, N, [list(range(a, a + F)) for a in (0, 4, 8)])
-    need = lib.zedo_joint_stream_marginal_state_bytes(S, H, J, lag, mf)
-    state = dirty(need + 8, 0x5A)
-    assert lib.zedo_joint_stream_marginal_reset(P(state), need, S, H, J, lag, mf, None, None) == 0
-    u2, x2, T2 = gather(xd, Td, ud, N, [[a, a + 1] for a in (0, 4, 8)])
-    tmp = outputs(S, 2 + lag, J, H) + [torch.empty((S, 2), dtype=torch.int64, device="cuda")]
-    assert lib.zedo_joint_stream_marginal_push(P(u2), P(x2), P(T2), S, 2, H, J, lag, mf, LAM, TAU, None, P(state), need,
-                                               *[P(t) for t in tmp], None) == 0
-    torch.cuda.synchronize()
-    before = state.clone()                                           # a state in use: two frames per stream
-    o = outputs(S, F + lag, J, H)
-    emit = torch.full((S, 2), -1, dtype=torch.int64, device="cuda")
+    S, F, starts = 3, 4, (0, 4, 8)
+    uu, xx, TT = gather(xd, Td, ud, N, [list(range(a, a + F)) for a in starts])
+    use = state_in_use(zh, CALL, xd, Td, ud, N, starts, lag, mf, LT)  # two frames per stream
+    state, need = use.state, use.need
+    out, emit = CALL.blank(S, F + lag, J, H), torch.full((S, 2), -1, dtype=torch.int64, device="cuda")
     fl = torch.ones(S, dtype=torch.int32, device="cuda")
-    ptrs = dict(u=P(uu), x=P(xx), T=P(TT), fl=P(fl), st=P(state), mean=P(o[0]), cov=P(o[1]), hmax=P(o[2]), wmax=P(o[3]), logz=P(o[4]), w=P(o[5]),
-                e=P(emit))
-
-    def call(f=F, h=H, j=J, s=S, lg=lag, m=mf, lm=LAM, tau=TAU, nbytes=need, **over):
-        q = dict(ptrs, **over)
-        return lib.zedo_joint_stream_marginal_push(q["u"], q["x"], q["T"], s, f, h, j, lg, m, lm, tau, q["fl"], q["st"], nbytes, q["mean"],
-                                                   q["cov"], q["hmax"], q["wmax"], q["logz"], q["w"], q["e"], None)
-
-    for k in ("u", "x", "st", "mean", "cov", "hmax", "wmax", "logz", "e"):
-        assert call(**{k: None}) == -1, k
-    assert call(h=1025, nbytes=2 ** 40) == -1 and call(h=0) == -1 and call(j=0) == -1 and call(s=0) == -1 and call(m=0) == -1
-    assert call(f=mf + 1) == -1 and call(f=-1) == -1
-    assert call(f=0, fl=None) == -1                                  # a push of no frames that flushes nothing
-    assert call(lg=-1) == -1 and call(lg=2 ** 31 - 1, nbytes=2 ** 40) == -1
-    assert call(lm=-1.0) == -1 and call(lm=float("nan")) == -1 and call(lm=float("inf")) == -1
-    for tau in (0.0, -0.0, -1.0, float("nan"), float("inf"), float("-inf")):
-        assert call(tau=tau) == -1, tau
-    assert call(st=ctypes.c_void_p(state.data_ptr() + 4)) == -1
-    assert call(nbytes=need - 1) == -3 and call(nbytes=0) == -3
-    for bad in (dict(h=1025), dict(lg=-1), dict(m=0)):
-        kw = dict(zip(("h", "lg", "m"), (H, lag, mf)))
-        kw.update(bad)
-        assert lib.zedo_joint_stream_marginal_reset(P(state), 2 ** 40, S, kw["h"], J, kw["lg"], kw["m"], None, None) == -1
-    assert lib.zedo_joint_stream_marginal_reset(None, need, S, H, J, lag, mf, None, None) == -1
-    assert lib.zedo_joint_stream_marginal_reset(ctypes.c_void_p(state.data_ptr() + 4), need, S, H, J, lag, mf, None, None) == -1
-    assert lib.zedo_joint_stream_marginal_reset(P(state), need - 1, S, H, J, lag, mf, None, None) == -3
+    ptrs = [P(uu), P(xx), P(TT), P(fl), P(state)] + [P(t) for t in out] + [P(emit)]
+    call = raw_push(lib, CALL, ptrs, S, F, H, J, lag, mf, LT, need)
+    reset_refusals(lib, CALL, use, S, H, J, lag, mf)
+    refusal_sweep(call, ptrs, CALL.required(), sizes=sizes(CALL, mf), weights=("lam",), taus=("tau",), workspace_slot=4, need=need,
+                  untouched=[(t, CALL.sentinel) for t in out] + [(emit, -1), (state, use.before)])
+    # the control of the sweep pushed four frames onto the two and flushed: six come out
+    assert emit.tolist() == [[0, 6]] * S and bool((state[need:] == 0x5A).all()) and not torch.equal(state, use.before)
+    # without T, without d_w and without flush; then a flush of no frames
+    assert call([P(t) for t in use.chunk2[:2]] + [None] + ptrs[3:10] + [None, ptrs[11]], f=2, no_flush=True) == 0
+    assert call([None, None, None] + ptrs[3:], f=0) == 0
     torch.cuda.synchronize()
-    assert all(bool((t == SENT).all()) for t in o) and bool((emit == -1).all()) and torch.equal(state, before)
-    # the controls: without T, without d_w and without flush; then a flush of no frames
-    assert call(f=2, T=None, w=None, fl=None, u=P(u2), x=P(x2)) == 0
-    assert call(f=0, u=None, x=None, T=None) == 0
-    torch.cuda.synchronize()
-    assert emit.tolist() == [[2, 2]] * S and bool((state[need:] == 0x5A).all()) and not torch.equal(state, before)
+    assert emit.tolist() == [[0, 2]] * S and bool((state[need:] == 0x5A).all())
 
 
 def test_pipeline_push_fuse_joints_temporal(zh, weights0):

@@ -4,25 +4,17 @@ is host arithmetic).  With R = lag + max_frames, SJ = S J and pad8 rounding up t
         A f64 [SJ,R,H] | X f64 [SJ,R,H,3] | l f64 [SJ,R,H] | t i64 [S] | dead i32 [SJ,R] | lastdead i32 [SJ]
 and 0 for a shape outside the entry points' range."""
 import ctypes
-import os
 
 import pytest
-import torch  # noqa: F401  (must precede dlopen of libzedo_hip.so: torch bundles its own HIP runtime)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "zedo-release_amd", "zedo_hip", "libzedo_hip.so")
+from _shared import host_fn  # (imports torch first: it must precede the dlopen of libzedo_hip.so, torch bundles its own HIP runtime)
+
 INT_MAX = 2 ** 31 - 1
 
 
 @pytest.fixture(scope="module")
 def fn():
-    if not os.path.exists(LIB):
-        import __graft_entry__
-        __graft_entry__.build()
-    f = ctypes.CDLL(LIB).zedo_joint_stream_marginal_state_bytes
-    f.restype = ctypes.c_size_t
-    f.argtypes = [ctypes.c_int] * 5
-    return f
+    return host_fn("zedo_joint_stream_marginal_state_bytes", ctypes.c_size_t, [ctypes.c_int] * 5)
 
 
 def pad(v, k):

@@ -7,18 +7,15 @@ documents, with R = lag + max_frames and SJ = S J:
         D f64 [SJ,R,H] | lastX f64 [SJ,H,3] | lastD f64 [SJ,H] | t i64 [S] | back i32 [SJ,R,H] | dead i32 [SJ,R] | lastdead i32 [SJ]
 and 0 for a shape the calls refuse (no GPU call: the function is host arithmetic)."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
-import torch  # noqa: F401  (must precede dlopen of libzedo_hip.so: torch bundles its own HIP runtime)
 
 from _joint_stream_ref import LAGS, check_inputs, chunkings, differ_share, emitted, fixed_lag
 from _joint_temporal_ref import case, dead_joint_case, joint_temporal_ref, reference
+from _shared import host_fn  # (imports torch first: it must precede the dlopen of libzedo_hip.so, torch bundles its own HIP runtime)
 from _temporal_ref import clips
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "zedo-release_amd", "zedo_hip", "libzedo_hip.so")
 INT_MAX = 2 ** 31 - 1
 
 
@@ -115,13 +112,7 @@ def test_the_counts_of_the_header_formula_add_up():
 # ---- zedo_joint_stream_state_bytes: host arithmetic ----
 @pytest.fixture(scope="module")
 def state_bytes():
-    if not os.path.exists(LIB):
-        import __graft_entry__
-        __graft_entry__.build()
-    fn = ctypes.CDLL(LIB).zedo_joint_stream_state_bytes
-    fn.restype = ctypes.c_size_t
-    fn.argtypes = [ctypes.c_int] * 5
-    return fn
+    return host_fn("zedo_joint_stream_state_bytes", ctypes.c_size_t, [ctypes.c_int] * 5)
 
 
 def pad(v, k):

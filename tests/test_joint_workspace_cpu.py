@@ -6,22 +6,17 @@ include/zedo_hip.h documents (no GPU call: the functions are host arithmetic).  
     zedo_joint_tree_marginal_max_h(J)   = min(1024, (163840 - 8192) // (48 J + 16))
 and 0 for a shape outside the entry point's range."""
 import ctypes
-import os
 
 import pytest
-import torch  # noqa: F401  (must precede dlopen of libzedo_hip.so: torch bundles its own HIP runtime)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "zedo-release_amd", "zedo_hip", "libzedo_hip.so")
+from _shared import host_lib  # (imports torch first: it must precede the dlopen of libzedo_hip.so, torch bundles its own HIP runtime)
+
 INT_MAX = 2 ** 31 - 1
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(LIB):
-        import __graft_entry__
-        __graft_entry__.build()
-    so = ctypes.CDLL(LIB)
+    so = host_lib()
     for name in ("zedo_joint_temporal_workspace_bytes", "zedo_joint_marginal_workspace_bytes", "zedo_joint_accel_workspace_bytes"):
         getattr(so, name).restype = ctypes.c_size_t
         getattr(so, name).argtypes = [ctypes.c_int] * 3

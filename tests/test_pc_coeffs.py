@@ -6,18 +6,14 @@ network's output into the score) from the sde object's own methods, folds them i
 fp32 to the inputs of tests/golden/samplers.npz (captured from the reference: tools/gen_golden.py::gen_samplers) they
 must reproduce what the reference's update rules gave, under the rule the generic surface is held to
 (tests/test_surface_gpu.py::test_pc_sampler_other_sdes_and_update_rules): max|d| < 1e-6 max(1, max|ref|)."""
-import ctypes
-import os
-
 import numpy as np
 import pytest
 import torch
 
-from _shared import make_sde, sampler_cases
+from _shared import host_lib, make_sde, sampler_cases
 from lib.algorithms.advanced import _pc_coeffs, sampling, sde_lib
 from lib.algorithms.advanced import utils as mutils
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SDES, PREDS, CORRS = sampler_cases()
 SNR, N_CORR = 0.16, 2          # what gen_samplers ran the correctors with
 
@@ -174,12 +170,8 @@ def test_the_module_does_not_need_the_library():
 
 
 def test_library_exports_the_pc_entry_points():
-    lib_path = os.path.join(ROOT, "zedo-release_amd", "zedo_hip", "libzedo_hip.so")
-    if not os.path.exists(lib_path):
-        import __graft_entry__
-        __graft_entry__.build()
     import zedo_hip
-    lib = ctypes.CDLL(lib_path)
+    lib = host_lib()
     for n in ("zedo_pc_plan_create", "zedo_pc_plan_destroy", "zedo_pc_workspace_bytes", "zedo_pc_step"):
         assert hasattr(lib, n) and n in zedo_hip.SIGNATURES, n
     assert lib.zedo_abi_version() == 5 and zedo_hip.abi_version() == 5

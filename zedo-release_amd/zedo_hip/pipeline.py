@@ -211,6 +211,18 @@ class Pipeline:
         with torch.cuda.device(self.device):
             return joint_reproj(x, T, self.uv, self.K, self.N, 0, return_rows=True)[2]
 
+    def _open_stream(self, name, cls, S, lag, max_frames, *weights):
+        """What the open_*_stream methods below share: a `cls` with H and the joint count of load() - the ZedoError speaks for `name`."""
+        if getattr(self, "uv", None) is None:
+            raise ZedoError(f"{name}: call load() first (the joint count is the problem's)")
+        return cls(S, self.H, self.uv.shape[1], lag, max_frames, *weights, self.device)
+
+    def _push_stream(self, name, js, x, T, flush):
+        """What the push_* methods below share: the unaries of _joint_unaries for the streams of js, pushed -> js.push(...) + (jerr,)."""
+        jerr = self._joint_unaries(name, x, T, js.S)
+        with torch.cuda.device(self.device):
+            return js.push(jerr, x, T, flush) + (jerr,)
+
     def aggregate_tree(self, x, T, mu=100.0, parent=None):
         """aggregate_reproj with the skeleton as a coupling, on the problem of load(): x [H*N,17,3] and T [H*N,3], ALL rows (a pose's every
         hypothesis takes part) -> (joint_h [N,17] i32, cost [N] f64, bone [N,17] f64, jerr [H*N,17] f64): the unaries are
@@ -272,9 +284,7 @@ class Pipeline:
         """The state of select_joints_temporal's chain for S live streams (JointStream): H and the joint count are those of the
         pipeline, every frame is decided `lag` frames after it went in, a push holds at most max_frames frames per stream.  lam and the
         choice of lag are untuned."""
-        if getattr(self, "uv", None) is None:
-            raise ZedoError("open_joint_stream: call load() first (the joint count is the problem's)")
-        return JointStream(S, self.H, self.uv.shape[1], lag, max_frames, lam, self.device)
+        return self._open_stream("open_joint_stream", JointStream, S, lag, max_frames, lam)
 
     def push_joints_temporal(self, js, x, T, flush=None):
         """select_joints_temporal on live input, on the problem of load() with N = S F poses - F new frames of each of the S streams of
@@ -283,9 +293,7 @@ class Pipeline:
         [H*N,17] f64): the unaries are zedo_joint_reproj's per-(row, joint) distances exactly as select_joints_temporal forms them; stream
         s emits the frames first[s] .. first[s] + count[s] - 1 of its clip (zedo_joint_stream_push).  The caller keeps x and T of the
         frames that are still to come out and assembles their poses with compose."""
-        jerr = self._joint_unaries("push_joints_temporal", x, T, js.S)
-        with torch.cuda.device(self.device):
-            return js.push(jerr, x, T, flush) + (jerr,)
+        return self._push_stream("push_joints_temporal", js, x, T, flush)
 
     def select_joints_accel(self, x, T, seq_start, lam=100.0, accel=100.0):
         """select_joints_temporal with a second-order motion model: the same inputs and outputs, each joint's path minimises its unaries
@@ -300,9 +308,7 @@ class Pipeline:
         """The state of select_joints_accel's chain over pairs for S live streams (JointAccelStream): H (at most 64) and the joint count
         are those of the pipeline, every frame is decided `lag` frames after it went in, a push holds at most max_frames frames per
         stream.  lam, accel and the choice of lag are untuned."""
-        if getattr(self, "uv", None) is None:
-            raise ZedoError("open_joint_accel_stream: call load() first (the joint count is the problem's)")
-        return JointAccelStream(S, self.H, self.uv.shape[1], lag, max_frames, lam, accel, self.device)
+        return self._open_stream("open_joint_accel_stream", JointAccelStream, S, lag, max_frames, lam, accel)
 
     def push_joints_accel(self, js, x, T, flush=None):
         """select_joints_accel on live input, on the problem of load() with N = S F poses - F new frames of each of the S streams of
@@ -311,9 +317,7 @@ class Pipeline:
         [H*N,17] f64): the unaries are zedo_joint_reproj's per-(row, joint) distances exactly as push_joints_temporal forms them; stream
         s emits the frames first[s] .. first[s] + count[s] - 1 of its clip, each as select_joints_accel decides it on the clip cut `lag`
         frames later (zedo_joint_accel_stream_push); joint_cost is the cost of the best path on that cut clip."""
-        jerr = self._joint_unaries("push_joints_accel", x, T, js.S)
-        with torch.cuda.device(self.device):
-            return js.push(jerr, x, T, flush) + (jerr,)
+        return self._push_stream("push_joints_accel", js, x, T, flush)
 
     def fuse_joints_temporal(self, x, T, seq_start, lam=100.0, tau=1.0):
         """Joint-wise fusion along a video without ground truth on the problem of load(): x [H*N,17,3] and T [H*N,3], ALL rows, seq_start =
@@ -329,9 +333,7 @@ class Pipeline:
         """The state of fuse_joints_temporal's chain model for S live streams (JointMarginalStream): H and the joint count are those of
         the pipeline, every frame's marginals are formed `lag` frames after it went in, a push holds at most max_frames frames per
         stream.  lam, tau and the choice of lag are untuned."""
-        if getattr(self, "uv", None) is None:
-            raise ZedoError("open_joint_fuse_stream: call load() first (the joint count is the problem's)")
-        return JointMarginalStream(S, self.H, self.uv.shape[1], lag, max_frames, lam, tau, self.device)
+        return self._open_stream("open_joint_fuse_stream", JointMarginalStream, S, lag, max_frames, lam, tau)
 
     def push_fuse_joints_temporal(self, js, x, T, flush=None):
         """fuse_joints_temporal on live input, on the problem of load() with N = S F poses - F new frames of each of the S streams of
@@ -340,9 +342,7 @@ class Pipeline:
         wmax [S,F+lag,17] f64, logz [S,F+lag,17] f64, jerr [H*N,17] f64): the unaries are zedo_joint_reproj's per-(row, joint) distances
         exactly as push_joints_temporal forms them; stream s emits the frames first[s] .. first[s] + count[s] - 1 of its clip, each as
         fuse_joints_temporal reports it on the clip cut `lag` frames later (zedo_joint_stream_marginal_push)."""
-        jerr = self._joint_unaries("push_fuse_joints_temporal", x, T, js.S)
-        with torch.cuda.device(self.device):
-            return js.push(jerr, x, T, flush) + (jerr,)
+        return self._push_stream("push_fuse_joints_temporal", js, x, T, flush)
 
     def fuse_joints_accel(self, x, T, seq_start, lam=100.0, accel=100.0, tau=1.0):
         """fuse_joints_temporal under the second-order motion model: the same inputs and outputs - (mean [N,17,3] f64, cov [N,17,6] f64,
