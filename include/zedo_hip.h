@@ -54,7 +54,9 @@ extern "C" {
                               * still 5 (additive): + zedo_joint_stream_marginal_state_bytes, zedo_joint_stream_marginal_reset,
                               *                       zedo_joint_stream_marginal_push;
                               * still 5 (additive): + zedo_joint_accel_stream_state_bytes, zedo_joint_accel_stream_reset,
-                              *                       zedo_joint_accel_stream_push */
+                              *                       zedo_joint_accel_stream_push;
+                              * still 5 (additive): + zedo_joint_accel_stream_marginal_state_bytes,
+                              *                       zedo_joint_accel_stream_marginal_reset, zedo_joint_accel_stream_marginal_push */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -706,6 +708,65 @@ int zedo_joint_accel_marginal(const double *d_junary, const float *d_x, const fl
                               int H, int N, int J, double lambda_v, double lambda_a, double tau,
                               void *d_workspace, size_t workspace_bytes,
                               double *d_mean, double *d_cov, int *d_hmax, double *d_wmax, double *d_logz, double *d_w, void *stream);
+
+/* ---- second-order fusion on a LIVE video: fixed-lag streaming sum-product over pairs ----------------------------------------
+ * zedo_joint_stream_marginal_push is the only soft answer on live input, and its motion term is a zero-velocity prior: the
+ * faster a limb moves, the more hypotheses share the mass.  zedo_joint_accel_marginal fixes that but needs the whole clip.  This
+ * is zedo_joint_accel_marginal's chain over pairs as an online call for S independent streams: frames are pushed in chunks of
+ * any size, the tables live in d_state between the calls, and a frame's marginals come out `lag` frames after the frame went in.
+ * lambda_v, lambda_a, tau and the lag are UNTUNED; accuracy on real video is UNMEASURED.
+ * The chunk (d_junary, d_x, d_T; rows (h,n) h-major, n = s*F + f), d_flush, d_which, d_emit [S,2], the emitted count and the
+ * `first` emitted frame, F = 0 being legal only with d_flush, rows at and after the count not being written, the outputs d_mean
+ * [S,F+lag,J,3], d_cov [S,F+lag,J,6], d_hmax (int32), d_wmax and d_logz [S,F+lag,J] and the optional d_w [S,F+lag,J,H] (NULL:
+ * not written), and the outputs of a dead (n,j) are those of zedo_joint_stream_marginal_push, word for word.  X, u, l, m, a, a',
+ * DEAD, the chains, A2, B2, M, pi, the order of every sum and the exclusion of a hypothesis are those of
+ * zedo_joint_accel_marginal on the stream's clip, word for word; A2 is a prefix quantity, which does not depend on the chunking.
+ *   For a live (n,j) let c0 be the first frame of n's chain, c_j(n) the chain's last frame on the frames the clip holds after
+ *   the push that emits n, and e = min(n + lag, c_j(n)).  Then
+ *     e == c0 (a chain of one frame so far):  logZ = LSE_h l[e,h]  and  w[n,h] = exp(l[n,h] - logZ)
+ *     otherwise:  B2[e] = 0 and logZ = LSE over all pairs of A2[e], in the order zedo_joint_accel_marginal takes;
+ *                 B2[m] for m = e-1 .. max(n, c0+1) by the backward recurrence;  pi[m] = exp((A2[m] + B2[m]) - logZ);
+ *                 w[n,h] = sum_h' pi[n][h',h] for n >= c0+1;  w[c0,h'] = sum_h pi[c0+1][h',h];  both sums ascending
+ *   d_logz is that logZ; mean, cov, hmax and wmax follow from w exactly as zedo_joint_accel_marginal forms them.
+ * In words: the outputs for frame n are those of zedo_joint_accel_marginal on the stream's clip cut after frame n + lag.  lag =
+ * 0 gives the filtering marginals, the column sums of the softmax of A2[n]; the outputs do not depend on the chunking; with
+ * lag >= the clip's length - 1 and a flush they are the offline call's bits; on a clip cut short, at any lag, they are the
+ * bits of the offline call on that cut.
+ * zedo_joint_accel_stream_marginal_reset is zedo_joint_stream_reset on this state.
+ * State (8-byte aligned, need not be initialised before its first reset, must have been reset before its first push), with
+ * R = lag + max_frames + 2 rows per ring, SJ = S*J chains and HH = H*H, in this order:
+ *   A2 float64 [SJ,R,HH] | X float64 [SJ,R,H,3] | l float64 [SJ,R,H] | the clip's frame count int64 [S] |
+ *   the dead flags of the ring's frames int32 [SJ,R]
+ * - zedo_joint_accel_stream_marginal_state_bytes = 8 (SJ R (HH + 4 H) + S) + 4 SJ R rounded up to 8; 0 for shapes the calls
+ * refuse.  That is 194 MB at S = 16, J = 17, H = 50, lag = 30, max_frames = 1, where zedo_joint_accel_stream_push holds 27 MB:
+ * the pair table of every frame in the window stays, 8 HH bytes per frame.  Frame m of a clip sits in row m % R.  The two extra
+ * rows stand where the sibling streams carry blocks of their own: with t the clip's frames before a push of F <= max_frames
+ * frames, the push writes the rows of frames t .. t+F-1 (their dead flags first); its forward step reads A2, X, l and the flag
+ * of frame t-1 and X and the flag of frame t-2; its emission reads frames >= max(0, t - lag) and X of the frame before the
+ * lowest of them, t - lag - 1.  The lowest frame read is t - lag - 1 (lag >= 1) or t - 2 (lag = 0); the highest written is
+ * t + F - 1; their distance is F + lag <= R - 2 or F + 1 <= R - 1: below R, so no row that is read has been overwritten, with
+ * lag = 0 and F = max_frames as well.
+ * Contract: that of zedo_joint_accel_stream_push plus tau - 1 <= H <= 64, J >= 1, S >= 1, max_frames >= 1, 0 <= F <=
+ * max_frames, lag >= 0, (lag + max_frames + 2)*S*J*H*H <= INT_MAX, finite lambda_v >= 0 and lambda_a >= 0, finite tau > 0;
+ * ZEDO_E_BADARG with nothing written and the state untouched for a NULL pointer other than d_T, d_w, d_flush (F > 0) and
+ * d_which, a size out of these ranges, H > 64, F = 0 without d_flush, a negative or non-finite lambda_v or lambda_a, tau <= 0
+ * or not finite, or a state that is not 8-byte aligned; ZEDO_E_WORKSPACE with nothing written and the state untouched if
+ * state_bytes is too small; allocates nothing, synchronises nothing, enqueues on `stream` only: legal under stream capture - a
+ * replay advances the state.  No atomics, no scratch: the bits do not depend on the run, the chunking, the content of the state
+ * before its reset, the alignment of d_x or whether d_w is given.  Every value read from the state is clamped before it is an
+ * index.  lambda_v, lambda_a and tau are taken to be the same in every push between a frame going in and coming out.
+ * One workgroup per (stream, joint) for the forward recurrence; one workgroup per (stream, output row, joint) for the backward
+ * walk, 104.7 KB of LDS each (one per CU), where frames of one (stream, joint) that share a closed horizon - a flush or a dead
+ * (frame, joint) - are served by ONE walk.  A whole clip pushed with lag = L - 1 and flushed costs one backward pass, as
+ * offline; a steady-state push costs F walks of lag frames per (stream, joint), which is inherent in fixed-lag smoothing. */
+size_t zedo_joint_accel_stream_marginal_state_bytes(int S, int H, int J, int lag, int max_frames);
+int zedo_joint_accel_stream_marginal_reset(void *d_state, size_t state_bytes, int S, int H, int J, int lag, int max_frames,
+                                           const int *d_which, void *stream);
+int zedo_joint_accel_stream_marginal_push(const double *d_junary, const float *d_x, const float *d_T, int S, int F, int H, int J,
+                                          int lag, int max_frames, double lambda_v, double lambda_a, double tau,
+                                          const int *d_flush, void *d_state, size_t state_bytes,
+                                          double *d_mean, double *d_cov, int *d_hmax, double *d_wmax, double *d_logz, double *d_w,
+                                          long long *d_emit, void *stream);
 
 /* ---- skeleton-coupled joint-wise aggregation WITHOUT ground truth: exact min-sum over the bone tree ------------------------
  * zedo_joint_reproj picks every joint of a pose on its own, and the chain models above couple a joint to itself along time.

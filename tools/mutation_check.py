@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: fifty-two one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: fifty-three one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -77,6 +77,10 @@ MUTANTS = [
     # the second-order selection on live streams (tests/test_joint_accel_stream_gpu.py; profiles/mutation_joint_accel_stream.txt): leaves
     # every other test green, and of that file the lag-0 comparisons, the clips that end before the shortened horizon matters and the refusals
     ("ZEDO_MUT_JAS_HORIZON", "zedo_joint_accel_stream_push: the horizon of frame n is taken as n + lag - 1, one frame short (zedo_joint_accel_stream.hip joint_accel_stream_emit_kernel)"),
+    # the second-order fusion on live streams (tests/test_joint_accel_stream_marginal_gpu.py; profiles/mutation_joint_accel_stream_marginal.txt):
+    # leaves every other test green, and of that file the lag-0 comparisons, the clips that end before the shortened horizon matters, the
+    # binding's and the pipeline's tests and the refusals
+    ("ZEDO_MUT_JASM_HORIZON", "zedo_joint_accel_stream_marginal_push: the horizon of frame n is taken as n + lag - 1, one frame short (zedo_joint_accel_stream_marginal.hip joint_accel_stream_marginal_emit_kernel)"),
     # the skeleton-coupled aggregation (tests/test_joint_tree_gpu.py, tests/test_select_joints_tree_driver_gpu.py) and, since its sum-product
     # twin shares the statement, the skeleton-coupled fusion's tests: leaves every other test green
     ("ZEDO_MUT_TREE_NO_HALF", "zedo_joint_tree_select and zedo_joint_tree_marginal: the bone term compares the assembled length with the SUM of the two hypotheses' lengths, the 0.5 is dropped (zedo_chain.h tr_bone: the recurrences and bone[n,.])"),

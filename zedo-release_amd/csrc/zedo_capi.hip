@@ -1053,6 +1053,46 @@ extern "C" int zedo_joint_accel_stream_push(const double *d_junary, const float 
     return ZEDO_OK;
 }
 
+// the fusion under the second-order model on live streams: A2, X and l of lag + max_frames + 2 frames per (stream, joint) in the caller's
+// state.  The shapes: those of the first-order streams at H <= 64, with two more rows per ring, and (lag + max_frames + 2) S J H^2 within int
+static bool accel_stream_marginal_dims_ok(int S, int H, int J, int lag, int max_frames) {
+    if (!stream_dims_ok(S, H, J, lag, max_frames) || H > JOINT_ACCEL_HMAX) return false;
+    return ((long long)lag + max_frames + 2) * ((long long)S * J * H) * H <= INT_MAX;
+}
+static int accel_stream_marginal_state_ok(const void *state, size_t state_bytes, int S, int H, int J, int lag, int max_frames) {
+    if (!state || !accel_stream_marginal_dims_ok(S, H, J, lag, max_frames) || (reinterpret_cast<uintptr_t>(state) & 7)) return ZEDO_E_BADARG;
+    return state_bytes < joint_accel_stream_marginal_bytes(S, H, J, lag, max_frames) ? ZEDO_E_WORKSPACE : ZEDO_OK;
+}
+
+extern "C" size_t zedo_joint_accel_stream_marginal_state_bytes(int S, int H, int J, int lag, int max_frames) {
+    return accel_stream_marginal_dims_ok(S, H, J, lag, max_frames) ? joint_accel_stream_marginal_bytes(S, H, J, lag, max_frames) : 0;
+}
+
+extern "C" int zedo_joint_accel_stream_marginal_reset(void *d_state, size_t state_bytes, int S, int H, int J, int lag, int max_frames,
+                                                      const int *d_which, void *stream) {
+    const int rc = accel_stream_marginal_state_ok(d_state, state_bytes, S, H, J, lag, max_frames);
+    if (rc != ZEDO_OK) return rc;
+    HIPCHK(launch_joint_accel_stream_marginal_reset(d_state, S, H, J, lag, max_frames, d_which, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
+extern "C" int zedo_joint_accel_stream_marginal_push(const double *d_junary, const float *d_x, const float *d_T, int S, int F, int H, int J,
+                                                     int lag, int max_frames, double lambda_v, double lambda_a, double tau,
+                                                     const int *d_flush, void *d_state, size_t state_bytes, double *d_mean, double *d_cov,
+                                                     int *d_hmax, double *d_wmax, double *d_logz, double *d_w, long long *d_emit,
+                                                     void *stream) {
+    if (!d_mean || !d_cov || !d_hmax || !d_wmax || !d_logz || !d_emit || F < 0 || F > max_frames) return ZEDO_E_BADARG;
+    if (F == 0 ? !d_flush : (!d_junary || !d_x)) return ZEDO_E_BADARG;                   // a push of no frames is a flush
+    if (!std::isfinite(lambda_v) || lambda_v < 0.0 || !std::isfinite(lambda_a) || lambda_a < 0.0) return ZEDO_E_BADARG;
+    if (!std::isfinite(tau) || !(tau > 0.0)) return ZEDO_E_BADARG;
+    const int rc = accel_stream_marginal_state_ok(d_state, state_bytes, S, H, J, lag, max_frames);
+    if (rc != ZEDO_OK) return rc;
+    HIPCHK(launch_joint_accel_stream_marginal_push(d_junary, d_x, d_T, S, F, H, J, lag, max_frames, lambda_v / tau, lambda_a / tau, tau,
+                                                   d_flush, d_state, d_mean, d_cov, d_hmax, d_wmax, d_logz, d_w, d_emit,
+                                                   (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
 // posterior marginals of the second-order model: forward-backward over pairs per (clip, joint), A2 in the workspace
 extern "C" size_t zedo_joint_accel_marginal_workspace_bytes(int N, int H, int J) {
     return chain_dims_ok(N, H, J, JOINT_ACCEL_HMAX) ? joint_accel_marginal_bytes(N, H, J) : 0;

@@ -1,12 +1,12 @@
 // What the label-free selection and fusion kernels share (zedo_temporal.hip, zedo_joint_temporal.hip, zedo_joint_stream.hip,
-// zedo_joint_stream_marginal.hip, zedo_joint_marginal.hip, zedo_joint_accel.hip, zedo_joint_accel_stream.hip, zedo_joint_accel_marginal.hip, zedo_joint_tree.hip, zedo_joint_tree_marginal.hip): the one
+// zedo_joint_stream_marginal.hip, zedo_joint_marginal.hip, zedo_joint_accel.hip, zedo_joint_accel_stream.hip, zedo_joint_accel_marginal.hip, zedo_joint_accel_stream_marginal.hip, zedo_joint_tree.hip, zedo_joint_tree_marginal.hip): the one
 // copy of their lane layout, their reductions and their staging.  The rules every user relies on live here and nowhere else:
 //   - a tie goes to the lowest index (strict comparisons, parts and waves combined in ascending order);
 //   - a sum is a butterfly inside each wave, then the waves in ascending order: a fixed order, no atomics;
 //   - a lane past H reads row H-1 and stores nothing;
 //   - an offset read from seq_start is clamped to 0 .. N before it is an address.
-// The recurrences themselves - what is minimised or summed - stay in their own files; the three that two files run, the first-order
-// chain's frame step, its sum-product twin and the second-order chain's frame step, are here.
+// The recurrences themselves - what is minimised or summed - stay in their own files; the four that two files run, the first-order
+// chain's frame step, its sum-product twin, the second-order chain's frame step and its sum-product twin, are here.
 #pragma once
 #include "zedo_internal.h"
 
@@ -398,6 +398,150 @@ __device__ __forceinline__ long long stream_horizon(const int *__restrict__ dr, 
     }
     return hi;
 }
+
+// ---- the second-order chain's sum-product step (zedo_joint_accel_marginal.hip on a whole clip, zedo_joint_accel_stream_marginal.hip on a
+// chunk of it and on the lag window): the step above with (min, +) replaced by (log-sum-exp, +) ----
+constexpr int JAM_CAP = 64;                                        // the pair tables of a (frame, joint) stay in the LDS
+
+// lse[k] = LSE_i (tab[i H + col[k]] - c_a |g[k] + Xb[i]|), i = 0 .. H-1, for the KA pairs of a lane: all lanes walk i in lockstep, Xb[i]
+// is a broadcast read and tab[i H + col] of neighbouring lanes is the same or the next double.  First walk: the largest term; second:
+// the sum of exp(term - largest), ascending in i (shifted by 0 where no term is above -inf: every exp is 0 and the result -inf).
+// |e| = sqrt(e0^2 + e1^2 + e2^2): the squares, then their sum ascending in c.
+template <int KA>
+__device__ __forceinline__ void jam_walk(const double *tab, const double *Xb, int H, const int (&col)[KA], const double (&g)[KA][3],
+                                         double c_a, double (&lse)[KA]) {
+    const double ninf = -__builtin_huge_val();
+    double sh[KA], sm[KA];
+#pragma unroll
+    for (int k = 0; k < KA; ++k) sh[k] = ninf;
+    for (int i = 0; i < H; ++i) {
+        const double p0 = Xb[i * 3], p1 = Xb[i * 3 + 1], p2 = Xb[i * 3 + 2];
+        const double *row = tab + i * H;
+#pragma unroll
+        for (int k = 0; k < KA; ++k) {
+            const double e0 = g[k][0] + p0, e1 = g[k][1] + p1, e2 = g[k][2] + p2;
+            const double t = row[col[k]] - c_a * sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+            if (t > sh[k]) sh[k] = t;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KA; ++k) { sh[k] = sh[k] > ninf ? sh[k] : 0.0; sm[k] = 0.0; }
+    for (int i = 0; i < H; ++i) {
+        const double p0 = Xb[i * 3], p1 = Xb[i * 3 + 1], p2 = Xb[i * 3 + 2];
+        const double *row = tab + i * H;
+#pragma unroll
+        for (int k = 0; k < KA; ++k) {
+            const double e0 = g[k][0] + p0, e1 = g[k][1] + p1, e2 = g[k][2] + p2;
+            const double t = row[col[k]] - c_a * sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+            sm[k] += exp(t - sh[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KA; ++k) lse[k] = sh[k] + log(sm[k]);
+}
+
+// LSE over the workgroup of the KA terms of every lane (-inf: no term), shifted by their largest: the lane's terms ascending in k, then
+// block_sum's fixed order.  At least one term is above -inf.  sred: CHAIN_W doubles of the LDS, free on entry and on return.
+template <int KA>
+__device__ __forceinline__ double jam_block_lse(const double (&t)[KA], double *sred, int tid) {
+    double v = t[0];
+#pragma unroll
+    for (int k = 1; k < KA; ++k) v = fmax(v, t[k]);
+    v = wave_max(v);
+    if ((tid & 63) == 0) sred[tid >> 6] = v;
+    __syncthreads();
+    v = sred[0];
+    for (int w = 1; w < CHAIN_W; ++w) v = fmax(v, sred[w]);
+    __syncthreads();                                               // sred is block_sum's next
+    double e[1] = {0.0};
+#pragma unroll
+    for (int k = 0; k < KA; ++k) e[0] += exp(t[k] - v);             // exp(-inf) = 0 where there is no term
+    block_sum<1>(e, sred, tid);
+    return v + log(e[0]);
+}
+
+// The forward value of a frame, between a kernel's barriers A and B, as statements in the kernel's own scope: A2[n] of the lane's pairs
+// into an [KA].  In scope: H, c_v, c_a; qh1, qh0 [KA]; scan (n continues a chain) and second, workgroup-uniform; of the LDS: sA = A2[n-1]
+// h''-major, X0, X1, X2 = X of frames n, n-1, n-2, L0, L1 = l of frames n, n-1.
+//   second (n-1 is a start):  A2[n][h',h] = l[n-1,h'] + (l[n,h] - c_v m[n,h',h])
+//   otherwise:  A2[n][h',h] = l[n,h] + (-c_v m[n,h',h] + LSE_h'' (A2[n-1][h'',h'] - c_a a[n,h'',h',h]))
+#define ZEDO_CHAIN_PAIR_FORWARD(KA)                                                                                                    \
+        if (scan) {                                                                                                                    \
+            ZEDO_CHAIN_PAIR_TERMS(KA, c_v, )                       /* g_c = X[n,h,c] - 2 X[n-1,h',c];  lm = c_v m[n,h',h] */           \
+            if (second) {                                                                                                              \
+                _Pragma("unroll") for (int k = 0; k < KA; ++k) an[k] = L1[qh1[k]] + (L0[qh0[k]] - lm[k]);                              \
+            } else {                                                                                                                   \
+                jam_walk<KA>(sA, X2, H, qh1, g, c_a, an);                                                                              \
+                _Pragma("unroll") for (int k = 0; k < KA; ++k) an[k] = L0[qh0[k]] + (an[k] - lm[k]);                                   \
+            }                                                                                                                          \
+        }
+
+// The backward body of a frame n, from barrier A to the outputs, as statements in the kernel's own scope: B2[n] into sB, the pair
+// marginals into sP, and everything that is read off them (ZEDO_CHAIN_MOMENTS) into the output row NJ of frame n - if EMIT - and, where
+// n is the second frame of its chain, into the row NJ - J of the chain's first frame, from the row sums of the same table.
+//   chain of one frame:  log Z = LSE_h l[n,h],  w[n,h] = exp(l[n,h] - log Z)
+//   chain end (n has pairs and `ends`):  B2[n] = 0,  log Z = LSE over all pairs of A2[n]
+//   otherwise, once per frame:  M[h+][h] = (l[n+1,h+] - c_v m[n+1,h,h+]) + B2[n+1][h,h+], stored h+-major: the walk's lanes of consecutive h
+//              read consecutive doubles; then  B2[n][h',h] = LSE_h+ (M[h+][h] - c_a a[n+1,h',h,h+]) - one square root per transition.  A lane
+//              keeps X[n-1,h'] - 2 X[n,h] and adds X[n+1,h+]: the second difference in ANOTHER association than the forward pass
+//   pi[n][h',h] = exp((A2[n][h',h] + B2[n][h',h]) - log Z) into the LDS;  w[n,h] = sum_h' pi[n][h',h], ascending, by lane h; the first
+//              frame c0 of a chain has no table: w[c0,h'] = sum_h pi[c0+1][h',h], ascending, formed at frame c0+1
+// In scope: H, HH, J, tid, hx, c_v, c_a_back, ninf, qnan; qh1, qh0, ac [KA] = A2[n] of the lane's pairs; is_dead, start, second, ends and
+// pairs = !is_dead && !start, workgroup-uniform; lz, carried from frame to frame; the outputs; of the LDS: sB = B2[n+1] at h H + h+, sM,
+// sP, Xp, X0, X1 = X of frames n+1, n, n-1, Lp, L0 = l of frames n+1, n, sred (6 CHAIN_W doubles) and sredi (CHAIN_W ints).
+#define ZEDO_CHAIN_PAIR_BACKWARD(KA, NJ, EMIT)                                                                                         \
+        double bn[KA];                                             /* B2[n] of this lane's pairs */                                    \
+        _Pragma("unroll") for (int k = 0; k < KA; ++k) bn[k] = 0.0;                                                                    \
+        __syncthreads();                                           /* A: B2[n+1], X and l of frames n+1, n, n-1 are in the LDS */      \
+        if (pairs && !ends) {                                                                                                          \
+            _Pragma("unroll") for (int k = 0; k < KA; ++k) {       /* the pair (h, h+) of frame n+1 at this lane's q */                \
+                const int q = tid + k * CHAIN_T, h = qh1[k], hp = qh0[k];                                                              \
+                if (q < HH) {                                                                                                          \
+                    const double d0 = Xp[hp * 3] - X0[h * 3], d1 = Xp[hp * 3 + 1] - X0[h * 3 + 1], d2 = Xp[hp * 3 + 2] - X0[h * 3 + 2]; \
+                    sM[hp * H + h] = (Lp[hp] - c_v * sqrt(d0 * d0 + d1 * d1 + d2 * d2)) + sB[q];                                       \
+                }                                                                                                                      \
+            }                                                                                                                          \
+            __syncthreads();                                       /* M is in the LDS; B2[n+1] has been read by every lane */          \
+            double g[KA][3];                                       /* g_c = X[n-1,h',c] - 2 X[n,h,c] */                                \
+            _Pragma("unroll") for (int k = 0; k < KA; ++k)                                                                             \
+                _Pragma("unroll") for (int c = 0; c < 3; ++c) g[k][c] = accel_lead(X1[qh1[k] * 3 + c], X0[qh0[k] * 3 + c]);            \
+            jam_walk<KA>(sM, Xp, H, qh0, g, c_a_back, bn);                                                                             \
+        }                                                                                                                              \
+        if (!is_dead && ends) {                                    /* (workgroup-uniform) log Z of the chain that ends here */         \
+            double t[KA];                                                                                                              \
+            _Pragma("unroll") for (int k = 0; k < KA; ++k)                                                                             \
+                t[k] = start ? (k == 0 && tid < H ? L0[tid] : ninf) : (tid + k * CHAIN_T < HH ? ac[k] : ninf);                         \
+            lz = jam_block_lse<KA>(t, sred, tid);                                                                                      \
+        }                                                                                                                              \
+        if (pairs) {                                                                                                                   \
+            _Pragma("unroll") for (int k = 0; k < KA; ++k) {                                                                           \
+                const int q = tid + k * CHAIN_T;                                                                                       \
+                if (q < HH) {                                                                                                          \
+                    sB[q] = bn[k];                                 /* B2[n][h',h] at h' H + h: frame n-1 reads it as B2[n+1][h,h+] */  \
+                    sP[q] = exp((ac[k] + bn[k]) - lz);                                                                                 \
+                }                                                                                                                      \
+            }                                                                                                                          \
+        }                                                                                                                              \
+        __syncthreads();                                           /* C: the pair marginals of frame n are in the LDS */               \
+        if (is_dead) {                                                                                                                 \
+            ZEDO_CHAIN_DEAD_OUTPUTS(1, tid, 0, true, NJ)                                                                               \
+        } else if (pairs || ends) {                                /* (a start with a successor is served by that successor, below) */ \
+            const int passes = pairs && second ? 2 : 1;            /* pass 1: frame n-1, the first of its chain, from the same table */ \
+            for (int p = (EMIT) ? 0 : 1; p < passes; ++p) {                                                                            \
+                const double *Xm = p ? X1 : X0;                                                                                        \
+                const double xm[1][3] = {{Xm[hx * 3], Xm[hx * 3 + 1], Xm[hx * 3 + 2]}};                                                \
+                double wv = 0.0;                                                                                                       \
+                if (tid < H) {                                                                                                         \
+                    if (!pairs) wv = exp(L0[tid] - lz);                                                                                \
+                    else if (p == 0)                                                                                                   \
+                        for (int h1 = 0; h1 < H; ++h1) wv += sP[h1 * H + tid];                                                         \
+                    else                                                                                                               \
+                        for (int h0 = 0; h0 < H; ++h0) wv += sP[tid * H + h0];                                                         \
+                }                                                                                                                      \
+                const size_t mj = (NJ) - (size_t)p * J;                                                                                \
+                ZEDO_CHAIN_MOMENTS(1, tid, 0, h < H, wv, xm, mj)                                                                       \
+            }                                                                                                                          \
+        }
 
 // ---- the bone tree: one workgroup per pose, everything in the LDS ----
 // sqrt(d0^2 + d1^2 + d2^2), d = a - b: products, then the sum ascending in c

@@ -284,6 +284,15 @@ size_t joint_accel_marginal_bytes(int N, int H, int J);
 hipError_t launch_joint_accel_marginal(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,
                                        int J, double c_v, double c_a, double tau, void *ws, double *mean, double *cov, int *hmax,
                                        double *wmax, double *logz, double *w, hipStream_t st);
+// the same posterior marginals on live streams (zedo_joint_accel_stream_marginal.hip); state: joint_accel_stream_marginal_bytes(S, H, J,
+// lag, max_frames), H <= 64, F <= max_frames; c_v = lambda_v / tau, c_a = lambda_a / tau
+size_t joint_accel_stream_marginal_bytes(int S, int H, int J, int lag, int max_frames);
+hipError_t launch_joint_accel_stream_marginal_reset(void *state, int S, int H, int J, int lag, int max_frames, const int *which,
+                                                    hipStream_t st);
+hipError_t launch_joint_accel_stream_marginal_push(const double *junary, const float *x, const float *T, int S, int F, int H, int J, int lag,
+                                                   int max_frames, double c_v, double c_a, double tau, const int *flush, void *state,
+                                                   double *mean, double *cov, int *hmax, double *wmax, double *logz, double *w,
+                                                   long long *emit, hipStream_t st);
 // skeleton-coupled joint-wise aggregation (zedo_joint_tree.hip): min-sum over the bone tree, one workgroup per pose, everything in the
 // LDS - joint_tree_lds_bytes(H, J) = 34 J H + 16 H + 4096 of the CU's TR_LDS bytes.  The host derives the post-order of the bones
 // (joint_tree_order: false for a parent array that is not a forest) and hands it to the kernel by value.

@@ -25,65 +25,6 @@
 
 namespace zedo {
 
-constexpr int JAM_CAP = 64;
-
-// lse[k] = LSE_i (tab[i H + col[k]] - c_a |g[k] + Xb[i]|), i = 0 .. H-1, for the KA pairs of a lane: all lanes walk i in lockstep, Xb[i]
-// is a broadcast read and tab[i H + col] of neighbouring lanes is the same or the next double.  First walk: the largest term; second:
-// the sum of exp(term - largest), ascending in i (shifted by 0 where no term is above -inf: every exp is 0 and the result -inf).
-// |e| = sqrt(e0^2 + e1^2 + e2^2): the squares, then their sum ascending in c.
-template <int KA>
-__device__ __forceinline__ void jam_walk(const double *tab, const double *Xb, int H, const int (&col)[KA], const double (&g)[KA][3],
-                                         double c_a, double (&lse)[KA]) {
-    const double ninf = -__builtin_huge_val();
-    double sh[KA], sm[KA];
-#pragma unroll
-    for (int k = 0; k < KA; ++k) sh[k] = ninf;
-    for (int i = 0; i < H; ++i) {
-        const double p0 = Xb[i * 3], p1 = Xb[i * 3 + 1], p2 = Xb[i * 3 + 2];
-        const double *row = tab + i * H;
-#pragma unroll
-        for (int k = 0; k < KA; ++k) {
-            const double e0 = g[k][0] + p0, e1 = g[k][1] + p1, e2 = g[k][2] + p2;
-            const double t = row[col[k]] - c_a * sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-            if (t > sh[k]) sh[k] = t;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < KA; ++k) { sh[k] = sh[k] > ninf ? sh[k] : 0.0; sm[k] = 0.0; }
-    for (int i = 0; i < H; ++i) {
-        const double p0 = Xb[i * 3], p1 = Xb[i * 3 + 1], p2 = Xb[i * 3 + 2];
-        const double *row = tab + i * H;
-#pragma unroll
-        for (int k = 0; k < KA; ++k) {
-            const double e0 = g[k][0] + p0, e1 = g[k][1] + p1, e2 = g[k][2] + p2;
-            const double t = row[col[k]] - c_a * sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-            sm[k] += exp(t - sh[k]);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < KA; ++k) lse[k] = sh[k] + log(sm[k]);
-}
-
-// LSE over the workgroup of the KA terms of every lane (-inf: no term), shifted by their largest: the lane's terms ascending in k, then
-// block_sum's fixed order.  At least one term is above -inf.  sred: CHAIN_W doubles of the LDS, free on entry and on return.
-template <int KA>
-__device__ __forceinline__ double jam_block_lse(const double (&t)[KA], double *sred, int tid) {
-    double v = t[0];
-#pragma unroll
-    for (int k = 1; k < KA; ++k) v = fmax(v, t[k]);
-    v = wave_max(v);
-    if ((tid & 63) == 0) sred[tid >> 6] = v;
-    __syncthreads();
-    v = sred[0];
-    for (int w = 1; w < CHAIN_W; ++w) v = fmax(v, sred[w]);
-    __syncthreads();                                               // sred is block_sum's next
-    double e[1] = {0.0};
-#pragma unroll
-    for (int k = 0; k < KA; ++k) e[0] += exp(t[k] - v);             // exp(-inf) = 0 where there is no term
-    block_sum<1>(e, sred, tid);
-    return v + log(e[0]);
-}
-
 // The forward recurrence of one (clip, joint): the lane layout, the LDS slots and the two barriers per frame of joint_accel_scan_kernel.
 // In the LDS: the table A2[n-1] as sA[h'' H + h'] (h''-major: what frame n-1 wrote at its own q), X of frames n, n-1 and n-2 and
 // l = -u / tau (-inf where the unary is not finite) of frames n and n-1.  A lane keeps g_c = X[n,h,c] - 2 X[n-1,h',c] of its pairs.
@@ -130,17 +71,7 @@ __global__ __launch_bounds__(CHAIN_T) void joint_accel_marginal_forward_kernel(c
         const double *X0 = sX[s0], *X1 = sX[s1], *X2 = sX[s2], *L0 = sL[n & 1], *L1 = sL[(n & 1) ^ 1];
         double an[KA];
         __syncthreads();                                           // A: A2[n-1], X[n], X[n-1], X[n-2], l[n], l[n-1] are in the LDS
-        if (scan) {
-            ZEDO_CHAIN_PAIR_TERMS(KA, c_v, )                       // g_c = X[n,h,c] - 2 X[n-1,h',c];  lm = c_v m[n,h',h]
-            if (second) {
-#pragma unroll
-                for (int k = 0; k < KA; ++k) an[k] = L1[qh1[k]] + (L0[qh0[k]] - lm[k]);
-            } else {
-                jam_walk<KA>(sA, X2, H, qh1, g, c_a, an);
-#pragma unroll
-                for (int k = 0; k < KA; ++k) an[k] = L0[qh0[k]] + (an[k] - lm[k]);
-            }
-        }
+        ZEDO_CHAIN_PAIR_FORWARD(KA)                                // the frame's value (zedo_chain.h): A2[n] of the lane's pairs into an
         __syncthreads();                                           // B: the LDS of frame n has been read by every lane
         if (scan) {
 #pragma unroll
@@ -233,63 +164,7 @@ __global__ __launch_bounds__(CHAIN_T) void joint_accel_marginal_backward_kernel(
         const bool ends = (n + 1 < b ? dead[nj + J] : 1) != 0;
         const bool pairs = !is_dead && !start;                     // (all workgroup-uniform) frame n has a table
         const double *Xp = sX[sp], *X0 = sX[s0], *X1 = sX[s1], *Lp = sL[sp], *L0 = sL[s0];
-        double bn[KA];                                             // B2[n] of this lane's pairs
-#pragma unroll
-        for (int k = 0; k < KA; ++k) bn[k] = 0.0;
-        __syncthreads();                                           // A: B2[n+1], X and l of frames n+1, n, n-1 are in the LDS
-        if (pairs && !ends) {
-#pragma unroll
-            for (int k = 0; k < KA; ++k) {                         // the pair (h, h+) of frame n+1 at this lane's q
-                const int q = tid + k * CHAIN_T, h = qh1[k], hp = qh0[k];
-                if (q < HH) {
-                    const double d0 = Xp[hp * 3] - X0[h * 3], d1 = Xp[hp * 3 + 1] - X0[h * 3 + 1], d2 = Xp[hp * 3 + 2] - X0[h * 3 + 2];
-                    sM[hp * H + h] = (Lp[hp] - c_v * sqrt(d0 * d0 + d1 * d1 + d2 * d2)) + sB[q];
-                }
-            }
-            __syncthreads();                                       // M is in the LDS; B2[n+1] has been read by every lane
-            double g[KA][3];                                       // g_c = X[n-1,h',c] - 2 X[n,h,c]
-#pragma unroll
-            for (int k = 0; k < KA; ++k)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) g[k][c] = accel_lead(X1[qh1[k] * 3 + c], X0[qh0[k] * 3 + c]);
-            jam_walk<KA>(sM, Xp, H, qh0, g, c_a_back, bn);
-        }
-        if (!is_dead && ends) {                                    // (workgroup-uniform) log Z of the chain that ends here
-            double t[KA];
-#pragma unroll
-            for (int k = 0; k < KA; ++k) t[k] = start ? (k == 0 && tid < H ? L0[tid] : ninf) : (tid + k * CHAIN_T < HH ? ac[k] : ninf);
-            lz = jam_block_lse<KA>(t, sred, tid);
-        }
-        if (pairs) {
-#pragma unroll
-            for (int k = 0; k < KA; ++k) {
-                const int q = tid + k * CHAIN_T;
-                if (q < HH) {
-                    sB[q] = bn[k];                                 // B2[n][h',h] at h' H + h: frame n-1 reads it as B2[n+1][h,h+]
-                    sP[q] = exp((ac[k] + bn[k]) - lz);
-                }
-            }
-        }
-        __syncthreads();                                           // C: the pair marginals of frame n are in the LDS
-        if (is_dead) {
-            ZEDO_CHAIN_DEAD_OUTPUTS(1, tid, 0, true, nj)
-        } else if (pairs || ends) {                                // (a start with a successor is served by that successor, below)
-            const int passes = pairs && second ? 2 : 1;            // pass 1: frame n-1, the first of its chain, from the same table
-            for (int p = 0; p < passes; ++p) {
-                const double *Xm = p ? X1 : X0;
-                const double xm[1][3] = {{Xm[hx * 3], Xm[hx * 3 + 1], Xm[hx * 3 + 2]}};
-                double wv = 0.0;
-                if (tid < H) {
-                    if (!pairs) wv = exp(L0[tid] - lz);
-                    else if (p == 0)
-                        for (int h1 = 0; h1 < H; ++h1) wv += sP[h1 * H + tid];
-                    else
-                        for (int h0 = 0; h0 < H; ++h0) wv += sP[tid * H + h0];
-                }
-                const size_t mj = nj - (size_t)p * J;
-                ZEDO_CHAIN_MOMENTS(1, tid, 0, h < H, wv, xm, mj)
-            }
-        }
+        ZEDO_CHAIN_PAIR_BACKWARD(KA, nj, true)                     // the frame's body (zedo_chain.h): B2[n], the pair marginals, the outputs
         if (tid < H) {                                             // frame n-2 into the slot of frame n+1: its last reader is above C
             sX[sp][tid * 3] = xc[0]; sX[sp][tid * 3 + 1] = xc[1]; sX[sp][tid * 3 + 2] = xc[2];
             sL[sp][tid] = lc;

@@ -84,6 +84,10 @@ SIGNATURES = {
     "zedo_joint_accel_stream_push": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "zedo_joint_accel_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_accel_marginal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "zedo_joint_accel_stream_marginal_state_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "zedo_joint_accel_stream_marginal_reset": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _vp]),
+    "zedo_joint_accel_stream_marginal_push": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, _d, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp]),
     "zedo_joint_stream_marginal_state_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "zedo_joint_stream_marginal_reset": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _vp]),
     "zedo_joint_stream_marginal_push": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _d, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -850,6 +854,51 @@ class JointAccelStream(JointStream):
                                                      self.state_bytes, _p(path, torch.int32), _p(cost, torch.float64),
                                                      _p(emit, torch.int64), _stream(dev)))
         return emit[:, 0], emit[:, 1], path[:, :rows], cost[:, :rows]
+
+
+def joint_accel_stream_marginal_state_bytes(S, H, J, lag, max_frames):
+    """The bytes of state zedo_joint_accel_stream_marginal_push needs for S streams of H hypotheses and J joints at this lag and at most
+    max_frames frames per push (host arithmetic: no GPU needed); 0 for a shape the calls refuse."""
+    return int(_lib.zedo_joint_accel_stream_marginal_state_bytes(int(S), int(H), int(J), int(lag), int(max_frames)))
+
+
+class JointAccelMarginalStream(JointStream):
+    """Joint-wise fusion on a live video under the second-order motion model (zedo_joint_accel_stream_marginal_push): the chain over pairs
+    of joint_accel_marginal for S independent streams, fed in chunks of at most max_frames frames, every frame's marginals formed `lag`
+    frames after it went in - the outputs of joint_accel_marginal on the stream's clip (the frames since its last reset or flush) cut
+    after frame n + lag: fixed-lag smoothing.  lag = 0 gives the filtering marginals; with lag >= the clip's length - 1 and a flush at
+    the end the outputs are joint_accel_marginal's bits.  At most 64 hypotheses; the state holds the pair table of every frame of the
+    window, 8 H^2 bytes per (stream, joint, frame).  Owns the state on `device` and resets it on creation.  lam, accel and tau as in
+    joint_accel_marginal, the same in every push; lam, accel, tau and the lag are untuned, and accuracy on real video is unmeasured.  A
+    steady-state push costs F backward walks of lag frames per (stream, joint)."""
+    _WHAT, _CALL = "JointAccelMarginalStream", "zedo_joint_accel_stream_marginal"
+    _RANGE = "1 <= H <= 64, lag >= 0, sizes >= 1, (lag + max_frames + 2) S J H^2 <= INT_MAX"
+
+    def __init__(self, S, H, J, lag, max_frames, lam=100.0, accel=100.0, tau=1.0, device=None):
+        self.accel, self.tau = float(accel), float(tau)
+        super().__init__(S, H, J, lag, max_frames, lam, device)
+
+    def push(self, junary, x, T=None, flush=None, return_weights=False):
+        """The chunk and flush of JointStream.push -> the tuple of JointMarginalStream.push: (first [S] i64, count [S] i64, mean
+        [S,F+lag,J,3] f64, cov [S,F+lag,J,6] f64, hmax [S,F+lag,J] i32, wmax [S,F+lag,J] f64, logz [S,F+lag,J] f64[, w [S,F+lag,J,H]
+        f64]), rows as there; the outputs of a row are joint_accel_marginal's.  junary = None: a push of no frames (flush required)."""
+        fl, F, dev = self._chunk(junary, x, T, flush)
+        S, H, J = self.S, self.H, self.J
+        with torch.cuda.device(dev):
+            rows = F + self.lag                                      # lag = 0 and no frames: a row nobody writes keeps the pointers non-NULL
+            mean, cov, hmax, wmax, logz, w = (None if t is None else t.view(S, max(rows, 1), *t.shape[1:])
+                                              for t in _marginal_outputs(S * max(rows, 1), J, H, dev, return_weights))
+            emit = torch.empty((S, 2), dtype=torch.int64, device=dev)
+            _check(_lib.zedo_joint_accel_stream_marginal_push(_p(junary, torch.float64), _p(x), _p(T), S, F, H, J, self.lag, self.max_frames,
+                                                              self.lam, self.accel, self.tau, _p(fl, torch.int32),
+                                                              _p(self.state, torch.uint8), self.state_bytes, _p(mean, torch.float64),
+                                                              _p(cov, torch.float64), _p(hmax, torch.int32), _p(wmax, torch.float64),
+                                                              _p(logz, torch.float64), _p(w, torch.float64), _p(emit, torch.int64),
+                                                              _stream(dev)))
+        out = (emit[:, 0], emit[:, 1]) + tuple(t[:, :rows] for t in (mean, cov, hmax, wmax, logz))
+        return out + (w[:, :rows],) if return_weights else out
+
+    flush = JointMarginalStream.flush
 
 
 # the 16 bones every ported dataset's get_skeleton() returns (H36M's 17 joints)

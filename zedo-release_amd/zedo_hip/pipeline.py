@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from . import (H36M_EDGES, SINGULAR_MSG, JointAccelStream, JointMarginalStream, JointStream, Schedule, Weights, ZedoError, ipo_fit, joint_accel_marginal, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
+from . import (H36M_EDGES, SINGULAR_MSG, JointAccelMarginalStream, JointAccelStream, JointMarginalStream, JointStream, Schedule, Weights, ZedoError, ipo_fit, joint_accel_marginal, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
                joint_temporal_select, joint_tree_marginal, joint_tree_select, skeleton_parents, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
@@ -354,6 +354,22 @@ class Pipeline:
         jerr = self._joint_unaries("fuse_joints_accel", x, T)
         with torch.cuda.device(self.device):
             return joint_accel_marginal(jerr, x, T, seq_start, self.N, lam, accel, tau) + (jerr,)
+
+    def open_joint_accel_fuse_stream(self, S, lag, max_frames, lam=100.0, accel=100.0, tau=1.0):
+        """The state of fuse_joints_accel's chain over pairs for S live streams (JointAccelMarginalStream): H (at most 64) and the joint
+        count are those of the pipeline, every frame's marginals are formed `lag` frames after it went in, a push holds at most
+        max_frames frames per stream.  lam, accel, tau and the lag are untuned; accuracy on real video is unmeasured."""
+        return self._open_stream("open_joint_accel_fuse_stream", JointAccelMarginalStream, S, lag, max_frames, lam, accel, tau)
+
+    def push_fuse_joints_accel(self, js, x, T, flush=None):
+        """fuse_joints_accel on live input, on the problem of load() with N = S F poses - F new frames of each of the S streams of
+        js = open_joint_accel_fuse_stream(...), pose n = s F + f: x [H*N,17,3] and T [H*N,3], ALL rows; flush: None, or [S] flags - the
+        streams whose clip ends here.  -> (first [S] i64, count [S] i64, mean [S,F+lag,17,3] f64, cov [S,F+lag,17,6] f64, hmax
+        [S,F+lag,17] i32, wmax [S,F+lag,17] f64, logz [S,F+lag,17] f64, jerr [H*N,17] f64): the unaries are zedo_joint_reproj's
+        per-(row, joint) distances exactly as push_joints_temporal forms them; stream s emits the frames first[s] .. first[s] + count[s]
+        - 1 of its clip, each as fuse_joints_accel reports it on the clip cut `lag` frames later
+        (zedo_joint_accel_stream_marginal_push).  lam, accel, tau and the lag are untuned; accuracy on real video is unmeasured."""
+        return self._push_stream("push_fuse_joints_accel", js, x, T, flush)
 
     def take(self, rows_full, idx):
         """The winning row of every pose: rows_full [H*N, ...] (all global rows, h-major), idx [N] -> rows_full.view(H, N, ...)[idx, arange(N)].
