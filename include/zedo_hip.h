@@ -56,7 +56,9 @@ extern "C" {
                               * still 5 (additive): + zedo_joint_accel_stream_state_bytes, zedo_joint_accel_stream_reset,
                               *                       zedo_joint_accel_stream_push;
                               * still 5 (additive): + zedo_joint_accel_stream_marginal_state_bytes,
-                              *                       zedo_joint_accel_stream_marginal_reset, zedo_joint_accel_stream_marginal_push */
+                              *                       zedo_joint_accel_stream_marginal_reset, zedo_joint_accel_stream_marginal_push;
+                              * still 5 (additive): + zedo_temporal_stream_state_bytes, zedo_temporal_stream_reset,
+                              *                       zedo_temporal_stream_push */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -469,6 +471,65 @@ int zedo_joint_stream_reset(void *d_state, size_t state_bytes, int S, int H, int
 int zedo_joint_stream_push(const double *d_junary, const float *d_x, const float *d_T, int S, int F, int H, int J, int lag,
                            int max_frames, double lambda, const int *d_flush, void *d_state, size_t state_bytes, int *d_path_h,
                            double *d_cost, long long *d_emit, void *stream);
+
+/* ---- pose-level selection on a LIVE video: the chain of zedo_temporal_select, fixed-lag, with the state in caller-owned memory ----
+ * Offline, every joint-wise answer along a video is assembled in the frame of the pose-level path of zedo_temporal_select
+ * (zedo_joint_compose with d_ref_h = that path), and that call needs the whole clip.  This is its chain as an online call for S
+ * independent streams at once, the sibling of zedo_joint_stream_push: frames are pushed in chunks of any size, the tables live in
+ * d_state between the calls, and the decision for a frame comes out `lag` frames after the frame went in.  It is the decision of
+ * zedo_temporal_select on the clip cut after frame n + lag; with a lag of at least the clip's length - 1 and a flush at the end
+ * the outputs are that call's bits.  The choice of lag is untuned; whether a fixed-lag path is closer to ground truth than the
+ * per-frame choice on real video is not measured.
+ * A stream's CLIP is the frames pushed since its last reset or flush, t = 0, 1, ..  u, m (the mean over J of the joint distances on
+ * x alone - there is no T here -, the sums ascending in c, then in j, divided by J), DEAD, "chain start", D and back are those of
+ * zedo_temporal_select, word for word, on that clip: prefix quantities, which do not depend on how the frames were cut into
+ * calls.  With lag >= 0:
+ *   frame n of a clip is EMITTED by the first push after which the clip holds frame n + lag, or by the push that flushes the
+ *   stream, whichever comes first, in frame order.
+ *   For a live frame n let c(n) be the last frame of n's chain on the frames the clip holds after that push - the first m >= n
+ *   whose successor is dead or absent - and e = min(n + lag, c(n)).  Then
+ *     h_e = the lowest h that minimises D[e,.];  h_{m-1} = back[m,h_m] for m = e .. n+1;
+ *     path[n] = h_n;  cost[n] = D[n,h_n].
+ *   A dead frame reports hypothesis 0 and cost +inf.  After a flush the stream's next frame is t = 0 of a new clip.
+ * So lag = 0 gives the lowest arg-min of D[n,.]; the outputs do not depend on the chunking; with lag >= the clip's length - 1 and
+ * a flush they are the bits of zedo_temporal_select on the clip, and at any lag those of that call on the clip cut after frame
+ * n + lag; with J = 1 they are the bits of zedo_joint_stream_push with d_T = NULL on the same tensors (as the offline pair).
+ * zedo_temporal_stream_push: the chunk is N = S*F frames in the layout of zedo_temporal_select - rows (h,n) h-major with
+ * n = s*F + f: d_unary [H*N] float64, d_x [H*N,J,3] fp32 - stream s's chunk is a "clip" of F frames of an offline call on the same
+ * tensors.  d_flush [S] int32 ON THE DEVICE (NULL: none): stream s is flushed after its chunk if d_flush[s] != 0.  F = 0 is legal
+ * only with d_flush; d_unary and d_x are then unused.
+ * Outputs: d_path_h [S, F+lag] int32 and d_cost [S, F+lag] float64, row r of stream s = the r-th frame this push emits for it;
+ * d_emit [S,2] int64 = the clip-local index of the first emitted frame (of the next one to be emitted if the count is 0) and the
+ * count.  Rows at and after the count are not written.  With t the frames the clip held before the push, the count is
+ *   held = min(lag, t) + F;   count = held if the stream is flushed, else max(0, held - lag);   first = max(0, t - lag)
+ * - the formula of zedo_joint_stream_push, computable on the host without reading d_emit.
+ * zedo_temporal_stream_reset empties the streams with d_which[s] != 0 (d_which [S] int32 ON THE DEVICE; NULL: all of them);
+ * pending frames are dropped.  The state need not be initialised before its first reset, and must have been reset before its
+ * first push.
+ * State (8-byte aligned), with R = lag + max_frames rows per ring, in this order:
+ *   D float64 [S,R,H] | D float64 [S,H] of the clip's last frame | the clip's frame count int64 [S] |
+ *   the transition costs of the current push float64 [S,max_frames,H,H] (scratch: its content between pushes is unspecified) |
+ *   back int32 [S,R,H] | the dead flags of the ring's frames int32 [S,R] | the dead flag of the last frame int32 [S] |
+ *   x of the clip's last frame AS THE fp32 IT ARRIVED IN [S,H,J,3] (the offline call converts x at each use: the same bits)
+ * - zedo_temporal_stream_state_bytes = 8 (S R H + S H + S + S max_frames H^2) + 4 (S R H + S R + S + 3 S H J) rounded up to 8; 0
+ * for shapes the calls refuse.  Frame m of a clip sits in row m % R.  A push writes the rows of its F <= max_frames frames and then
+ * reads at most the lag frames before them: never a row it has overwritten (R = 1 - lag 0, max_frames 1 - included).
+ * Contract: 1 <= H <= 1024 (D[t-1,.] stays in the LDS: the resident recurrence of zedo_temporal_select only), J >= 1, S >= 1,
+ * max_frames >= 1, 0 <= F <= max_frames, lag >= 0, (lag + max_frames)*S*H, S*max_frames*H*H and 3*S*H*J each <= INT_MAX, finite
+ * lambda >= 0; ZEDO_E_BADARG with nothing written and the state untouched for a NULL pointer other than d_flush (F > 0) and
+ * d_which, a size out of these ranges, F = 0 without d_flush, a negative or non-finite lambda, or a state that is not 8-byte
+ * aligned; ZEDO_E_WORKSPACE with nothing written and the state untouched if state_bytes is too small; allocates nothing,
+ * synchronises nothing, enqueues on `stream` only: legal under stream capture - a replay advances the state.  No atomics: the
+ * bits do not depend on the run, the chunking, the content of the state before its reset or the alignment of d_x.  Every value
+ * read from the state is clamped before it is an index.  Five launches per push: the dead flags, the transition costs (parallel
+ * over frame, h' and h), one workgroup per stream for the recurrence, one wave per (emitted frame, stream) for the decision - at
+ * most lag dependent reads of back - and the frame counts. */
+size_t zedo_temporal_stream_state_bytes(int S, int H, int J, int lag, int max_frames);
+int zedo_temporal_stream_reset(void *d_state, size_t state_bytes, int S, int H, int J, int lag, int max_frames, const int *d_which,
+                               void *stream);
+int zedo_temporal_stream_push(const double *d_unary, const float *d_x, int S, int F, int H, int J, int lag, int max_frames,
+                              double lambda, const int *d_flush, void *d_state, size_t state_bytes, int *d_path_h, double *d_cost,
+                              long long *d_emit, void *stream);
 
 /* ---- joint-wise fusion on a LIVE video WITHOUT ground truth: fixed-lag streaming sum-product ----------------------------------
  * zedo_joint_stream_push is a hard decision: one hypothesis per joint, no spread.  zedo_joint_marginal (below) gives the soft

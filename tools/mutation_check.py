@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sensitivity of the GPU parity suite: fifty-three one-line mutations of the HIP path, each of which must turn
+"""Sensitivity of the GPU parity suite: fifty-four one-line mutations of the HIP path, each of which must turn
 at least one `-m gpu` test red (run on the GPU box from the repo root: `python tools/mutation_check.py [out.txt]`).
 
 Each mutant is the product library built with ONE extra -D flag (the hooks are `#ifdef ZEDO_MUT_*` lines in csrc/,
@@ -62,6 +62,9 @@ MUTANTS = [
     ("ZEDO_MUT_JT_NO_T", "zedo_joint_temporal_select and zedo_joint_stream_push: the motion term is taken on x alone although d_T was given (zedo_chain.h ZEDO_CHAIN_STEP_T: joint_temporal_scan_kernel and joint_stream_scan_kernel)"),
     # the joint-wise selection on live streams (tests/test_joint_stream_gpu.py): leaves every other test green
     ("ZEDO_MUT_JS_HORIZON", "zedo_joint_stream_push: the horizon of frame n is taken as n + lag - 1, one frame short (zedo_joint_stream.hip joint_stream_emit_kernel)"),
+    # the pose-level selection on live streams (tests/test_temporal_stream_gpu.py; profiles/mutation_temporal_stream.txt): leaves every
+    # other test green, and in that file the tests that push every clip whole or carry one frame per clip
+    ("ZEDO_MUT_TSTREAM_LASTX", "zedo_temporal_stream_push: the state's copy of x is not refreshed after a push, the next push's first transition is taken from stale poses (zedo_temporal_stream.hip temporal_stream_scan_kernel)"),
     # the joint-wise fusion on live streams (tests/test_joint_stream_marginal_gpu.py; profiles/mutation_joint_stream_marginal.txt): leaves
     # every other test green, and of that file the lag-0 comparisons, the cells whose clips end before the shortened horizon matters, the
     # clip of one frame and the refusals; the tests that compare the call with itself go red - every one of them also holds it to the

@@ -958,6 +958,44 @@ extern "C" int zedo_joint_stream_push(const double *d_junary, const float *d_x, 
     return ZEDO_OK;
 }
 
+// ---- the pose-level chain of zedo_temporal_select on live streams: the resident scan only (H <= 1024, TS_CAP of zedo_temporal.h) ----
+// the shapes the three entry points accept: (lag + max_frames) S H, S max_frames H H and 3 S H J within int
+static bool temporal_stream_dims_ok(int S, int H, int J, int lag, int max_frames) {
+    if (S < 1 || H < 1 || J < 1 || H > JOINT_CHAIN_HMAX || lag < 0 || max_frames < 1) return false;
+    const long long sh = (long long)S * H, rows = (long long)lag + max_frames, sm = (long long)S * max_frames;
+    if (sh > INT_MAX || rows > INT_MAX || sm > INT_MAX) return false;
+    return rows * sh <= INT_MAX && sm * H * H <= INT_MAX && sh * J <= INT_MAX / 3;
+}
+static int temporal_stream_state_ok(const void *state, size_t state_bytes, int S, int H, int J, int lag, int max_frames) {
+    if (!state || !temporal_stream_dims_ok(S, H, J, lag, max_frames) || (reinterpret_cast<uintptr_t>(state) & 7)) return ZEDO_E_BADARG;
+    return state_bytes < temporal_stream_bytes(S, H, J, lag, max_frames) ? ZEDO_E_WORKSPACE : ZEDO_OK;
+}
+
+extern "C" size_t zedo_temporal_stream_state_bytes(int S, int H, int J, int lag, int max_frames) {
+    return temporal_stream_dims_ok(S, H, J, lag, max_frames) ? temporal_stream_bytes(S, H, J, lag, max_frames) : 0;
+}
+
+extern "C" int zedo_temporal_stream_reset(void *d_state, size_t state_bytes, int S, int H, int J, int lag, int max_frames,
+                                          const int *d_which, void *stream) {
+    const int rc = temporal_stream_state_ok(d_state, state_bytes, S, H, J, lag, max_frames);
+    if (rc != ZEDO_OK) return rc;
+    HIPCHK(launch_temporal_stream_reset(d_state, S, H, J, lag, max_frames, d_which, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
+extern "C" int zedo_temporal_stream_push(const double *d_unary, const float *d_x, int S, int F, int H, int J, int lag, int max_frames,
+                                         double lambda, const int *d_flush, void *d_state, size_t state_bytes, int *d_path_h,
+                                         double *d_cost, long long *d_emit, void *stream) {
+    if (!d_path_h || !d_cost || !d_emit || F < 0 || F > max_frames) return ZEDO_E_BADARG;
+    if (F == 0 ? !d_flush : (!d_unary || !d_x)) return ZEDO_E_BADARG;                    // a push of no frames is a flush
+    if (!std::isfinite(lambda) || lambda < 0.0) return ZEDO_E_BADARG;
+    const int rc = temporal_stream_state_ok(d_state, state_bytes, S, H, J, lag, max_frames);
+    if (rc != ZEDO_OK) return rc;
+    HIPCHK(launch_temporal_stream_push(d_unary, d_x, S, F, H, J, lag, max_frames, lambda, d_flush, d_state, d_path_h, d_cost, d_emit,
+                                       (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
 // the fusion on live streams: A, X and l of lag + max_frames frames per (stream, joint) in the caller's state
 extern "C" size_t zedo_joint_stream_marginal_state_bytes(int S, int H, int J, int lag, int max_frames) {
     return stream_dims_ok(S, H, J, lag, max_frames) ? joint_stream_marginal_bytes(S, H, J, lag, max_frames) : 0;

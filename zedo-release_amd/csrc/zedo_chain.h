@@ -1,4 +1,4 @@
-// What the label-free selection and fusion kernels share (zedo_temporal.hip, zedo_joint_temporal.hip, zedo_joint_stream.hip,
+// What the label-free selection and fusion kernels share (zedo_temporal.hip, zedo_temporal_stream.hip, zedo_joint_temporal.hip, zedo_joint_stream.hip,
 // zedo_joint_stream_marginal.hip, zedo_joint_marginal.hip, zedo_joint_accel.hip, zedo_joint_accel_stream.hip, zedo_joint_accel_marginal.hip, zedo_joint_accel_stream_marginal.hip, zedo_joint_tree.hip, zedo_joint_tree_marginal.hip): the one
 // copy of their lane layout, their reductions and their staging.  The rules every user relies on live here and nowhere else:
 //   - a tie goes to the lowest index (strict comparisons, parts and waves combined in ascending order);
@@ -202,6 +202,11 @@ __global__ __launch_bounds__(256) void joint_stream_dead_kernel(const double *__
                                          int R, int *__restrict__ dead);
 __global__ __launch_bounds__(256) void joint_stream_advance_kernel(const int *__restrict__ flush, int S, int F, int lag, long long *__restrict__ t,
                                             long long *__restrict__ emit);
+// and the decision of the first-order chains, whatever a chain is made of - J chains per stream, tables D [SJ,R,H], back [SJ,R,H], dead
+// [SJ,R]: one wave per (stream, output row, joint).  The pose-level stream (zedo_temporal_stream.hip) takes it with J = 1.
+__global__ __launch_bounds__(CHAIN_T) void joint_stream_emit_kernel(const long long *__restrict__ tcount, const int *__restrict__ flush, int S, int F,
+                                                  int H, int J, int R, int lag, const double *__restrict__ D, const int *__restrict__ back,
+                                                  const int *__restrict__ dead, int *__restrict__ path, double *__restrict__ cost);
 
 // ---- the first-order chain's sum-product step (zedo_joint_marginal.hip on a whole clip, zedo_joint_stream_marginal.hip on a chunk of
 // it and on the lag window): a Viterbi step with (min, +) replaced by (log-sum-exp, +) ----

@@ -248,6 +248,14 @@ size_t joint_temporal_bytes(int N, int H, int J);
 hipError_t launch_joint_temporal_select(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,
                                         int J, double lambda, void *ws, int *path, double *cost, hipStream_t st);
 hipError_t launch_joint_temporal_dead(const double *junary, int H, int NJ, int *dead, hipStream_t st);
+// the pose-level chain of zedo_temporal.hip on live streams (zedo_temporal_stream.hip); state: temporal_stream_bytes(S, H, J, lag,
+// max_frames), H <= 1024, F <= max_frames
+size_t temporal_stream_bytes(int S, int H, int J, int lag, int max_frames);
+hipError_t launch_temporal_stream_reset(void *state, int S, int H, int J, int lag, int max_frames, const int *which, hipStream_t st);
+hipError_t launch_temporal_stream_push(const double *unary, const float *x, int S, int F, int H, int J, int lag, int max_frames,
+                                       double lambda, const int *flush, void *state, int *path, double *cost, long long *emit,
+                                       hipStream_t st);
+
 // the same chain on live streams (zedo_joint_stream.hip); state: joint_stream_bytes(S, H, J, lag, max_frames), H <= 1024, F <= max_frames
 size_t joint_stream_bytes(int S, int H, int J, int lag, int max_frames);
 hipError_t launch_joint_stream_reset(void *state, int S, int H, int J, int lag, int max_frames, const int *which, hipStream_t st);

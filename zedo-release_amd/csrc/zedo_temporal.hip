@@ -8,8 +8,9 @@
 //   temporal_backtrack_kernel   the backward pass, one workgroup per clip, runs of the back table staged through the LDS
 // The host cuts the frames into chunks of C (whatever transition costs the caller's workspace holds) and launches the transition and the
 // scan kernel per chunk; D and back live in the workspace for all frames, so the result does not depend on C.  No atomics.  The arg-min
-// reduction and the workspace carving are zedo_chain.h's.
-#include "zedo_chain.h"
+// reduction and the workspace carving are zedo_chain.h's; the statements of a transition tile and of a frame of the resident scan are
+// zedo_temporal.h's, where the call on live streams (zedo_temporal_stream.hip) takes them from as well.
+#include "zedo_temporal.h"
 
 #include <algorithm>
 
@@ -23,64 +24,17 @@ __global__ __launch_bounds__(256) void temporal_dead_kernel(const double *__rest
     dead[n] = any ? 0 : 1;
 }
 
-// m[n,h',h] = (1/J) sum_j || x[h,n,j] - x[h',n-1,j] ||, sums ascending in c, then in j.  One workgroup per (frame n of the chunk, tile of
-// TT_H hypotheses h of frame n, tile of TT_P hypotheses h' of frame n-1): the tiles' poses arrive in the LDS TT_J joints at a time
-// (coalesced along a pose's coordinates, any alignment, any J), each of the 256 lanes keeps the running sums of its TT_P / 4 pairs in
-// registers across the joint pieces - the order of the additions is that of one loop over j.  [hyp][TT_LD] with an odd TT_LD: the 64
-// lanes of a wave read 64 different h at an odd word stride (no bank conflict) and one h' (a broadcast).  Written as
-// M[n - c0][h'][h]: the scan's lanes (one per h) read a row of it coalesced, and a wave of this kernel writes 512 contiguous bytes.
-constexpr int TT_H = 64, TT_P = 16, TT_J = 32, TT_LD = TT_J * 3 + 1, TT_T = 256, TT_K = TT_P / (TT_T / TT_H);
-static_assert(TT_T == 4 * TT_H && TT_K * 4 == TT_P && (TT_LD & 1), "four h' rows per pass over the 64 h lanes, odd LDS row stride");
+// m[n,h',h] of the frames of a chunk (ZEDO_TEMPORAL_TILE of zedo_temporal.h): frame n - 1 is row n - 1 of the same tensor.  Written as
+// M[n - c0][h'][h].
 __global__ __launch_bounds__(TT_T) void temporal_transition_kernel(const float *__restrict__ x, int H, int N, int J, int c0,
                                                                    double *__restrict__ M) {
     __shared__ float sc[TT_H * TT_LD];                             // frame n, hypotheses h0 ..
     __shared__ float sp[TT_P * TT_LD];                             // frame n-1, hypotheses p0 ..
     const int n = c0 + blockIdx.x;
     if (n < 1) return;                                             // frame 0 has no predecessor (workgroup-uniform)
-    const int tid = threadIdx.x, h0 = blockIdx.y * TT_H, p0 = blockIdx.z * TT_P;
-    const int nh = min(TT_H, H - h0), np = min(TT_P, H - p0);
-    const int lh = tid & (TT_H - 1), lp = tid / TT_H;             // this lane's h and the first of its h' (then every fourth)
+    ZEDO_TEMPORAL_TILE_LANES
     const size_t hs = (size_t)N * J * 3;                           // floats from one hypothesis of a frame to the next
-    double acc[TT_K];
-#pragma unroll
-    for (int k = 0; k < TT_K; ++k) acc[k] = 0.0;
-    for (int j0 = 0; j0 < J; j0 += TT_J) {
-        const int ne = min(TT_J, J - j0) * 3;                      // floats of this piece per pose
-#ifdef ZEDO_MUT_TT_PIECE   // tools/mutation_check.py only: every piece stages joints 0 .. of the pose again (valid addresses: ne <= 3 J)
-        const int js = 0;
-#else
-        const int js = j0;
-#endif
-        __syncthreads();                                           // the previous piece has been read by every lane
-        for (int q = tid; q < nh * ne; q += TT_T) {
-            const int r = q / ne, e = q - r * ne;
-            sc[r * TT_LD + e] = x[(size_t)(h0 + r) * hs + ((size_t)n * J + js) * 3 + e];
-        }
-        for (int q = tid; q < np * ne; q += TT_T) {
-            const int r = q / ne, e = q - r * ne;
-            sp[r * TT_LD + e] = x[(size_t)(p0 + r) * hs + ((size_t)(n - 1) * J + js) * 3 + e];
-        }
-        __syncthreads();                                           // the lanes read what other lanes have staged
-        if (lh < nh) {
-            const float *a = sc + lh * TT_LD;
-            for (int e = 0; e < ne; e += 3) {
-                const double a0 = (double)a[e], a1 = (double)a[e + 1], a2 = (double)a[e + 2];
-#pragma unroll
-                for (int k = 0; k < TT_K; ++k) {
-                    const float *b = sp + min(lp + 4 * k, np - 1) * TT_LD;          // (a row past the tile is computed and not stored)
-                    const double d0 = a0 - (double)b[e], d1 = a1 - (double)b[e + 1], d2 = a2 - (double)b[e + 2];
-                    acc[k] += sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-                }
-            }
-        }
-    }
-    if (lh < nh) {
-#pragma unroll
-        for (int k = 0; k < TT_K; ++k) {
-            const int p = lp + 4 * k;
-            if (p < np) M[((size_t)blockIdx.x * H + (p0 + p)) * H + (h0 + lh)] = acc[k] / (double)J;
-        }
-    }
+    ZEDO_TEMPORAL_TILE(x[(size_t)(h0 + r) * hs + ((size_t)n * J + js) * 3 + e], x[(size_t)(p0 + r) * hs + ((size_t)(n - 1) * J + js) * 3 + e])
 }
 
 // The forward recurrence.  One workgroup per clip s walks the frames of the chunk [c0, c0 + cnt) that fall inside
@@ -94,7 +48,6 @@ __global__ __launch_bounds__(TT_T) void temporal_transition_kernel(const float *
 // TS_PF transition costs of the lane's first h - is fetched BEFORE the barrier that ends frame n.
 // A frame that ends a chain (last of the clip, or frame n+1 dead) also gets the lowest arg-min of D[n,.] (endh[n]): the backward pass
 // starts there and needs no reduction of its own.
-constexpr int TS_CAP = 1024, TS_PF = 16;
 template <bool RESIDENT>
 __global__ __launch_bounds__(256) void temporal_scan_kernel(const double *__restrict__ unary, const double *__restrict__ M,
                                                             const int *__restrict__ seq_start, const int *__restrict__ dead, int H, int N,
@@ -133,41 +86,9 @@ __global__ __launch_bounds__(256) void temporal_scan_kernel(const double *__rest
         __syncthreads();                                           // D[n-1,.] of every lane is in sD[cur] (RESIDENT) / in the table
         const double *Mn = M + (size_t)(n - c0) * HH;
         if (is_dead || start) {
-            for (int h = tid; h < H; h += T) {
-                const double u0 = h == tid ? uc : unary[(size_t)h * N + n];
-                const double d = (!is_dead && finite64(u0)) ? u0 : inf;
-                D[(size_t)n * H + h] = d;
-                back[(size_t)n * H + h] = -1;
-                if (RESIDENT) sD[(cur ^ 1) * TS_CAP + h] = d;
-            }
+            ZEDO_TEMPORAL_FRAME_START(unary[(size_t)h * N + n], D[(size_t)n * H + h], back[(size_t)n * H + h])
         } else if (RESIDENT) {
-            const double *prev = sD + cur * TS_CAP;
-            for (int h = tid; h < H; h += T) {
-                const bool first = h == tid;
-                const double u0 = first ? uc : unary[(size_t)h * N + n];
-                double best = inf;
-                int bh = 0;
-                auto take = [&](int hp, double m) {
-#ifdef ZEDO_MUT_TEMPORAL_LAMBDA   // tools/mutation_check.py only: the motion term is not weighted
-                    const double c = prev[hp] + m;
-#else
-                    const double c = prev[hp] + lambda * m;
-#endif
-                    if (hp == 0 || c < best) { best = c; bh = hp; }      // strict: the lowest h' that attains the minimum
-                };
-                int hp = 0;
-                if (first) {
-#pragma unroll
-                    for (int k = 0; k < TS_PF; ++k) if (k < H) take(k, mc[k]);
-                    hp = min(TS_PF, H);
-                }
-#pragma unroll 8
-                for (; hp < H; ++hp) take(hp, Mn[(size_t)hp * H + h]);
-                const double d = (finite64(u0) ? u0 : inf) + best;
-                D[(size_t)n * H + h] = d;
-                back[(size_t)n * H + h] = bh;
-                sD[(cur ^ 1) * TS_CAP + h] = d;
-            }
+            ZEDO_TEMPORAL_FRAME_RESIDENT(unary[(size_t)h * N + n], D[(size_t)n * H + h], back[(size_t)n * H + h])
         } else {
             // H above TS_CAP: every group of T hypotheses walks D[n-1,.] through the LDS in pieces of TS_CAP; all lanes take every barrier
             for (int g = 0; g < H; g += T) {
@@ -182,11 +103,7 @@ __global__ __launch_bounds__(256) void temporal_scan_kernel(const double *__rest
                     if (h < H)
 #pragma unroll 8
                         for (int q = 0; q < nq; ++q) {
-#ifdef ZEDO_MUT_TEMPORAL_LAMBDA
-                            const double c = sD[q] + Mn[(size_t)(q0 + q) * H + h];
-#else
-                            const double c = sD[q] + lambda * Mn[(size_t)(q0 + q) * H + h];
-#endif
+                            const double c = sD[q] + ZEDO_TEMPORAL_WEIGHTED(Mn[(size_t)(q0 + q) * H + h]);
                             if (q0 + q == 0 || c < best) { best = c; bh = q0 + q; }
                         }
                 }

@@ -77,6 +77,9 @@ SIGNATURES = {
     "zedo_joint_stream_state_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "zedo_joint_stream_reset": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _vp]),
     "zedo_joint_stream_push": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "zedo_temporal_stream_state_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "zedo_temporal_stream_reset": (_i, [_vp, _sz, _i, _i, _i, _i, _i, _vp, _vp]),
+    "zedo_temporal_stream_push": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "zedo_joint_accel_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_accel_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp]),
     "zedo_joint_accel_stream_state_bytes": (_sz, [_i, _i, _i, _i, _i]),
@@ -547,11 +550,11 @@ def joint_reproj(x, T, uv, K, N=None, row_offset=0, return_rows=False):
     return (best, best_h, jerr) if return_rows else (best, best_h)
 
 
-def joint_compose(x_full, T_full, joint_idx, ref_idx=None, N=None):
+def joint_compose(x_full, T_full, joint_idx, ref_idx=None, N=None, check=True):
     """The pose assembled joint by joint (zedo_joint_compose): x_full [H*N,J,3] and T_full [H*N,3] (ALL rows, h-major), joint_idx [N,J]
     i32 -> pose [N,J,3] f32, joint (n, j) = x + T of hypothesis joint_idx[n,j]: in the camera frame (ref_idx None) or minus the
     translation of hypothesis ref_idx[n] ([N] i32: root-relative to that hypothesis's frame).  Like take_rows, an index of -1 or one
-    outside the hypotheses is a ValueError (synchronises to look)."""
+    outside the hypotheses is a ValueError (synchronises to look; check=False does not look: the call makes such joints NaN)."""
     _need_gpu()
     dev = _device_of(x_full, T_full, joint_idx, ref_idx)
     J = x_full.shape[1]
@@ -563,7 +566,7 @@ def joint_compose(x_full, T_full, joint_idx, ref_idx=None, N=None):
                          f"{tuple(T_full.shape)}, {tuple(joint_idx.shape)}, {None if ref_idx is None else tuple(ref_idx.shape)} with N = {N}")
     H = rows // N
     for name, i in (("joint_idx", joint_idx), ("ref_idx", ref_idx)):
-        if i is not None and bool(((i < 0) | (i >= H)).any()):
+        if check and i is not None and bool(((i < 0) | (i >= H)).any()):
             raise ValueError(f"joint_compose: {name} holds -1 (nothing was selected) or an index outside the {H} hypotheses")
     with torch.cuda.device(dev):
         pose = torch.empty((N, J, 3), dtype=torch.float32, device=dev)
@@ -750,6 +753,58 @@ class JointStream:
     def flush(self, which=None):
         """Ends the clips of the streams with which[s] != 0 (None: all) and emits their pending frames: a push of no frames."""
         return self.push(None, None, None, [1] * self.S if which is None else which)
+
+
+def temporal_stream_state_bytes(S, H, J, lag, max_frames):
+    """The bytes of state zedo_temporal_stream_push needs for S streams of H hypotheses and J joints at this lag and at most max_frames
+    frames per push (host arithmetic: no GPU needed); 0 for a shape the calls refuse."""
+    return int(_lib.zedo_temporal_stream_state_bytes(int(S), int(H), int(J), int(lag), int(max_frames)))
+
+
+class TemporalStream(JointStream):
+    """Pose-level selection on a live video (zedo_temporal_stream_push): the chain of temporal_select for S independent streams, fed in
+    chunks of at most max_frames frames, every frame decided `lag` frames after it went in - the decision of temporal_select on the
+    stream's clip (the frames since its last reset or flush) cut after frame n + lag.  With lag >= the clip's length - 1 and a flush at
+    the end the outputs are temporal_select's bits.  Owns the state on `device` and resets it on creation.  lam as in temporal_select
+    (untuned); the choice of lag is untuned as well, and whether a fixed-lag path is closer to ground truth than the per-frame arg-min
+    is not measured.  The state holds max_frames H^2 transition costs per stream."""
+
+    _WHAT, _CALL = "TemporalStream", "zedo_temporal_stream"
+    _RANGE = "1 <= H <= 1024, lag >= 0, sizes >= 1, (lag + max_frames) S H, S max_frames H^2 and 3 S H J <= INT_MAX"
+
+    def push(self, unary, x, flush=None):
+        """unary [H*S*F] f64, x [H*S*F,J,3] f32: F <= max_frames new frames of every stream, rows (h, n) h-major with n = s F + f -
+        stream s's chunk is a clip of F frames of temporal_select on the same tensors; flush: None, or [S] flags - the streams whose
+        clip ends with this chunk.  -> (first [S] i64, count [S] i64, path [S,F+lag] i32, cost [S,F+lag] f64): stream s emits the frames
+        first[s] .. first[s] + count[s] - 1 of its clip in the rows 0 .. count[s] - 1 of path[s] and cost[s]; the rows after them are
+        not written.  count[s] = held if flushed, else max(0, held - lag), with held = min(lag, frames the clip held before) + F.
+        unary = None: a push of no frames (flush required)."""
+        fl = self._flags(flush)
+        S, H, J = self.S, self.H, self.J
+        if unary is None:
+            if x is not None or fl is None:
+                raise ValueError(f"{self._WHAT}.push: a push of no frames takes flush and nothing else")
+            F, dev = 0, self.device
+        else:
+            rows = x.shape[0]
+            F = rows // (H * S)
+            if rows != H * S * F or F < 1 or tuple(x.shape) != (rows, J, 3) or tuple(unary.shape) != (rows,):
+                raise ValueError(f"{self._WHAT}.push: unary [H*S*F], x [H*S*F,J,3] with H = {H}, S = {S}, J = {J} expected, got "
+                                 f"{tuple(unary.shape)}, {tuple(x.shape)}")
+            dev = _device_of(unary, x, self.state)
+        with torch.cuda.device(dev):
+            rows = F + self.lag                                      # lag = 0 and no frames: a row nobody writes keeps the pointers non-NULL
+            path = torch.empty((S, max(rows, 1)), dtype=torch.int32, device=dev)
+            cost = torch.empty((S, max(rows, 1)), dtype=torch.float64, device=dev)
+            emit = torch.empty((S, 2), dtype=torch.int64, device=dev)
+            _check(_lib.zedo_temporal_stream_push(_p(unary, torch.float64), _p(x), S, F, H, J, self.lag, self.max_frames, self.lam,
+                                                  _p(fl, torch.int32), _p(self.state, torch.uint8), self.state_bytes, _p(path, torch.int32),
+                                                  _p(cost, torch.float64), _p(emit, torch.int64), _stream(dev)))
+        return emit[:, 0], emit[:, 1], path[:, :rows], cost[:, :rows]
+
+    def flush(self, which=None):
+        """Ends the clips of the streams with which[s] != 0 (None: all) and emits their pending frames: a push of no frames."""
+        return self.push(None, None, [1] * self.S if which is None else which)
 
 
 def joint_stream_marginal_state_bytes(S, H, J, lag, max_frames):

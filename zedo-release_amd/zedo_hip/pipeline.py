@@ -9,7 +9,8 @@ batched as rows (h, n) and every stage running in libzedo_hip.so.
                    or, without ground truth, of the confidence-weighted reprojection error of x + T (select_reproj),
                    or per JOINT of the joint's reprojection distance, the pose assembled from the winners (aggregate_reproj, compose),
                    or along the clips of a video: reprojection error plus a motion cost, by Viterbi (select_temporal),
-                   or both: per joint along the clips, one Viterbi chain per joint (select_joints_temporal, compose)
+                   or both: per joint along the clips, one Viterbi chain per joint (select_joints_temporal, compose),
+                   or on a live video, fixed-lag: the joints' chains in the frame of the pose-level chain (open_live_joints)
     pruning      = opt-in, DURING the loop: at the steps of a plan keep, per pose, the K hypotheses with the smallest reprojection
                    error and carry on with K x N rows (parse_prune_plan, run_pruned)
 
@@ -21,7 +22,7 @@ import os
 import numpy as np
 import torch
 
-from . import (H36M_EDGES, SINGULAR_MSG, JointAccelMarginalStream, JointAccelStream, JointMarginalStream, JointStream, Schedule, Weights, ZedoError, ipo_fit, joint_accel_marginal, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
+from . import (H36M_EDGES, SINGULAR_MSG, JointAccelMarginalStream, JointAccelStream, JointMarginalStream, JointStream, Schedule, TemporalStream, Weights, ZedoError, ipo_fit, joint_accel_marginal, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
                joint_temporal_select, joint_tree_marginal, joint_tree_select, skeleton_parents, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
 
 
@@ -295,6 +296,80 @@ class Pipeline:
         frames that are still to come out and assembles their poses with compose."""
         return self._push_stream("push_joints_temporal", js, x, T, flush)
 
+    def open_pose_stream(self, S, lag, max_frames, lam=100.0):
+        """The state of select_temporal's chain for S live streams (TemporalStream): H and the joint count are those of the pipeline,
+        every frame is decided `lag` frames after it went in, a push holds at most max_frames frames per stream.  lam and the choice of
+        lag are untuned."""
+        return self._open_stream("open_pose_stream", TemporalStream, S, lag, max_frames, lam)
+
+    def push_temporal(self, ps, x, T, flush=None):
+        """select_temporal on live input, on the problem of load() with N = S F poses - F new frames of each of the S streams of
+        ps = open_pose_stream(...), pose n = s F + f: x [H*N,17,3] and T [H*N,3], ALL rows; flush: None, or [S] flags - the streams
+        whose clip ends here.  -> (first [S] i64, count [S] i64, path [S,F+lag] i32, cost [S,F+lag] f64, err [H*N] f64): the unaries
+        are zedo_min_reproj's per-row errors exactly as select_temporal forms them; stream s emits the frames first[s] .. first[s] +
+        count[s] - 1 of its clip (zedo_temporal_stream_push)."""
+        if x.shape[0] != self.H * self.N or self.N % ps.S:
+            raise ValueError(f"push_temporal: all {self.H * self.N} rows of a whole number of frames of {ps.S} streams expected, "
+                             f"got {x.shape[0]} rows for {self.N} poses")
+        with torch.cuda.device(self.device):
+            err, _, _ = min_reproj(x, T, self.uv, self.K, self.conf, self.N, 0)
+            return ps.push(err, x, flush) + (err,)
+
+    def open_live_joints(self, S, lag, max_frames, lam=100.0):
+        """What a camera needs of --select joints-temporal, for S live streams (LiveJoints): the joints' chains (open_joint_stream) and
+        the pose-level chain whose frame their poses are written in (open_pose_stream), at the same S, lag, max_frames and lam, and x
+        and T of the up to `lag` frames per stream that have not come out yet.  lam and the choice of lag are untuned."""
+        return LiveJoints(self.open_joint_stream(S, lag, max_frames, lam), self.open_pose_stream(S, lag, max_frames, lam))
+
+    def push_live_joints(self, lj, x, T, flush=None):
+        """select_joints_temporal and select_temporal on live input, assembled: the problem of load() holds N = S F poses - F new
+        frames of each of the S streams of lj = open_live_joints(...), pose n = s F + f; x [H*N,17,3] and T [H*N,3], ALL rows; flush:
+        None, or [S] flags (a sequence; a tensor is read back) - the streams whose clip ends here.  -> (first [S] i64, count [S] i64,
+        pose [S,F+lag,17,3] f32, joint_path [S,F+lag,17] i32, path [S,F+lag] i32, T_sel [S,F+lag,3] f32): stream s emits the frames
+        first[s] .. first[s] + count[s] - 1 of its clip in the rows 0 .. count[s] - 1; pose is zedo_joint_compose of the frame with
+        the joint stream's decisions in the frame of the pose stream's decision `path`, T_sel that hypothesis's translation.  Rows at
+        and after count[s] are NaN in pose and T_sel and -1 in joint_path and path.  With lag >= the clip's length - 1 and a flush, pose
+        is bit for bit the pose --select joints-temporal writes for the clip.  The frame counts are kept on the host from the header's
+        formula: d_emit is not read back."""
+        js, ps = lj.joints, lj.pose
+        S, H, lag = js.S, js.H, js.lag
+        J = x.shape[1]
+        jerr = self._joint_unaries("push_live_joints", x, T, S)
+        F = self.N // S
+        if flush is None:
+            fl = [0] * S
+        else:
+            fl = [1 if v else 0 for v in (flush.tolist() if isinstance(flush, torch.Tensor) else flush)]
+            if len(fl) != S:
+                raise ValueError(f"push_live_joints: one flag per stream ([{S}]) expected, got {len(fl)}")
+        with torch.cuda.device(self.device):
+            err, _, _ = min_reproj(x, T, self.uv, self.K, self.conf, self.N, 0)
+            first, count, jp, _ = js.push(jerr, x, T, flush)
+            _, _, pp, _ = ps.push(err, x, flush)
+            rows = F + lag
+            # the window of a stream: the lag frames before the chunk (those the clip does not hold yet: never read), then the chunk
+            win_x = torch.cat([lj.pend_x, x.reshape(H, S, F, J, 3)], 2)
+            win_T = torch.cat([lj.pend_T, T.reshape(H, S, F, 3)], 2)
+            held = [min(lag, t) + F for t in lj.t]
+            cnt = [h if f else max(0, h - lag) for h, f in zip(held, fl)]
+            # output row r of stream s is the clip's frame max(0, t - lag) + r: slot lag - min(lag, t) + r of the window
+            slot = np.minimum(np.array([lag - min(lag, t) for t in lj.t])[:, None] + np.arange(rows)[None, :], rows - 1)
+            valid = torch.as_tensor(np.arange(rows)[None, :] < np.array(cnt)[:, None], device=self.device)
+            slot = torch.as_tensor(slot, device=self.device)
+            s_ix = torch.arange(S, device=self.device)[:, None]
+            gx, gT = win_x[:, s_ix, slot].contiguous(), win_T[:, s_ix, slot].contiguous()      # [H,S,rows,J,3], [H,S,rows,3]
+            jidx = torch.where(valid[:, :, None], jp, torch.zeros_like(jp)).reshape(S * rows, J)
+            ref = torch.where(valid, pp, torch.zeros_like(pp)).reshape(S * rows)
+            pose = joint_compose(gx.view(H * S * rows, J, 3), gT.view(H * S * rows, 3), jidx, ref, S * rows, check=False)
+            nan, minus = pose.new_tensor(float("nan")), pp.new_tensor(-1)
+            pose = torch.where(valid[:, :, None, None], pose.view(S, rows, J, 3), nan)
+            T_sel = torch.gather(gT, 0, ref.view(1, S, rows, 1).expand(1, S, rows, 3).to(torch.int64))[0]
+            out = (first, count, pose, torch.where(valid[:, :, None], jp, minus), torch.where(valid, pp, minus),
+                   torch.where(valid[:, :, None], T_sel, nan))
+            lj.pend_x, lj.pend_T = win_x[:, :, F:].contiguous(), win_T[:, :, F:].contiguous()
+            lj.t = [0 if f else t + F for t, f in zip(lj.t, fl)]
+        return out
+
     def select_joints_accel(self, x, T, seq_start, lam=100.0, accel=100.0):
         """select_joints_temporal with a second-order motion model: the same inputs and outputs, each joint's path minimises its unaries
         plus lam times its displacement plus accel (pixels per metre, default untuned) times its second difference X[n] - 2 X[n-1] +
@@ -375,6 +450,26 @@ class Pipeline:
         """The winning row of every pose: rows_full [H*N, ...] (all global rows, h-major), idx [N] -> rows_full.view(H, N, ...)[idx, arange(N)].
         An index of -1 (a pose no row was selected for) is an error."""
         return take_rows(rows_full, idx, self.H, self.N)
+
+
+class LiveJoints:
+    """What Pipeline.push_live_joints keeps between pushes (Pipeline.open_live_joints): .joints, a JointStream, and .pose, a
+    TemporalStream of the same S, lag and max_frames; .pend_x [H,S,lag,J,3] and .pend_T [H,S,lag,3], x and T of the last `lag` frames
+    pushed per stream - among them the frames that have not come out yet -, on the device; .t [S], the frames every stream's clip
+    holds, on the host."""
+
+    def __init__(self, joints, pose):
+        assert (joints.S, joints.H, joints.J, joints.lag, joints.max_frames) == (pose.S, pose.H, pose.J, pose.lag, pose.max_frames)
+        self.joints, self.pose = joints, pose
+        self.pend_x = torch.zeros((joints.H, joints.S, joints.lag, joints.J, 3), dtype=torch.float32, device=joints.device)
+        self.pend_T = torch.zeros((joints.H, joints.S, joints.lag, 3), dtype=torch.float32, device=joints.device)
+        self.t = [0] * joints.S
+
+    def reset(self):
+        """Empties every stream; pending frames are dropped."""
+        self.joints.reset()
+        self.pose.reset()
+        self.t = [0] * self.joints.S
 
 
 def take_rows(rows_full, idx, H, N):
