@@ -58,7 +58,8 @@ extern "C" {
                               * still 5 (additive): + zedo_joint_accel_stream_marginal_state_bytes,
                               *                       zedo_joint_accel_stream_marginal_reset, zedo_joint_accel_stream_marginal_push;
                               * still 5 (additive): + zedo_temporal_stream_state_bytes, zedo_temporal_stream_reset,
-                              *                       zedo_temporal_stream_push */
+                              *                       zedo_temporal_stream_push;
+                              * still 5 (additive): + zedo_temporal_marginal_workspace_bytes, zedo_temporal_marginal */
 
 #define ZEDO_OK 0
 #define ZEDO_E_BADARG (-1)      /* NULL pointer, non-positive size, unsupported dimension */
@@ -625,6 +626,66 @@ size_t zedo_joint_marginal_workspace_bytes(int N, int H, int J);
 int zedo_joint_marginal(const double *d_junary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
                         int H, int N, int J, double lambda, double tau, void *d_workspace, size_t workspace_bytes,
                         double *d_mean, double *d_cov, int *d_hmax, double *d_wmax, double *d_logz, double *d_w, void *stream);
+
+/* ---- fusing WHOLE hypotheses along a video WITHOUT ground truth: posterior mean pose and spread ----------------------------
+ * zedo_temporal_select answers with one hypothesis index per frame: it cannot say how sure it is, and the selected pose jumps
+ * where the index changes.  This is the sum-product twin of its max-product recurrence, exactly as zedo_joint_marginal is the
+ * twin of zedo_joint_temporal_select: the same energy read as a probability at a temperature tau,
+ *   p(path over a chain) proportional to exp(-(sum_n u[n,h_n] + lambda sum_n m[n,h_{n-1},h_n]) / tau),
+ * and from it, exactly (forward-backward in the log domain), the posterior marginal of every hypothesis of every frame - a
+ * state is a whole pose the network produced, with real bone lengths -, the posterior mean pose, the covariance of every joint
+ * under those marginals and the most probable hypothesis with its probability.  Whether the fused pose is closer to ground
+ * truth than a selected one on real video is UNMEASURED; lambda = 100 and tau = 1, the binding's defaults, are UNTUNED.
+ * Inputs: d_unary [H*N] float64, d_x [H*N,J,3] fp32 and d_seq_start [n_seq+1] int32 ON THE DEVICE are those of
+ * zedo_temporal_select, word for word: rows (h,n) h-major, ALL rows; every entry of d_seq_start is clamped to 0 .. N before use
+ * and is never an address, and with an array that breaks its rules the result is unspecified.  tau: finite, > 0, the
+ * temperature in cost units (pixels on zedo_min_reproj's errors).  d_T [H*N,3] fp32 is optional and enters ONLY the position
+ * the moments are taken of, X[h,n,j,c] = (double)x[h,n,j,c] + (double)T[h,n,c] (x alone when it is NULL) - not the motion
+ * term, which stays that of zedo_temporal_select.
+ * All arithmetic in float64.  u, DEAD, "chain start" and m[n,h',h] = (1/J) sum_j sqrt(sum_c (x[h,n,j,c] - x[h',n-1,j,c])^2)
+ * (sums ascending in c, then in j) are those of zedo_temporal_select.  With l[n,h] = -u[n,h] / tau (-inf when the hypothesis is
+ * excluded), c = lambda / tau, LSE the log of a sum of exponentials:
+ *   forward   chain start:  A[n,h] = l[n,h]
+ *             otherwise:    A[n,h] = l[n,h] + LSE_h' (A[n-1,h'] - c m[n,h',h])
+ *   backward  chain end (the clip's last frame, or frame n+1 dead):  B[n,h] = 0  and  logZ = LSE_h A[n,h]
+ *             otherwise:    B[n,h] = LSE_h' (l[n+1,h'] + B[n+1,h'] - c m[n+1,h,h'])
+ *   marginal  w[n,h] = exp((A[n,h] + B[n,h]) - logZ);  an excluded hypothesis has w = 0 exactly
+ * Every LSE takes two walks over its terms and is shifted by their TRUE maximum: safe for any finite c m, and at a small tau
+ * the largest term contributes exactly 1.  (lambda / tau and u / tau are taken to be finite.)  Every sum runs in a fixed order:
+ * the LSE of a recurrence over h' ascending, by the one lane that owns h (no split to combine); logZ over the workgroup of
+ * T = min(256, H rounded up to 64) lanes - lane t adds h = t, t + T, .. ascending, then a butterfly inside each wave of 64
+ * (offsets 32, 16, .. 1), then the waves ascending; the mean and the covariance over h ascending, by one lane per (frame,
+ * joint).
+ * Outputs (all required but d_w):
+ *   d_mean [N,J,3]  sum_h w X (metres; the frame of x, or of x + T)
+ *   d_cov  [N,J,6]  sum_h w (X - mean)(X - mean)^T in the order xx, xy, xz, yy, yz, zz (m^2), from the centred differences
+ *   d_hmax [N] int32  the lowest h with the largest marginal;  d_wmax [N]  that marginal
+ *   d_logz [N]      the chain's log-partition value logZ, repeated on every frame of the chain
+ *   d_w    [N,H]    optional (NULL: not written, and every other output keeps its bits): the marginals
+ * A dead frame reports NaN in mean and cov, hypothesis 0, wmax = 0, logz = -inf and a row of zeros in d_w.
+ * Workspace (8-byte aligned, need not be initialised): A [N,H] float64, B [N,H] float64 (overwritten by the marginals at the
+ * end), logZ [N] float64, one int32 flag per frame (padded to 8 bytes), then C*H*H float64 transition costs of a chunk of C
+ * frames.  zedo_temporal_marginal_workspace_bytes(N, H, chunk_frames) returns the bytes for C = min(chunk_frames, N);
+ * chunk_frames <= 0: the largest C whose transition costs stay at or under 256 MB (at least one frame); 0 for sizes the call
+ * refuses.  The call uses the largest C that workspace_bytes admits, capped at N, and returns the SAME BITS for every C: A, B
+ * and logZ of every frame live in the workspace, and what crosses a chunk boundary - A of the frame before, B of the frame
+ * after, the chain's logZ - goes through them.  The forward pass walks the chunks ascending, the backward pass DESCENDING, and
+ * the backward pass computes the transition costs of its chunk AGAIN, in the transposed layout its lanes read coalesced (the
+ * same bits: (a - b)^2 = (b - a)^2 exactly, and the joint order is unchanged): every transition cost is computed twice,
+ * whatever C is.  That is the price of a workspace that holds one chunk of them.
+ * Contract: 1 <= H <= 1024 (A[n-1,.] stays in the LDS: the resident recurrence only, as zedo_temporal_stream_push), J >= 1,
+ * N >= 1, 1 <= n_seq <= N, finite lambda >= 0, finite tau > 0; ZEDO_E_BADARG with nothing written for a NULL pointer other
+ * than d_T and d_w, a non-positive size, H > 1024, n_seq > N, H*N (or N*J: one lane per (frame, joint)) above INT_MAX, a
+ * negative or non-finite lambda, tau <= 0 or not finite, or a workspace that is not 8-byte aligned; ZEDO_E_WORKSPACE with
+ * nothing written if not even one frame of transition costs fits; allocates nothing, synchronises nothing, enqueues on
+ * `stream` only: legal under stream capture; no atomics: bit-identical from run to run, for any alignment of d_x and any
+ * workspace content, with and without d_w.  One workgroup per clip, twice: a single long clip is serial in time on one CU,
+ * as in zedo_temporal_select.  The moments are parallel over (frame, joint) and read d_x twice (the mean, then the centred
+ * differences). */
+size_t zedo_temporal_marginal_workspace_bytes(int N, int H, int chunk_frames);
+int zedo_temporal_marginal(const double *d_unary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq,
+                           int H, int N, int J, double lambda, double tau, void *d_workspace, size_t workspace_bytes,
+                           double *d_mean, double *d_cov, int *d_hmax, double *d_wmax, double *d_logz, double *d_w, void *stream);
 
 /* ---- joint-wise selection along a video WITHOUT ground truth: a second-order motion model ----------------------------------
  * zedo_joint_temporal_select charges lambda times the DISPLACEMENT of a joint between consecutive choices: a zero-velocity

@@ -72,6 +72,10 @@ MUTANTS = [
     ("ZEDO_MUT_JSM_HORIZON", "zedo_joint_stream_marginal_push: the horizon of frame n is taken as n + lag - 1, one frame short (zedo_joint_stream_marginal.hip joint_stream_marginal_emit_kernel)"),
     # the joint-wise fusion (tests/test_joint_marginal_gpu.py, tests/test_select_joints_fused_driver_gpu.py): leaves every other test green
     ("ZEDO_MUT_JM_NO_BACKWARD", "zedo_joint_marginal: B = 0 on every frame - the filtering marginals, not the smoothed ones (zedo_joint_marginal.hip joint_marginal_backward_kernel)"),
+    # the pose-level fusion (tests/test_temporal_marginal_gpu.py; profiles/mutation_temporal_marginal.txt): leaves every other test green,
+    # and of that file the case of one frame (1, 1, 1, 1), the five tests of the bits against the chunk, the workspace, the stream, capture,
+    # the alignment and d_w and the clamped offsets, which compare the call with itself, and the pipeline test
+    ("ZEDO_MUT_TM_NO_BACKWARD", "zedo_temporal_marginal: B = 0 on every frame - the filtering marginals, not the smoothed ones (zedo_temporal_marginal.hip temporal_marginal_backward_kernel)"),
     # the second-order joint-wise selection (tests/test_joint_accel_gpu.py, tests/test_select_joints_accel_driver_gpu.py) and, since its
     # sum-product twin shares the statement, the second-order fusion (tests/test_joint_accel_marginal_gpu.py); leaves the tests of the
     # first-order chain green (tests/test_joint_temporal_gpu.py, tests/test_joint_stream_gpu.py, tests/test_select_joints_temporal_driver_gpu.py;

@@ -1039,6 +1039,34 @@ extern "C" int zedo_joint_marginal(const double *d_junary, const float *d_x, con
     return ZEDO_OK;
 }
 
+// posterior marginals of the pose-level chain of zedo_temporal_select: A, B, logZ and the dead flags in the workspace, then a chunk of
+// transition costs as for that call; the resident recurrence only (H <= 1024)
+static bool temporal_marginal_dims_ok(int N, int H) { return N >= 1 && H >= 1 && H <= JOINT_CHAIN_HMAX && (long long)H * N <= INT_MAX; }
+
+extern "C" size_t zedo_temporal_marginal_workspace_bytes(int N, int H, int chunk_frames) {
+    if (!temporal_marginal_dims_ok(N, H)) return 0;
+    const size_t per = (size_t)H * H * sizeof(double);
+    size_t c = chunk_frames > 0 ? (size_t)chunk_frames : std::max<size_t>(1, TEMPORAL_DEFAULT_VARIABLE / per);
+    c = std::min<size_t>(c, (size_t)N);
+    return temporal_marginal_fixed_bytes(N, H) + c * per;
+}
+
+extern "C" int zedo_temporal_marginal(const double *d_unary, const float *d_x, const float *d_T, const int *d_seq_start, int n_seq, int H,
+                                      int N, int J, double lambda, double tau, void *d_workspace, size_t workspace_bytes, double *d_mean,
+                                      double *d_cov, int *d_hmax, double *d_wmax, double *d_logz, double *d_w, void *stream) {
+    if (!d_unary || !d_x || !d_seq_start || !d_workspace || !d_mean || !d_cov || !d_hmax || !d_wmax || !d_logz) return ZEDO_E_BADARG;
+    if (!temporal_marginal_dims_ok(N, H) || J < 1 || n_seq < 1 || n_seq > N) return ZEDO_E_BADARG;
+    if ((long long)N * J > INT_MAX) return ZEDO_E_BADARG;                                 // one lane per (frame, joint)
+    if (!std::isfinite(lambda) || lambda < 0.0 || !std::isfinite(tau) || !(tau > 0.0)) return ZEDO_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(d_workspace) & 7) return ZEDO_E_BADARG;               // the tables are float64
+    const size_t fixed = temporal_marginal_fixed_bytes(N, H), per = (size_t)H * H * sizeof(double);
+    if (workspace_bytes < fixed + per) return ZEDO_E_WORKSPACE;
+    const int chunk = (int)std::min<size_t>((workspace_bytes - fixed) / per, (size_t)N);
+    HIPCHK(launch_temporal_marginal(d_unary, d_x, d_T, d_seq_start, n_seq, H, N, J, lambda / tau, tau, d_workspace, chunk, d_mean, d_cov,
+                                    d_hmax, d_wmax, d_logz, d_w, (hipStream_t)stream));
+    return ZEDO_OK;
+}
+
 // the second-order motion model: one chain over pairs of hypotheses per (clip, joint)
 extern "C" size_t zedo_joint_accel_workspace_bytes(int N, int H, int J) {
     return chain_dims_ok(N, H, J, JOINT_ACCEL_HMAX) ? joint_accel_bytes(N, H, J) : 0;

@@ -275,6 +275,12 @@ size_t joint_marginal_bytes(int N, int H, int J);
 hipError_t launch_joint_marginal(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N, int J,
                                  double c, double tau, void *ws, double *mean, double *cov, int *hmax, double *wmax, double *logz, double *w,
                                  hipStream_t st);
+// posterior marginals of the pose-level chain of zedo_temporal.hip (zedo_temporal_marginal.hip); ws: temporal_marginal_fixed_bytes(N, H)
+// of tables, then chunk * H * H doubles of transition costs; H <= 1024; c = lambda / tau
+size_t temporal_marginal_fixed_bytes(int N, int H);
+hipError_t launch_temporal_marginal(const double *unary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N, int J,
+                                    double c, double tau, void *ws, int chunk, double *mean, double *cov, int *hmax, double *wmax,
+                                    double *logz, double *w, hipStream_t st);
 // joint-wise selection with a second-order motion model (zedo_joint_accel.hip); ws: joint_accel_bytes(N, H, J), H <= 64
 size_t joint_accel_bytes(int N, int H, int J);
 hipError_t launch_joint_accel_select(const double *junary, const float *x, const float *T, const int *seq_start, int n_seq, int H, int N,

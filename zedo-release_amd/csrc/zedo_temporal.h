@@ -64,6 +64,12 @@ static_assert(TT_T == 4 * TT_H && TT_K * 4 == TT_P && (TT_LD & 1), "four h' rows
         }                                                                                                                              \
     }
 
+// The two kernels of zedo_temporal.hip that do not know what a chain does with its costs and serve the fusion call
+// (zedo_temporal_marginal.hip) as well: the dead flag of every frame, and the tile above on the frames c0 .. of a chunk, as M[n - c0][h'][h].
+__global__ __launch_bounds__(256) void temporal_dead_kernel(const double *__restrict__ unary, int H, int N, int *__restrict__ dead);
+__global__ __launch_bounds__(TT_T) void temporal_transition_kernel(const float *__restrict__ x, int H, int N, int J, int c0,
+                                                                   double *__restrict__ M);
+
 // ---- a frame of the forward recurrence with D[n-1,.] resident in the LDS (H <= TS_CAP) ----
 // Lane t owns h = t, t + T, ..; D[n-1,.] is in sD[cur TS_CAP ..], the lanes drop D[n,h] into the other half and ONE barrier per frame
 // hands it over.  TS_PF: the transition costs of the lane's first h that were fetched a frame ahead.

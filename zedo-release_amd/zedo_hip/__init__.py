@@ -97,6 +97,8 @@ SIGNATURES = {
                                              _vp]),
     "zedo_joint_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
     "zedo_joint_marginal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "zedo_temporal_marginal_workspace_bytes": (_sz, [_i, _i, _i]),
+    "zedo_temporal_marginal": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _d, _d, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "zedo_joint_tree_select": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _vp, _vp, _vp, _vp]),
     "zedo_joint_tree_marginal_max_h": (_i, [_i]),
     "zedo_joint_tree_marginal": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1049,6 +1051,35 @@ def joint_marginal(junary, x_full, T_full, seq_start, N=None, lam=100.0, tau=1.0
                                         float(lam), float(tau), _p(ws, torch.uint8), nbytes, _p(mean, torch.float64),
                                         _p(cov, torch.float64), _p(hmax, torch.int32), _p(wmax, torch.float64), _p(logz, torch.float64),
                                         _p(w, torch.float64), _stream(dev)))
+    return (mean, cov, hmax, wmax, logz, w) if return_weights else (mean, cov, hmax, wmax, logz)
+
+
+def temporal_marginal_workspace_bytes(N, H, chunk_frames=0):
+    """The bytes of workspace zedo_temporal_marginal takes for N frames of H hypotheses with chunk_frames frames of transition costs held
+    at once (0: at most 256 MB of them) - host arithmetic: no GPU needed; 0 for a shape the call refuses."""
+    return int(_lib.zedo_temporal_marginal_workspace_bytes(int(N), int(H), int(chunk_frames)))
+
+
+def temporal_marginal(unary, x_full, T_full, seq_start, N=None, lam=100.0, tau=1.0, chunk_frames=0, return_weights=False):
+    """Fusing whole hypotheses along a video without ground truth (zedo_temporal_marginal): the inputs of temporal_select, T_full [H*N,3]
+    f32 or None and a temperature tau > 0 in cost units -> (mean [N,J,3] f64, cov [N,J,6] f64, hmax [N] i32, wmax [N] f64, logz [N]
+    f64[, w [N,H] f64]): per clip the posterior marginals w of the hypotheses - whole poses - under p(path) ~ exp(-(unaries + lam * mean
+    joint displacements) / tau), the chain model temporal_select optimises (forward-backward, fp64), and from them the posterior mean
+    pose, every joint's covariance (xx, xy, xz, yy, yz, zz; m^2), the most probable hypothesis of a frame, its probability and the
+    chain's log-partition value.  T_full enters only the positions the moments are taken of (x + T), not the motion term.  A dead
+    frame reports NaN, 0, 0 and -inf.  lam = 100 and tau = 1 are untuned.  At most 1024 hypotheses.  chunk_frames: frames of transition
+    costs held at once (0: at most 256 MB); the result does not depend on it.  Whether the fused pose is closer to ground truth than a
+    selected one is not measured."""
+    dev, seq, N, H, J = _chain_inputs("temporal_marginal", unary, x_full, T_full, seq_start, N, joint_wise=False)
+    with torch.cuda.device(dev):
+        nbytes, ws = _workspace(_lib.zedo_temporal_marginal_workspace_bytes, dev, N, H, int(chunk_frames))
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        mean, cov, hmax, wmax, logz = f64(N, J, 3), f64(N, J, 6), torch.empty((N,), dtype=torch.int32, device=dev), f64(N), f64(N)
+        w = f64(N, H) if return_weights else None
+        _check(_lib.zedo_temporal_marginal(_p(unary, torch.float64), _p(x_full), _p(T_full), _p(seq, torch.int32), seq.numel() - 1, H, N, J,
+                                           float(lam), float(tau), _p(ws, torch.uint8), nbytes, _p(mean, torch.float64),
+                                           _p(cov, torch.float64), _p(hmax, torch.int32), _p(wmax, torch.float64), _p(logz, torch.float64),
+                                           _p(w, torch.float64), _stream(dev)))
     return (mean, cov, hmax, wmax, logz, w) if return_weights else (mean, cov, hmax, wmax, logz)
 
 

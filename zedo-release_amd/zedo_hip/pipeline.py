@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import (H36M_EDGES, SINGULAR_MSG, JointAccelMarginalStream, JointAccelStream, JointMarginalStream, JointStream, Schedule, TemporalStream, Weights, ZedoError, ipo_fit, joint_accel_marginal, joint_accel_select, joint_compose, joint_marginal, joint_reproj,
-               joint_temporal_select, joint_tree_marginal, joint_tree_select, skeleton_parents, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_select)
+               joint_temporal_select, joint_tree_marginal, joint_tree_select, skeleton_parents, min_mpjpe_both, min_reproj, oil_run, prune_gather, prune_rank, reproj_degenerate, reproj_prepare, rotate_init, temporal_marginal, temporal_select)
 
 
 def linspace_f32(start, end, steps):
@@ -403,6 +403,19 @@ class Pipeline:
         jerr = self._joint_unaries("fuse_joints_temporal", x, T)
         with torch.cuda.device(self.device):
             return joint_marginal(jerr, x, T, seq_start, self.N, lam, tau) + (jerr,)
+
+    def fuse_temporal(self, x, T, seq_start, lam=100.0, tau=1.0):
+        """Pose-level fusion along a video without ground truth on the problem of load(): x [H*N,17,3] and T [H*N,3], ALL rows, seq_start
+        = the first frame of every clip and N -> (mean [N,17,3] f64, cov [N,17,6] f64, hmax [N] i32, wmax [N] f64, logz [N] f64, err_rows
+        [H*N] f64): the unaries are zedo_min_reproj's per-row errors (pixels), exactly as select_temporal forms them; the posterior mean
+        pose in the camera frame (x + T), every joint's covariance, the most probable hypothesis of every frame and its probability
+        under the chain model select_temporal optimises, at the temperature tau in pixels (zedo_temporal_marginal; lam and tau untuned;
+        whether the fused pose is closer to ground truth than the selected one is not measured)."""
+        if x.shape[0] != self.H * self.N:
+            raise ValueError(f"fuse_temporal: all {self.H * self.N} rows expected, got {x.shape[0]}")
+        with torch.cuda.device(self.device):
+            err, _, _ = min_reproj(x, T, self.uv, self.K, self.conf, self.N, 0)
+            return temporal_marginal(err, x, T, seq_start, self.N, lam, tau) + (err,)
 
     def open_joint_fuse_stream(self, S, lag, max_frames, lam=100.0, tau=1.0):
         """The state of fuse_joints_temporal's chain model for S live streams (JointMarginalStream): H and the joint count are those of
