@@ -226,3 +226,38 @@ def child_main(path):
     out["seam"] = round_trip_across_the_table_end(zh, inp["seam"])
     torch.cuda.synchronize()
     print("RESULT " + json.dumps(out))
+
+
+# ---- tests/test_ipo_key_lists_gpu.py: every key-list length in the kernel ZEDO_IPO_KERNEL pins ------------------------------------------
+
+KEY_LIST_ITERS = 500
+
+
+def key_list_cases():
+    from _shared import IPO_FORM_IDS, IPO_FORM_KEYS, IPO_LENGTH_KEYS
+    names = [f"k{len(kl)}" for _, kl in IPO_LENGTH_KEYS] + IPO_FORM_IDS
+    return [(name, J, kl, N, axes) for name, (J, kl) in zip(names, IPO_LENGTH_KEYS + IPO_FORM_KEYS) for N in (8, 64) for axes in ("z", "xyz")]
+
+
+def key_lists_child_main():
+    """make_ipo_problem(21, N, H = 2) with every list of IPO_LENGTH_KEYS and IPO_FORM_KEYS, N = 8 and 64, axes "z" and "xyz":
+    KEY_LIST_ITERS iterations through zedo_ipo_fit_resume from it_begin = 0 with a state buffer that arrives dirty
+    -> {case: SHA-256 over R, T, q, scale and all 15 state columns}; every output finite."""
+    import json
+    import torch
+    import zedo_hip as zh
+    from _shared import dev, make_ipo_problem
+    out, probs = {}, {}
+    for name, J, kl, N, axes in key_list_cases():
+        if (J, N) not in probs:
+            probs[(J, N)] = tuple(dev(a) for a in make_ipo_problem(J, N, H=2))
+        x0, uv, K = probs[(J, N)]
+        B = 2 * N
+        st = dirty_state(B)
+        res = zh.ipo_fit(x0, uv, K, kl, axes, IPO_T, IPO_MIN, IPO_MAX, KEY_LIST_ITERS, N * len(kl) * 2, B, return_params=True, state=st,
+                         it_begin=0)
+        assert all(bool(torch.isfinite(t).all()) for t in res) and bool(torch.isfinite(st[:B]).all()), (name, N, axes)
+        assert bool((st[B:].view(torch.int32) == -1).all()), (name, N, axes, "rows behind B were written")
+        out[f"{name}_N{N}_{axes}"] = digest(*res, st[:B])
+    torch.cuda.synchronize()
+    print("RESULT " + json.dumps(out))

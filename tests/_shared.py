@@ -103,6 +103,16 @@ IPO_KEYS = [(2, [0, 1]), (5, [0, 2, 4]), (5, [0, 1, 2, 3, 4]), (21, [0, 1, 4, 20
             (17, [0, 1, 4])]
 KEYS = [(17, [0, 1, 4]), (17, list(range(17))), (5, list(range(5))), (21, [0, 1, 4, 20])]          # the general-intrinsics problems
 TWIN_AXES = ["", "x", "y", "xy", "xz", "yz"]                                   # "z" and "xyz": the existing twin tests
+# The key-list lengths that IPO_KEYS, KEYS and the keylist_* entries of tests/golden/ipo_custom.npz leave out (tests/test_ipo_key_lists_gpu.py,
+# tests/test_ipo_key_lists_ref.py): 5 is coprime to 21, so the k entries (5 i + k) mod 21 are distinct and unsorted; the lists of 10, 11, 15 and 16 reach index 20,
+# and the lists of 6, 11, 13 and 16 hold the root, the others do not (tests/test_ipo_key_lists_ref.py pins all of it).  make_ipo_problem(21, N) supplies the problem.
+IPO_NEW_LENGTHS = (6, 7, 9, 10, 11, 13, 14, 15, 16)
+IPO_LENGTH_KEYS = [(21, [(5 * i + k) % 21 for i in range(k)]) for k in IPO_NEW_LENGTHS]
+_K11 = IPO_LENGTH_KEYS[IPO_NEW_LENGTHS.index(11)][1]
+# the forms a key list may take beside "ascending, no repeats": the k = 11 list sorted and reversed (the order is a statement about
+# rounding only), and a list with two repeated indices (the reference gathers x[:, keylist]; the normaliser counts all 7 entries)
+IPO_FORM_KEYS = [(21, sorted(_K11)), (21, _K11[::-1]), (21, [0, 4, 4, 9, 20, 9, 13])]
+IPO_FORM_IDS = ["k11-sorted", "k11-reversed", "k7-repeats"]
 
 
 def ulp32(a):
@@ -225,6 +235,58 @@ class MomentRule:
 
     def holds(self):
         return self.delta <= self.bound
+
+
+@functools.lru_cache(maxsize=None)
+def ipo_oracle_trace(J, kl, N, axes, iters=50):
+    """The float64 oracle's first ``iters`` iterations on make_ipo_problem(J, N) (pinhole K) with the key list kl (a tuple):
+    (oracle arguments, normaliser N k 2, the trace, states[i] = packed state after i iterations, the key joints that move).
+    A key joint at the root contributes no gradient: its residual is not counted when a pose-iteration is called ambiguous."""
+    import zedo_oracle as O
+    kl = list(kl)
+    cl, uvn, Kn = make_ipo_problem(J, N)
+    norm = N * len(kl) * 2
+    c64, K64 = uvn.astype(np.float64), Kn.astype(np.float64)
+    x64 = np.broadcast_to(cl[0][None], (N, J, 3)).astype(np.float64)
+    args = (x64[:, kl], O.ipo_init_T(c64, K64, IPO_T, dtype=np.float64), K64, c64[:, kl])
+    tr = []
+    O.ipo_fit(*args, axes, IPO_MIN, IPO_MAX, iters, normaliser=norm, dtype=np.float64, trace=tr)
+    states = [initial_state(N)] + [state_of(t) for t in tr]
+    moving = np.abs(cl[0][kl]).max(-1) > 0
+    return args, norm, tr, states, moving
+
+
+def ipo_ambiguous(J, kl, N, axes, iters=50):
+    """How many of the first ``iters`` x N pose-iterations of ipo_oracle_trace are ambiguous: some residual of a moving key joint is
+    below 1e-3 px, so that its sign - the L1 gradient - is not a statement about the arithmetic.  From the oracle alone."""
+    _, _, tr, _, moving = ipo_oracle_trace(J, tuple(kl), N, axes, iters)
+    return sum(int((t[7][:, moving, :].reshape(N, -1).min(1) < 1e-3).sum()) for t in tr)
+
+
+def ipo_single_iterations_from_the_oracle(zh, J, kl, N, axes):
+    """The one copy of the single-iteration method (tests/test_joint_counts_gpu.py, tests/test_ipo_key_lists_gpu.py): each of the
+    first 50 Adam iterations on its own through zedo_ipo_fit_resume from the oracle's float64 state, handed over in fp32.  Asserted
+    here, per iteration: |delta parameter| <= 1e-6 on the poses whose residuals are all sign-unambiguous (|e| >= 1e-3 px; a key joint
+    at the root is not counted).  The second moments of the same pose-iterations go into a MomentRule.
+    -> (largest parameter delta, ambiguous pose-iterations, the rule): the caller asserts its cap on the ambiguous share, the rule,
+    and that neither is vacuous."""
+    cl, uvn, Kn = make_ipo_problem(J, N)
+    x0, uv, K = dev(cl), dev(uvn), dev(Kn)
+    args, norm, tr, states, moving = ipo_oracle_trace(J, tuple(kl), N, axes)
+    worst, n_amb, rule_v = 0.0, 0, MomentRule()
+    for it in range(50):
+        st = dev(states[it].astype(np.float32))
+        zh.ipo_fit(x0, uv, K, kl, axes, IPO_T, IPO_MIN, IPO_MAX, 1, norm, N, state=st, it_begin=it)
+        out = st.cpu().numpy().astype(np.float64)
+        clear = tr[it][7][:, moving, :].reshape(N, -1).min(1) >= 1e-3
+        n_amb += int((~clear).sum())
+        if clear.any():
+            d = float(np.abs(out - states[it + 1])[clear, :5].max())
+            worst = max(worst, d)
+            assert d <= 1e-6, (it, d)
+            o32 = oracle_resume(args, axes, norm, states[it], it, 1, np.float32)[0]
+            rule_v.add(out[clear, 10:], o32[clear, 10:], states[it + 1][clear, 10:])
+    return worst, n_amb, rule_v
 
 
 @functools.lru_cache(maxsize=None)

@@ -16,8 +16,8 @@ import numpy as np
 import pytest
 
 import _procrustes_ref as PR
-from _shared import (IPO_KEYS, IPO_MAX, IPO_MIN, IPO_T, MomentRule, cameras, cfg_path, dev, initial_state, make_ipo_problem, oracle_resume,
-                     report_env as _report, state_of, ulp32, zh)  # noqa: F401  (fixture)
+from _shared import (IPO_KEYS, IPO_MAX, IPO_MIN, IPO_T, cameras, cfg_path, dev, ipo_single_iterations_from_the_oracle, make_ipo_problem,
+                     report_env as _report, ulp32, zh)  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -463,31 +463,7 @@ def test_ipo_single_iterations_from_the_oracle_state(zh, J, kl, N, axes):
     residuals are all sign-unambiguous (|e| >= 1e-3 px; a key joint at the root contributes no gradient and is not counted); the
     second moments of the same pose-iterations by the rule of test_ipo_single_iterations_from_reference_state (_shared.MomentRule).
     uv is [N, J, 2] and x0 [1, J, 3] with J up to 33: key indices reach past 16, the strides are J."""
-    import zedo_oracle as O
-    cl, uvn, Kn = make_ipo_problem(J, N)
-    x0, uv, K = dev(cl), dev(uvn), dev(Kn)
-    norm = N * len(kl) * 2
-    c64, K64 = uvn.astype(np.float64), Kn.astype(np.float64)
-    x64 = np.broadcast_to(cl[0][None], (N, J, 3)).astype(np.float64)
-    args = (x64[:, kl], O.ipo_init_T(c64, K64, IPO_T, dtype=np.float64), K64, c64[:, kl])
-    tr = []
-    O.ipo_fit(*args, axes, IPO_MIN, IPO_MAX, 50, normaliser=norm, dtype=np.float64, trace=tr)
-
-    states = [initial_state(N)] + [state_of(t) for t in tr]
-    moving = np.abs(cl[0][kl]).max(-1) > 0
-    worst, n_amb, rule_v = 0.0, 0, MomentRule()
-    for it in range(50):
-        st = dev(states[it].astype(np.float32))
-        zh.ipo_fit(x0, uv, K, kl, axes, IPO_T, IPO_MIN, IPO_MAX, 1, norm, N, state=st, it_begin=it)
-        out = st.cpu().numpy().astype(np.float64)
-        clear = tr[it][7][:, moving, :].reshape(N, -1).min(1) >= 1e-3
-        n_amb += int((~clear).sum())
-        if clear.any():
-            d = float(np.abs(out - states[it + 1])[clear, :5].max())
-            worst = max(worst, d)
-            assert d <= 1e-6, (it, d)
-            o32 = oracle_resume(args, axes, norm, states[it], it, 1, np.float32)[0]
-            rule_v.add(out[clear, 10:], o32[clear, 10:], states[it + 1][clear, 10:])
+    worst, n_amb, rule_v = ipo_single_iterations_from_the_oracle(zh, J, kl, N, axes)          # the method, with its per-iteration assertion
     _report(dict(test="joint_counts_ipo", J=J, k=len(kl), N=N, axes=axes, ambiguous_pose_iterations=n_amb, max_param_delta=worst,
                  max_v_delta=rule_v.delta, fp32_oracle_v_delta=rule_v.delta32, v_bound=rule_v.bound, v_ratio=rule_v.ratio))
     assert n_amb <= 0.05 * 50 * N, n_amb

@@ -118,6 +118,10 @@ MUTANTS = [
     ("ZEDO_MUT_IPO_CLAMP_LO", "IPO: the clamp backward tests scale <= max only, the lower bound is forgotten, in both kernels - three cells of the earlier single-iteration tests reach it from trajectory states, none at the boundary or in the lane-per-row kernel (zedo_geom.hip)"),
     ("ZEDO_MUT_IPO_STORE_V", "zedo_ipo_fit_resume: the scale's exp_avg is stored into the slot of its exp_avg_sq, state[14] (zedo_geom.hip ipo_store)"),
     ("ZEDO_MUT_IPO_ROW_LOAD_V", "zedo_ipo_fit_resume: the lane-per-row kernel resumes with exp_avg_sq = 0, the half-wave kernel does not (zedo_geom.hip ipo_row_kernel)"),
+    # every key-list length the ABI accepts (tests/test_ipo_key_lists_gpu.py; profiles/mutation_ipo_key_lists.txt: run against the seven
+    # files that launch the IPO kernels).  It changes no address and leaves every test green that existed before: none launched the
+    # lane-per-row kernel with eleven key joints
+    ("ZEDO_MUT_IPO_ROW_CASE", "IPO: case 11 of the lane-per-row dispatch launches ipo_row_kernel<10>, the eleventh key joint is lost in that kernel only - the slip a 17-line macro switch invites (zedo_geom.hip launch_ipo_fit)"),
     ("ZEDO_MUT_TREEMARG_NO_DOWN", "zedo_joint_tree_marginal: Dn = 0 on every joint - the downward pass is dropped, a joint hears from its subtree only (zedo_joint_tree_marginal.hip joint_tree_marginal_kernel)"),
 ]
 

@@ -707,9 +707,14 @@ hipError_t launch_ipo_fit(const float *x0, const float *uv, const float *K, cons
     const float inv_norm = (float)(1.0 / normaliser);
     if (row) {
         const dim3 grid((B + IPO_ROW_TB - 1) / IPO_ROW_TB), block(IPO_ROW_TB);
+#ifdef ZEDO_MUT_IPO_ROW_CASE  // tools/mutation_check.py only: case 11 launches the instantiation for 10 key joints (the eleventh is lost, no address changes)
+#define ZEDO_IPO_ROW_KJ(KJ) ((KJ) == 11 ? 10 : (KJ))
+#else
+#define ZEDO_IPO_ROW_KJ(KJ) (KJ)
+#endif
 #define ZEDO_IPO_ROW_CASE(KJ)                                                                                                                   \
         case KJ:                                                                                                                                \
-            hipLaunchKernelGGL(ipo_row_kernel<KJ>, grid, block, 0, st, x0, uv, K, keys, axes_mask, ipo_T, min_scale, max_scale, iters, inv_norm, R, T, \
+            hipLaunchKernelGGL(ipo_row_kernel<ZEDO_IPO_ROW_KJ(KJ)>, grid, block, 0, st, x0, uv, K, keys, axes_mask, ipo_T, min_scale, max_scale, iters, inv_norm, R, T, \
                                q, scale, state, it_begin, b1p0, b2p0, B, N, J, row_offset);                                                    \
             break;
         switch (k) {
@@ -719,6 +724,7 @@ hipError_t launch_ipo_fit(const float *x0, const float *uv, const float *K, cons
             default: return hipErrorInvalidValue;
         }
 #undef ZEDO_IPO_ROW_CASE
+#undef ZEDO_IPO_ROW_KJ
         return hipGetLastError();
     }
     hipLaunchKernelGGL(ipo_kernel, dim3((B + 1) / 2), dim3(64), 0, st, x0, uv, K, keys, k,
